@@ -9,10 +9,14 @@ resident in HBM before the timed region.  With --gpus N the 8 tasks are sharded 
 (one process per GPU, launched by torch.distributed.run) and the flat outer gradient is
 all-reduced over RCCL/xGMI; the meta-batch stays 8 tasks, so scaling is "strong".
 
-Extra legs (rank 0, N=1 only): `roofline` times every launch of the grouped fp32-MFMA GEMM family
-with HIP events on the launch stream (mtts_profile_gemm) over one more meta-step and reports the
-dominant instantiation against the 157.3 TFLOP/s fp32-matrix peak; `cpu_baseline` times the oracle
-(torch fp32 restatement, kind "port") on the host cores for a bounded sample of the same workload.
+A plain run sets up, warms up, times the --steps meta-steps, optionally writes what the last timed step
+computed (--dump-outputs DIR) and prints the headline line.  Everything else is measured or checked
+only with --full: the second-order step, N > 1 replica / exchange verification, `roofline` (every
+launch of the grouped fp32-MFMA GEMM family timed with HIP events on the launch stream,
+mtts_profile_gemm, over one more meta-step, dominant instantiation against the 157.3 TFLOP/s
+fp32-matrix peak), `cpu_baseline` (the oracle, torch fp32 restatement, kind "port", on the host cores
+for a bounded sample of the same workload), the parity check of the timed configuration, and the
+auxiliary legs (inference C5, mel L1 vs the reference fixture, baseline C2, front-end).
 """
 from __future__ import annotations
 
@@ -42,6 +46,8 @@ PARITY_RTOL = 2e-3  # per-task query losses of the timed configuration (dropout 
 # gradient comparison meaningless.  Timing does not depend on the weight values.
 WEIGHT_SCALE = 0.5
 EXCHANGE_RTOL = 5e-3   # N > 1: all-reduced outer gradient vs the single-handle 8-task gradient (grouped-vs-alone bound of tests/test_gpu_timed_config.py)
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: positions of the flat parameter vector written for theta / outer_grad (16 MB each)
+DUMP_SEED = 20240611
 
 
 def noam_lr(step, d_model=256, warm=4000, anneal=(300000, 400000, 500000), rate=0.3):
@@ -138,11 +144,37 @@ def _oracle_state(dims):
     return params, buffers, names
 
 
+def host_cpu_budget():
+    """Host CPUs this process may keep busy: its affinity set, capped by a cgroup CPU quota and by OMP_NUM_THREADS when the environment
+    sets one.  On a shared host os.cpu_count() reports the whole machine while the job is granted a fraction of it; thread pools and
+    process counts sized by the machine then only thrash."""
+    n = len(os.sched_getaffinity(0))
+    for path in ("/sys/fs/cgroup/cpu.max", "/sys/fs/cgroup/cpu/cpu.cfs_quota_us"):
+        try:
+            with open(path) as fh:
+                fields = fh.read().split()
+            if path.endswith("cpu.max"):
+                quota, period = fields[0], fields[1]
+            else:
+                with open("/sys/fs/cgroup/cpu/cpu.cfs_period_us") as fh:
+                    quota, period = fields[0], fh.read().strip()
+            if quota not in ("max", "-1") and int(period) > 0:
+                n = min(n, max(1, -(-int(quota) // int(period))))
+            break
+        except (OSError, ValueError, IndexError):
+            continue
+    omp = os.environ.get("OMP_NUM_THREADS", "").strip()
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def _cpu_partition(nproc):
-    """Host hardware threads this process may use, grouped by physical core (sysfs topology) and dealt to `nproc` task processes in
-    contiguous runs of whole cores of one package.  Each entry: the cpu ids of the group ordered one-hardware-thread-per-core first,
-    then the SMT siblings — so that the first t ids are the right affinity set for t <= cores threads."""
-    allowed = sorted(os.sched_getaffinity(0))
+    """Host hardware threads this process may use (the first host_cpu_budget() of its affinity set), grouped by physical core (sysfs
+    topology) and dealt to `nproc` task processes in contiguous runs of whole cores of one package.  Each entry: the cpu ids of the group
+    ordered one-hardware-thread-per-core first, then the SMT siblings — so that the first t ids are the right affinity set for t <= cores
+    threads."""
+    allowed = sorted(os.sched_getaffinity(0))[:host_cpu_budget()]
     cores = {}
     for c in allowed:
         try:
@@ -260,6 +292,7 @@ def cpu_baseline(dims, mods, budget_s=25.0, concurrent=True, dropout=True, make_
     from meta_tts_amd import synth
     from oracle import fs2_oracle as O
     host_cores = os.cpu_count() or torch.get_num_threads()
+    budget = host_cpu_budget()
     make_task = make_task or synth.make_task
     inner_steps = inner_steps or INNER_STEPS
     grad_samples = grad_samples or GRAD_SAMPLES
@@ -269,7 +302,7 @@ def cpu_baseline(dims, mods, budget_s=25.0, concurrent=True, dropout=True, make_
     sup0, qry0 = make_task(0)
     tb0 = O.to_torch_batch(sup0)
     sweep = {}
-    for nthr in sorted({t for t in (8, 16, 32, 64, 128) if t <= host_cores}):
+    for nthr in sorted({t for t in (8, 16, 32, 64, 128) if t <= budget} or {budget}):
         if sweep and min(sweep.values()) * 2.5 < list(sweep.values())[-1]:
             break  # past the optimum: more threads only thrash on these GEMM sizes (256 threads measured 175 s per step)
         torch.set_num_threads(nthr)
@@ -339,7 +372,7 @@ def cpu_baseline(dims, mods, budget_s=25.0, concurrent=True, dropout=True, make_
     top = conc if best_leg == "concurrent" else seq
     return {"value": top["value"], "unit": "meta-steps/s", "cores": int(top["cores"]), "kind": "port", "sample": top["sample"], "leg": best_leg,
             "query_losses": q_ref, "grad_samples": g_ref, "query_mels": mels_ref, "query_pass_kinks": kinks,
-            "host_cores": int(host_cores), "thread_sweep_s_per_inner_step": {str(k): v for k, v in sweep.items()},
+            "host_cores": int(host_cores), "cpu_budget": int(budget), "thread_sweep_s_per_inner_step": {str(k): v for k, v in sweep.items()},
             "sequential": seq, "concurrent": conc if conc is not None else {"error": conc_err},
             "full_box": ({"value": full_box["value"], "unit": "meta-steps/s", "cores": full_box["cores"], "physical_cores": full_box["physical_cores"],
                           "s_per_meta_step": full_box["s_per_meta_step"], "sample": full_box["sample"]} if full_box is not None else None),
@@ -689,11 +722,55 @@ def _tiny_dims():
     return ModelDims(mc, pc, n_speaker=12, vocab=40)
 
 
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the last timed meta-step computed, read back (weights, optimizer state and batches untouched; the query losses
+    are re-read by mtts_loss from the step's own query-pass outputs), as float32 .npy files (about 40 MB) so that two builds can be compared
+    output for output:
+      query_losses    [tasks, 6]               total, mel, postnet mel, pitch, energy, duration loss of each task's query pass
+      query_mel_post  [tasks, B, T, n_mel]     each task's query-pass mel_post, frames past the utterance's length zeroed
+      theta           [DUMP_SAMPLE]            the parameters after the step's clip + Adam update,
+      outer_grad      [DUMP_SAMPLE]            and the step's outer gradient, both at the same fixed positions (seed DUMP_SEED) of the flat
+                                               vector of every parameter tensor in name order"""
+    os.makedirs(out_dir, exist_ok=True)
+    eng.synchronize()
+    tasks = eng.n_tasks[1]
+    np.save(os.path.join(out_dir, "query_losses.npy"), np.asarray(eng.loss(1), np.float32))
+    outs = [eng.outputs(1, j) for j in range(tasks)]
+    B = max(o["mel_post"].shape[0] for o in outs)
+    T = max(o["mel_post"].shape[1] for o in outs)
+    mel = np.zeros((tasks, B, T, eng.dims.n_mel), np.float32)
+    for j, o in enumerate(outs):
+        for b, length in enumerate(o["mel_lens"]):
+            t = min(int(length), o["mel_post"].shape[1])
+            mel[j, b, :t] = o["mel_post"][b, :t]
+    np.save(os.path.join(out_dir, "query_mel_post.npy"), mel)
+    names = sorted(eng.params)
+    sizes = [int(np.prod(eng.params[nm][0])) for nm in names]
+    total = sum(sizes)
+    k = min(DUMP_SAMPLE, total)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=k, replace=False))
+    bounds = np.searchsorted(idx, np.cumsum([0] + sizes))
+    for which, fname in ((0, "theta"), (1, "outer_grad")):
+        vals = np.empty(k, np.float32)
+        off = 0
+        for i, (nm, sz) in enumerate(zip(names, sizes)):
+            lo, hi = bounds[i], bounds[i + 1]
+            if hi > lo:
+                vals[lo:hi] = eng.export(nm, which).reshape(-1)[idx[lo:hi] - off]
+            off += sz
+        np.save(os.path.join(out_dir, fname + ".npy"), vals)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: second order, N > 1 self-verification, roofline, CPU baseline, parity check "
+                         "against the oracle, the auxiliary legs (the --no-* options below trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed meta-step computed as DIR/<name>.npy (float32, about 40 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cpu-concurrent", action="store_true", help="skip the 8-process concurrent leg of the CPU baseline")
     ap.add_argument("--no-roofline", action="store_true")
@@ -714,6 +791,9 @@ def main():
     ap.add_argument("--selftest-spawn", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--selftest-emu", action="store_true", help=argparse.SUPPRESS)   # tests/test_bench_spawn.py: this file's N-rank flow on CPU (gloo + SIMT emulator, tiny model)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full
 
     rc = maybe_self_launch(args)
     if rc is not None:
@@ -905,13 +985,8 @@ def main():
     for _ in range(args.warmup):
         meta_step()
     dt = timed(args.steps, timed_ar=True)
-    # host time to ENQUEUE one meta-step from an idle stream (the device is still running it when the call returns): the host's own cost of the step's
-    # ~1 500-1 750 launches.  (Inside the timed loop the host runs ahead until the queue's ring is full, so its loop time there equals the device's.)
-    dev_sync()
-    t_h = time.perf_counter()
-    meta_step()
-    host_enqueue_ms = 1e3 * (time.perf_counter() - t_h)
-    dev_sync()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
     inner_upd = eng.inner_update_launches   # launches of the last timed inner step's SGD update (> 0: module by module behind its backward)
     bucket_agreement = eng.allreduce_bucket_agreement if (n > 1 and outer is None) else None   # 1: the ranks agreed on the bucket table in mtts_comm_init
     ar_ms = None
@@ -919,15 +994,24 @@ def main():
     if ar_events:
         dev_sync()
         ar_ms = float(np.mean([c.ms() for c in ar_events]))  # events on the stream RCCL was enqueued on (torch's current stream)
-    # cost of the per-step ingestion alone (host -> HBM + plans), for the record
-    dev_sync()
-    t_in = time.perf_counter()
-    for _ in range(3):
-        ingest()
-    dev_sync()
-    ingest_ms = 1e3 * (time.perf_counter() - t_in) / 3
+    host_enqueue_ms = ingest_ms = None
+    if full:
+        # host time to ENQUEUE one meta-step from an idle stream (the device is still running it when the call returns): the host's own cost of the
+        # step's ~1 500-1 750 launches.  (Inside the timed loop the host runs ahead until the queue's ring is full, so its loop time there equals the
+        # device's.)
+        dev_sync()
+        t_h = time.perf_counter()
+        meta_step()
+        host_enqueue_ms = 1e3 * (time.perf_counter() - t_h)
+        dev_sync()
+        # cost of the per-step ingestion alone (host -> HBM + plans), for the record
+        t_in = time.perf_counter()
+        for _ in range(3):
+            ingest()
+        dev_sync()
+        ingest_ms = 1e3 * (time.perf_counter() - t_in) / 3
     so = None
-    if args.order == 1 and not args.no_second_order:
+    if full and args.order == 1 and not args.no_second_order:
         # the same meta-step in the reference's training mode (second-order, config C4 per-GPU work), all ranks
         meta_step(2)
         so_steps = max(1, min(args.steps, 3))
@@ -936,7 +1020,7 @@ def main():
               "workload": "same 8-task meta-step, second-order MAML (Hessian-vector recursion through the 5 inner steps)"}
     # ---- N > 1: the run verifies itself ---------------------------------------------------------------------------------
     replicas, exchange = None, None
-    if n > 1:
+    if full and n > 1:
         # (1) every rank ends the timed steps with bit-identical weights, Adam moments and BatchNorm buffers: CRC32 of each, all-gathered
         if emu and rank == n - 1 and os.environ.get("MTTS_SELFTEST_BREAK_REPLICA"):   # tests/test_bench_spawn.py: the check must bite
             w = eng.export("mel_linear.bias").copy(); w[0] += 1e-6
@@ -987,9 +1071,9 @@ def main():
         ingest()
     q_losses = None
     roof = None
-    if rank == 0:
+    if full and rank == 0:
         q_losses, _ = eng.meta_grad(inner_steps, INNER_LR, 1.0 / META_BATCH, fetch_losses=True)
-    if rank == 0 and not args.no_roofline:
+    if full and rank == 0 and not args.no_roofline:
         # (N > 1: rank 0's own launches — its share of the tasks; no collective is armed here, the other ranks wait in the closing barrier)
         rows, recs = gemm_profile(eng, lambda: eng.meta_grad(inner_steps, INNER_LR, 1.0 / META_BATCH, second_order=(args.order == 2), fetch_losses=False), sites=True)
         roof = roofline_of(rows, "kernels" if len(local) == META_BATCH else None)     # (the committed PMC traffic figures are per launch of the 8-task step)
@@ -1010,7 +1094,7 @@ def main():
             so["whole_step_frac_survey_convention"] = round(35.5 / (so["ms_per_step"] * 1e-3) / (FP32_MATRIX_PEAK_TFLOPS * n), 4)
             so["roofline"]["note"] = "achieved = EXECUTED contraction flops of the launches (tangent pairs included) / launch time"
     hbm = None
-    if rank == 0 and n == 1 and not emu and not args.no_roofline:
+    if full and rank == 0 and n == 1 and not emu and not args.no_roofline:
         # the HBM-bound tail of the step, reported as achieved GB/s against the 8 TB/s HBM3E peak: fused clip + Adam
         # (grad-norm reduction + update: 32 B per parameter) timed on its own with events on the launch stream
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1027,9 +1111,9 @@ def main():
                              "bytes_model": "per parameter: 4 (grad, norm pass) + 4 (grad) + 12 (theta, m, v read) + 12 (written)"}}
     cpu = None
     cpu_error = None
-    if os.environ.get("MTTS_ABLATE_LN", "0") not in ("", "0") and not args.no_cpu_baseline:
+    if os.environ.get("MTTS_ABLATE_LN", "0") not in ("", "0") and full and not args.no_cpu_baseline:
         raise SystemExit("bench.py: MTTS_ABLATE_LN is a timing-only ablation (wrong results): run it with --no-cpu-baseline (no parity gate, no headline line)")
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         # (N > 1: still rank 0, on the box's host cores, while the other ranks wait in the closing barrier)
         try:
             cpu = cpu_baseline(dims, mods, concurrent=(not args.no_cpu_concurrent) and not emu, dropout=not args.no_dropout, make_task=make_task,
@@ -1062,11 +1146,14 @@ def main():
         # whose exactly priced contribution shrinks the residual.  Both errors are reported per task.
         from oracle import arbiter as ARB
         jobs = []
+        budget = host_cpu_budget()
+        arb_procs = min(m, max(1, budget // 2))                  # float64 oracle workers: many processes of few threads (it does not scale with threads)
+        arb_threads = max(1, min(16, budget // arb_procs))
         for jt in range(m):
             eo = eng.outputs(1, jt)
             e_grads = {name: eng.export(name, 2, jt).astype(np.float64) * META_BATCH for name in grad_samples}   # backward ran with grad_scale = 1 / META_BATCH
             o_grads = {name: (g if g is not None else np.zeros_like(e_grads[name])) for name, g in cpu["grad_samples"][jt].items()}
-            jobs.append(dict(task=local[jt], group_index=jt, threads=16, dropout_seed=None if args.no_dropout else DROPOUT_SEED, steps=inner_steps, lr=INNER_LR,
+            jobs.append(dict(task=local[jt], group_index=jt, threads=arb_threads, dropout_seed=None if args.no_dropout else DROPOUT_SEED, steps=inner_steps, lr=INNER_LR,
                              weight_scale=WEIGHT_SCALE, modules=list(mods), names=list(grad_samples),
                              parties={"engine": {"grads": e_grads, "mel": eo["mel"], "mel_post": eo["mel_post"]},
                                       "oracle32": {"grads": o_grads, "mel": cpu["query_mels"][jt][0], "mel_post": cpu["query_mels"][jt][1]}}))
@@ -1075,7 +1162,7 @@ def main():
         arb_error = None
         try:
             t_arb = time.perf_counter()
-            reports = [ARB.synth_task_worker(jb) for jb in jobs] if emu else ARB.run_pool(jobs, processes=min(len(jobs), max(1, (os.cpu_count() or 8) // 16)))
+            reports = [ARB.synth_task_worker(jb) for jb in jobs] if emu else ARB.run_pool(jobs, processes=arb_procs)
             arb_s = time.perf_counter() - t_arb
             digests = [dict(task=r["task"], **ARB.summarize(r)) for r in reports]
             def worst(key):
@@ -1130,14 +1217,14 @@ def main():
             aux_errors[name] = f"{type(ex).__name__}: {ex}"
             return None
     infer = None
-    if rank == 0 and n == 1 and not emu and not args.no_inference:
+    if full and rank == 0 and n == 1 and not emu and not args.no_inference:
         infer = guarded("inference_c5", inference_leg, dims, mods, local_rank)
-    mel_l1 = guarded("mel_l1_vs_reference", mel_l1_leg, dims, local_rank) if (rank == 0 and n == 1 and not emu) else None
+    mel_l1 = guarded("mel_l1_vs_reference", mel_l1_leg, dims, local_rank) if (full and rank == 0 and n == 1 and not emu) else None
     c2 = None
-    if rank == 0 and n == 1 and not emu and not args.no_baseline_c2:
+    if full and rank == 0 and n == 1 and not emu and not args.no_baseline_c2:
         c2 = guarded("baseline_c2", baseline_c2_leg, dims, local_rank, noam_lr, trn)
     front = None
-    if rank == 0 and n == 1 and not emu and not args.no_frontend and part == n:
+    if full and rank == 0 and n == 1 and not emu and not args.no_frontend and part == n:
         front = guarded("frontend", frontend_leg, local_rank)
     if n > 1:
         dist.barrier()
@@ -1156,22 +1243,22 @@ def main():
                            "inner_update": ("module by module behind the backward, %d launches per inner step on a stream of its own" % inner_upd)
                                            if inner_upd > 0 else "one launch between the backward and the next forward"},
                 **({"emulated_world": part, "note": "diagnostic: rank-0 share of an emulated multi-rank run, no collective"} if part != n else {}),
-                "batch_ingest_ms_per_step": round(ingest_ms, 3),
-                "host_enqueue_ms_from_idle": round(host_enqueue_ms, 3),
                 "rccl_ranks": n if n > 1 else None, "allreduce_impl": ar_impl, "allreduce_ms_per_step": round(ar_ms, 3) if ar_ms is not None else None,
                 "allreduce_payload_mbytes": round(4e-6 * eng.n_total, 1) if n > 1 else None,
                 "allreduce_overlap": ({"on": bool(ar_overlapped[0]), "collectives_per_step": ar_launches, "bucket_table_agreed_across_ranks": (bucket_agreement == 1) if bucket_agreement is not None else None,
                                        "what": "one ncclAllReduce per module bucket in backward-completion order (PostNet, decoder 5 + mel_linear .. decoder 0, variance adaptor, speaker table, "
                                                "encoder 3 .. 0 + word embedding) + the exchange tail, on a communication stream behind events of the main / weight-gradient streams; "
                                                "allreduce_ms_per_step = what mtts_allreduce_outer still waits for (exposed)"} if n > 1 else None),
-                "allreduce_carries": "flat outer gradient + 6 loss scalars (sync_dist mean) + PostNet BatchNorm running buffers (rank 0's, as DDP broadcast_buffers)" if n > 1 else None,
-                "replicas": replicas, "outer_gradient_vs_single_handle": exchange,
-                "query_total_loss_mean": round(float(q_losses[:, 0].mean()), 5) if q_losses is not None else None}
+                "allreduce_carries": "flat outer gradient + 6 loss scalars (sync_dist mean) + PostNet BatchNorm running buffers (rank 0's, as DDP broadcast_buffers)" if n > 1 else None}
+        if full:
+            line.update({"batch_ingest_ms_per_step": round(ingest_ms, 3), "host_enqueue_ms_from_idle": round(host_enqueue_ms, 3),
+                         "replicas": replicas, "outer_gradient_vs_single_handle": exchange,
+                         "query_total_loss_mean": round(float(q_losses[:, 0].mean()), 5) if q_losses is not None else None,
+                         "parity_check": parity})
         if emu:
             line["selftest"] = "emu: CPU self-test of the N-rank flow (gloo + SIMT emulator, tiny model) - NOT a bench result"
         if so is not None:
             line["second_order"] = so
-        line["parity_check"] = parity
         if mel_l1 is not None:
             line["mel_l1_vs_reference"] = mel_l1
         if infer is not None:

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -52,8 +54,8 @@ def test_two_rank_bench_line_is_judgeable_and_verifies_itself():
     parity verdict of the float64 arbiter, and the run must have verified itself: replicas bit-identical after the timed steps (CRC32 of theta /
     Adam m / Adam v / BatchNorm buffers, all-gathered), the all-reduced outer gradient equal to the single-handle 8-task gradient, and report the
     exchange (ranks, exposed ms, collectives per step)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest-emu", "--steps", "1", "--warmup", "0", "--no-second-order"],
-                         env=_env(), capture_output=True, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest-emu", "--full", "--steps", "1", "--warmup", "0",
+                          "--no-second-order"], env=_env(), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -72,8 +74,8 @@ def test_two_rank_bench_line_is_judgeable_and_verifies_itself():
 
 def test_emulate_world_reports_the_emulated_share():
     """`--emulate-world 8` on one process holds ONE task in its launches and says so (config.tasks_per_gpu was 8 in round 5)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--selftest-emu", "--emulate-world", "8", "--steps", "1", "--warmup", "0",
-                          "--no-second-order", "--no-cpu-baseline"], env=_env(), capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--selftest-emu", "--full", "--emulate-world", "8", "--steps", "1",
+                          "--warmup", "0", "--no-second-order", "--no-cpu-baseline"], env=_env(), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")][0]
     assert d["n_gpus"] == 1 and d["emulated_world"] == 8 and d["config"]["tasks_per_gpu"] == 1 and d["roofline"]["tasks_in_the_launches"] == 1
@@ -84,7 +86,36 @@ def test_replica_check_bites():
     """The self-verification is not decorative: one float of one rank's weights off by 1e-6 after the timed steps and the run refuses to print a line."""
     env = _env()
     env["MTTS_SELFTEST_BREAK_REPLICA"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest-emu", "--steps", "1", "--warmup", "0", "--no-second-order",
-                          "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest-emu", "--full", "--steps", "1", "--warmup", "0",
+                          "--no-second-order", "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode != 0
     assert "replicas diverged" in out.stderr and not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the run times --steps meta-steps and prints the headline only (no roofline / CPU baseline / parity legs); --dump-outputs
+    writes what the last timed step computed as float32 .npy files, and the same arguments give the same arrays (the emulator runs the kernels
+    serially: bit-identical)."""
+    runs = []
+    for k in range(2):
+        out_dir = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--selftest-emu", "--emulate-world", "8", "--steps", "2", "--warmup", "1",
+                              "--dump-outputs", str(out_dir)], env=_env(), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = lines[0]
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "meta-steps/s" and d["higher_is_better"] is True
+        assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1e3 * 1e-2 and d["dtype"] == "f32"
+        for key in ("roofline", "cpu_baseline", "parity_check", "second_order", "replicas", "host_enqueue_ms_from_idle"):
+            assert key not in d, key
+        files = {f: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+        assert set(files) == {"query_losses.npy", "query_mel_post.npy", "theta.npy", "outer_grad.npy"}
+        assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 << 20
+        for a in files.values():
+            assert a.dtype == np.float32 and np.all(np.isfinite(a))
+        assert files["query_losses.npy"].shape == (1, 6) and files["query_mel_post.npy"].ndim == 4
+        assert files["theta.npy"].shape == files["outer_grad.npy"].shape and np.abs(files["outer_grad.npy"]).max() > 0
+        runs.append(files)
+    for f in runs[0]:
+        np.testing.assert_array_equal(runs[0][f], runs[1][f])

@@ -14,7 +14,7 @@ def run(env_over, extra):
         if "=" in kv:
             k, v = kv.split("=", 1)
             env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-inference", "--no-frontend", "--no-baseline-c2"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-inference", "--no-frontend", "--no-baseline-c2"] + extra
     p = subprocess.run(cmd, env=env, capture_output=True, text=True)
     for ln in reversed(p.stdout.strip().splitlines()):
         if ln.startswith("{"):

@@ -2,7 +2,7 @@
 # A/B over the ranks of the scaling curve: tools/ab_world.sh OUT "ENV1" "ENV2" ... — for every variant the step of a rank holding 8 / 4 / 2 / 1 tasks
 # (bench.py --emulate-world 1 / 2 / 4 / 8), first order (and second order with SO=1).
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; OUT=gpurun_out/$1; shift; mkdir -p $OUT
-X="--no-cpu-baseline --no-inference --no-frontend --no-baseline-c2 --no-roofline --steps 6 --warmup 2"
+X="--full --no-cpu-baseline --no-inference --no-frontend --no-baseline-c2 --no-roofline --steps 6 --warmup 2"
 [ "${SO:-0}" = "1" ] || X="$X --no-second-order"
 for V in "$@"; do
   echo "== $V"

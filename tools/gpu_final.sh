@@ -13,9 +13,9 @@ for cfg in "17047 1024 2304 3064" "17047 1024 2304 1064" "4096 4096 4096 3064" "
 ./tools/mfma_peak 100000 2>&1 | tail -3 >> $OUT/clock_probe.txt
 timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log; grep -E "passed|failed|^FAILED|pytest rc" $OUT/pytest.log | tail -6
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 X="--no-cpu-baseline --no-inference --no-frontend --no-baseline-c2"
-timeout 400 python bench.py --steps 10 --warmup 3 --emulate-world 8 $X > $OUT/bench_w8.json 2> $OUT/bench_w8.err
+timeout 400 python bench.py --steps 10 --warmup 3 --emulate-world 8 --full $X > $OUT/bench_w8.json 2> $OUT/bench_w8.err
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof8 -o trace -- python $R/bench.py --steps 5 --warmup 1 $X --no-roofline --no-second-order > $R/$OUT/prof8.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof8so -o trace -- python $R/bench.py --steps 3 --warmup 1 $X --no-roofline --order 2 --no-second-order > $R/$OUT/prof8so.log 2>&1
@@ -39,7 +39,7 @@ done
 cd $R
 # the per-rank step of an N-rank job, N = 2 / 4 / 8 (first and second order)
 for w in 2 4 8; do
-  timeout 400 python bench.py --steps 6 --warmup 2 --emulate-world $w $X --no-roofline > $OUT/bench_w$w.tmp 2>/dev/null
+  timeout 400 python bench.py --steps 6 --warmup 2 --emulate-world $w --full $X --no-roofline > $OUT/bench_w$w.tmp 2>/dev/null
   python -c "
 import json; d=json.load(open('$OUT/bench_w$w.tmp')); print('emulate-world $w tasks/rank', d['config']['tasks_per_gpu'], 'FO ms', d['ms_per_step'], 'SO ms', (d.get('second_order') or {}).get('ms_per_step'))" >> $OUT/emulate_world.txt
 done

@@ -2,7 +2,7 @@
 # Single-task rank (--emulate-world 8): where the step's time is.  (a) default placement, (b) everything on ONE stream (no deferred weight
 # gradients, no run-ahead, no side-stream predictors, monolithic SGD step): per-launch GEMM records of both + kernel traces.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; OUT=gpurun_out/${1:-r06p1}; mkdir -p $OUT; export TMPDIR=/tmp; R=$PWD
-X="--no-cpu-baseline --no-inference --no-frontend --no-baseline-c2 --no-second-order --emulate-world 8"
+X="--full --no-cpu-baseline --no-inference --no-frontend --no-baseline-c2 --no-second-order --emulate-world 8"
 SER="MTTS_DEFER_WGRAD=0 MTTS_ENC_AHEAD=0 MTTS_ENC_AHEAD_QUERY=0 MTTS_PRED_SIDE=0 MTTS_PRED_EARLY=0 MTTS_UPD_OVERLAP=0 MTTS_SIDE_PRED_ALL=0 MTTS_ENC_AHEAD_ALL=0"
 MTTS_BENCH_KEEP_SITES=$R/$OUT/sites_default.csv python bench.py --steps 6 --warmup 2 $X > $OUT/bench_default.json 2> $OUT/bench_default.err
 env $SER MTTS_BENCH_KEEP_SITES=$R/$OUT/sites_serial.csv python bench.py --steps 6 --warmup 2 $X > $OUT/bench_serial.json 2> $OUT/bench_serial.err
