@@ -417,6 +417,33 @@ const char* mtts_stft_last_error(mtts_stft* h);
 int mtts_stft_load(mtts_stft* h, const float* forward_basis, const float* mel_basis);
 int mtts_stft_mel_spectrogram(mtts_stft* h, const float* wav, int n_samples, float* mel, float* energy);
 
+/* ---- spectrogram -> waveform: the inverse half of the same handle (Griffin-Lim) -----------------
+ * Frames are frame-major ([frame][bin], F = filter_length / 2 + 1 bins), the transpose of the reference's (B, F, T) tensors.
+ * load_inverse: inverse_basis [2F][filter_length] = the reference's `STFT.inverse_basis` buffer (np.linalg.pinv(scale *
+ * fourier_basis).T in float32, scale = filter_length / hop_length, times the window, stft.py:33-45); window_sq [filter_length] = the
+ * squared centre-padded window that `window_sumsquare` adds up (audio_processing.py:7-63).  Both required.
+ * transform: STFT.transform (stft.py:52-77) of one waveform: reflect padding by filter_length / 2 WITHOUT clipping, magnitude
+ * sqrt(re^2 + im^2) and phase atan2(im, re), each [T][F], T = n_samples / hop_length + 1.  Returns T, < 0 on error
+ * (n_samples <= filter_length / 2: the reference's F.pad raises).
+ * inverse: STFT.inverse (stft.py:79-119) of n_utts spectrograms of n_frames[u] frames each: magnitude, phase [sum T][F];
+ * overlap-add, division by the window envelope where it exceeds float32 tiny, x filter_length / hop_length, trim filter_length / 2
+ * at both ends.  out: the waveforms packed one after another, hop_length * (T_u - 1) samples each.
+ * griffin_lim: audio_processing.py:66-80 with the starting phases `angles` [sum T][F] drawn by the caller (the reference draws
+ * np.angle(np.exp(2j pi U[0, 1)))), then n_iters x (transform, inverse with the new phase and the fixed magnitude).
+ * n_iters = 0 is `inverse`.
+ * inv_mel: the computation of tools.py:18-37 (inv_mel_spec) up to the waveform: log_mel [sum Tm][n_mel] (the mel basis of
+ * mtts_stft_load must be loaded), magnitude = 1000 * exp(mel)^T @ mel_basis with the LAST frame of every utterance dropped, then
+ * griffin_lim with angles [sum (Tm - 1)][F].  out: hop_length * (Tm_u - 2) samples per utterance.
+ * inverse / griffin_lim / inv_mel return the total number of output samples, < 0 on error.  With n_iters > 0 every T must satisfy
+ * hop_length * (T - 1) > filter_length / 2 (the next transform's reflect padding; T >= 1 otherwise), n_iters >= 0; errors are reported
+ * before any launch.  The workspace grows on demand beyond what max_samples reserved.  All utterances of a call share every launch.
+ * Synchronous. */
+int mtts_stft_load_inverse(mtts_stft* h, const float* inverse_basis, const float* window_sq);
+int mtts_stft_transform(mtts_stft* h, const float* wav, int n_samples, float* magnitude, float* phase);
+int64_t mtts_stft_inverse(mtts_stft* h, int n_utts, const int* n_frames, const float* magnitude, const float* phase, float* out);
+int64_t mtts_stft_griffin_lim(mtts_stft* h, int n_utts, const int* n_frames, const float* magnitude, const float* angles, int n_iters, float* out);
+int64_t mtts_stft_inv_mel(mtts_stft* h, int n_utts, const int* n_mel_frames, const float* log_mel, const float* angles, int n_iters, float* out);
+
 #ifdef __cplusplus
 }
 #endif

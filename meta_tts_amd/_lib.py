@@ -144,6 +144,11 @@ EXPORTS = {
     "mtts_stft_last_error": (C.c_char_p, [C.c_void_p]),
     "mtts_stft_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_stft_mel_spectrogram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mtts_stft_load_inverse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_stft_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mtts_stft_inverse": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_stft_griffin_lim": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mtts_stft_inv_mel": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mtts_vocoder_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_void_p)]),
     "mtts_vocoder_destroy": (None, [C.c_void_p]),

@@ -1,12 +1,14 @@
-"""`TacotronSTFT` on libmtts.so (reference audio/stft.py:128-178).
+"""`STFT` and `TacotronSTFT` on libmtts.so (reference audio/stft.py:15-178).
 
 The bases are built on the host exactly as the reference builds its buffers — `np.fft.fft(np.eye(n))` split into real / imaginary
 rows and multiplied by the periodic Hann window (stft.py:27-46; scipy.signal.get_window, as there) — and the Slaney mel filter
 bank of `librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax)` (librosa is not part of this image: restated from its documented
-algorithm, htk=False, norm="slaney").  The device does the framing, both contractions, magnitude, log and energy."""
+algorithm, htk=False, norm="slaney").  The device does the framing, both contractions, magnitude, log and energy; in the inverse
+direction (csrc/griffin.h) the inverse-basis contraction, the overlap-add and whole Griffin-Lim loops."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -25,6 +27,149 @@ def forward_basis(filter_length: int, win_length: int, window: str = "hann") -> 
     lpad = (filter_length - win_length) // 2                                                    # librosa.util.pad_center
     w = np.pad(w, (lpad, filter_length - win_length - lpad))
     return (basis * w.astype(np.float32)[None, :]).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=8)
+def _inverse_basis(filter_length: int, hop_length: int, win_length: int, window: str) -> np.ndarray:
+    fb = np.fft.fft(np.eye(filter_length))
+    cutoff = filter_length // 2 + 1
+    fourier = np.vstack([np.real(fb[:cutoff, :]), np.imag(fb[:cutoff, :])])
+    inv = np.linalg.pinv((filter_length / hop_length) * fourier).T.astype(np.float32)       # torch.FloatTensor(...) in the reference
+    from .audio_processing import _window
+    w = _window(window, win_length, filter_length).astype(np.float32)
+    out = (inv * w[None, :]).astype(np.float32)
+    out.setflags(write=False)
+    return out
+
+
+def inverse_basis(filter_length: int, hop_length: int, win_length: int, window: str = "hann") -> np.ndarray:
+    """[2 * (filter_length // 2 + 1)][filter_length] float32 — STFT.inverse_basis (stft.py:33-45) without its singleton channel axis:
+    np.linalg.pinv(scale * fourier_basis).T with scale = filter_length / hop_length, cast to float32, times the float32 window."""
+    assert filter_length >= win_length
+    return _inverse_basis(int(filter_length), int(hop_length), int(win_length), window).copy()
+
+
+def _np32(x):
+    return np.ascontiguousarray(np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, np.float32))
+
+
+class STFT:
+    """audio/stft.py:15-125 on the device.  `transform(x)` takes (B, n) waveforms and returns (magnitude, phase), each (B, F, T) float32;
+    `inverse(magnitude, phase)` takes (B, F, T) and returns (B, 1, hop * (T - 1)); `forward(x)` is inverse(transform(x)).  Inputs may be
+    numpy arrays or torch tensors; outputs are numpy.  Only string windows (scipy.signal.get_window) are supported.
+
+    A TacotronSTFT's `stft_fn` shares that TacotronSTFT's device handle (pass `_handle`); a stand-alone STFT owns one."""
+
+    def __init__(self, filter_length, hop_length, win_length, window="hann", *, max_samples=22050 * 40, device=0, lib_path=None,
+                 _handle=None):
+        if window is None:
+            raise NotImplementedError("STFT(window=None): the device path divides by the window envelope; pass a window name")
+        self.filter_length, self.hop_length, self.win_length, self.window = filter_length, hop_length, win_length, window
+        self.n_bins = filter_length // 2 + 1
+        self.forward_basis = forward_basis(filter_length, win_length, window)
+        self._inverse_loaded = False
+        if _handle is not None:
+            self.lib, self.h, self._owner = _handle[0], _handle[1], False
+        else:
+            self.lib = _lib.load(lib_path)
+            h = C.c_void_p()
+            if self.lib.mtts_stft_create(filter_length, hop_length, 1, max_samples, device, C.byref(h)) != 0:
+                raise MttsError(self.lib.mtts_stft_last_error(None).decode())
+            self.h, self._owner = h, True
+            self._check(self.lib.mtts_stft_load(self.h, self.forward_basis.ctypes.data_as(C.c_void_p), None))
+
+    @property
+    def inverse_basis(self) -> np.ndarray:
+        return inverse_basis(self.filter_length, self.hop_length, self.win_length, self.window)
+
+    def _ensure_inverse(self):
+        """The inverse basis (a pseudo-inverse on the host) and the squared window go to the device on first use."""
+        if self._inverse_loaded:
+            return
+        from .audio_processing import _window
+        ib = self.inverse_basis
+        wsq = (_window(self.window, self.win_length, self.filter_length) ** 2).astype(np.float32)
+        self._check(self.lib.mtts_stft_load_inverse(self.h, ib.ctypes.data_as(C.c_void_p), wsq.ctypes.data_as(C.c_void_p)))
+        self._inverse_loaded = True
+
+    def _check(self, rc):
+        if rc < 0:
+            raise MttsError(self.lib.mtts_stft_last_error(self.h).decode())
+        return rc
+
+    def close(self):
+        if getattr(self, "_owner", False) and getattr(self, "h", None):
+            self.lib.mtts_stft_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def _frames_of(self, n_frames, what, transforms=True):
+        n = np.asarray(n_frames, np.int32).reshape(-1)
+        bad = (n < 1) | (transforms & (self.hop_length * (n.astype(np.int64) - 1) <= self.filter_length // 2))
+        if bad.any():
+            raise MttsError(f"{what}: spectrogram too short: {int(n[bad][0])} frames give a waveform of hop_length * (T - 1) samples, which must exceed "
+                            f"filter_length / 2 = {self.filter_length // 2} (the reference's reflection padding raises)")
+        return np.ascontiguousarray(n)
+
+    def transform(self, input_data):
+        """stft.py:52-77: reflect padding WITHOUT clipping, (magnitude, phase) each (B, F, T)."""
+        x = _np32(input_data)
+        if x.ndim == 1:
+            x = x[None]
+        n = x.shape[1]
+        if n <= self.filter_length // 2:
+            raise MttsError(f"transform: {n} samples is too short for the reflection padding of filter_length / 2 = {self.filter_length // 2}")
+        T = n // self.hop_length + 1
+        mag = np.empty((x.shape[0], T, self.n_bins), np.float32)
+        ph = np.empty_like(mag)
+        for b in range(x.shape[0]):
+            row = np.ascontiguousarray(x[b])
+            got = self._check(self.lib.mtts_stft_transform(self.h, row.ctypes.data_as(C.c_void_p), n, mag[b].ctypes.data_as(C.c_void_p),
+                                                           ph[b].ctypes.data_as(C.c_void_p)))
+            assert got == T
+        return mag.transpose(0, 2, 1), ph.transpose(0, 2, 1)
+
+    def _packed(self, fn, mats, frames, extra, n_out):
+        self._ensure_inverse()
+        out = np.empty(int(n_out), np.float32)
+        got = self._check(fn(self.h, len(frames), frames.ctypes.data_as(C.c_void_p), *[m.ctypes.data_as(C.c_void_p) for m in mats], *extra,
+                             out.ctypes.data_as(C.c_void_p)))
+        assert got == n_out, (got, n_out)
+        return out
+
+    def _batched(self, magnitude, angles, n_iters):
+        """(B, F, T) magnitude and angles -> (B, hop * (T - 1)) through one device call."""
+        m, a = _np32(magnitude), _np32(angles)
+        if m.ndim == 2:
+            m, a = m[None], a[None]
+        assert m.shape == a.shape and m.shape[1] == self.n_bins, (m.shape, a.shape)
+        B, _, T = m.shape
+        frames = self._frames_of([T] * B, "inverse" if not n_iters else "griffin_lim", transforms=bool(n_iters))
+        mf = np.ascontiguousarray(m.transpose(0, 2, 1)).reshape(B * T, self.n_bins)
+        af = np.ascontiguousarray(a.transpose(0, 2, 1)).reshape(B * T, self.n_bins)
+        L = self.hop_length * (T - 1)
+        if n_iters is None:
+            out = self._packed(self.lib.mtts_stft_inverse, (mf, af), frames, (), B * L)
+        else:
+            if int(n_iters) < 0:
+                raise MttsError("griffin_lim: n_iters < 0")
+            out = self._packed(self.lib.mtts_stft_griffin_lim, (mf, af), frames, (int(n_iters),), B * L)
+        return out.reshape(B, L)
+
+    def inverse(self, magnitude, phase):
+        """stft.py:79-119: (B, F, T) magnitude and phase -> (B, 1, hop * (T - 1)) float32."""
+        return self._batched(magnitude, phase, None)[:, None, :]
+
+    def griffin_lim_with_angles(self, magnitudes, angles, n_iters):
+        """audio_processing.py:66-80 from given starting phases: (B, F, T) -> (B, hop * (T - 1))."""
+        return self._batched(magnitudes, angles, n_iters)
+
+    def forward(self, input_data):
+        magnitude, phase = self.transform(input_data)
+        return self.inverse(magnitude, phase)
+
+    __call__ = forward
 
 
 def _hz_to_mel(f):
@@ -72,6 +217,8 @@ class TacotronSTFT:
             raise MttsError(self.lib.mtts_stft_last_error(None).decode())
         self.h = h
         self._check(self.lib.mtts_stft_load(self.h, self.forward_basis.ctypes.data_as(C.c_void_p), self.mel_basis.ctypes.data_as(C.c_void_p)))
+        self.stft_fn = STFT(filter_length, hop_length, win_length, _handle=(self.lib, self.h))   # stft.py:140 (shares this handle)
+        self._stft_fn = self.stft_fn   # the name audio/tools.py:inv_mel_spec reads (the reference's TacotronSTFT lacks it)
 
     def _check(self, rc):
         if rc < 0:
@@ -84,10 +231,36 @@ class TacotronSTFT:
 
     def close(self):
         if getattr(self, "h", None):
+            if getattr(self, "stft_fn", None) is not None:
+                self.stft_fn.h = None
             self.lib.mtts_stft_destroy(self.h)
             self.h = None
 
     __del__ = close
+
+    def spectral_normalize(self, magnitudes):
+        from .audio_processing import dynamic_range_compression
+        return dynamic_range_compression(magnitudes)
+
+    def spectral_de_normalize(self, magnitudes):
+        from .audio_processing import dynamic_range_decompression
+        return dynamic_range_decompression(magnitudes)
+
+    def inv_mel_with_angles(self, log_mels, angles, n_iters):
+        """tools.py:18-37 up to the waveform for a list of log-mels (n_mel, Tm_u) and starting phases (F, Tm_u - 1): one device call,
+        returns the list of waveforms (hop * (Tm_u - 2) samples each)."""
+        mels = [_np32(m) for m in log_mels]
+        if int(n_iters) < 0:
+            raise MttsError("inv_mel: n_iters < 0")
+        tm = np.asarray([m.shape[1] for m in mels], np.int32)
+        for m, a in zip(mels, angles):
+            assert m.shape[0] == self.n_mel_channels and a.shape == (self.stft_fn.n_bins, m.shape[1] - 1), (m.shape, a.shape)
+        self.stft_fn._frames_of(tm - 1, "inv_mel (the last mel frame is dropped)", transforms=int(n_iters) > 0)
+        lm = np.ascontiguousarray(np.concatenate([m.T for m in mels], axis=0))
+        af = np.ascontiguousarray(np.concatenate([_np32(a).T for a in angles], axis=0))
+        lens = self.hop_length * (tm.astype(np.int64) - 2)
+        out = self.stft_fn._packed(self.lib.mtts_stft_inv_mel, (lm, af), np.ascontiguousarray(tm), (int(n_iters),), int(lens.sum()))
+        return np.split(out, np.cumsum(lens)[:-1])
 
     def mel_spectrogram(self, y):
         y = np.ascontiguousarray(np.asarray(y.detach().cpu().numpy() if hasattr(y, "detach") else y, np.float32))

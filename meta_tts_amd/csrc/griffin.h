@@ -1,0 +1,348 @@
+// Spectrogram -> waveform on the device: the inverse half of the reference's `audio` package.
+//
+// Reference: audio/stft.py:52-77 (STFT.transform: reflect padding by n_fft/2 WITHOUT the [-1, 1] clip of get_mel_from_wav, strided Conv1d
+// against the windowed Fourier basis, magnitude and atan2 phase), :79-119 (STFT.inverse: conv_transpose1d of [M cos p | M sin p] against
+// the windowed pseudo-inverse basis, division by the window's sum-square envelope where it exceeds float32 `tiny`, x n_fft / hop, trim
+// n_fft / 2 at both ends), audio/audio_processing.py:7-80 (window_sumsquare, griffin_lim) and audio/tools.py:18-37 (inv_mel_spec:
+// exp(mel)^T @ mel_basis x 1000, last frame dropped, Griffin-Lim).
+//
+// MI355X layout.  Every utterance of a call goes through the same launches; frames are rows ([frame][bin], the engine's layout).
+//   * R [sum T][ld_spec] = [M cos p | M sin p | 0 pad] — the recombined spectrum, zero padded to the GEMM's K alignment;
+//   * inverse GEMM (NT against the stored transpose of the inverse basis, [n_fft][ld_spec], zero padded columns):
+//     frames [sum T][n_fft] = R * inverse_basis;
+//   * overlap-add (gl_overlap_add_kernel): a deterministic gather of the <= ceil(n_fft / hop) frames that cover a sample, the envelope
+//     derived from the squared window in the same loop, and the next transform's reflect-padded input written directly (the trimmed
+//     waveform on the last pass);
+//   * forward GEMM: melfront.h's implicit GEMM over overlapping rows (lda = hop) of the packed padded signals against the forward
+//     basis.  Every padded signal starts at a multiple of hop, so one NT launch covers all utterances; the rows that straddle two
+//     utterances are dropped through GemmArgs::c_rowmap and the spectrum lands compact in R's buffer;
+//   * phasor (gl_phasor_kernel, in place): R = M * (re, im) / |z| = (M cos atan2, M sin atan2) without the transcendentals.
+// One Griffin-Lim iteration is these four launches on the handle's stream.
+#pragma once
+#include <cfloat>
+#include <string>
+#include <vector>
+
+#include "melfront.h"
+
+namespace mtts {
+
+struct GlUtt {
+    int T;            // frames of the spectrogram (the waveform has hop * (T - 1) samples)
+    int frame0;       // first row of this utterance in R / frames
+    long long xp0;    // first sample of its reflect-padded signal (a multiple of hop)
+    long long out0;   // first sample of its waveform in the packed output
+};
+
+// xp[j] = x[reflect(j - pad)] for j < n + 2 * pad  (STFT.transform's F.pad(mode="reflect"); no clip: that belongs to get_mel_from_wav)
+__global__ void gl_reflect_pad_kernel(const float* x, int n, int pad, float* xp) {
+    const long long total = (long long)n + 2 * pad;
+    for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < total; j += (long long)gridDim.x * blockDim.x) {
+        long long s = j - pad;
+        if (s < 0) s = -s;
+        else if (s >= n) s = 2LL * (n - 1) - s;
+        xp[j] = x[s];
+    }
+}
+
+// spec [T][ld] = [re | im] -> magnitude [T][F] = sqrt(re^2 + im^2), phase [T][F] = atan2(im, re)   (stft.py:71-75)
+__global__ void gl_mag_phase_kernel(const float* spec, int ld, int T, int F, float* mag, float* phase) {
+    const long long total = (long long)T * F;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long t = i / F;
+        const int f = (int)(i - t * F);
+        const float re = spec[t * ld + f], im = spec[t * ld + F + f];
+        mag[i] = sqrtf(re * re + im * im);
+        phase[i] = atan2f(im, re);
+    }
+}
+
+// out [rows][ldo] = exp(log_mel [rows][n_mel]), columns n_mel .. ldo zeroed (TacotronSTFT.spectral_de_normalize, C = 1)
+__global__ void gl_exp_rows_kernel(const float* x, int rows, int n_mel, float* out, int ldo) {
+    const long long total = (long long)rows * ldo;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / ldo;
+        const int c = (int)(i - r * ldo);
+        out[i] = c < n_mel ? expf(x[r * n_mel + c]) : 0.f;
+    }
+}
+
+// First pass: R[t] = [M cos a | M sin a | 0] from the host-drawn angles a [T][F]   (stft.py:80-82)
+__global__ void gl_phasor_init_kernel(const float* mag, int ldm, const float* ang, int T, int F, float* R, int ldr) {
+    const long long total = (long long)T * ldr;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long t = i / ldr;
+        const int c = (int)(i - t * ldr);
+        float v = 0.f;
+        if (c < 2 * F) {
+            const int f = c < F ? c : c - F;
+            const float m = mag[t * ldm + f], a = ang[t * F + f];
+            v = c < F ? m * cosf(a) : m * sinf(a);
+        }
+        R[i] = v;
+    }
+}
+
+// In place: R[t] = [re | im | pad] -> [M re / |z| | M im / |z| | 0]  =  (M cos atan2(im, re), M sin atan2(im, re)).
+// |z| == 0 follows atan2's signs: re = +0 -> (M, 0), re = -0 -> (-M, 0).  A pair whose squares underflow is rescaled first.
+__global__ void gl_phasor_kernel(float* R, int ldr, const float* mag, int ldm, int T, int F) {
+    const long long total = (long long)T * (ldr - F);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long t = i / (ldr - F);
+        const int f = (int)(i - t * (ldr - F));
+        float* row = R + t * ldr;
+        if (f >= F) {                         // padding columns 2F .. ldr
+            if (F + f < ldr) row[F + f] = 0.f;
+            continue;
+        }
+        float re = row[f], im = row[F + f];
+        const float m = mag[t * ldm + f];
+        float r = sqrtf(re * re + im * im);
+        if (!(r > 0.f)) {
+            const float s = fmaxf(fabsf(re), fabsf(im));
+            if (s > 0.f) { re /= s; im /= s; r = sqrtf(re * re + im * im); }
+        }
+        float c, sn;
+        if (r > 0.f) { c = re / r; sn = im / r; }
+        else { c = copysignf(1.f, re); sn = 0.f; }
+        row[f] = m * c;
+        row[F + f] = m * sn;
+    }
+}
+
+// Overlap-add of the inverse transform (conv_transpose1d with stride hop), envelope division, hop-ratio scale and trim, per sample a
+// gather of the frames that cover it (no atomics).  blockIdx.y = utterance.  mode 0: write the next transform's reflect-padded input
+// at xp0 (n + n_fft samples); mode 1: write the trimmed waveform at out0 (n = hop * (T - 1) samples).
+__global__ void gl_overlap_add_kernel(const float* frames, const GlUtt* utts, const float* win2, int n_fft, int hop, float scale, float* dst,
+                                      int mode) {
+    const GlUtt u = utts[blockIdx.y];
+    const long long n = (long long)hop * (u.T - 1), half = n_fft / 2;
+    const long long total = mode == 0 ? n + n_fft : n;
+    const float* fr = frames + (long long)u.frame0 * n_fft;
+    for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < total; j += (long long)gridDim.x * blockDim.x) {
+        long long s = j;
+        if (mode == 0) {
+            s = j - half;
+            if (s < 0) s = -s;
+            else if (s >= n) s = 2 * (n - 1) - s;
+        }
+        const long long p = s + half;                                 // position in the untrimmed overlap-add
+        long long t_lo = p - n_fft + 1 <= 0 ? 0 : (p - n_fft + hop) / hop;
+        long long t_hi = p / hop;
+        if (t_hi > u.T - 1) t_hi = u.T - 1;
+        float acc = 0.f, env = 0.f;
+        for (long long t = t_lo; t <= t_hi; ++t) {
+            const int k = (int)(p - t * hop);
+            acc += fr[t * n_fft + k];
+            env += win2[k];                                           // window_sumsquare: frames added in order
+        }
+        if (env > FLT_MIN) acc /= env;                                // np.finfo(float32).tiny
+        acc *= scale;
+        dst[(mode == 0 ? u.xp0 : u.out0) + j] = acc;
+    }
+}
+
+class GriffinLim {
+public:
+    MelFront* mf = nullptr;
+    float* invT = nullptr;        // [n_fft][ld_spec]: transpose of the windowed inverse basis, columns 2F .. ld_spec zero
+    float* win2 = nullptr;        // [n_fft] squared, centre-padded window
+    bool have_inverse = false;
+    // workspace, grown on demand (sizes in elements)
+    float *xp = nullptr, *R = nullptr, *frames = nullptr, *mag = nullptr, *ang = nullptr, *lmel = nullptr, *emel = nullptr, *out = nullptr;
+    int* rowmap = nullptr;
+    GlUtt* utts = nullptr;
+    size_t c_xp = 0, c_R = 0, c_frames = 0, c_mag = 0, c_ang = 0, c_lmel = 0, c_emel = 0, c_out = 0, c_rowmap = 0, c_utts = 0;
+    std::vector<int> h_rowmap, h_melmap;
+    std::vector<GlUtt> h_utts;
+
+    void set_error(const std::string& s) { mf->set_error(s); }   // (MF_CHECK)
+    int err(const std::string& s) { set_error(s); return -1; }
+    void destroy() {
+        for (float* p : {invT, win2, xp, R, frames, mag, ang, lmel, emel, out}) if (p) hipFree(p);
+        if (rowmap) hipFree(rowmap);
+        if (utts) hipFree(utts);
+        invT = win2 = xp = R = frames = mag = ang = lmel = emel = out = nullptr;
+        rowmap = nullptr; utts = nullptr;
+    }
+    template <class T>
+    int grow(T*& p, size_t& cap, size_t need, const char* what) {
+        if (need <= cap) return 0;
+        const size_t floor_ = (size_t)mf->cap_T * 2;                      // a first reservation sized from the handle's max_samples
+        size_t n = std::max(need + need / 4, floor_);
+        if (p) { hipStreamSynchronize(mf->stream); hipFree(p); p = nullptr; cap = 0; }
+        if (hipMalloc((void**)&p, n * sizeof(T)) != hipSuccess) { p = nullptr; return err(std::string("hipMalloc failed (Griffin-Lim workspace: ") + what + ")"); }
+        cap = n;
+        return 0;
+    }
+
+    // inverse_basis: [2F][n_fft] (stft.py:33-45: pinv(scale * fourier_basis).T, float32, x window); window_sq: [n_fft] (window_sumsquare)
+    int load(const float* inverse_basis, const float* window_sq) {
+        const int n_fft = mf->n_fft, F = mf->F, ld = mf->ld_spec;
+        if (!inverse_basis || !window_sq) return err("mtts_stft_load_inverse: NULL inverse basis or squared window");
+        if (!invT && hipMalloc((void**)&invT, (size_t)n_fft * ld * sizeof(float)) != hipSuccess) { invT = nullptr; return err("hipMalloc failed (inverse basis)"); }
+        if (!win2 && hipMalloc((void**)&win2, (size_t)n_fft * sizeof(float)) != hipSuccess) { win2 = nullptr; return err("hipMalloc failed (window)"); }
+        std::vector<float> t((size_t)n_fft * ld, 0.f);
+        for (int c = 0; c < 2 * F; ++c)
+            for (int k = 0; k < n_fft; ++k) t[(size_t)k * ld + c] = inverse_basis[(size_t)c * n_fft + k];
+        if (hipMemcpy(invT, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(win2, window_sq, (size_t)n_fft * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            return err("hipMemcpy failed (inverse basis)");
+        have_inverse = true;
+        return 0;
+    }
+
+    int check_gemm() {
+        if (mf->gx.error) { std::string e = std::string("GEMM launcher: ") + mf->gx.error; mf->gx.error = nullptr; return err(e); }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return err(std::string("kernel launch failed: ") + hipGetErrorString(e));
+        return 0;
+    }
+
+    // STFT.transform of one waveform: magnitude / phase [T][F]; returns T
+    int transform(const float* wav_host, int n, float* mag_host, float* phase_host) {
+        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F, ld = mf->ld_spec;
+        if (!mf->have_basis) return err("STFT forward basis not loaded");
+        if (!wav_host || !mag_host || !phase_host) return err("mtts_stft_transform: NULL argument");
+        if (n <= n_fft / 2) return err("waveform too short for the reflection padding (need n_samples > filter_length / 2)");
+        const int T = n / hop + 1;
+        if (grow(out, c_out, (size_t)n, "waveform") || grow(xp, c_xp, (size_t)n + n_fft + 64, "padded signal") ||
+            grow(R, c_R, (size_t)T * ld + 64, "spectrum") || grow(mag, c_mag, (size_t)T * F, "magnitude") || grow(ang, c_ang, (size_t)T * F, "phase"))
+            return -1;
+        hipStream_t st = mf->stream;
+        MF_CHECK(hipMemcpyAsync(out, wav_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+        MTTS_LAUNCH(gl_reflect_pad_kernel, dim3(512), dim3(256), st, (const float*)out, n, n_fft / 2, xp);
+        forward_gemm(T, nullptr);
+        MTTS_LAUNCH(gl_mag_phase_kernel, dim3(512), dim3(256), st, (const float*)R, ld, T, F, mag, ang);
+        if (check_gemm()) return -1;
+        MF_CHECK(hipMemcpyAsync(mag_host, mag, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
+        MF_CHECK(hipMemcpyAsync(phase_host, ang, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
+        MF_CHECK(hipStreamSynchronize(st));
+        return T;
+    }
+
+    // griffin_lim (audio_processing.py:66-80) of n_utts spectrograms: magnitude / angles [sum T][F] frame-major, waveforms packed
+    // (hop * (T_u - 1) samples each).  n_iters = 0 is STFT.inverse(magnitude, angles).  Returns the total number of samples.
+    long long griffin_lim(int n_utts, const int* n_frames, const float* mag_host, const float* ang_host, int n_iters, float* out_host) {
+        if (!mag_host) return err("mtts_stft_griffin_lim: NULL magnitude");
+        long long rows = 0;
+        if (prepare(n_utts, n_frames, ang_host, n_iters, out_host, rows)) return -1;
+        const int F = mf->F;
+        if (grow(mag, c_mag, (size_t)rows * F, "magnitude")) return -1;
+        MF_CHECK(hipMemcpyAsync(mag, mag_host, (size_t)rows * F * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+        return run(rows, mag, F, n_iters, out_host);
+    }
+
+    // inv_mel_spec (tools.py:18-37): log_mel [sum Tm][n_mel] frame-major; angles [sum (Tm - 1)][F]
+    long long inv_mel(int n_utts, const int* n_mel_frames, const float* log_mel, const float* ang_host, int n_iters, float* out_host) {
+        if (!mf->have_mel) return err("mel basis not loaded");
+        if (!log_mel || !n_mel_frames || n_utts < 1) return err("mtts_stft_inv_mel: bad arguments");
+        std::vector<int> T(n_utts);
+        for (int u = 0; u < n_utts; ++u) T[u] = n_mel_frames[u] - 1;            // spec_from_mel[:, :, :-1]
+        long long rows = 0;
+        if (prepare(n_utts, T.data(), ang_host, n_iters, out_host, rows)) return -1;
+        const int n_mel = mf->n_mel, ldm = (n_mel + 3) & ~3, ld_mag = mf->ld_mag;
+        const long long mrows = rows + n_utts;
+        h_melmap.resize((size_t)mrows);
+        for (int u = 0, r = 0, o = 0; u < n_utts; ++u) {
+            for (int t = 0; t <= T[u]; ++t) h_melmap[(size_t)r++] = t < T[u] ? o + t : -1;   // the last frame of every utterance is dropped
+            o += T[u];
+        }
+        if (grow(lmel, c_lmel, (size_t)mrows * n_mel, "log-mel") || grow(emel, c_emel, (size_t)mrows * ldm + 64, "mel") ||
+            grow(mag, c_mag, (size_t)rows * ld_mag, "magnitude") || grow(rowmap, c_rowmap, (size_t)std::max<long long>(mrows, (long long)h_rowmap.size()), "row map"))
+            return -1;
+        hipStream_t st = mf->stream;
+        MF_CHECK(hipMemcpyAsync(lmel, log_mel, (size_t)mrows * n_mel * sizeof(float), hipMemcpyHostToDevice, st));
+        MF_CHECK(hipMemcpyAsync(rowmap, h_melmap.data(), (size_t)mrows * sizeof(int), hipMemcpyHostToDevice, st));
+        MTTS_LAUNCH(gl_exp_rows_kernel, dim3(512), dim3(256), st, (const float*)lmel, (int)mrows, n_mel, emel, ldm);
+        {   // magnitude [sum T][F] = 1000 * exp(mel)[sum Tm][n_mel] * mel_basis[n_mel][F], the last frame of each utterance dropped
+            GemmArgs g;
+            g.A = emel; g.lda = ldm; g.B = mf->melb; g.ldb = ld_mag; g.C = mag; g.ldc = ld_mag;
+            g.M = (int)mrows; g.N = F_(); g.K = n_mel; g.alpha = 1000.f; g.c_rowmap = rowmap;
+            gemm_launch(mf->gx, GEMM_NN, g, (int)mrows, F_(), 1, st, 0, 2.0 * mrows * F_() * n_mel, 0);
+        }
+        if (check_gemm()) return -1;
+        return run(rows, mag, ld_mag, n_iters, out_host);   // (run re-uploads the forward row map over the mel one)
+    }
+
+private:
+    int F_() const { return mf->F; }
+    long long total_out = 0, total_rows = 0;   // output samples and forward-GEMM rows of the prepared call
+
+    // validation (before any launch), packing, workspace, upload of the angles
+    int prepare(int n_utts, const int* T, const float* ang_host, int n_iters, float* out_host, long long& rows) {
+        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F, ld = mf->ld_spec;
+        if (!have_inverse) return err("inverse basis not loaded (mtts_stft_load_inverse)");
+        if (!mf->have_basis) return err("STFT forward basis not loaded");
+        if (n_utts < 1 || !T || !ang_host || !out_host) return err("Griffin-Lim: bad arguments (n_utts < 1 or NULL pointer)");
+        if (n_iters < 0) return err("Griffin-Lim: n_iters < 0");
+        h_utts.resize(n_utts);
+        long long nfr = 0, xp_rows = 0, outs = 0;
+        const int rows_per_pad_extra = (n_fft + hop - 1) / hop - 1;   // straddling rows between two packed padded signals
+        for (int u = 0; u < n_utts; ++u) {
+            if (T[u] < 1 || (n_iters > 0 && (long long)hop * (T[u] - 1) <= n_fft / 2))
+                return err("spectrogram too short: the waveform of T frames has hop * (T - 1) samples and must exceed filter_length / 2 "
+                           "for the reflection padding of the next transform (inv_mel: T = mel frames - 1)");
+            h_utts[u] = GlUtt{T[u], (int)nfr, xp_rows * hop, outs};
+            nfr += T[u];
+            xp_rows += T[u] + rows_per_pad_extra;
+            outs += (long long)hop * (T[u] - 1);
+        }
+        if (nfr > (1LL << 30) / std::max(ld, n_fft)) return err("Griffin-Lim: too many frames in one call");
+        h_rowmap.assign((size_t)xp_rows, -1);
+        for (int u = 0; u < n_utts; ++u)
+            for (int t = 0; t < T[u]; ++t) h_rowmap[(size_t)(h_utts[u].xp0 / hop + t)] = h_utts[u].frame0 + t;
+        if (grow(xp, c_xp, (size_t)xp_rows * hop + n_fft + 64, "padded signals") || grow(R, c_R, (size_t)nfr * ld + 64, "spectrum") ||
+            grow(frames, c_frames, (size_t)nfr * n_fft + 64, "frames") || grow(ang, c_ang, (size_t)nfr * F, "angles") ||
+            grow(out, c_out, (size_t)outs + 64, "waveform") || grow(rowmap, c_rowmap, (size_t)xp_rows, "row map") ||
+            grow(utts, c_utts, (size_t)n_utts, "utterances"))
+            return -1;
+        hipStream_t st = mf->stream;
+        MF_CHECK(hipMemcpyAsync(ang, ang_host, (size_t)nfr * F * sizeof(float), hipMemcpyHostToDevice, st));
+        MF_CHECK(hipMemcpyAsync(utts, h_utts.data(), (size_t)n_utts * sizeof(GlUtt), hipMemcpyHostToDevice, st));
+        MF_CHECK(hipMemsetAsync(xp, 0, ((size_t)xp_rows * hop + n_fft + 64) * sizeof(float), st));   // (gaps read only by dropped rows)
+        rows = nfr;
+        total_rows = xp_rows;
+        total_out = outs;
+        return 0;
+    }
+
+    // spec rows (compact through `map`, or rows 0..M when map == nullptr) = overlapping frames of xp * forward_basis^T
+    void forward_gemm(long long M, const int* map) {
+        GemmArgs g;
+        g.A = xp; g.lda = mf->hop; g.B = mf->basis; g.ldb = mf->n_fft; g.C = R; g.ldc = mf->ld_spec;
+        g.M = (int)M; g.N = 2 * mf->F; g.K = mf->n_fft; g.c_rowmap = map;
+        gemm_launch(mf->gx, GEMM_NT, g, (int)M, 2 * mf->F, 1, mf->stream, 0, 2.0 * M * 2.0 * mf->F * mf->n_fft, 0);
+    }
+
+    long long run(long long rows, const float* M, int ldm, int n_iters, float* out_host) {
+        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F, ld = mf->ld_spec, n_utts = (int)h_utts.size();
+        hipStream_t st = mf->stream;
+        MF_CHECK(hipMemcpyAsync(rowmap, h_rowmap.data(), h_rowmap.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        long long max_len = 0;
+        for (const GlUtt& u : h_utts) max_len = std::max(max_len, (long long)hop * (u.T - 1) + n_fft);
+        const dim3 ola_grid((unsigned)std::min<long long>((max_len + 255) / 256, 4096), (unsigned)n_utts);
+        const float scale = (float)((double)n_fft / hop);
+        MTTS_LAUNCH(gl_phasor_init_kernel, dim3(1024), dim3(256), st, M, ldm, (const float*)ang, (int)rows, F, R, ld);
+        for (int it = 0;; ++it) {
+            {   // frames [rows][n_fft] = R [rows][2F] * inverse_basis [2F][n_fft]
+                GemmArgs g;
+                g.A = R; g.lda = ld; g.B = invT; g.ldb = ld; g.C = frames; g.ldc = n_fft;
+                g.M = (int)rows; g.N = n_fft; g.K = 2 * F;
+                gemm_launch(mf->gx, GEMM_NT, g, (int)rows, n_fft, 1, st, 0, 2.0 * rows * 2.0 * F * n_fft, 0);
+            }
+            const bool last = it == n_iters;
+            MTTS_LAUNCH(gl_overlap_add_kernel, ola_grid, dim3(256), st, (const float*)frames, (const GlUtt*)utts, (const float*)win2, n_fft, hop, scale,
+                        last ? out : xp, last ? 1 : 0);
+            if (last) break;
+            forward_gemm(total_rows, rowmap);
+            MTTS_LAUNCH(gl_phasor_kernel, dim3(1024), dim3(256), st, R, ld, M, ldm, (int)rows, F);
+        }
+        if (check_gemm()) return -1;
+        MF_CHECK(hipMemcpyAsync(out_host, out, (size_t)total_out * sizeof(float), hipMemcpyDeviceToHost, st));
+        MF_CHECK(hipStreamSynchronize(st));
+        return total_out;
+    }
+};
+
+}  // namespace mtts

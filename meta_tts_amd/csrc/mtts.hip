@@ -8,6 +8,7 @@
 #include "vocoder.h"
 #include "dvector.h"
 #include "melfront.h"
+#include "griffin.h"
 
 using namespace mtts;
 
@@ -42,6 +43,7 @@ struct mtts_dvector {
 };
 struct mtts_stft {
     MelFront m;
+    GriffinLim gl;
 };
 
 extern "C" {
@@ -678,6 +680,7 @@ int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_sampl
     if (!out) { g_create_error = "bad arguments"; return -1; }
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
     mtts_stft* h = new mtts_stft();
+    h->gl.mf = &h->m;
     if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; h->m.destroy(); delete h; return -1; }
     *out = h;
     return 0;
@@ -686,6 +689,7 @@ int mtts_stft_set_stream(mtts_stft* h, void* s) { if (!h) return -1; h->m.stream
 void mtts_stft_destroy(mtts_stft* h) {
     if (!h) return;
     hipDeviceSynchronize();
+    h->gl.destroy();
     h->m.destroy();
     delete h;
 }
@@ -693,6 +697,20 @@ const char* mtts_stft_last_error(mtts_stft* h) { return h ? h->m.last_error.c_st
 int mtts_stft_load(mtts_stft* h, const float* forward_basis, const float* mel_basis) { return h->m.load(forward_basis, mel_basis); }
 int mtts_stft_mel_spectrogram(mtts_stft* h, const float* wav, int n_samples, float* mel, float* energy) {
     return h->m.mel_spectrogram(wav, n_samples, mel, energy);
+}
+// ---- spectrogram -> waveform (griffin.h; reference audio/stft.py:52-119, audio/audio_processing.py:7-80, audio/tools.py:18-37) --------
+int mtts_stft_load_inverse(mtts_stft* h, const float* inverse_basis, const float* window_sq) { return h ? h->gl.load(inverse_basis, window_sq) : -1; }
+int mtts_stft_transform(mtts_stft* h, const float* wav, int n_samples, float* magnitude, float* phase) {
+    return h ? h->gl.transform(wav, n_samples, magnitude, phase) : -1;
+}
+int64_t mtts_stft_inverse(mtts_stft* h, int n_utts, const int* n_frames, const float* magnitude, const float* phase, float* out) {
+    return h ? h->gl.griffin_lim(n_utts, n_frames, magnitude, phase, 0, out) : -1;
+}
+int64_t mtts_stft_griffin_lim(mtts_stft* h, int n_utts, const int* n_frames, const float* magnitude, const float* angles, int n_iters, float* out) {
+    return h ? h->gl.griffin_lim(n_utts, n_frames, magnitude, angles, n_iters, out) : -1;
+}
+int64_t mtts_stft_inv_mel(mtts_stft* h, int n_utts, const int* n_mel_frames, const float* log_mel, const float* angles, int n_iters, float* out) {
+    return h ? h->gl.inv_mel(n_utts, n_mel_frames, log_mel, angles, n_iters, out) : -1;
 }
 
 }  // extern "C"
