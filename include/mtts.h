@@ -444,6 +444,34 @@ int64_t mtts_stft_inverse(mtts_stft* h, int n_utts, const int* n_frames, const f
 int64_t mtts_stft_griffin_lim(mtts_stft* h, int n_utts, const int* n_frames, const float* magnitude, const float* angles, int n_iters, float* out);
 int64_t mtts_stft_inv_mel(mtts_stft* h, int n_utts, const int* n_mel_frames, const float* log_mel, const float* angles, int n_iters, float* out);
 
+/* ---- waveform batches -> the values of the preprocessed feature tree (the reference's preprocessor/preprocessor.py) -------------
+ * The device steps of `Preprocessor.process_utterance` (:188-306) and `build_from_path` (:60-185) on the same handle.  All
+ * utterances of a call share every launch; host pointers go in and out; every function returns 0, or < 0 with the reason in
+ * mtts_stft_last_error, and every error below is reported before any launch.  dtype: 0 = float32, 1 = float64.  Synchronous.
+ * mel_batch: get_mel_from_wav (:227-229) of n_utts waveforms packed one after another in `wavs` (n_samples[u] each), each result
+ * truncated to keep_frames[u] frames (sum(duration); < 0 or keep_frames == NULL: all): T_u = min(n_samples[u] / hop_length + 1,
+ * keep_frames[u]); mel [sum T][n_mel] log-mel (frame-major, the layout the tree stores), energy [sum T].  Errors: n_samples[u] <=
+ * filter_length / 2, keep_frames[u] == 0.  An utterance's rows are bit-identical whatever else is in the call.
+ * phoneme_average: :231-261 for n_utts utterances: values packed [sum n_frames], durations packed [sum n_phones], out packed
+ * [sum n_phones] of the same dtype.  interpolate != 0 (pitch): interp1d over the zero (unvoiced) frames first, linear between the
+ * nearest voiced frames, the first / last voiced value outside them.  Then the reference's in-place loop values[i] =
+ * mean(values[pos : pos + d]) (0 where d == 0), pos = durations before i, first n_phones entries — including its aliasing when
+ * some pos < i (more zero durations than frames so far), where a later mean reads entries the loop has already overwritten.
+ * float64 is summed in float64, float32 in float32.  Errors: n_phones > n_frames (S > T), negative durations, interpolate with
+ * fewer than two voiced frames (the reference drops utterances with at most one).
+ * outlier_stats: remove_outlier (:348-356) for n_utts value sets packed in `values` (n_values[u] each, at most 4096): the 25th /
+ * 75th percentile by numpy's linear rule, keep[i] = (p25 - 1.5 IQR < v < p75 + 1.5 IQR) as packed bytes, and partials [n_utts][3] =
+ * (count, mean, sum of squared deviations) of the kept values in float64, the sums `StandardScaler.partial_fit` forms.
+ * merge_stats: partial_fit's update (:106-109; sklearn's incremental mean / variance) of state = (count, mean, M2) — zeros to
+ * start — with n_partials partials in the order given; deterministic.  mean = state[1], the population std = sqrt(state[2] / state[0]).
+ * normalize: :358-369 over n packed values: out [n] float64 = (values - mean) / std, minmax = (min, max) of out.  Error: std == 0. */
+int mtts_stft_mel_batch(mtts_stft* h, int n_utts, const int* n_samples, const int* keep_frames, const float* wavs, float* mel, float* energy);
+int mtts_stft_phoneme_average(mtts_stft* h, int n_utts, const int* n_frames, const int* n_phones, const int* durations, const void* values, int dtype,
+                              int interpolate, void* out);
+int mtts_stft_outlier_stats(mtts_stft* h, int n_utts, const int* n_values, const void* values, int dtype, unsigned char* keep, double* partials);
+int mtts_stft_merge_stats(mtts_stft* h, double* state, int n_partials, const double* partials);
+int mtts_stft_normalize(mtts_stft* h, int64_t n, const void* values, int dtype, double mean, double std, double* out, double* minmax);
+
 #ifdef __cplusplus
 }
 #endif

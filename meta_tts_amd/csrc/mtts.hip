@@ -9,6 +9,7 @@
 #include "dvector.h"
 #include "melfront.h"
 #include "griffin.h"
+#include "preprocess.h"
 
 using namespace mtts;
 
@@ -44,6 +45,7 @@ struct mtts_dvector {
 struct mtts_stft {
     MelFront m;
     GriffinLim gl;
+    Preprocess pp;
 };
 
 extern "C" {
@@ -681,6 +683,7 @@ int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_sampl
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
     mtts_stft* h = new mtts_stft();
     h->gl.mf = &h->m;
+    h->pp.mf = &h->m;
     if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; h->m.destroy(); delete h; return -1; }
     *out = h;
     return 0;
@@ -690,6 +693,7 @@ void mtts_stft_destroy(mtts_stft* h) {
     if (!h) return;
     hipDeviceSynchronize();
     h->gl.destroy();
+    h->pp.destroy();
     h->m.destroy();
     delete h;
 }
@@ -711,6 +715,24 @@ int64_t mtts_stft_griffin_lim(mtts_stft* h, int n_utts, const int* n_frames, con
 }
 int64_t mtts_stft_inv_mel(mtts_stft* h, int n_utts, const int* n_mel_frames, const float* log_mel, const float* angles, int n_iters, float* out) {
     return h ? h->gl.inv_mel(n_utts, n_mel_frames, log_mel, angles, n_iters, out) : -1;
+}
+
+// ---- waveform batches -> feature-tree values (preprocess.h; reference preprocessor/preprocessor.py:60-185,188-306,348-369) ------------
+int mtts_stft_mel_batch(mtts_stft* h, int n_utts, const int* n_samples, const int* keep_frames, const float* wavs, float* mel, float* energy) {
+    return h ? h->pp.mel_batch(n_utts, n_samples, keep_frames, wavs, mel, energy) : -1;
+}
+int mtts_stft_phoneme_average(mtts_stft* h, int n_utts, const int* n_frames, const int* n_phones, const int* durations, const void* values, int dtype,
+                              int interpolate, void* out) {
+    return h ? h->pp.phoneme_average(n_utts, n_frames, n_phones, durations, values, dtype, interpolate, out) : -1;
+}
+int mtts_stft_outlier_stats(mtts_stft* h, int n_utts, const int* n_values, const void* values, int dtype, unsigned char* keep, double* partials) {
+    return h ? h->pp.outlier_stats(n_utts, n_values, values, dtype, keep, partials) : -1;
+}
+int mtts_stft_merge_stats(mtts_stft* h, double* state, int n_partials, const double* partials) {
+    return h ? h->pp.merge_stats(state, n_partials, partials) : -1;
+}
+int mtts_stft_normalize(mtts_stft* h, int64_t n, const void* values, int dtype, double mean, double std, double* out, double* minmax) {
+    return h ? h->pp.normalize(n, values, dtype, mean, std, out, minmax) : -1;
 }
 
 }  // extern "C"
