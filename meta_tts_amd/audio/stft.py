@@ -3,8 +3,9 @@
 The bases are built on the host exactly as the reference builds its buffers — `np.fft.fft(np.eye(n))` split into real / imaginary
 rows and multiplied by the periodic Hann window (stft.py:27-46; scipy.signal.get_window, as there) — and the Slaney mel filter
 bank of `librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax)` (librosa is not part of this image: restated from its documented
-algorithm, htk=False, norm="slaney").  The device does the framing, both contractions, magnitude, log and energy; in the inverse
-direction (csrc/griffin.h) the inverse-basis contraction, the overlap-add and whole Griffin-Lim loops."""
+algorithm, htk=False, norm="slaney").  The device does the framing, both contractions, magnitude, log and energy (csrc/melfront.h,
+the front-end every audio stage shares); in the inverse direction (csrc/griffin.h) the inverse-basis contraction, the overlap-add
+and whole Griffin-Lim loops."""
 from __future__ import annotations
 
 import ctypes as C
@@ -49,16 +50,49 @@ def inverse_basis(filter_length: int, hop_length: int, win_length: int, window: 
     return _inverse_basis(int(filter_length), int(hop_length), int(win_length), window).copy()
 
 
+class _Handle:
+    """One `mtts_stft` device handle: create, error check, close.  An STFT, the TacotronSTFT it belongs to and a Preprocessor built on
+    that TacotronSTFT all hold the same one."""
+
+    def __init__(self, filter_length, hop_length, n_mel, max_samples, device, lib_path):
+        self.lib = _lib.load(lib_path)
+        h = C.c_void_p()
+        if self.lib.mtts_stft_create(filter_length, hop_length, n_mel, max_samples, device, C.byref(h)) != 0:
+            raise MttsError(self.lib.mtts_stft_last_error(None).decode())
+        self.h = h
+
+    def check(self, rc):
+        if rc < 0:
+            raise MttsError(self.lib.mtts_stft_last_error(self.h).decode())
+        return rc
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mtts_stft_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+
+class _OnHandle:
+    """`lib`, `h` and `_check` of the `_Handle` in `self._dev`."""
+    lib = property(lambda self: self._dev.lib)
+    h = property(lambda self: self._dev.h)
+
+    def _check(self, rc):
+        return self._dev.check(rc)
+
+
 def _np32(x):
     return np.ascontiguousarray(np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, np.float32))
 
 
-class STFT:
+class STFT(_OnHandle):
     """audio/stft.py:15-125 on the device.  `transform(x)` takes (B, n) waveforms and returns (magnitude, phase), each (B, F, T) float32;
     `inverse(magnitude, phase)` takes (B, F, T) and returns (B, 1, hop * (T - 1)); `forward(x)` is inverse(transform(x)).  Inputs may be
     numpy arrays or torch tensors; outputs are numpy.  Only string windows (scipy.signal.get_window) are supported.
 
-    A TacotronSTFT's `stft_fn` shares that TacotronSTFT's device handle (pass `_handle`); a stand-alone STFT owns one."""
+    A TacotronSTFT's `stft_fn` shares that TacotronSTFT's device handle (its `_Handle`, passed as `_handle`); a stand-alone STFT owns one."""
 
     def __init__(self, filter_length, hop_length, win_length, window="hann", *, max_samples=22050 * 40, device=0, lib_path=None,
                  _handle=None):
@@ -68,14 +102,9 @@ class STFT:
         self.n_bins = filter_length // 2 + 1
         self.forward_basis = forward_basis(filter_length, win_length, window)
         self._inverse_loaded = False
-        if _handle is not None:
-            self.lib, self.h, self._owner = _handle[0], _handle[1], False
-        else:
-            self.lib = _lib.load(lib_path)
-            h = C.c_void_p()
-            if self.lib.mtts_stft_create(filter_length, hop_length, 1, max_samples, device, C.byref(h)) != 0:
-                raise MttsError(self.lib.mtts_stft_last_error(None).decode())
-            self.h, self._owner = h, True
+        self._owner = _handle is None
+        self._dev = _handle if _handle is not None else _Handle(filter_length, hop_length, 1, max_samples, device, lib_path)
+        if self._owner:
             self._check(self.lib.mtts_stft_load(self.h, self.forward_basis.ctypes.data_as(C.c_void_p), None))
 
     @property
@@ -92,17 +121,9 @@ class STFT:
         self._check(self.lib.mtts_stft_load_inverse(self.h, ib.ctypes.data_as(C.c_void_p), wsq.ctypes.data_as(C.c_void_p)))
         self._inverse_loaded = True
 
-    def _check(self, rc):
-        if rc < 0:
-            raise MttsError(self.lib.mtts_stft_last_error(self.h).decode())
-        return rc
-
     def close(self):
-        if getattr(self, "_owner", False) and getattr(self, "h", None):
-            self.lib.mtts_stft_destroy(self.h)
-        self.h = None
-
-    __del__ = close
+        if self._owner:
+            self._dev.close()
 
     def _frames_of(self, n_frames, what, transforms=True):
         n = np.asarray(n_frames, np.int32).reshape(-1)
@@ -201,42 +222,27 @@ def mel_filterbank(sr: int, n_fft: int, n_mels: int, fmin: float = 0.0, fmax=Non
     return w.astype(np.float32)
 
 
-class TacotronSTFT:
+class TacotronSTFT(_OnHandle):
     """audio/stft.py:128: same constructor arguments; `mel_spectrogram(y)` takes (B, T) waveforms in [-1, 1] and returns
     (mel (B, n_mel, T'), energy (B, T')) float32 arrays."""
 
     def __init__(self, filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin, mel_fmax, *, max_samples=22050 * 40,
                  device=0, lib_path=None):
-        self.lib = _lib.load(lib_path)
         self.filter_length, self.hop_length, self.win_length = filter_length, hop_length, win_length
         self.n_mel_channels, self.sampling_rate = n_mel_channels, sampling_rate
         self.forward_basis = forward_basis(filter_length, win_length)
         self.mel_basis = mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin or 0.0, mel_fmax)
-        h = C.c_void_p()
-        if self.lib.mtts_stft_create(filter_length, hop_length, n_mel_channels, max_samples, device, C.byref(h)) != 0:
-            raise MttsError(self.lib.mtts_stft_last_error(None).decode())
-        self.h = h
+        self._dev = _Handle(filter_length, hop_length, n_mel_channels, max_samples, device, lib_path)
         self._check(self.lib.mtts_stft_load(self.h, self.forward_basis.ctypes.data_as(C.c_void_p), self.mel_basis.ctypes.data_as(C.c_void_p)))
-        self.stft_fn = STFT(filter_length, hop_length, win_length, _handle=(self.lib, self.h))   # stft.py:140 (shares this handle)
+        self.stft_fn = STFT(filter_length, hop_length, win_length, _handle=self._dev)   # stft.py:140 (shares this handle)
         self._stft_fn = self.stft_fn   # the name audio/tools.py:inv_mel_spec reads (the reference's TacotronSTFT lacks it)
-
-    def _check(self, rc):
-        if rc < 0:
-            raise MttsError(self.lib.mtts_stft_last_error(self.h).decode())
-        return rc
 
     def set_stream(self, stream_ptr: int):
         if self.lib.mtts_stft_set_stream(self.h, C.c_void_p(stream_ptr)) != 0:
             raise RuntimeError("mtts_stft_set_stream failed")
 
     def close(self):
-        if getattr(self, "h", None):
-            if getattr(self, "stft_fn", None) is not None:
-                self.stft_fn.h = None
-            self.lib.mtts_stft_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._dev.close()
 
     def spectral_normalize(self, magnitudes):
         from .audio_processing import dynamic_range_compression

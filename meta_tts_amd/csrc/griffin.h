@@ -13,11 +13,12 @@
 //   * overlap-add (gl_overlap_add_kernel): a deterministic gather of the <= ceil(n_fft / hop) frames that cover a sample, the envelope
 //     derived from the squared window in the same loop, and the next transform's reflect-padded input written directly (the trimmed
 //     waveform on the last pass);
-//   * forward GEMM: melfront.h's implicit GEMM over overlapping rows (lda = hop) of the packed padded signals against the forward
-//     basis.  Every padded signal starts at a multiple of hop, so one NT launch covers all utterances; the rows that straddle two
-//     utterances are dropped through GemmArgs::c_rowmap and the spectrum lands compact in R's buffer;
+//   * forward GEMM: melfront.h's MelFront::forward_stft over the packed padded signals (MelFront's packing: one NT launch covers all
+//     utterances, the straddling rows are dropped through the row map and the spectrum lands compact in R's buffer);
 //   * phasor (gl_phasor_kernel, in place): R = M * (re, im) / |z| = (M cos atan2, M sin atan2) without the transcendentals.
-// One Griffin-Lim iteration is these four launches on the handle's stream.
+// One Griffin-Lim iteration is these four launches on the handle's stream.  The packed waveforms, the padded signals, R, the magnitude,
+// the log-mel, the row map and the utterance table live in MelFront's workspace; this file owns the frames, the angles, exp(mel), the
+// mel GEMM's row map, the inverse basis and the squared window.
 #pragma once
 #include <cfloat>
 #include <string>
@@ -26,24 +27,6 @@
 #include "melfront.h"
 
 namespace mtts {
-
-struct GlUtt {
-    int T;            // frames of the spectrogram (the waveform has hop * (T - 1) samples)
-    int frame0;       // first row of this utterance in R / frames
-    long long xp0;    // first sample of its reflect-padded signal (a multiple of hop)
-    long long out0;   // first sample of its waveform in the packed output
-};
-
-// xp[j] = x[reflect(j - pad)] for j < n + 2 * pad  (STFT.transform's F.pad(mode="reflect"); no clip: that belongs to get_mel_from_wav)
-__global__ void gl_reflect_pad_kernel(const float* x, int n, int pad, float* xp) {
-    const long long total = (long long)n + 2 * pad;
-    for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < total; j += (long long)gridDim.x * blockDim.x) {
-        long long s = j - pad;
-        if (s < 0) s = -s;
-        else if (s >= n) s = 2LL * (n - 1) - s;
-        xp[j] = x[s];
-    }
-}
 
 // spec [T][ld] = [re | im] -> magnitude [T][F] = sqrt(re^2 + im^2), phase [T][F] = atan2(im, re)   (stft.py:71-75)
 __global__ void gl_mag_phase_kernel(const float* spec, int ld, int T, int F, float* mag, float* phase) {
@@ -112,10 +95,10 @@ __global__ void gl_phasor_kernel(float* R, int ldr, const float* mag, int ldm, i
 
 // Overlap-add of the inverse transform (conv_transpose1d with stride hop), envelope division, hop-ratio scale and trim, per sample a
 // gather of the frames that cover it (no atomics).  blockIdx.y = utterance.  mode 0: write the next transform's reflect-padded input
-// at xp0 (n + n_fft samples); mode 1: write the trimmed waveform at out0 (n = hop * (T - 1) samples).
-__global__ void gl_overlap_add_kernel(const float* frames, const GlUtt* utts, const float* win2, int n_fft, int hop, float scale, float* dst,
+// at xp0 (n + n_fft samples); mode 1: write the trimmed waveform at wav0 (n = hop * (T - 1) samples).
+__global__ void gl_overlap_add_kernel(const float* frames, const StftUtt* utts, const float* win2, int n_fft, int hop, float scale, float* dst,
                                       int mode) {
-    const GlUtt u = utts[blockIdx.y];
+    const StftUtt u = utts[blockIdx.y];
     const long long n = (long long)hop * (u.T - 1), half = n_fft / 2;
     const long long total = mode == 0 ? n + n_fft : n;
     const float* fr = frames + (long long)u.frame0 * n_fft;
@@ -138,7 +121,7 @@ __global__ void gl_overlap_add_kernel(const float* frames, const GlUtt* utts, co
         }
         if (env > FLT_MIN) acc /= env;                                // np.finfo(float32).tiny
         acc *= scale;
-        dst[(mode == 0 ? u.xp0 : u.out0) + j] = acc;
+        dst[(mode == 0 ? u.xp0 : u.wav0) + j] = acc;
     }
 }
 
@@ -148,32 +131,16 @@ public:
     float* invT = nullptr;        // [n_fft][ld_spec]: transpose of the windowed inverse basis, columns 2F .. ld_spec zero
     float* win2 = nullptr;        // [n_fft] squared, centre-padded window
     bool have_inverse = false;
-    // workspace, grown on demand (sizes in elements)
-    float *xp = nullptr, *R = nullptr, *frames = nullptr, *mag = nullptr, *ang = nullptr, *lmel = nullptr, *emel = nullptr, *out = nullptr;
-    int* rowmap = nullptr;
-    GlUtt* utts = nullptr;
-    size_t c_xp = 0, c_R = 0, c_frames = 0, c_mag = 0, c_ang = 0, c_lmel = 0, c_emel = 0, c_out = 0, c_rowmap = 0, c_utts = 0;
-    std::vector<int> h_rowmap, h_melmap;
-    std::vector<GlUtt> h_utts;
+    DevBuf<float> frames, ang, emel;   // inverse GEMM's output [sum T][n_fft]; angles / phase [sum T][F]; exp(log-mel) [sum Tm][ldm]
+    DevBuf<int> melmap;                // inv_mel's row map: the last mel frame of every utterance dropped
+    std::vector<int> h_melmap;
 
-    void set_error(const std::string& s) { mf->set_error(s); }   // (MF_CHECK)
-    int err(const std::string& s) { set_error(s); return -1; }
+    int err(const std::string& s) { return mf->err(s); }   // (MF_CHECK)
     void destroy() {
-        for (float* p : {invT, win2, xp, R, frames, mag, ang, lmel, emel, out}) if (p) hipFree(p);
-        if (rowmap) hipFree(rowmap);
-        if (utts) hipFree(utts);
-        invT = win2 = xp = R = frames = mag = ang = lmel = emel = out = nullptr;
-        rowmap = nullptr; utts = nullptr;
-    }
-    template <class T>
-    int grow(T*& p, size_t& cap, size_t need, const char* what) {
-        if (need <= cap) return 0;
-        const size_t floor_ = (size_t)mf->cap_T * 2;                      // a first reservation sized from the handle's max_samples
-        size_t n = std::max(need + need / 4, floor_);
-        if (p) { hipStreamSynchronize(mf->stream); hipFree(p); p = nullptr; cap = 0; }
-        if (hipMalloc((void**)&p, n * sizeof(T)) != hipSuccess) { p = nullptr; return err(std::string("hipMalloc failed (Griffin-Lim workspace: ") + what + ")"); }
-        cap = n;
-        return 0;
+        for (float* p : {invT, win2}) if (p) hipFree(p);
+        invT = win2 = nullptr;
+        for (DevBuf<float>* b : {&frames, &ang, &emel}) b->release();
+        melmap.release();
     }
 
     // inverse_basis: [2F][n_fft] (stft.py:33-45: pinv(scale * fourier_basis).T, float32, x window); window_sq: [n_fft] (window_sumsquare)
@@ -192,30 +159,21 @@ public:
         return 0;
     }
 
-    int check_gemm() {
-        if (mf->gx.error) { std::string e = std::string("GEMM launcher: ") + mf->gx.error; mf->gx.error = nullptr; return err(e); }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return err(std::string("kernel launch failed: ") + hipGetErrorString(e));
-        return 0;
-    }
-
-    // STFT.transform of one waveform: magnitude / phase [T][F]; returns T
+    // STFT.transform of one waveform (no clip, no max_samples bound): magnitude / phase [T][F]; returns T
     int transform(const float* wav_host, int n, float* mag_host, float* phase_host) {
-        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F, ld = mf->ld_spec;
+        const int F = mf->F;
         if (!mf->have_basis) return err("STFT forward basis not loaded");
         if (!wav_host || !mag_host || !phase_host) return err("mtts_stft_transform: NULL argument");
-        if (n <= n_fft / 2) return err("waveform too short for the reflection padding (need n_samples > filter_length / 2)");
-        const int T = n / hop + 1;
-        if (grow(out, c_out, (size_t)n, "waveform") || grow(xp, c_xp, (size_t)n + n_fft + 64, "padded signal") ||
-            grow(R, c_R, (size_t)T * ld + 64, "spectrum") || grow(mag, c_mag, (size_t)T * F, "magnitude") || grow(ang, c_ang, (size_t)T * F, "phase"))
-            return -1;
+        if (n <= mf->n_fft / 2) return err("waveform too short for the reflection padding (need n_samples > filter_length / 2)");
+        const int T = mf->frames_of(n);
+        mf->pack_begin();
+        mf->pack_add(n, T);
+        if (mf->stage("mtts_stft_transform", false) || mf->grow(ang, (size_t)T * F, "phase") || mf->pad_waveforms(wav_host, false, false)) return -1;
         hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(out, wav_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-        MTTS_LAUNCH(gl_reflect_pad_kernel, dim3(512), dim3(256), st, (const float*)out, n, n_fft / 2, xp);
-        forward_gemm(T, nullptr);
-        MTTS_LAUNCH(gl_mag_phase_kernel, dim3(512), dim3(256), st, (const float*)R, ld, T, F, mag, ang);
-        if (check_gemm()) return -1;
-        MF_CHECK(hipMemcpyAsync(mag_host, mag, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
+        mf->forward_stft(T, nullptr, 0);
+        MTTS_LAUNCH(gl_mag_phase_kernel, dim3(512), dim3(256), st, (const float*)mf->spec, mf->ld_spec, T, F, mf->mag.p, ang.p);
+        if (mf->check_launch()) return -1;
+        MF_CHECK(hipMemcpyAsync(mag_host, mf->mag, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
         MF_CHECK(hipMemcpyAsync(phase_host, ang, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
         MF_CHECK(hipStreamSynchronize(st));
         return T;
@@ -225,12 +183,10 @@ public:
     // (hop * (T_u - 1) samples each).  n_iters = 0 is STFT.inverse(magnitude, angles).  Returns the total number of samples.
     long long griffin_lim(int n_utts, const int* n_frames, const float* mag_host, const float* ang_host, int n_iters, float* out_host) {
         if (!mag_host) return err("mtts_stft_griffin_lim: NULL magnitude");
-        long long rows = 0;
-        if (prepare(n_utts, n_frames, ang_host, n_iters, out_host, rows)) return -1;
+        if (prepare(n_utts, n_frames, ang_host, n_iters, out_host)) return -1;
         const int F = mf->F;
-        if (grow(mag, c_mag, (size_t)rows * F, "magnitude")) return -1;
-        MF_CHECK(hipMemcpyAsync(mag, mag_host, (size_t)rows * F * sizeof(float), hipMemcpyHostToDevice, mf->stream));
-        return run(rows, mag, F, n_iters, out_host);
+        MF_CHECK(hipMemcpyAsync(mf->mag, mag_host, (size_t)mf->n_frames * F * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+        return run(mf->mag, F, n_iters, out_host);
     }
 
     // inv_mel_spec (tools.py:18-37): log_mel [sum Tm][n_mel] frame-major; angles [sum (Tm - 1)][F]
@@ -239,89 +195,58 @@ public:
         if (!log_mel || !n_mel_frames || n_utts < 1) return err("mtts_stft_inv_mel: bad arguments");
         std::vector<int> T(n_utts);
         for (int u = 0; u < n_utts; ++u) T[u] = n_mel_frames[u] - 1;            // spec_from_mel[:, :, :-1]
-        long long rows = 0;
-        if (prepare(n_utts, T.data(), ang_host, n_iters, out_host, rows)) return -1;
-        const int n_mel = mf->n_mel, ldm = (n_mel + 3) & ~3, ld_mag = mf->ld_mag;
-        const long long mrows = rows + n_utts;
+        if (prepare(n_utts, T.data(), ang_host, n_iters, out_host)) return -1;
+        const int F = mf->F, n_mel = mf->n_mel, ldm = (n_mel + 3) & ~3, ld_mag = mf->ld_mag;
+        const long long mrows = mf->n_frames + n_utts;
         h_melmap.resize((size_t)mrows);
         for (int u = 0, r = 0, o = 0; u < n_utts; ++u) {
             for (int t = 0; t <= T[u]; ++t) h_melmap[(size_t)r++] = t < T[u] ? o + t : -1;   // the last frame of every utterance is dropped
             o += T[u];
         }
-        if (grow(lmel, c_lmel, (size_t)mrows * n_mel, "log-mel") || grow(emel, c_emel, (size_t)mrows * ldm + 64, "mel") ||
-            grow(mag, c_mag, (size_t)rows * ld_mag, "magnitude") || grow(rowmap, c_rowmap, (size_t)std::max<long long>(mrows, (long long)h_rowmap.size()), "row map"))
+        if (mf->grow(mf->mel, (size_t)mrows * n_mel, "log-mel") || mf->grow(emel, (size_t)mrows * ldm + 64, "exp(mel)") || mf->grow(melmap, (size_t)mrows, "mel row map"))
             return -1;
         hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(lmel, log_mel, (size_t)mrows * n_mel * sizeof(float), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(rowmap, h_melmap.data(), (size_t)mrows * sizeof(int), hipMemcpyHostToDevice, st));
-        MTTS_LAUNCH(gl_exp_rows_kernel, dim3(512), dim3(256), st, (const float*)lmel, (int)mrows, n_mel, emel, ldm);
+        MF_CHECK(hipMemcpyAsync(mf->mel, log_mel, (size_t)mrows * n_mel * sizeof(float), hipMemcpyHostToDevice, st));
+        MF_CHECK(hipMemcpyAsync(melmap, h_melmap.data(), (size_t)mrows * sizeof(int), hipMemcpyHostToDevice, st));
+        MTTS_LAUNCH(gl_exp_rows_kernel, dim3(512), dim3(256), st, (const float*)mf->mel, (int)mrows, n_mel, emel.p, ldm);
         {   // magnitude [sum T][F] = 1000 * exp(mel)[sum Tm][n_mel] * mel_basis[n_mel][F], the last frame of each utterance dropped
             GemmArgs g;
-            g.A = emel; g.lda = ldm; g.B = mf->melb; g.ldb = ld_mag; g.C = mag; g.ldc = ld_mag;
-            g.M = (int)mrows; g.N = F_(); g.K = n_mel; g.alpha = 1000.f; g.c_rowmap = rowmap;
-            gemm_launch(mf->gx, GEMM_NN, g, (int)mrows, F_(), 1, st, 0, 2.0 * mrows * F_() * n_mel, 0);
+            g.A = emel; g.lda = ldm; g.B = mf->melb; g.ldb = ld_mag; g.C = mf->mag; g.ldc = ld_mag;
+            g.M = (int)mrows; g.N = F; g.K = n_mel; g.alpha = 1000.f; g.c_rowmap = melmap;
+            gemm_launch(mf->gx, GEMM_NN, g, (int)mrows, F, 1, st, 0, 2.0 * mrows * F * n_mel, 0);
         }
-        if (check_gemm()) return -1;
-        return run(rows, mag, ld_mag, n_iters, out_host);   // (run re-uploads the forward row map over the mel one)
+        if (mf->check_launch()) return -1;
+        return run(mf->mag, ld_mag, n_iters, out_host);
     }
 
 private:
-    int F_() const { return mf->F; }
-    long long total_out = 0, total_rows = 0;   // output samples and forward-GEMM rows of the prepared call
-
-    // validation (before any launch), packing, workspace, upload of the angles
-    int prepare(int n_utts, const int* T, const float* ang_host, int n_iters, float* out_host, long long& rows) {
-        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F, ld = mf->ld_spec;
+    // validation (before any launch), MelFront's packing and workspace, upload of the angles
+    int prepare(int n_utts, const int* T, const float* ang_host, int n_iters, float* out_host) {
+        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F;
         if (!have_inverse) return err("inverse basis not loaded (mtts_stft_load_inverse)");
         if (!mf->have_basis) return err("STFT forward basis not loaded");
         if (n_utts < 1 || !T || !ang_host || !out_host) return err("Griffin-Lim: bad arguments (n_utts < 1 or NULL pointer)");
         if (n_iters < 0) return err("Griffin-Lim: n_iters < 0");
-        h_utts.resize(n_utts);
-        long long nfr = 0, xp_rows = 0, outs = 0;
-        const int rows_per_pad_extra = (n_fft + hop - 1) / hop - 1;   // straddling rows between two packed padded signals
+        mf->pack_begin();
         for (int u = 0; u < n_utts; ++u) {
             if (T[u] < 1 || (n_iters > 0 && (long long)hop * (T[u] - 1) <= n_fft / 2))
                 return err("spectrogram too short: the waveform of T frames has hop * (T - 1) samples and must exceed filter_length / 2 "
                            "for the reflection padding of the next transform (inv_mel: T = mel frames - 1)");
-            h_utts[u] = GlUtt{T[u], (int)nfr, xp_rows * hop, outs};
-            nfr += T[u];
-            xp_rows += T[u] + rows_per_pad_extra;
-            outs += (long long)hop * (T[u] - 1);
+            mf->pack_add((long long)hop * (T[u] - 1), T[u]);
         }
-        if (nfr > (1LL << 30) / std::max(ld, n_fft)) return err("Griffin-Lim: too many frames in one call");
-        h_rowmap.assign((size_t)xp_rows, -1);
-        for (int u = 0; u < n_utts; ++u)
-            for (int t = 0; t < T[u]; ++t) h_rowmap[(size_t)(h_utts[u].xp0 / hop + t)] = h_utts[u].frame0 + t;
-        if (grow(xp, c_xp, (size_t)xp_rows * hop + n_fft + 64, "padded signals") || grow(R, c_R, (size_t)nfr * ld + 64, "spectrum") ||
-            grow(frames, c_frames, (size_t)nfr * n_fft + 64, "frames") || grow(ang, c_ang, (size_t)nfr * F, "angles") ||
-            grow(out, c_out, (size_t)outs + 64, "waveform") || grow(rowmap, c_rowmap, (size_t)xp_rows, "row map") ||
-            grow(utts, c_utts, (size_t)n_utts, "utterances"))
-            return -1;
-        hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(ang, ang_host, (size_t)nfr * F * sizeof(float), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(utts, h_utts.data(), (size_t)n_utts * sizeof(GlUtt), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemsetAsync(xp, 0, ((size_t)xp_rows * hop + n_fft + 64) * sizeof(float), st));   // (gaps read only by dropped rows)
-        rows = nfr;
-        total_rows = xp_rows;
-        total_out = outs;
+        const size_t rows = (size_t)mf->n_frames;
+        if (mf->stage("Griffin-Lim", true) || mf->grow(frames, rows * n_fft + 64, "frames") || mf->grow(ang, rows * F, "angles")) return -1;
+        MF_CHECK(hipMemcpyAsync(ang, ang_host, rows * F * sizeof(float), hipMemcpyHostToDevice, mf->stream));
         return 0;
     }
 
-    // spec rows (compact through `map`, or rows 0..M when map == nullptr) = overlapping frames of xp * forward_basis^T
-    void forward_gemm(long long M, const int* map) {
-        GemmArgs g;
-        g.A = xp; g.lda = mf->hop; g.B = mf->basis; g.ldb = mf->n_fft; g.C = R; g.ldc = mf->ld_spec;
-        g.M = (int)M; g.N = 2 * mf->F; g.K = mf->n_fft; g.c_rowmap = map;
-        gemm_launch(mf->gx, GEMM_NT, g, (int)M, 2 * mf->F, 1, mf->stream, 0, 2.0 * M * 2.0 * mf->F * mf->n_fft, 0);
-    }
-
-    long long run(long long rows, const float* M, int ldm, int n_iters, float* out_host) {
-        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F, ld = mf->ld_spec, n_utts = (int)h_utts.size();
+    // the prepared call: M [sum T][ldm] magnitudes on the device -> out_host, the packed waveforms
+    long long run(const float* M, int ldm, int n_iters, float* out_host) {
+        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F, ld = mf->ld_spec, n_utts = (int)mf->h_utts.size();
+        const long long rows = mf->n_frames;
+        float* R = mf->spec;
         hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(rowmap, h_rowmap.data(), h_rowmap.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        long long max_len = 0;
-        for (const GlUtt& u : h_utts) max_len = std::max(max_len, (long long)hop * (u.T - 1) + n_fft);
-        const dim3 ola_grid((unsigned)std::min<long long>((max_len + 255) / 256, 4096), (unsigned)n_utts);
+        const dim3 ola_grid((unsigned)std::min<long long>((mf->max_span + 255) / 256, 4096), (unsigned)n_utts);
         const float scale = (float)((double)n_fft / hop);
         MTTS_LAUNCH(gl_phasor_init_kernel, dim3(1024), dim3(256), st, M, ldm, (const float*)ang, (int)rows, F, R, ld);
         for (int it = 0;; ++it) {
@@ -332,16 +257,16 @@ private:
                 gemm_launch(mf->gx, GEMM_NT, g, (int)rows, n_fft, 1, st, 0, 2.0 * rows * 2.0 * F * n_fft, 0);
             }
             const bool last = it == n_iters;
-            MTTS_LAUNCH(gl_overlap_add_kernel, ola_grid, dim3(256), st, (const float*)frames, (const GlUtt*)utts, (const float*)win2, n_fft, hop, scale,
-                        last ? out : xp, last ? 1 : 0);
+            MTTS_LAUNCH(gl_overlap_add_kernel, ola_grid, dim3(256), st, (const float*)frames, (const StftUtt*)mf->utts, (const float*)win2, n_fft, hop, scale,
+                        last ? mf->wav.p : mf->xp.p, last ? 1 : 0);
             if (last) break;
-            forward_gemm(total_rows, rowmap);
+            mf->forward_stft(mf->xp_rows, mf->rowmap, 0);
             MTTS_LAUNCH(gl_phasor_kernel, dim3(1024), dim3(256), st, R, ld, M, ldm, (int)rows, F);
         }
-        if (check_gemm()) return -1;
-        MF_CHECK(hipMemcpyAsync(out_host, out, (size_t)total_out * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (mf->check_launch()) return -1;
+        MF_CHECK(hipMemcpyAsync(out_host, mf->wav, (size_t)mf->n_samples * sizeof(float), hipMemcpyDeviceToHost, st));
         MF_CHECK(hipStreamSynchronize(st));
-        return total_out;
+        return mf->n_samples;
     }
 };
 

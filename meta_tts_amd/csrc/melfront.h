@@ -1,4 +1,4 @@
-// Waveform -> log-mel spectrogram + frame energy on the device: the feature front-end of the preprocessing stage.
+// The STFT front-end every audio stage of an mtts_stft handle shares, and waveform -> log-mel spectrogram + frame energy on top of it.
 //
 // Reference: audio/stft.py:15-77 (STFT.transform: reflect padding by n_fft/2, a strided Conv1d against the windowed real / imaginary
 // Fourier basis, magnitude) and :128-178 (TacotronSTFT.mel_spectrogram: mel_basis @ magnitude, log(clamp(., 1e-5)), energy = L2 norm
@@ -8,6 +8,16 @@
 // span x[t*hop .. t*hop + n_fft), i.e. an A operand with lda = hop < K = n_fft, no framing copy — against the [2*(n_fft/2+1)][n_fft]
 // basis on the fp32 matrix cores (gemm.h); magnitude and energy are one wavefront-per-frame pass; the mel projection is a second
 // GEMM whose epilogue-side log/clamp runs as a small row kernel.  Output rows are [frame][n_mel] (the engine's mel layout).
+//
+// What is shared (MelFront; griffin.h and preprocess.h build on it and keep only the buffers that are theirs):
+//   * packing (pack_begin / pack_add / stage): the utterances of a call are described by StftUtt; every reflect-padded signal starts
+//     at a multiple of hop, so ONE forward GEMM covers all of them, and the rows that straddle two signals are dropped through
+//     GemmArgs::c_rowmap (the spectrum lands compact, [sum T] rows).  A single-utterance entry stages without the map;
+//   * stft_reflect_pad_kernel (clip on or off), forward_stft (the overlapping-row GEMM), mel_from_spectrum (magnitude + energy, mel
+//     GEMM, log-clamp, download), check_launch, and the grow-on-demand workspace (DevBuf): one set of wav / padded signal / spectrum /
+//     magnitude / mel / energy buffers per handle, which every entry point may use because each is synchronous on the handle's stream.
+// The workspace is allocated by the first call that needs it, not at create: max_samples only bounds mel_spectrogram's input, and a
+// create with an absurd max_samples succeeds where it used to fail in hipMalloc (the first call that large fails instead).
 #pragma once
 #include <string>
 #include <vector>
@@ -17,16 +27,28 @@
 
 namespace mtts {
 
-// xp[j] = clip(x[reflect(j - pad)], -1, 1) for j < n + 2 * pad   (F.pad(..., mode="reflect") of stft.py:60-65 after tools.py:9)
-__global__ void wav_reflect_pad_kernel(const float* x, int n, int pad, float* xp) {
-    const long long total = (long long)n + 2 * pad;
+struct StftUtt {
+    int n;            // samples of the waveform (Griffin-Lim: hop * (T - 1))
+    int T;            // frames kept (<= n / hop + 1)
+    int frame0;       // first row of this utterance in the compact spectrum / frames
+    int pad_;
+    long long wav0;   // first sample of its waveform in the packed waveforms
+    long long xp0;    // first sample of its reflect-padded signal (a multiple of hop)
+};
+
+// xp[xp0 + j] = wav[wav0 + reflect(j - n_fft / 2)], clipped to [-1, 1] when `clip` (tools.py:9; STFT.transform itself does not clip),
+// for the hop * (T - 1) + n_fft samples the kept frames read (F.pad(..., mode="reflect") of stft.py:60-65).  blockIdx.y = utterance
+// of the table `utts`; utts == nullptr: the one utterance passed by value.
+__global__ void stft_reflect_pad_kernel(const float* wav, const StftUtt* utts, StftUtt one, int n_fft, int hop, int clip, float* xp) {
+    const StftUtt u = utts ? utts[blockIdx.y] : one;
+    const long long total = (long long)hop * (u.T - 1) + n_fft, pad = n_fft / 2;
     for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < total; j += (long long)gridDim.x * blockDim.x) {
         long long s = j - pad;
         if (s < 0) s = -s;
-        else if (s >= n) s = 2LL * (n - 1) - s;
-        float v = x[s];
-        v = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
-        xp[j] = v;
+        else if (s >= u.n) s = 2LL * (u.n - 1) - s;
+        float v = wav[u.wav0 + s];
+        if (clip) v = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
+        xp[u.xp0 + j] = v;
     }
 }
 
@@ -59,44 +81,56 @@ __global__ void log_clamp_kernel(float* x, long long n, float clip) {
     }
 }
 
+// A device buffer that grows on demand (MelFront::grow); cap in elements.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    operator T*() const { return p; }
+    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+};
+
+#define MF_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return err(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
 class MelFront {
 public:
-    int n_fft = 1024, hop = 256, n_mel = 80, F = 513, cap_samples = 0, cap_T = 0;
+    int n_fft = 1024, hop = 256, n_mel = 80, F = 513, cap_samples = 0;
     int ld_spec = 0, ld_mag = 0;
     hipStream_t stream = nullptr;
     std::string last_error;
     GemmCtx gx;
     float *basis = nullptr, *melb = nullptr;   // [2F][n_fft] windowed Fourier basis; [n_mel][ld_mag] mel filter bank (zero padded)
-    float *wav = nullptr, *wavp = nullptr, *spec = nullptr, *mag = nullptr, *mel = nullptr, *energy = nullptr;
     bool have_basis = false, have_mel = false;
+    // the handle's workspace: packed waveforms, packed reflect-padded signals, spectrum [sum T][ld_spec] (Griffin-Lim's recombined
+    // spectrum R), magnitude [sum T][ld_mag], (log-)mel [sum T][n_mel], energy [sum T], the forward GEMM's row map, the utterance table
+    DevBuf<float> wav, xp, spec, mag, mel, energy;
+    DevBuf<int> rowmap;
+    DevBuf<StftUtt> utts;
+    // the packed call (pack_begin / pack_add): totals over its utterances
+    std::vector<StftUtt> h_utts;
+    std::vector<int> h_rowmap;
+    long long n_frames = 0, xp_rows = 0, n_samples = 0, max_span = 0;   // sum T, forward-GEMM rows, sum n, longest padded span
 
-    void set_error(const std::string& s) { last_error = s; }
-#define MF_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return -1; } } while (0)
+    int err(const std::string& s) { last_error = s; return -1; }
 
     int init(int filter_length, int hop_length, int n_mel_channels, int max_samples) {
         n_fft = filter_length; hop = hop_length; n_mel = n_mel_channels; cap_samples = max_samples;
-        if (n_fft < 16 || (n_fft & 3) || hop < 4 || (hop & 3) || hop > n_fft || n_mel < 1 || n_mel > 1024 || max_samples <= n_fft / 2) {
-            set_error("unsupported STFT configuration (filter_length % 4, hop_length % 4 <= filter_length, max_samples > filter_length / 2)");
-            return -1;
-        }
+        if (n_fft < 16 || (n_fft & 3) || hop < 4 || (hop & 3) || hop > n_fft || n_mel < 1 || n_mel > 1024 || max_samples <= n_fft / 2)
+            return err("unsupported STFT configuration (filter_length % 4, hop_length % 4 <= filter_length, max_samples > filter_length / 2)");
         F = n_fft / 2 + 1;
         ld_spec = (2 * F + 3) & ~3;
         ld_mag = (F + 3) & ~3;
-        cap_T = max_samples / hop + 1;
         MF_CHECK(hipMalloc((void**)&basis, (size_t)2 * F * n_fft * sizeof(float)));
         MF_CHECK(hipMalloc((void**)&melb, (size_t)n_mel * ld_mag * sizeof(float)));
         MF_CHECK(hipMemset(melb, 0, (size_t)n_mel * ld_mag * sizeof(float)));
-        MF_CHECK(hipMalloc((void**)&wav, (size_t)max_samples * sizeof(float)));
-        MF_CHECK(hipMalloc((void**)&wavp, ((size_t)max_samples + n_fft + 64) * sizeof(float)));
-        MF_CHECK(hipMalloc((void**)&spec, ((size_t)cap_T * ld_spec + 64) * sizeof(float)));
-        MF_CHECK(hipMalloc((void**)&mag, ((size_t)cap_T * ld_mag + 64) * sizeof(float)));
-        MF_CHECK(hipMalloc((void**)&mel, ((size_t)cap_T * n_mel + 64) * sizeof(float)));
-        MF_CHECK(hipMalloc((void**)&energy, (size_t)cap_T * sizeof(float)));
-        if (gx.alloc_workspace()) { set_error("hipMalloc failed (split-K workspace)"); return -1; }
+        if (gx.alloc_workspace()) return err("hipMalloc failed (split-K workspace)");
         return 0;
     }
     void destroy() {
-        for (float* p : {basis, melb, wav, wavp, spec, mag, mel, energy}) if (p) hipFree(p);
+        for (float* p : {basis, melb}) if (p) hipFree(p);
+        for (DevBuf<float>* b : {&wav, &xp, &spec, &mag, &mel, &energy}) b->release();
+        rowmap.release();
+        utts.release();
         gx.release();
     }
     // forward_basis: [2F][n_fft] (stft.py:27-46, window applied); mel_basis: [n_mel][F] (stft.py:143-147)
@@ -111,36 +145,100 @@ public:
         }
         return 0;
     }
+
+    template <class T>
+    int grow(DevBuf<T>& b, size_t need, const char* what) {
+        if (need <= b.cap) return 0;
+        const size_t n = std::max(need + need / 4, (size_t)1024);
+        if (b.p) { hipStreamSynchronize(stream); b.release(); }
+        if (hipMalloc((void**)&b.p, n * sizeof(T)) != hipSuccess) { b.p = nullptr; return err(std::string("hipMalloc failed (STFT workspace: ") + what + ")"); }
+        b.cap = n;
+        return 0;
+    }
+    // Launches are asynchronous: what the GEMM launcher refused is in gx.error, what the runtime refused in hipGetLastError().
+    int check_launch() {
+        if (gx.error) { const std::string e = std::string("GEMM launcher: ") + gx.error; gx.error = nullptr; return err(e); }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return err(std::string("kernel launch failed: ") + hipGetErrorString(e));
+        return 0;
+    }
+
     int frames_of(int n_samples) const { return n_samples / hop + 1; }   // conv1d over the padded signal: (n + n_fft - n_fft) / hop + 1
-    // wav_host [n_samples] -> mel_host [T][n_mel] (log-mel), energy_host [T]; returns T, < 0 on error
-    int mel_spectrogram(const float* wav_host, int n_samples, float* mel_host, float* energy_host) {
-        if (!have_basis || !have_mel) { set_error("STFT bases not loaded"); return -1; }
-        if (!wav_host || !mel_host || !energy_host || n_samples <= n_fft / 2 || n_samples > cap_samples) {
-            set_error("bad waveform length (need filter_length / 2 < n_samples <= max_samples: reflection padding reads n_fft / 2 samples)");
+
+    // ---- packing: host only, so a caller validates utterance by utterance before anything is launched ------------------------------
+    void pack_begin() { h_utts.clear(); n_frames = xp_rows = n_samples = max_span = 0; }
+    // one more utterance of n samples of which T frames are kept; its padded signal starts at the next free multiple of hop
+    // (a count beyond what StftUtt's ints hold is refused by stage)
+    void pack_add(long long n, int T) {
+        h_utts.push_back(StftUtt{(int)n, T, (int)n_frames, 0, n_samples, xp_rows * hop});
+        n_frames += T;
+        n_samples += n;
+        xp_rows += T + (n_fft + hop - 1) / hop - 1;   // + the rows that straddle into the next padded signal
+        max_span = std::max(max_span, (long long)hop * (T - 1) + n_fft);
+    }
+    // Workspace for the packed call.  mapped: also the row map (forward-GEMM row -> compact row, -1 for a straddling row) and the
+    // utterance table on the device, and the padded signals zeroed (the gaps are read only by dropped rows).
+    int stage(const char* who, bool mapped) {
+        if (n_frames > (1LL << 30) / std::max(ld_spec, n_fft) || xp_rows > (1LL << 30) || n_samples > (1LL << 31) - 1)
+            return err(std::string(who) + ": too many frames in one call");
+        const size_t rows = (size_t)n_frames, xp_len = (size_t)xp_rows * hop + n_fft + 64;
+        if (grow(wav, (size_t)n_samples + 64, "waveforms") || grow(xp, xp_len, "padded signals") || grow(spec, rows * ld_spec + 64, "spectrum") ||
+            grow(mag, rows * ld_mag + 64, "magnitude") || grow(mel, rows * n_mel + 64, "mel") || grow(energy, rows, "energy"))
             return -1;
-        }
-        const int T = frames_of(n_samples);
+        if (!mapped) return 0;
+        h_rowmap.assign((size_t)xp_rows, -1);
+        for (const StftUtt& u : h_utts)
+            for (int t = 0; t < u.T; ++t) h_rowmap[(size_t)(u.xp0 / hop + t)] = u.frame0 + t;
+        if (grow(rowmap, (size_t)xp_rows, "row map") || grow(utts, h_utts.size(), "utterances")) return -1;
+        MF_CHECK(hipMemcpyAsync(utts, h_utts.data(), h_utts.size() * sizeof(StftUtt), hipMemcpyHostToDevice, stream));
+        MF_CHECK(hipMemcpyAsync(rowmap, h_rowmap.data(), (size_t)xp_rows * sizeof(int), hipMemcpyHostToDevice, stream));
+        MF_CHECK(hipMemsetAsync(xp, 0, xp_len * sizeof(float), stream));
+        return 0;
+    }
+    // wav_host (the staged call's waveforms one after another) -> the reflect-padded signals
+    int pad_waveforms(const float* wav_host, bool clip, bool mapped) {
         MF_CHECK(hipMemcpyAsync(wav, wav_host, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, stream));
-        MTTS_LAUNCH(wav_reflect_pad_kernel, dim3(1024), dim3(256), stream, (const float*)wav, n_samples, n_fft / 2, wavp);
-        {   // frames x basis: C[T][2F] = A[T][n_fft] (rows overlap: lda = hop) * basis[2F][n_fft]^T
-            GemmArgs g;
-            g.A = wavp; g.lda = hop; g.B = basis; g.ldb = n_fft; g.C = spec; g.ldc = ld_spec;
-            g.M = T; g.N = 2 * F; g.K = n_fft;
-            gemm_launch(gx, GEMM_NT, g, T, 2 * F, 1, stream, 0, 2.0 * T * 2.0 * F * n_fft, 0);
-        }
-        MTTS_LAUNCH(stft_magnitude_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), stream, (const float*)spec, ld_spec, T, F, mag, ld_mag, energy);
+        const dim3 grid((unsigned)std::min<long long>((max_span + 255) / 256, 1024), (unsigned)h_utts.size());
+        MTTS_LAUNCH(stft_reflect_pad_kernel, grid, dim3(256), stream, (const float*)wav, (const StftUtt*)(mapped ? utts.p : nullptr), h_utts[0], n_fft, hop,
+                    clip ? 1 : 0, xp.p);
+        return 0;
+    }
+    // spec rows (compact through `map`, or rows 0 .. M when map == nullptr) = overlapping frames of xp (lda = hop) * basis[2F][n_fft]^T
+    void forward_stft(long long M, const int* map, int tile) {
+        GemmArgs g;
+        g.A = xp; g.lda = hop; g.B = basis; g.ldb = n_fft; g.C = spec; g.ldc = ld_spec;
+        g.M = (int)M; g.N = 2 * F; g.K = n_fft; g.c_rowmap = map;
+        gemm_launch(gx, GEMM_NT, g, (int)M, 2 * F, 1, stream, tile, 2.0 * M * 2.0 * F * n_fft, 0);
+    }
+    // spectrum of the staged call -> mel_host [sum T][n_mel] (log-mel), energy_host [sum T]
+    int mel_from_spectrum(int tile, float* mel_host, float* energy_host) {
+        const long long T = n_frames;
+        MTTS_LAUNCH(stft_magnitude_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), stream, (const float*)spec, ld_spec, (int)T, F, mag.p, ld_mag, energy.p);
         {   // mel[T][n_mel] = mag[T][F] * mel_basis[n_mel][F]^T   (both zero padded to ld_mag columns)
             GemmArgs g;
             g.A = mag; g.lda = ld_mag; g.B = melb; g.ldb = ld_mag; g.C = mel; g.ldc = n_mel;
-            g.M = T; g.N = n_mel; g.K = ld_mag;
-            gemm_launch(gx, GEMM_NT, g, T, n_mel, 1, stream, 0, 2.0 * T * (double)n_mel * F, 0);
+            g.M = (int)T; g.N = n_mel; g.K = ld_mag;
+            gemm_launch(gx, GEMM_NT, g, (int)T, n_mel, 1, stream, tile, 2.0 * T * (double)n_mel * F, 0);
         }
-        MTTS_LAUNCH(log_clamp_kernel, dim3(256), dim3(256), stream, mel, (long long)T * n_mel, 1e-5f);
-        MF_CHECK(hipGetLastError());
+        MTTS_LAUNCH(log_clamp_kernel, dim3((unsigned)std::min<long long>((T * n_mel + 255) / 256, 1024)), dim3(256), stream, mel.p, T * n_mel, 1e-5f);
+        if (check_launch()) return -1;
         MF_CHECK(hipMemcpyAsync(mel_host, mel, (size_t)T * n_mel * sizeof(float), hipMemcpyDeviceToHost, stream));
         MF_CHECK(hipMemcpyAsync(energy_host, energy, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, stream));
         MF_CHECK(hipStreamSynchronize(stream));
-        return T;
+        return 0;
+    }
+
+    // wav_host [n_samples] -> mel_host [T][n_mel] (log-mel), energy_host [T]; returns T, < 0 on error
+    int mel_spectrogram(const float* wav_host, int n_samples_, float* mel_host, float* energy_host) {
+        if (!have_basis || !have_mel) return err("STFT bases not loaded");
+        if (!wav_host || !mel_host || !energy_host || n_samples_ <= n_fft / 2 || n_samples_ > cap_samples)
+            return err("bad waveform length (need filter_length / 2 < n_samples <= max_samples: reflection padding reads n_fft / 2 samples)");
+        const int T = frames_of(n_samples_);
+        pack_begin();
+        pack_add(n_samples_, T);
+        if (stage("mtts_stft_mel_spectrogram", false) || pad_waveforms(wav_host, true, false)) return -1;
+        forward_stft(T, nullptr, 0);
+        return mel_from_spectrum(0, mel_host, energy_host) ? -1 : T;
     }
 };
 

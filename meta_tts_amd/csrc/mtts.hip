@@ -677,7 +677,8 @@ int mtts_dvector_set_optimizer_step(mtts_dvector* h, int step) { h->d.adam_steps
 int mtts_dvector_export(mtts_dvector* h, const char* name, int which, float* out, int64_t numel) { return h->d.export_state(name, which, out, numel); }
 int mtts_dvector_import(mtts_dvector* h, const char* name, int which, const float* data, int64_t numel) { return h->d.import_state(name, which, data, numel); }
 
-// ---- waveform -> log-mel + energy (melfront.h; reference audio/stft.py:128-178, audio/tools.py:8-15) ----------------------
+// ---- waveform -> log-mel + energy (melfront.h, whose MelFront also holds the STFT front-end and the workspace that griffin.h and
+// preprocess.h share; reference audio/stft.py:128-178, audio/tools.py:8-15) ----------------------
 int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_samples, int device, mtts_stft** out) {
     if (!out) { g_create_error = "bad arguments"; return -1; }
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
@@ -698,9 +699,9 @@ void mtts_stft_destroy(mtts_stft* h) {
     delete h;
 }
 const char* mtts_stft_last_error(mtts_stft* h) { return h ? h->m.last_error.c_str() : g_create_error.c_str(); }
-int mtts_stft_load(mtts_stft* h, const float* forward_basis, const float* mel_basis) { return h->m.load(forward_basis, mel_basis); }
+int mtts_stft_load(mtts_stft* h, const float* forward_basis, const float* mel_basis) { return h ? h->m.load(forward_basis, mel_basis) : -1; }
 int mtts_stft_mel_spectrogram(mtts_stft* h, const float* wav, int n_samples, float* mel, float* energy) {
-    return h->m.mel_spectrogram(wav, n_samples, mel, energy);
+    return h ? h->m.mel_spectrogram(wav, n_samples, mel, energy) : -1;
 }
 // ---- spectrogram -> waveform (griffin.h; reference audio/stft.py:52-119, audio/audio_processing.py:7-80, audio/tools.py:18-37) --------
 int mtts_stft_load_inverse(mtts_stft* h, const float* inverse_basis, const float* window_sq) { return h ? h->gl.load(inverse_basis, window_sq) : -1; }

@@ -7,11 +7,10 @@
 // minimum / maximum of the normalised values).
 //
 // MI355X layout.  Every utterance of a call goes through the same launches; only descriptor tables are built by a host loop.
-//   * front-end (Preprocess::mel_batch): one clip + reflect-pad kernel writes every utterance's padded signal at a multiple of hop
-//     (griffin.h's packing), the forward STFT is ONE implicit GEMM over overlapping rows (lda = hop) whose rows between two utterances
-//     are dropped through GemmArgs::c_rowmap, then melfront.h's magnitude + energy pass, the mel GEMM and the log-clamp over the
-//     compact [sum T] rows.  Both GEMMs name their kernel explicitly (no split-K, no size-dependent choice), so an utterance's rows
-//     do not depend on what else is in the call.
+//   * front-end (Preprocess::mel_batch): melfront.h's shared pieces with every utterance packed into one call — the clip +
+//     reflect-pad kernel, ONE forward-STFT GEMM whose rows between two utterances are dropped, the magnitude + energy pass, the mel
+//     GEMM and the log-clamp over the compact [sum T] rows, all in MelFront's workspace.  Both GEMMs name their kernel explicitly (no
+//     split-K, no size-dependent choice), so an utterance's rows do not depend on what else is in the call.
 //   * pp_segment_kernel<T>: one workgroup per utterance; interpolation by nearest-voiced-left / right walks, the duration prefix sum,
 //     and the segment means (T = double for pitch, float for energy).  The reference's loop writes pitch[i] while later means read
 //     pitch[pos : pos + d]; when some pos < i (more zero durations than frames so far) a later mean reads an already overwritten
@@ -26,31 +25,15 @@
 #include <string>
 #include <vector>
 
-#include "griffin.h"
+#include "melfront.h"
 
 namespace mtts {
 
 constexpr int kPpMaxValues = 4096;   // values of one utterance the outlier kernel sorts in LDS (32 KiB of doubles)
 constexpr int kPpThreads = 256;
 
-struct PpWav { int n; int T; long long wav0; long long xp0; };   // samples, kept frames, first sample (packed input / padded signal)
 struct PpSeq { int T; int S; long long x0; long long d0; };      // frames at x0 of the packed values, phones at d0 of the packed durations
 struct PpVal { int n; int pad_; long long x0; };                 // values of one utterance of the outlier step
-
-// xp[xp0 + j] = clip(wav[wav0 + reflect(j - pad)], -1, 1) for the hop * (T - 1) + n_fft samples the kept frames read
-// (tools.py:9 + stft.py:60-65).  blockIdx.y = utterance.
-__global__ void pp_clip_pad_kernel(const float* wav, const PpWav* utts, int pad, int hop, int n_fft, float* xp) {
-    const PpWav u = utts[blockIdx.y];
-    const long long total = (long long)hop * (u.T - 1) + n_fft;
-    for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < total; j += (long long)gridDim.x * blockDim.x) {
-        long long s = j - pad;
-        if (s < 0) s = -s;
-        else if (s >= u.n) s = 2LL * (u.n - 1) - s;
-        float v = wav[u.wav0 + s];
-        v = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
-        xp[u.xp0 + j] = v;
-    }
-}
 
 // Block-wide fixed-tree reductions through LDS (deterministic; fp64 has no wave_sum).  `red` holds blockDim.x doubles.
 __device__ __forceinline__ double pp_block_sum(double v, double* red) {
@@ -231,94 +214,35 @@ __global__ void pp_normalize_kernel(const T* x, long long n, double mean, double
 class Preprocess {
 public:
     MelFront* mf = nullptr;
-    struct Buf { void* p = nullptr; size_t cap = 0; };
-    Buf wav, xp, spec, mag, mel, energy, rowmap, descs, vals, work, durs, pos, outb, keepb, parts;
-    std::vector<int> h_rowmap;
-    std::vector<PpWav> h_wav;
+    // sized in bytes (values are float or double): values, interpolated copy, durations and their prefix sums, segment means or
+    // normalised values, keep mask, per-utterance or per-workgroup partials, the PpSeq / PpVal table
+    DevBuf<unsigned char> vals, work, durs, pos, outb, keepb, parts, descs;
     std::vector<PpSeq> h_seq;
     std::vector<PpVal> h_val;
     std::vector<double> h_minmax;
 
-    void set_error(const std::string& s) { mf->set_error(s); }   // (MF_CHECK)
-    int err(const std::string& s) { set_error(s); return -1; }
+    int err(const std::string& s) { return mf->err(s); }   // (MF_CHECK)
     void destroy() {
-        for (Buf* b : {&wav, &xp, &spec, &mag, &mel, &energy, &rowmap, &descs, &vals, &work, &durs, &pos, &outb, &keepb, &parts})
-            if (b->p) { hipFree(b->p); b->p = nullptr; b->cap = 0; }
-    }
-    int grow(Buf& b, size_t bytes, const char* what) {   // the workspace grows on demand, as Griffin-Lim's does
-        if (bytes <= b.cap) return 0;
-        const size_t n = std::max(bytes + bytes / 4, (size_t)4096);
-        if (b.p) { hipStreamSynchronize(mf->stream); hipFree(b.p); b.p = nullptr; b.cap = 0; }
-        if (hipMalloc(&b.p, n) != hipSuccess) { b.p = nullptr; return err(std::string("hipMalloc failed (preprocessing workspace: ") + what + ")"); }
-        b.cap = n;
-        return 0;
-    }
-    int check_launch() {
-        if (mf->gx.error) { std::string e = std::string("GEMM launcher: ") + mf->gx.error; mf->gx.error = nullptr; return err(e); }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return err(std::string("kernel launch failed: ") + hipGetErrorString(e));
-        return 0;
+        for (DevBuf<unsigned char>* b : {&vals, &work, &durs, &pos, &outb, &keepb, &parts, &descs}) b->release();
     }
 
     // get_mel_from_wav of n_utts waveforms (packed in wav_host), each truncated to keep_frames[u] frames (< 0: all):
     // mel_host [sum T][n_mel] log-mel, energy_host [sum T]; T_u = min(n_u / hop + 1, keep_u)   (preprocessor.py:227-229)
     int mel_batch(int n_utts, const int* n_samples, const int* keep_frames, const float* wav_host, float* mel_host, float* energy_host) {
-        const int n_fft = mf->n_fft, hop = mf->hop, F = mf->F, ld = mf->ld_spec, ld_mag = mf->ld_mag, n_mel = mf->n_mel;
+        const int n_fft = mf->n_fft;
         if (!mf->have_basis || !mf->have_mel) return err("STFT bases not loaded");
         if (n_utts < 1 || !n_samples || !wav_host || !mel_host || !energy_host) return err("mtts_stft_mel_batch: bad arguments (n_utts < 1 or NULL pointer)");
-        h_wav.resize((size_t)n_utts);
-        long long samples = 0, rows = 0, xp_rows = 0, max_span = 0;
-        const int extra = (n_fft + hop - 1) / hop - 1;   // rows that straddle two packed padded signals
+        mf->pack_begin();
         for (int u = 0; u < n_utts; ++u) {
             const int n = n_samples[u], keep = keep_frames ? keep_frames[u] : -1;
             if (n <= n_fft / 2)
                 return err("mtts_stft_mel_batch: utterance " + std::to_string(u) + ": waveform too short for the reflection padding (need n_samples > filter_length / 2)");
             if (keep == 0) return err("mtts_stft_mel_batch: utterance " + std::to_string(u) + ": keep_frames == 0 (sum(duration) == 0: nothing to keep)");
-            const int full = n / hop + 1, T = keep < 0 ? full : std::min(full, keep);
-            h_wav[(size_t)u] = PpWav{n, T, samples, xp_rows * hop};
-            samples += n;
-            rows += T;
-            xp_rows += T + extra;
-            max_span = std::max(max_span, (long long)hop * (T - 1) + n_fft);
+            mf->pack_add(n, keep < 0 ? mf->frames_of(n) : std::min(mf->frames_of(n), keep));
         }
-        if (rows > (1LL << 30) / std::max(ld, n_fft) || xp_rows > (1LL << 30) || samples > (1LL << 31) - 1)
-            return err("mtts_stft_mel_batch: too many frames in one call");
-        h_rowmap.assign((size_t)xp_rows, -1);
-        for (int u = 0, r = 0; u < n_utts; ++u)
-            for (int t = 0; t < h_wav[(size_t)u].T; ++t) h_rowmap[(size_t)(h_wav[(size_t)u].xp0 / hop + t)] = r++;
-        const size_t xp_len = (size_t)xp_rows * hop + n_fft + 64;
-        if (grow(wav, (size_t)samples * sizeof(float), "waveforms") || grow(xp, xp_len * sizeof(float), "padded signals") ||
-            grow(spec, ((size_t)rows * ld + 64) * sizeof(float), "spectrum") || grow(mag, ((size_t)rows * ld_mag + 64) * sizeof(float), "magnitude") ||
-            grow(mel, ((size_t)rows * n_mel + 64) * sizeof(float), "mel") || grow(energy, (size_t)rows * sizeof(float), "energy") ||
-            grow(rowmap, (size_t)xp_rows * sizeof(int), "row map") || grow(descs, (size_t)n_utts * sizeof(PpWav), "utterances"))
-            return -1;
-        hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(wav.p, wav_host, (size_t)samples * sizeof(float), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(descs.p, h_wav.data(), (size_t)n_utts * sizeof(PpWav), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(rowmap.p, h_rowmap.data(), (size_t)xp_rows * sizeof(int), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemsetAsync(xp.p, 0, xp_len * sizeof(float), st));   // (gaps are read only by dropped rows)
-        const dim3 pad_grid((unsigned)std::min<long long>((max_span + 255) / 256, 1024), (unsigned)n_utts);
-        MTTS_LAUNCH(pp_clip_pad_kernel, pad_grid, dim3(256), st, (const float*)wav.p, (const PpWav*)descs.p, n_fft / 2, hop, n_fft, (float*)xp.p);
-        {   // spec [sum T][2F] = overlapping frames of the packed padded signals * basis^T, rows between utterances dropped
-            GemmArgs g;
-            g.A = (const float*)xp.p; g.lda = hop; g.B = mf->basis; g.ldb = n_fft; g.C = (float*)spec.p; g.ldc = ld;
-            g.M = (int)xp_rows; g.N = 2 * F; g.K = n_fft; g.c_rowmap = (const int*)rowmap.p;
-            gemm_launch(mf->gx, GEMM_NT, g, (int)xp_rows, 2 * F, 1, st, n_fft >= 1024 ? 3064 : 64, 2.0 * xp_rows * 2.0 * F * n_fft, 0);
-        }
-        MTTS_LAUNCH(stft_magnitude_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), st, (const float*)spec.p, ld, (int)rows, F, (float*)mag.p, ld_mag,
-                    (float*)energy.p);
-        {   // mel [sum T][n_mel] = mag * mel_basis^T (both zero padded to ld_mag columns)
-            GemmArgs g;
-            g.A = (const float*)mag.p; g.lda = ld_mag; g.B = mf->melb; g.ldb = ld_mag; g.C = (float*)mel.p; g.ldc = n_mel;
-            g.M = (int)rows; g.N = n_mel; g.K = ld_mag;
-            gemm_launch(mf->gx, GEMM_NT, g, (int)rows, n_mel, 1, st, 64, 2.0 * rows * (double)n_mel * F, 0);
-        }
-        MTTS_LAUNCH(log_clamp_kernel, dim3(1024), dim3(256), st, (float*)mel.p, rows * n_mel, 1e-5f);
-        if (check_launch()) return -1;
-        MF_CHECK(hipMemcpyAsync(mel_host, mel.p, (size_t)rows * n_mel * sizeof(float), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipMemcpyAsync(energy_host, energy.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipStreamSynchronize(st));
-        return 0;
+        if (mf->stage("mtts_stft_mel_batch", true) || mf->pad_waveforms(wav_host, true, true)) return -1;
+        mf->forward_stft(mf->xp_rows, mf->rowmap, n_fft >= 1024 ? 3064 : 64);
+        return mf->mel_from_spectrum(64, mel_host, energy_host);
     }
 
     // preprocessor.py:231-261.  values: packed [sum T] (dtype 0: float32, 1: float64); durations: packed [sum S]; out: packed [sum S]
@@ -347,9 +271,9 @@ public:
         }
         if (nx > (1LL << 30)) return err("mtts_stft_phoneme_average: too many frames in one call");
         const size_t esz = dtype ? sizeof(double) : sizeof(float);
-        if (grow(vals, (size_t)nx * esz, "values") || grow(work, (size_t)nx * esz, "interpolated values") || grow(durs, (size_t)nd * sizeof(int), "durations") ||
-            grow(pos, (size_t)nd * sizeof(int), "duration prefix sums") || grow(outb, (size_t)nd * esz, "segment means") ||
-            grow(descs, (size_t)n_utts * sizeof(PpSeq), "utterances"))
+        if (mf->grow(vals, (size_t)nx * esz, "values") || mf->grow(work, (size_t)nx * esz, "interpolated values") || mf->grow(durs, (size_t)nd * sizeof(int), "durations") ||
+            mf->grow(pos, (size_t)nd * sizeof(int), "duration prefix sums") || mf->grow(outb, (size_t)nd * esz, "segment means") ||
+            mf->grow(descs, (size_t)n_utts * sizeof(PpSeq), "utterances"))
             return -1;
         hipStream_t st = mf->stream;
         MF_CHECK(hipMemcpyAsync(vals.p, values, (size_t)nx * esz, hipMemcpyHostToDevice, st));
@@ -361,7 +285,7 @@ public:
         else
             MTTS_LAUNCH(pp_segment_kernel<float>, dim3((unsigned)n_utts), dim3(kPpThreads), st, (const float*)vals.p, (float*)work.p, (const int*)durs.p,
                         (int*)pos.p, (const PpSeq*)descs.p, (float*)outb.p, interpolate);
-        if (check_launch()) return -1;
+        if (mf->check_launch()) return -1;
         MF_CHECK(hipMemcpyAsync(out_host, outb.p, (size_t)nd * esz, hipMemcpyDeviceToHost, st));
         MF_CHECK(hipStreamSynchronize(st));
         return 0;
@@ -381,8 +305,8 @@ public:
             nx += n_values[u];
         }
         const size_t esz = dtype ? sizeof(double) : sizeof(float);
-        if (grow(vals, (size_t)std::max<long long>(nx, 1) * esz, "values") || grow(keepb, (size_t)std::max<long long>(nx, 1), "keep mask") ||
-            grow(parts, (size_t)n_utts * 3 * sizeof(double), "partial statistics") || grow(descs, (size_t)n_utts * sizeof(PpVal), "utterances"))
+        if (mf->grow(vals, (size_t)std::max<long long>(nx, 1) * esz, "values") || mf->grow(keepb, (size_t)std::max<long long>(nx, 1), "keep mask") ||
+            mf->grow(parts, (size_t)n_utts * 3 * sizeof(double), "partial statistics") || mf->grow(descs, (size_t)n_utts * sizeof(PpVal), "utterances"))
             return -1;
         hipStream_t st = mf->stream;
         MF_CHECK(hipMemcpyAsync(vals.p, values, (size_t)nx * esz, hipMemcpyHostToDevice, st));
@@ -393,7 +317,7 @@ public:
         else
             MTTS_LAUNCH(pp_outlier_stats_kernel<float>, dim3((unsigned)n_utts), dim3(kPpThreads), st, (const float*)vals.p, (const PpVal*)descs.p,
                         (unsigned char*)keepb.p, (double*)parts.p);
-        if (check_launch()) return -1;
+        if (mf->check_launch()) return -1;
         MF_CHECK(hipMemcpyAsync(keep_host, keepb.p, (size_t)nx, hipMemcpyDeviceToHost, st));
         MF_CHECK(hipMemcpyAsync(partials_host, parts.p, (size_t)n_utts * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
         MF_CHECK(hipStreamSynchronize(st));
@@ -427,8 +351,8 @@ public:
         if (!(stdv != 0.0)) return err("mtts_stft_normalize: std == 0");
         const size_t esz = dtype ? sizeof(double) : sizeof(float);
         const int blocks = (int)std::min<long long>((n + kPpThreads - 1) / kPpThreads, 256);
-        if (grow(vals, (size_t)n * esz, "values") || grow(outb, (size_t)n * sizeof(double), "normalised values") ||
-            grow(parts, (size_t)blocks * 2 * sizeof(double), "min / max partials"))
+        if (mf->grow(vals, (size_t)n * esz, "values") || mf->grow(outb, (size_t)n * sizeof(double), "normalised values") ||
+            mf->grow(parts, (size_t)blocks * 2 * sizeof(double), "min / max partials"))
             return -1;
         hipStream_t st = mf->stream;
         MF_CHECK(hipMemcpyAsync(vals.p, values, (size_t)n * esz, hipMemcpyHostToDevice, st));
@@ -436,7 +360,7 @@ public:
             MTTS_LAUNCH(pp_normalize_kernel<double>, dim3((unsigned)blocks), dim3(kPpThreads), st, (const double*)vals.p, n, mean, stdv, (double*)outb.p, (double*)parts.p);
         else
             MTTS_LAUNCH(pp_normalize_kernel<float>, dim3((unsigned)blocks), dim3(kPpThreads), st, (const float*)vals.p, n, mean, stdv, (double*)outb.p, (double*)parts.p);
-        if (check_launch()) return -1;
+        if (mf->check_launch()) return -1;
         h_minmax.resize((size_t)blocks * 2);
         MF_CHECK(hipMemcpyAsync(out_host, outb.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
         MF_CHECK(hipMemcpyAsync(h_minmax.data(), parts.p, (size_t)blocks * 2 * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -2,9 +2,9 @@
 (`mel/ pitch/ energy/ duration/*.npy`, `stats.json`, `speakers.json`, `<subset>.txt`) that `meta_tts_amd.data.FeatureDataset` reads.
 
 The device does the batched mel / energy front-end, the pitch interpolation, the phoneme-level segment means, the outlier filter
-with the partial statistics, and the normalisation with its min / max (csrc/preprocess.h); every utterance of a call shares every
-launch.  The host does what is text or file handling: the TextGrid reader, `get_alignment`, the walk over the corpus, the `.npy`
-files.  Two third-party steps are injected, not restated: pitch extraction (`f0_fn`; the default calls pyworld's DIO + StoneMask as
+with the partial statistics, and the normalisation with its min / max (csrc/preprocess.h, the front-end through csrc/melfront.h);
+every utterance of a call shares every launch.  The host does what is text or file handling: the TextGrid reader, `get_alignment`,
+the walk over the corpus, the `.npy` files.  Two third-party steps are injected, not restated: pitch extraction (`f0_fn`; the default calls pyworld's DIO + StoneMask as
 the reference does and raises when pyworld is missing) and the speaker-encoder reference mels (`spk_ref_fn`; skipped when absent).
 Wavs are read with scipy.io.wavfile (or an injected loader) and are NOT resampled: a file whose rate differs from the config's raises.
 
@@ -20,7 +20,7 @@ import re
 
 import numpy as np
 
-from .audio.stft import TacotronSTFT
+from .audio.stft import TacotronSTFT, _OnHandle
 from .engine import MttsError
 
 Interval = collections.namedtuple("Interval", "start_time end_time text")
@@ -109,7 +109,7 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class Preprocessor:
+class Preprocessor(_OnHandle):
     """preprocessor/preprocessor.py:18 with the same preprocess-config keys (config/preprocess/LibriTTS.yaml)."""
 
     def __init__(self, config, *, max_samples=22050 * 40, device=0, lib_path=None):
@@ -129,7 +129,7 @@ class Preprocessor:
         self.STFT = TacotronSTFT(pp["stft"]["filter_length"], pp["stft"]["hop_length"], pp["stft"]["win_length"], pp["mel"]["n_mel_channels"],
                                  pp["audio"]["sampling_rate"], pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"], max_samples=max_samples, device=device,
                                  lib_path=lib_path)
-        self.lib, self.h = self.STFT.lib, self.STFT.h
+        self._dev = self.STFT._dev   # the TacotronSTFT's handle: this class's device steps run on it
         self.train_set = self.val_set = self.test_set = None
         if "subsets" in config:
             self.train_set = config["subsets"].get("train", None)
@@ -140,11 +140,6 @@ class Preprocessor:
         if getattr(self, "STFT", None) is not None:
             self.STFT.close()
             self.STFT = None
-
-    def _check(self, rc):
-        if rc < 0:
-            raise MttsError(self.lib.mtts_stft_last_error(self.STFT.h).decode())
-        return rc
 
     # ---- host: alignment ---------------------------------------------------------------------------------------------------------
     def get_alignment(self, tier):

@@ -1,4 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY — torch restatement of the reference's mel front-end, the checker of meta_tts_amd/csrc/melfront.h.
+"""TEST INFRASTRUCTURE ONLY — torch restatement of the reference's mel front-end, the checker of meta_tts_amd/csrc/melfront.h (MelFront: the
+shared STFT front-end, and mel_spectrogram / mel_batch on it).
 
 PINNED (round 3) by tests/golden/stft.npz — outputs of the REFERENCE's own audio/stft.py + audio/tools.py run in the build container by
 tests/golden/make_stft_golden.py (librosa's three padding helpers shimmed, `.cuda()` made the identity): the windowed Fourier basis,
