@@ -472,6 +472,43 @@ int mtts_stft_outlier_stats(mtts_stft* h, int n_utts, const int* n_values, const
 int mtts_stft_merge_stats(mtts_stft* h, double* state, int n_partials, const double* partials);
 int mtts_stft_normalize(mtts_stft* h, int64_t n, const void* values, int dtype, double mean, double std, double* out, double* minmax);
 
+/* ---- speaker-similarity evaluation: wavs -> d-vectors, similarity, centroids -----------------------------
+ * Replaces the device-worthy part of the reference's `evaluation/` package (wavs_to_dvector.py: `encoder.embed_utterance(
+ * preprocess_wav(path))` one wav at a time on the CPU; pair_similarity.py:68-88, centroid_similarity.py:47-118: cosine similarity;
+ * wavs_to_dvector.py:176-183: centroids) and `spk_ref_mel_slices` of preprocessor/preprocessor.py:263-299.  resemblyzer is un-vendored:
+ * its front-end is restated from the published recipe.  NOT built: its `preprocess_wav` (resampling, -30 dBFS normalisation, webrtcvad
+ * trimming) — waveforms are 16 kHz float32 as they are.
+ * power_mel_batch: resemblyzer's `wav_to_mel_spectrogram` of n_utts waveforms packed in `wavs` as they are: mel [sum T][n_mel], T_u =
+ * n_samples[u] / hop_length + 1, = mel_basis @ (re^2 + im^2) of the centred, reflect-padded frames (power; no clip, no log, no clamp).
+ * An utterance's rows are bit-identical whatever else is in the call.  Errors (before any launch): n_samples[u] <= filter_length / 2.
+ * embed_device: mtts_dvector_embed over a partial stack mels_dev [n_partials][frames][n_mels] that is ALREADY on the device (read in
+ * place); utt_offsets, out, partial_out are host arrays as in embed.  The input projections name a fixed GEMM kernel: the d-vector of an
+ * utterance is bit-identical alone, in any batch and under any chunking.  Synchronous.
+ * embed_wavs: n_utts waveforms packed one after another in `wavs` (n_samples[u] each) -> out [n_utts][emb].  `stft` is an mtts_stft
+ * handle created at filter_length 400, hop_length 160, n_mel 40 and loaded with forward_basis(400, 400, "hann") and the mel filter bank
+ * of (16000, 400, 40).  Per utterance: the partial rule (windows of partial_frames mel frames every frame_step frames over
+ * ceil((n + 1) / hop) frames, the last dropped when (n - its first sample) / (partial_frames * hop) < min_coverage and it is not the
+ * only one; resemblyzer: partial_frames 160, frame_step round(16000 / 1.3 / 160) = 77, min_coverage 0.75), zero-extension of the
+ * waveform to the last window's end, mel = mel_basis @ (re^2 + im^2) of the centred, reflect-padded frames (power, no log, no clamp),
+ * the windows gathered on the device into the encoder's partial stack, then embed_device.  n_partials_out [n_utts] = windows per
+ * utterance; slices_out (or NULL) = those stacks [sum n_partials][partial_frames][n_mel] — the `spk_ref_mel_slices` payload.
+ * h == NULL: front-end only (slices_out required, out ignored).  All utterances of a chunk share every launch; a chunk is as many
+ * consecutive utterances as fit the encoder's max_partials / max_utts; results do not depend on the chunking (bit-identical).  With the
+ * two handles on different streams the stages are ordered by events.  Refused before any launch, with the reason in BOTH handles'
+ * last_error: NULL pointers, n_samples[u] <= filter_length / 2, one utterance with more partials than max_partials, handles on
+ * different devices, a partial shape the encoder was not created for, bases not loaded.  Synchronous.
+ * cosine_indexed: sim[i] = <a, b> / (max(||a||, eps) max(||b||, eps)), a = a[index_a[i]], b = b[index_b[i]] (torch's
+ * nn.CosineSimilarity(dim=1, eps)); a [n_a][dim], b [n_b][dim], n pairs; host arrays.  The reference's np.repeat expansions become
+ * index arrays.  centroids: out[s] = m / ||m||_2, m = mean of vectors[offsets[s] .. offsets[s + 1]) (ragged lists, offsets [n_speakers
+ * + 1] from 0; dim <= 1024).  Both accumulate in float64 in a fixed order (deterministic, no atomics) and round once. */
+int mtts_stft_power_mel_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, float* mel);
+int mtts_dvector_embed_device(mtts_dvector* h, const float* mels_dev, int n_partials, const int* utt_offsets, int n_utts, float* out, float* partial_out);
+int mtts_dvector_embed_wavs(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
+                            double min_coverage, float* out, int* n_partials_out, float* slices_out);
+int mtts_dvector_cosine_indexed(mtts_dvector* h, const float* a, int n_a, const float* b, int n_b, int dim, int n, const int* index_a, const int* index_b,
+                                double eps, float* sim);
+int mtts_dvector_centroids(mtts_dvector* h, const float* vectors, const int* offsets, int n_speakers, int dim, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,12 @@ EXPORTS = {
     "mtts_dvector_set_optimizer_step": (C.c_int, [C.c_void_p, C.c_int]),
     "mtts_dvector_export": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int64]),
     "mtts_dvector_import": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int64]),
+    "mtts_dvector_embed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mtts_dvector_embed_wavs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "mtts_dvector_cosine_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
+                                              C.c_void_p]),
+    "mtts_dvector_centroids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mtts_get_speaker_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mtts_set_extra_grad_sumsq": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mtts_grad_norm_dev": (C.c_void_p, [C.c_void_p]),
@@ -154,6 +160,7 @@ EXPORTS = {
     "mtts_stft_outlier_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mtts_stft_merge_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mtts_stft_normalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "mtts_stft_power_mel_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_vocoder_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_void_p)]),
     "mtts_vocoder_destroy": (None, [C.c_void_p]),

@@ -332,15 +332,35 @@ public:
     // mels_host [N][T][n_mels]; utt_off [B+1] partial offsets (utt_off[0] = 0, utt_off[B] = N); out_host [B][E]; part_host [N][E] or null
     int embed(const float* mels_host, int N, const int* utt_off, int B, float* out_host, float* part_host, bool train = false) {
         if (train && !train_ready) { set_error("mtts_dvector_enable_training first"); return -1; }
-        if (!mels_host || !utt_off || !out_host || N < 1 || N > cap_N || B < 1 || B > cap_B) { set_error("bad d-vector arguments"); return -1; }
+        if (check_batch(mels_host, N, utt_off, B, out_host) != 0) return -1;
+        if (dirty && refresh() != 0) return -1;
+        DV_CHECK(hipMemcpyAsync(mels, mels_host, (size_t)N * T * n_mels * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (forward(mels, N, utt_off, B, out_host, part_host, train, 0) != 0) return -1;
+        DV_CHECK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    // The same forward over a partial stack that is already on the device (mels_dev [N][T][n_mels], read in place).  The input
+    // projections name their kernel (64x64 tile; no launch queue, no size-dependent choice), so an utterance's d-vector is
+    // bit-identical alone, in any batch and under any chunking.  sync = false: the copies to out_host / part_host are only enqueued.
+    int forward_device(const float* mels_dev, int N, const int* utt_off, int B, float* out_host, float* part_host, bool sync = true) {
+        if (check_batch(mels_dev, N, utt_off, B, out_host) != 0) return -1;
+        if (dirty && refresh() != 0) return -1;
+        if (forward(mels_dev, N, utt_off, B, out_host, part_host, false, 64) != 0) return -1;
+        if (sync) DV_CHECK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int check_batch(const float* mels_any, int N, const int* utt_off, int B, const float* out_host) {
+        if (!mels_any || !utt_off || !out_host || N < 1 || N > cap_N || B < 1 || B > cap_B) { set_error("bad d-vector arguments"); return -1; }
         if (utt_off[0] != 0 || utt_off[B] != N) { set_error("utterance offsets must cover [0, N)"); return -1; }
         for (int b = 0; b < B; ++b)   // an utterance without partials has no embedding (the reference's mean over an empty slice is NaN)
             if (utt_off[b + 1] <= utt_off[b]) { set_error("every utterance needs at least one partial utterance (offsets must increase)"); return -1; }
-        if (dirty && refresh() != 0) return -1;
+        return 0;
+    }
+    // x0: [N][T][n_mels] on the device; tile: the input projections' GEMM tile code (0: through the launch queue)
+    int forward(const float* x0, int N, const int* utt_off, int B, float* out_host, float* part_host, bool train, int tile) {
         const long long rows = (long long)N * T;
-        DV_CHECK(hipMemcpyAsync(mels, mels_host, (size_t)rows * n_mels * sizeof(float), hipMemcpyHostToDevice, stream));
         DV_CHECK(hipMemcpyAsync(off_dev, utt_off, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-        const float* x = mels;
+        const float* x = x0;
         for (int l = 0; l < layers; ++l) {
             const std::string s = std::to_string(l);
             GemmArgs g;
@@ -349,7 +369,7 @@ public:
             g.C = xp; g.ldc = 4 * H;
             g.M = (int)rows; g.N = 4 * H; g.K = in_dim(l);
             g.bias = bsum + (long long)l * 4 * H;
-            gemm_launch(gx, GEMM_NT, g, (int)rows, 4 * H, 1, stream, 0, 2.0 * rows * 4.0 * H * in_dim(l), 0);
+            gemm_launch(gx, GEMM_NT, g, (int)rows, 4 * H, 1, stream, tile, 2.0 * rows * 4.0 * H * in_dim(l), 0);
             float* hs = train ? hkeep[l] : ((l + 1 < layers) ? hseq[l & 1] : nullptr);
             MTTS_LAUNCH(lstm_recurrent_kernel, dim3((unsigned)N), dim3((unsigned)H), stream, (const float*)xp,
                         (const float*)(whhT + (long long)l * 4 * H * H), hs, hlast, T, H, train ? gates[l] : (float*)nullptr,
@@ -360,10 +380,10 @@ public:
                     (const float*)(params + find("linear.bias")), part, H, E, train ? eraw : (float*)nullptr);
         if (train) { last_N = N; last_B = B; have_forward = true; }
         MTTS_LAUNCH(dvec_utterance_kernel, dim3((unsigned)B), dim3((unsigned)((E + 63) & ~63)), stream, (const float*)part, (const int*)off_dev, out, E);
+        if (gx.error) { set_error(std::string("GEMM launcher: ") + gx.error); gx.error = nullptr; return -1; }
         DV_CHECK(hipGetLastError());
         DV_CHECK(hipMemcpyAsync(out_host, out, (size_t)B * E * sizeof(float), hipMemcpyDeviceToHost, stream));
         if (part_host) DV_CHECK(hipMemcpyAsync(part_host, part, (size_t)N * E * sizeof(float), hipMemcpyDeviceToHost, stream));
-        DV_CHECK(hipStreamSynchronize(stream));
         return 0;
     }
 

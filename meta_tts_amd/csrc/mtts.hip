@@ -10,6 +10,7 @@
 #include "melfront.h"
 #include "griffin.h"
 #include "preprocess.h"
+#include "speakereval.h"
 
 using namespace mtts;
 
@@ -41,11 +42,14 @@ struct mtts_vocoder {
 };
 struct mtts_dvector {
     DVector d;
+    SpeakerScore sc;
+    int device = 0;
 };
 struct mtts_stft {
     MelFront m;
     GriffinLim gl;
     Preprocess pp;
+    SpeakerEval se;
 };
 
 extern "C" {
@@ -648,6 +652,9 @@ int mtts_dvector_create(int n_mels, int hidden, int layers, int emb, int max_par
     if (!out) { g_create_error = "bad arguments"; return -1; }
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
     mtts_dvector* h = new mtts_dvector();
+    h->device = device;
+    h->sc.last_error = &h->d.last_error;
+    h->sc.stream = &h->d.stream;
     if (h->d.init(n_mels, hidden, layers, emb, max_partials, frames, max_utts) != 0) { g_create_error = h->d.last_error; h->d.destroy(); delete h; return -1; }
     *out = h;
     return 0;
@@ -656,6 +663,7 @@ int mtts_dvector_set_stream(mtts_dvector* h, void* s) { if (!h) return -1; h->d.
 void mtts_dvector_destroy(mtts_dvector* h) {
     if (!h) return;
     hipDeviceSynchronize();
+    h->sc.destroy();
     h->d.destroy();
     delete h;
 }
@@ -685,6 +693,8 @@ int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_sampl
     mtts_stft* h = new mtts_stft();
     h->gl.mf = &h->m;
     h->pp.mf = &h->m;
+    h->se.mf = &h->m;
+    h->se.device = device;
     if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; h->m.destroy(); delete h; return -1; }
     *out = h;
     return 0;
@@ -695,6 +705,7 @@ void mtts_stft_destroy(mtts_stft* h) {
     hipDeviceSynchronize();
     h->gl.destroy();
     h->pp.destroy();
+    h->se.destroy();
     h->m.destroy();
     delete h;
 }
@@ -734,6 +745,29 @@ int mtts_stft_merge_stats(mtts_stft* h, double* state, int n_partials, const dou
 }
 int mtts_stft_normalize(mtts_stft* h, int64_t n, const void* values, int dtype, double mean, double std, double* out, double* minmax) {
     return h ? h->pp.normalize(n, values, dtype, mean, std, out, minmax) : -1;
+}
+
+// ---- speaker-similarity evaluation (speakereval.h; reference evaluation/wavs_to_dvector.py, pair_similarity.py, centroid_similarity.py) ----
+int mtts_stft_power_mel_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, float* mel) {
+    return h ? h->se.power_mel_batch(n_utts, n_samples, wavs, mel) : -1;
+}
+int mtts_dvector_embed_device(mtts_dvector* h, const float* mels_dev, int n_partials, const int* utt_offsets, int n_utts, float* out, float* partial_out) {
+    return h ? h->d.forward_device(mels_dev, n_partials, utt_offsets, n_utts, out, partial_out) : -1;
+}
+int mtts_dvector_embed_wavs(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
+                            double min_coverage, float* out, int* n_partials_out, float* slices_out) {
+    if (!stft) { g_create_error = "mtts_dvector_embed_wavs: NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
+    const int rc = stft->se.embed_wavs(h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, partial_frames, frame_step, min_coverage, out,
+                                       n_partials_out, slices_out);
+    if (rc != 0 && h) h->d.set_error(stft->m.last_error);
+    return rc;
+}
+int mtts_dvector_cosine_indexed(mtts_dvector* h, const float* a, int n_a, const float* b, int n_b, int dim, int n, const int* index_a, const int* index_b,
+                                double eps, float* sim) {
+    return h ? h->sc.cosine_indexed(a, n_a, b, n_b, dim, n, index_a, index_b, eps, sim) : -1;
+}
+int mtts_dvector_centroids(mtts_dvector* h, const float* vectors, const int* offsets, int n_speakers, int dim, float* out) {
+    return h ? h->sc.centroids(vectors, offsets, n_speakers, dim, out) : -1;
 }
 
 }  // extern "C"

@@ -1,0 +1,547 @@
+"""Speaker-similarity evaluation of a test run's result tree — the reference's `evaluation/` package on libmtts.so
+(evaluation/wavs_to_dvector.py, pair_similarity.py, centroid_similarity.py, speaker_verification.py:32-59,301-305).
+
+The hot path is wav -> d-vector: thousands of utterances, each about sixteen 160-frame partial utterances through LSTM(40, 256, 3).
+`SpeakerEmbedder` owns an `mtts_stft` handle at the speaker encoder's front-end configuration (n_fft 400, hop 160, 40 mels, 16 kHz)
+and an `mtts_dvector` handle, and sends whole batches of waveforms through ONE chain of launches (csrc/speakereval.h): packed STFT,
+power spectrum, mel projection, the partial windows gathered on the device, the encoder.  The cosine similarities and the speaker
+centroids are device kernels too (index arrays in place of the reference's np.repeat copies); the DET / ROC curves behind EER and AUC
+are a few hundred scores and run on the host in numpy (sklearn's det_curve / roc_curve / auc restated; sklearn is not imported).
+
+resemblyzer is not vendored by the reference and not part of this project: its `wav_to_mel_spectrogram` and
+`VoiceEncoder.compute_partial_slices` are restated here from the published recipe.  Its `preprocess_wav` (resampling to 16 kHz,
+-30 dBFS volume normalisation, webrtcvad silence trimming) is NOT built: every waveform handed to this module is taken as 16 kHz
+float32 as it is.  Figures (the reference's matplotlib / seaborn plots) are out of scope."""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+import random
+from typing import Callable, Dict, List, Optional, Sequence
+
+import numpy as np
+
+from .audio.stft import _Handle, forward_basis, mel_filterbank
+from .engine import MttsError
+from .speaker_encoder import EMBED, HIDDEN, LAYERS, MEL_N_CHANNELS, PARTIAL_FRAMES, DVectorEncoder
+
+SAMPLING_RATE = 16000          # resemblyzer hparams: sampling_rate
+MEL_WINDOW_LENGTH = 25         # ms -> n_fft = 400
+MEL_WINDOW_STEP = 10           # ms -> hop = 160
+N_FFT = SAMPLING_RATE * MEL_WINDOW_LENGTH // 1000
+HOP = SAMPLING_RATE * MEL_WINDOW_STEP // 1000
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def frame_step_of(rate: float = 1.3) -> int:
+    """Frames between two partial utterances: round(sampling_rate / rate / samples_per_frame) (np.round: half to even)."""
+    return int(np.round((SAMPLING_RATE / rate) / HOP))
+
+
+def compute_partial_slices(n_samples: int, rate: float = 1.3, min_coverage: float = 0.75):
+    """resemblyzer's `VoiceEncoder.compute_partial_slices`: (wav_slices, mel_slices) of the 160-frame windows every
+    `frame_step_of(rate)` frames; the last window is dropped when it covers less than `min_coverage` of its span and is not the
+    only one.  The caller zero-extends the waveform to wav_slices[-1].stop (preprocessor.py:272-274)."""
+    assert 0 < min_coverage <= 1
+    n_frames = -(-(int(n_samples) + 1) // HOP)                    # ceil((n_samples + 1) / samples_per_frame)
+    frame_step = frame_step_of(rate)
+    assert 0 < frame_step <= PARTIAL_FRAMES
+    wav_slices, mel_slices = [], []
+    steps = max(1, n_frames - PARTIAL_FRAMES + frame_step + 1)
+    for i in range(0, steps, frame_step):
+        mel_slices.append(slice(i, i + PARTIAL_FRAMES))
+        wav_slices.append(slice(i * HOP, (i + PARTIAL_FRAMES) * HOP))
+    last = wav_slices[-1]
+    coverage = (n_samples - last.start) / (last.stop - last.start)
+    if coverage < min_coverage and len(mel_slices) > 1:
+        mel_slices, wav_slices = mel_slices[:-1], wav_slices[:-1]
+    return wav_slices, mel_slices
+
+
+class SpeakerEmbedder:
+    """The speaker encoder end to end on the device.  `state_dict`: the resemblyzer `VoiceEncoder` weights in torch's names
+    (lstm.weight_ih_l0 ... linear.bias; None: deterministic synthetic weights, for tests and benchmarks); `encoder=False` builds the
+    front-end only (`reference_mel_slices` for preprocessing).  Waveforms are 16 kHz float32 and are NOT resampled, normalised or
+    trimmed (resemblyzer's `preprocess_wav` is not part of this project)."""
+
+    def __init__(self, state_dict=None, max_partials: int = 2048, max_utts: int = 256, hidden: int = HIDDEN, emb: int = EMBED, layers: int = LAYERS,
+                 rate: float = 1.3, min_coverage: float = 0.75, device: int = 0, lib_path=None, encoder: bool = True):
+        self.rate, self.min_coverage, self.frame_step = rate, min_coverage, frame_step_of(rate)
+        self.emb = emb
+        self._dev = _Handle(N_FFT, HOP, MEL_N_CHANNELS, SAMPLING_RATE * 60, device, lib_path)
+        self.lib = self._dev.lib
+        self.forward_basis = forward_basis(N_FFT, N_FFT, "hann")
+        self.mel_basis = mel_filterbank(SAMPLING_RATE, N_FFT, MEL_N_CHANNELS)
+        self._dev.check(self.lib.mtts_stft_load(self._dev.h, _ptr(self.forward_basis), _ptr(self.mel_basis)))
+        self.encoder = DVectorEncoder(state_dict, max_partials=max_partials, max_utts=max_utts, hidden=hidden, emb=emb, layers=layers, device=device,
+                                      lib_path=lib_path) if encoder else None
+
+    def set_streams(self, stft_stream: int, encoder_stream: Optional[int] = None):
+        """HIP streams of the two handles (the stages are ordered by events when they differ)."""
+        if self.lib.mtts_stft_set_stream(self._dev.h, C.c_void_p(stft_stream)) != 0:
+            raise RuntimeError("mtts_stft_set_stream failed")
+        if self.encoder is not None:
+            self.encoder.set_stream(stft_stream if encoder_stream is None else encoder_stream)
+
+    def close(self):
+        if self.encoder is not None:
+            self.encoder.close()
+        self._dev.close()
+
+    @staticmethod
+    def _pack(wavs):
+        ws = [np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1)) for w in wavs]
+        if not ws:
+            raise MttsError("no waveforms")
+        return ws, np.asarray([len(w) for w in ws], np.int32), np.ascontiguousarray(np.concatenate(ws))
+
+    def wav_to_mel_spectrogram(self, wavs) -> List[np.ndarray]:
+        """resemblyzer's `wav_to_mel_spectrogram` for a list of waveforms: [(T_u, 40) float32], T_u = len // 160 + 1."""
+        ws, n, packed = self._pack(wavs)
+        T = n // HOP + 1
+        mel = np.empty((int(T.sum()), MEL_N_CHANNELS), np.float32)
+        self._dev.check(self.lib.mtts_stft_power_mel_batch(self._dev.h, len(ws), _ptr(n), _ptr(packed), _ptr(mel)))
+        return np.split(mel, np.cumsum(T)[:-1])
+
+    def _run(self, wavs, want_vectors: bool, want_slices: bool):
+        ws, n, packed = self._pack(wavs)
+        counts = np.asarray([len(compute_partial_slices(int(k), self.rate, self.min_coverage)[1]) for k in n], np.int32)
+        got = np.empty(len(ws), np.int32)
+        out = np.empty((len(ws), self.emb), np.float32) if want_vectors else None
+        slices = np.empty((int(counts.sum()), PARTIAL_FRAMES, MEL_N_CHANNELS), np.float32) if want_slices else None
+        enc = self.encoder.h if want_vectors else None
+        self._dev.check(self.lib.mtts_dvector_embed_wavs(enc, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step,
+                                                         float(self.min_coverage), _ptr(out) if want_vectors else None, _ptr(got),
+                                                         _ptr(slices) if want_slices else None))
+        assert np.array_equal(got, counts), (got, counts)   # the device entry and compute_partial_slices state the same rule
+        return out, (np.split(slices, np.cumsum(counts)[:-1]) if want_slices else None)
+
+    def embed_utterances(self, wavs, return_slices: bool = False):
+        """`VoiceEncoder.embed_utterance` (rate 1.3, min_coverage 0.75) of a list of 16 kHz float32 waveforms -> (B, emb) float32, every
+        row L2-normalised.  One chain of launches per chunk of utterances (as many as fit the encoder's max_partials)."""
+        if self.encoder is None:
+            raise MttsError("SpeakerEmbedder(encoder=False) has no encoder")
+        out, slices = self._run(wavs, True, return_slices)
+        return (out, slices) if return_slices else out
+
+    def embed_utterance(self, wav):
+        return self.embed_utterances([wav])[0]
+
+    def reference_mel_slices(self, wav) -> np.ndarray:
+        """The `spk_ref_mel_slices` payload of preprocessor.py:263-299 for one waveform: (n_partials, 160, 40) float32."""
+        return self._run([wav], False, True)[1][0]
+
+    # ---- scoring kernels ---------------------------------------------------------------------------------------------------------
+    def _scorer(self):
+        if self.encoder is None:
+            raise MttsError("scoring runs on the encoder's handle: SpeakerEmbedder(encoder=False) has none")
+        return self.encoder
+
+    def cosine_similarity(self, a, b, index_a=None, index_b=None, eps: float = 1e-6) -> np.ndarray:
+        """nn.CosineSimilarity(dim=1, eps) of a[index_a[i]] and b[index_b[i]] (default: row i of each) -> float32 [n]."""
+        enc = self._scorer()
+        a, b = np.ascontiguousarray(np.asarray(a, np.float32)), np.ascontiguousarray(np.asarray(b, np.float32))
+        ia = np.ascontiguousarray(np.arange(len(a)) if index_a is None else index_a, dtype=np.int32)
+        ib = np.ascontiguousarray(np.arange(len(b)) if index_b is None else index_b, dtype=np.int32)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or len(ia) != len(ib):
+            raise ValueError(f"cosine_similarity: shapes {a.shape} {b.shape}, {len(ia)} / {len(ib)} indices")
+        sim = np.empty(len(ia), np.float32)
+        enc._check(self.lib.mtts_dvector_cosine_indexed(enc.h, _ptr(a), len(a), _ptr(b), len(b), a.shape[1], len(ia), _ptr(ia), _ptr(ib), float(eps), _ptr(sim)))
+        return sim
+
+    def centroids(self, enrollment_list) -> np.ndarray:
+        """wavs_to_dvector.py:176-183: per speaker, the mean of its (ragged) list of d-vectors, L2-normalised -> (n_speaker, dim) float32."""
+        enc = self._scorer()
+        lists = [np.asarray(v, np.float32).reshape(len(v), -1) for v in enrollment_list]
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in lists])]), dtype=np.int32)
+        vecs = np.ascontiguousarray(np.concatenate(lists, axis=0))
+        out = np.empty((len(lists), vecs.shape[1]), np.float32)
+        enc._check(self.lib.mtts_dvector_centroids(enc.h, _ptr(vecs), _ptr(off), len(lists), vecs.shape[1], _ptr(out)))
+        return out
+
+
+def read_wav_16k(path: str) -> np.ndarray:
+    """`preprocessor.read_wav` (signed PCM scaled by its full range, unsigned 8-bit re-centred, float as it is, channels averaged)
+    for a file that must be 16 kHz."""
+    from .preprocessor import read_wav
+    wav, rate = read_wav(path)
+    if int(rate) != SAMPLING_RATE:
+        raise MttsError(f"{path}: sampling rate {rate}, the speaker encoder takes {SAMPLING_RATE} Hz (no resampling here: pass a wav_loader that resamples)")
+    return wav
+
+
+# ---- the reference's class surface -----------------------------------------------------------------------------------------------------
+class EvalConfig:
+    """What evaluation/config.py holds: `corpus`, `data_dir_dict` ('recon', 'real', 'enrollment' and one entry per mode),
+    `n_speaker`, `n_sample`, `mode_step_list` = [(mode, [steps])], and `work_dir` under which npy/<corpus>/, json/<corpus>/ and
+    txt/<corpus>/ are written (the reference writes them under its working directory)."""
+
+    def __init__(self, corpus: str, data_dir_dict: Dict[str, str], n_speaker: int, n_sample: int, mode_step_list, work_dir: str = "."):
+        self.corpus, self.data_dir_dict, self.n_speaker, self.n_sample = corpus, dict(data_dir_dict), int(n_speaker), int(n_sample)
+        self.mode_step_list = [(m, list(s)) for m, s in mode_step_list]
+        self.work_dir = work_dir
+
+    def path(self, kind: str, name: str) -> str:
+        d = os.path.join(self.work_dir, kind, self.corpus)
+        os.makedirs(d, exist_ok=True)
+        return os.path.join(d, name)
+
+
+def _testing_dir(data_dir: str) -> str:
+    d = os.path.join(data_dir, "audio/Testing/step_100000")          # wavs_to_dvector.py:247-250
+    return d if os.path.exists(d) else os.path.join(data_dir, "audio/Testing")
+
+
+class WavsToDvector:
+    """wavs_to_dvector.py: every wav of a test run -> d-vectors, saved as npy/<corpus>/<mode>_dvector.npy (an existing file is loaded
+    instead, as in the reference).  `wav_loader(path) -> 16 kHz float32 waveform` (default: `read_wav_16k`).  All wavs of a mode go to
+    the device in one `embed_utterances` call."""
+
+    def __init__(self, config: EvalConfig, embedder: SpeakerEmbedder, wav_loader: Optional[Callable[[str], np.ndarray]] = None, pair_list=None,
+                 rng: Optional[random.Random] = None, run: bool = True):
+        self.config, self.embedder = config, embedder
+        self.corpus, self.data_dir_dict = config.corpus, config.data_dir_dict
+        self.n_sample, self.n_speaker, self.mode_step_list = config.n_sample, config.n_speaker, config.mode_step_list
+        self.wav_loader = wav_loader or read_wav_16k
+        self.rng = rng or random.Random()
+        with open(os.path.join(self.data_dir_dict["recon"], "test_SQids.json")) as f:
+            self.sq_list = json.load(f)
+        self.speaker_id_map, self.inv_speaker_id_map = self.get_speaker_id_map()
+        self.enrollment_filelist = self.get_enrollment_filelist()
+        self.real_filelist = self.get_real_filelist()
+        pair_json = config.path("json", "pair.json")
+        if pair_list is not None:
+            self.pair_list = pair_list
+        elif os.path.exists(pair_json):
+            with open(pair_json) as f:
+                self.pair_list = json.load(f)
+        else:
+            self.pair_list = self.get_and_save_pair_list()
+        if run:
+            self.dvector_list_dict = self.get_dvector()
+
+    def files_to_dvectors(self, paths: Sequence[str]) -> np.ndarray:
+        return self.embedder.embed_utterances([self.wav_loader(p) for p in paths])
+
+    def get_speaker_id_map(self):
+        fwd, inv = {}, {}
+        for speaker_id in range(self.n_speaker):
+            real = str(self.sq_list[speaker_id * self.n_sample]["qry_id"][0].split("_")[0])
+            fwd[speaker_id], inv[real] = real, speaker_id
+        return fwd, inv
+
+    def get_enrollment_filelist(self):
+        """All real wavs of each speaker (the reference takes a set; sorted here so that a run is reproducible)."""
+        out = []
+        for speaker_id in range(self.n_speaker):
+            wav_dir = os.path.join(self.data_dir_dict["enrollment"], self.speaker_id_map[speaker_id])
+            out.append([os.path.join(wav_dir, f) for f in sorted(os.listdir(wav_dir)) if f.endswith(".wav")])
+        return out
+
+    def get_real_filelist(self):
+        out = []
+        for speaker_id in range(self.n_speaker):
+            for sample_id in range(self.n_sample):
+                q = self.sq_list[speaker_id * self.n_sample + sample_id]
+                out.append(os.path.join(self.data_dir_dict["real"], self.speaker_id_map[speaker_id], q["qry_id"][0] + ".wav"))
+        return out
+
+    def get_and_save_pair_list(self):
+        """wavs_to_dvector.py:137-168: per test sample 4 positive files (the speaker's own) and 4 negative ones (one of each of 4 others)."""
+        pair_list = [dict() for _ in range(self.n_speaker * self.n_sample)]
+        for speaker_id in range(self.n_speaker):
+            for sample_id in range(self.n_sample):
+                data_id = speaker_id * self.n_sample + sample_id
+                pair_list[data_id]["p"] = [os.path.basename(p) for p in self.rng.sample(self.enrollment_filelist[speaker_id], 4)]
+                others = self.rng.sample([i for i in range(self.n_speaker) if i != speaker_id], 4)
+                pair_list[data_id]["n"] = [os.path.basename(self.rng.sample(self.enrollment_filelist[s], 1)[0]) for s in others]
+        with open(self.config.path("json", "pair.json"), "w", encoding="utf8") as fp:
+            json.dump(pair_list, fp)
+        return pair_list
+
+    def get_centroid_dvector_list(self, enrollment_list):
+        return self.embedder.centroids(enrollment_list)
+
+    def get_pair_dvector_list(self):
+        pos, neg = [], []
+        for data_id in range(self.n_speaker * self.n_sample):
+            pos += self.pair_list[data_id]["p"]
+            neg += self.pair_list[data_id]["n"]
+        path_of = lambda f: os.path.join(self.data_dir_dict["real"], f.split("_")[0], f)   # noqa: E731
+        both = self.files_to_dvectors([path_of(f) for f in pos + neg])
+        return np.stack([both[: len(pos)], both[len(pos):]])
+
+    def get_enrollment_dvector_list(self):
+        flat = self.files_to_dvectors([p for files in self.enrollment_filelist for p in files])
+        cuts = np.cumsum([len(files) for files in self.enrollment_filelist])[:-1]
+        out = np.empty(self.n_speaker, object)
+        out[:] = np.split(flat, cuts)
+        return out
+
+    def get_real_dvector_list(self):
+        return self.files_to_dvectors(self.real_filelist)
+
+    def _find(self, wav_dir: str, suffix: str) -> Optional[str]:
+        for wav_file in sorted(os.listdir(wav_dir)):     # (the reference takes the first os.listdir hit; a task directory holds one)
+            if wav_file.endswith(suffix):
+                return os.path.join(wav_dir, wav_file)
+        return None
+
+    def get_recon_dvector_list(self, data_dir: str):
+        root = _testing_dir(data_dir)
+        paths = [self._find(os.path.join(root, f"test_{data_id:03d}"), "recon.wav") for data_id in range(self.n_speaker * self.n_sample)]
+        return self.files_to_dvectors([p for p in paths if p is not None])
+
+    def get_syn_dvector_list(self, data_dir: str, step: int = 10):
+        """wavs_to_dvector.py:266-301, including the 1-shot layout test_###_0 .. test_###_4."""
+        root, paths = _testing_dir(data_dir), []
+        for data_id in range(self.n_speaker * self.n_sample):
+            d = os.path.join(root, f"test_{data_id:03d}")
+            if os.path.exists(d):
+                dirs = [d]
+            else:
+                assert os.path.exists(d + "_0"), d
+                dirs = [f"{d}_{i}" for i in range(5)]
+            for wav_dir in dirs:
+                p = self._find(wav_dir, f"FTstep_{step}.synth.wav")
+                if p is not None:
+                    paths.append(p)
+        return self.files_to_dvectors(paths)
+
+    def get_dvector(self):
+        d = {}
+        makers = {"enrollment": self.get_enrollment_dvector_list, "centroid": lambda: self.get_centroid_dvector_list(d["enrollment"]),
+                  "pair": self.get_pair_dvector_list, "real": self.get_real_dvector_list,
+                  "recon": lambda: self.get_recon_dvector_list(self.data_dir_dict["recon"])}
+        for mode in ["enrollment", "centroid", "pair", "real", "recon"]:
+            path = self.config.path("npy", f"{mode}_dvector.npy")
+            if os.path.exists(path):
+                d[mode] = np.load(path, allow_pickle=True)
+            else:
+                d[mode] = makers[mode]()
+                np.save(path, d[mode], allow_pickle=True)
+        for mode, steps in self.mode_step_list:
+            for step in steps:
+                path = self.config.path("npy", f"{mode}_step{step}_dvector.npy")
+                if os.path.exists(path):
+                    d[f"{mode}_step{step}"] = np.load(path, allow_pickle=True)
+                else:
+                    d[f"{mode}_step{step}"] = self.get_syn_dvector_list(self.data_dir_dict[mode], step)
+                    np.save(path, d[f"{mode}_step{step}"], allow_pickle=True)
+        return d
+
+
+class PairSimilarity:
+    """pair_similarity.py: cosine similarity of every test d-vector with its 4 positive and 4 negative enrollment d-vectors."""
+
+    def __init__(self, config: EvalConfig, embedder: SpeakerEmbedder):
+        self.config, self.embedder = config, embedder
+        self.corpus, self.mode_step_list = config.corpus, config.mode_step_list
+        self.dvector_list_dict, self.pair_similarity_dict = {}, {}
+
+    def _modes(self):
+        return ["recon", "real"] + [f"{m}_step{s}" for m, steps in self.mode_step_list for s in steps]
+
+    def load_dvector(self):
+        for mode in ["pair"] + self._modes():
+            self.dvector_list_dict[mode] = np.load(self.config.path("npy", f"{mode}_dvector.npy"), allow_pickle=True)
+
+    def compute_pair_similarity(self, check_list) -> np.ndarray:
+        """pair_similarity.py:68-88 -> [2, 4 * len(check_list)] (positive row, negative row).  The reference's np.repeat(check_list, 4)
+        and, in the five-fold layout, np.repeat(pair, 5, axis=1) are index arrays here."""
+        check = np.asarray(check_list, np.float32)
+        pair = np.asarray(self.dvector_list_dict["pair"], np.float32)
+        n = 4 * len(check)
+        it = np.arange(n, dtype=np.int32) // 4
+        if n == pair.shape[1]:
+            ip = np.arange(n, dtype=np.int32)
+        else:
+            assert n == pair.shape[1] * 5, (n, pair.shape)
+            ip = np.arange(n, dtype=np.int32) // 5
+        return np.stack([self.embedder.cosine_similarity(check, pair[0], it, ip), self.embedder.cosine_similarity(check, pair[1], it, ip)])
+
+    def get_pair_similarity(self):
+        for mode in self._modes():
+            path = self.config.path("npy", f"{mode}_pair_sim.npy")
+            if os.path.exists(path):
+                self.pair_similarity_dict[mode] = np.load(path, allow_pickle=True)
+            else:
+                self.pair_similarity_dict[mode] = self.compute_pair_similarity(self.dvector_list_dict[mode])
+                np.save(path, self.pair_similarity_dict[mode], allow_pickle=True)
+
+    def save_pair_similarity(self):
+        np.save(self.config.path("npy", "pair_similarity.npy"), self.pair_similarity_dict, allow_pickle=True)
+
+    def load_pair_similarity(self):
+        self.pair_similarity_dict = np.load(self.config.path("npy", "pair_similarity.npy"), allow_pickle=True)[()]
+
+
+def check_shuffle_map(map_list, n_speaker: int, n_sample: int):
+    """The invariants centroid_similarity.py:160-168 asserts: no sample is mapped to its own speaker's centroid, and every speaker's
+    centroid is drawn exactly n_sample times."""
+    m = np.asarray(map_list).reshape(-1)
+    if len(m) != n_speaker * n_sample or m.min() < 0 or m.max() >= n_speaker * n_sample:
+        raise ValueError("shuffle map: wrong length or index out of range")
+    spk = m // n_sample
+    if np.any(spk == np.arange(len(m)) // n_sample):
+        raise ValueError("shuffle map: a sample is mapped to its own speaker's centroid")
+    if np.any(np.bincount(spk, minlength=n_speaker) != n_sample):
+        raise ValueError("shuffle map: a speaker's centroid is not drawn n_sample times")
+
+
+def custom_shuffle_map(n_speaker: int, n_sample: int, rng: Optional[random.Random] = None) -> List[int]:
+    """centroid_similarity.py:134-159: a cross-speaker index map (into the n_sample-times repeated centroids), re-drawn until the last
+    speaker still has n_sample foreign slots to draw from."""
+    rng = rng or random.Random()
+    if n_speaker < 2:
+        raise ValueError("recon_random needs at least two speakers")
+    while True:
+        map_list, count, ok = [0] * (n_speaker * n_sample), [0] * n_speaker, True
+        for i in range(n_speaker):
+            pool = [j for j in range(n_speaker) if j != i for _ in range(n_sample - count[j])]
+            if len(pool) < n_sample:
+                ok = False
+                break
+            for t, tgt in enumerate(rng.sample(pool, n_sample)):
+                map_list[i * n_sample + t] = tgt * n_sample + count[tgt]
+                count[tgt] += 1
+        if ok:
+            check_shuffle_map(map_list, n_speaker, n_sample)
+            return map_list
+
+
+class CentroidSimilarity:
+    """centroid_similarity.py: cosine similarity of every test d-vector with its speaker's centroid, plus `recon_random` (recon
+    d-vectors against other speakers' centroids through a cross-speaker index map, supplied or generated)."""
+
+    def __init__(self, config: EvalConfig, embedder: SpeakerEmbedder, shuffle_map=None, rng: Optional[random.Random] = None):
+        self.config, self.embedder = config, embedder
+        self.n_speaker, self.n_sample, self.mode_step_list = config.n_speaker, config.n_sample, config.mode_step_list
+        self.shuffle_map = shuffle_map if shuffle_map is not None else custom_shuffle_map(self.n_speaker, self.n_sample, rng)
+        check_shuffle_map(self.shuffle_map, self.n_speaker, self.n_sample)
+        self.dvector_list_dict, self.similarity_list_dict = {}, {}
+
+    def load_dvector(self):
+        for mode in ["recon", "centroid", "real"] + [f"{m}_step{s}" for m, steps in self.mode_step_list for s in steps]:
+            self.dvector_list_dict[mode] = np.load(self.config.path("npy", f"{mode}_dvector.npy"), allow_pickle=True)
+
+    def compute_centroid_similarity(self, mode: str) -> np.ndarray:
+        cent = np.asarray(self.dvector_list_dict["centroid"], np.float32)
+        if mode == "recon_random":        # :77-80: shuffled, n_sample-times repeated centroids vs recon
+            test = np.asarray(self.dvector_list_dict["recon"], np.float32)
+            ic = np.asarray(self.shuffle_map, np.int32) // self.n_sample
+        else:
+            test = np.asarray(self.dvector_list_dict[mode], np.float32)
+            per = self.n_sample if len(test) == self.n_speaker * self.n_sample else 5 * self.n_sample   # :101-110 (five-fold layout)
+            assert len(test) == self.n_speaker * per, (len(test), self.n_speaker, per)
+            ic = np.arange(len(test), dtype=np.int32) // per
+        return self.embedder.cosine_similarity(cent, test, ic, np.arange(len(test), dtype=np.int32))
+
+    def get_centroid_similarity(self):
+        for mode in ["recon_random", "recon"] + [f"{m}_step{s}" for m, steps in self.mode_step_list for s in steps]:
+            path = self.config.path("npy", f"{mode}_centroid_sim.npy")
+            if os.path.exists(path):
+                self.similarity_list_dict[mode] = np.load(path, allow_pickle=True)
+            else:
+                self.similarity_list_dict[mode] = self.compute_centroid_similarity(mode)
+                np.save(path, self.similarity_list_dict[mode], allow_pickle=True)
+
+    def save_centroid_similarity(self):
+        np.save(self.config.path("npy", "centroid_similarity_dict.npy"), self.similarity_list_dict, allow_pickle=True)
+
+
+# ---- DET / ROC on the host (sklearn.metrics restated: _binary_clf_curve, det_curve, roc_curve(drop_intermediate=True), auc) ------------
+def _binary_clf_curve(y_true, y_score):
+    y_true, y_score = np.asarray(y_true).reshape(-1) == 1, np.asarray(y_score).reshape(-1)
+    order = np.argsort(y_score, kind="mergesort")[::-1]
+    y_score, y_true = y_score[order], y_true[order]
+    threshold_idxs = np.r_[np.where(np.diff(y_score))[0], y_true.size - 1]
+    tps = np.cumsum(y_true * 1.0, dtype=np.float64)[threshold_idxs]
+    fps = 1 + threshold_idxs - tps
+    return fps, tps, y_score[threshold_idxs]
+
+
+def det_curve(y_true, y_score, drop_intermediate: bool = False):
+    """(fpr, fnr, thresholds), false positives decreasing (sklearn 1.7's det_curve; drop_intermediate=False is its default and
+    what the reference's call gets)."""
+    if len(np.unique(np.asarray(y_true))) != 2:
+        raise ValueError("Only one class is present in y_true. Detection error tradeoff curve is not defined in that case.")
+    fps, tps, thresholds = _binary_clf_curve(y_true, y_score)
+    # a threshold at inf where everything is predicted negative (tps = fps = 0)
+    tps, fps, thresholds = np.concatenate(([0], tps)), np.concatenate(([0], fps)), np.concatenate(([np.inf], thresholds))
+    if drop_intermediate and len(fps) > 2:
+        keep = np.where(np.concatenate([[True], np.logical_or(np.diff(tps[:-1]), np.diff(tps[1:])), [True]]))[0]
+        fps, tps, thresholds = fps[keep], tps[keep], thresholds[keep]
+    fns = tps[-1] - tps
+    p_count, n_count = tps[-1], fps[-1]
+    first_ind = fps.searchsorted(fps[0], side="right") - 1 if fps.searchsorted(fps[0], side="right") > 0 else None
+    last_ind = tps.searchsorted(tps[-1]) + 1
+    sl = slice(first_ind, last_ind)
+    return fps[sl][::-1] / n_count, fns[sl][::-1] / p_count, thresholds[sl][::-1]
+
+
+def roc_curve(y_true, y_score):
+    fps, tps, thresholds = _binary_clf_curve(y_true, y_score)
+    if len(fps) > 2:
+        keep = np.where(np.r_[True, np.logical_or(np.diff(fps, 2), np.diff(tps, 2)), True])[0]
+        fps, tps, thresholds = fps[keep], tps[keep], thresholds[keep]
+    tps, fps, thresholds = np.r_[0, tps], np.r_[0, fps], np.r_[np.inf, thresholds]
+    return fps / fps[-1], tps / tps[-1], thresholds
+
+
+def auc(x, y) -> float:
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    dx = np.diff(x)
+    direction = 1
+    if np.any(dx < 0):
+        if not np.all(dx <= 0):
+            raise ValueError("x is neither increasing nor decreasing")
+        direction = -1
+    trapezoid = getattr(np, "trapezoid", None) or np.trapz
+    return float(direction * trapezoid(y, x))
+
+
+class SpeakerVerification:
+    """speaker_verification.py:32-59 (EER and its threshold per mode from the pair similarities, written to txt/<corpus>/<output>)
+    and :281-315 (AUC per mode: real positives against the mode's positives)."""
+
+    def __init__(self, config: EvalConfig, output_path: str = "eer.txt", det_drop_intermediate: bool = False):
+        self.config = config
+        self.output_path = config.path("txt", output_path)
+        self.det_drop_intermediate = det_drop_intermediate
+        self.pair_similarity_dict, self.threshold_dict, self.eer_dict, self.auc_dict = {}, {}, {}, {}
+
+    def load_pair_similarity(self):
+        self.pair_similarity_dict = np.load(self.config.path("npy", "pair_similarity.npy"), allow_pickle=True)[()]
+
+    def get_eer(self, write: bool = True):
+        for mode, s_list in self.pair_similarity_dict.items():
+            y_score = s_list.flatten()
+            y_true = np.ones_like(s_list)
+            y_true[1, :] = 0
+            fpr, fnr, thresholds = det_curve(y_true.flatten(), y_score, self.det_drop_intermediate)
+            min_index = np.argmin(np.abs(fpr - fnr))
+            self.eer_dict[mode] = np.mean((fpr[min_index], fnr[min_index]))
+            self.threshold_dict[mode] = thresholds[min_index]
+        if write:
+            with open(self.output_path, "w+") as f:
+                for mode in self.pair_similarity_dict:
+                    f.write(mode + ":\n")
+                    f.write(f"threshold:{self.threshold_dict[mode]:.4f}\t")
+                    f.write(f"EER:{self.eer_dict[mode]:.4f}\n")
+        return self.eer_dict
+
+    def get_auc(self):
+        real_score = self.pair_similarity_dict["real"][0]
+        for mode, s_list in self.pair_similarity_dict.items():
+            if s_list.shape[1] != len(real_score):   # the reference's labels assume as many real scores as mode scores (not the five-fold layout)
+                continue
+            y_score = np.concatenate([real_score, s_list[0]])
+            y_true = np.repeat(np.array([1, 0]), s_list.shape[1])
+            fpr, tpr, _ = roc_curve(y_true, y_score)
+            self.auc_dict[mode] = auc(fpr, tpr)
+        return self.auc_dict

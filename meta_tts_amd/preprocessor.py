@@ -284,9 +284,35 @@ class Preprocessor(_OnHandle):
             results[k] = Utterance(info, pitches[j][pkeep[j]], energies[j][ekeep[j]], int(mels[j].shape[0]), pparts[j].copy(), eparts[j].copy())
         return results
 
+    def speaker_reference_fn(self, embedder, wav_loader=None, resample=None):
+        """A ready-made `spk_ref_fn` for `build_from_path` / `process_utterances` (preprocessor.py:263-299): (speaker, basename) -> the
+        (n_partials, 160, 40) float32 `spk_ref_mel_slices` of the WHOLE raw file <raw_path>/<subset>/<speaker>/<basename>.wav, computed on
+        the device by `embedder` (a meta_tts_amd.evaluation.SpeakerEmbedder; `encoder=False` is enough).  The speaker encoder takes
+        16 kHz waveforms and resemblyzer's `preprocess_wav` (resampling, volume normalisation, silence trimming) is not part of this
+        project: a file at another rate needs `resample(wav, rate) -> 16 kHz float32 waveform`, else it is an error."""
+        from .evaluation import SAMPLING_RATE
+        wav_loader = wav_loader or read_wav
+        subsets = [d for ds in (self.train_set, self.val_set, self.test_set) for d in (ds if isinstance(ds, list) else [ds]) if isinstance(d, str)]
+
+        def spk_ref_fn(speaker, basename):
+            for dset in subsets:
+                path = os.path.join(self.in_dir, dset, speaker, f"{basename}.wav")
+                if os.path.exists(path):
+                    break
+            else:
+                raise MttsError(f"speaker reference: no raw wav for {speaker}/{basename}")
+            wav, rate = wav_loader(path)
+            if int(rate) != SAMPLING_RATE:
+                if resample is None:
+                    raise MttsError(f"{path}: sampling rate {rate}, the speaker encoder takes {SAMPLING_RATE} Hz (no resampling here: pass resample=)")
+                wav = resample(wav, rate)
+            return embedder.reference_mel_slices(np.asarray(wav, np.float32))
+        return spk_ref_fn
+
     def build_from_path(self, f0_fn=None, batch_utterances=32, wav_loader=None, spk_ref_fn=None):
         """preprocessor.py:60-185.  f0_fn(wav, sampling_rate, hop_length) -> float64[T] (default: pyworld); wav_loader(path) -> (float32
-        wav, rate) (default: scipy.io.wavfile); spk_ref_fn(speaker, basename) -> the spk_ref_mel_slices array (default: not written).
+        wav, rate) (default: scipy.io.wavfile); spk_ref_fn(speaker, basename) -> the spk_ref_mel_slices array (default: not written;
+        `speaker_reference_fn` makes one on the device).
         `batch_utterances` utterances share each device call.  Returns {subset: [metadata lines]}."""
         f0_fn = f0_fn or pyworld_f0
         wav_loader = wav_loader or read_wav

@@ -110,6 +110,17 @@ class DVectorEncoder:
                                                 out.ctypes.data_as(C.c_void_p), part.ctypes.data_as(C.c_void_p) if return_partials else None))
         return (out, part) if return_partials else out
 
+    def embed_device(self, mels_dev: int, n_partials: int, utt_offsets, return_partials=False):
+        """`embed` over a partial stack (n_partials, frames, n_mels) that is already on the device: `mels_dev` is its device address
+        (e.g. a torch tensor's data_ptr()); utt_offsets: the n_utts + 1 partial offsets.  The input projections name a fixed GEMM
+        kernel, so an utterance's d-vector does not depend on what else is in the batch."""
+        off = np.ascontiguousarray(utt_offsets, dtype=np.int32)
+        out = np.empty((len(off) - 1, self.cfg["emb"]), np.float32)
+        part = np.empty((int(n_partials), self.cfg["emb"]), np.float32) if return_partials else None
+        self._check(self.lib.mtts_dvector_embed_device(self.h, C.c_void_p(mels_dev), int(n_partials), off.ctypes.data_as(C.c_void_p), len(off) - 1,
+                                                       out.ctypes.data_as(C.c_void_p), part.ctypes.data_as(C.c_void_p) if return_partials else None))
+        return (out, part) if return_partials else out
+
     def __call__(self, args):
         ref_mels, ref_slices = args
         return self.embed_train(ref_mels, ref_slices) if self.training else self.embed(ref_mels, ref_slices)
