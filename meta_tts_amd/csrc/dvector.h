@@ -236,8 +236,9 @@ public:
     int last_N = 0, last_B = 0, adam_steps = 0;
     bool have_forward = false;
 
-    void set_error(const std::string& s) { last_error = s; }
-#define DV_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return -1; } } while (0)
+    DevHeap mem;   // every device block of this handle, the scoring workspace included (devres.h)
+    int err(const std::string& s) { last_error = s; return -1; }
+    void set_error(const std::string& s) { err(s); }
     long long find(const std::string& n) const { for (auto& t : tensors) if (t.name == n) return t.off; return -1; }
     int in_dim(int l) const { return l == 0 ? n_mels : H; }
 
@@ -255,52 +256,45 @@ public:
             add("lstm.bias_ih_l" + s, 4LL * H); add("lstm.bias_hh_l" + s, 4LL * H);
         }
         add("linear.weight", (long long)E * H); add("linear.bias", E);
-        DV_CHECK(hipMalloc((void**)&params, (size_t)n_params * sizeof(float)));
-        DV_CHECK(hipMemset(params, 0, (size_t)n_params * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&whhT, (size_t)layers * 4 * H * H * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&linT, (size_t)E * H * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&bsum, (size_t)layers * 4 * H * sizeof(float)));
+        DEV_CHECK(mem.alloc(params, (size_t)n_params * sizeof(float)));
+        DEV_CHECK(hipMemset(params, 0, (size_t)n_params * sizeof(float)));
+        DEV_CHECK(mem.alloc(whhT, (size_t)layers * 4 * H * H * sizeof(float)));
+        DEV_CHECK(mem.alloc(linT, (size_t)E * H * sizeof(float)));
+        DEV_CHECK(mem.alloc(bsum, (size_t)layers * 4 * H * sizeof(float)));
         const size_t rows = (size_t)cap_N * T;
-        DV_CHECK(hipMalloc((void**)&mels, (rows * n_mels + 64) * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&xp, rows * 4 * H * sizeof(float)));
-        for (int i = 0; i < 2; ++i) DV_CHECK(hipMalloc((void**)&hseq[i], (rows * H + 64) * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&hlast, (size_t)cap_N * H * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&part, (size_t)cap_N * E * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&out, (size_t)cap_B * E * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&off_dev, (size_t)(cap_B + 1) * sizeof(int)));
-        if (gx.alloc_workspace() != 0) { set_error("split-K workspace allocation failed"); return -1; }
+        DEV_CHECK(mem.alloc(mels, (rows * n_mels + 64) * sizeof(float)));
+        DEV_CHECK(mem.alloc(xp, rows * 4 * H * sizeof(float)));
+        for (int i = 0; i < 2; ++i) DEV_CHECK(mem.alloc(hseq[i], (rows * H + 64) * sizeof(float)));
+        DEV_CHECK(mem.alloc(hlast, (size_t)cap_N * H * sizeof(float)));
+        DEV_CHECK(mem.alloc(part, (size_t)cap_N * E * sizeof(float)));
+        DEV_CHECK(mem.alloc(out, (size_t)cap_B * E * sizeof(float)));
+        DEV_CHECK(mem.alloc(off_dev, (size_t)(cap_B + 1) * sizeof(int)));
+        if (gx.alloc_workspace(mem)) return err("out of device memory (split-K workspace)");
         return 0;
-    }
-    void destroy() {
-        for (float* p : {params, whhT, linT, bsum, mels, xp, hseq[0], hseq[1], hlast, part, out}) if (p) hipFree(p);
-        if (off_dev) hipFree(off_dev);
-        for (auto* v : {&gates, &cseq, &hprev, &hkeep}) for (float* p : *v) if (p) hipFree(p);
-        for (float* p : {dgates, dxbuf[0], dxbuf[1], eraw, dpart, dz, dh_last, dout, grads, adam_m, adam_v, ones4, sq_partial, sq_out}) if (p) hipFree(p);
-        gx.release();
     }
     int enable_training() {
         if (train_ready) return 0;
         const size_t rows = (size_t)cap_N * T;
-        gates.assign(layers, nullptr); cseq.assign(layers, nullptr); hprev.assign(layers, nullptr); hkeep.assign(layers, nullptr);
+        for (auto* v : {&gates, &cseq, &hprev, &hkeep}) v->resize(layers, nullptr);   // (what an earlier, failed attempt got is taken again below)
         for (int l = 0; l < layers; ++l) {
-            DV_CHECK(hipMalloc((void**)&gates[l], (rows * 4 * H + 64) * sizeof(float)));
-            DV_CHECK(hipMalloc((void**)&cseq[l], (rows * H + 64) * sizeof(float)));
-            DV_CHECK(hipMalloc((void**)&hprev[l], (rows * H + 64) * sizeof(float)));
-            DV_CHECK(hipMalloc((void**)&hkeep[l], (rows * H + 64) * sizeof(float)));
+            DEV_CHECK(mem.alloc(gates[l], (rows * 4 * H + 64) * sizeof(float)));
+            DEV_CHECK(mem.alloc(cseq[l], (rows * H + 64) * sizeof(float)));
+            DEV_CHECK(mem.alloc(hprev[l], (rows * H + 64) * sizeof(float)));
+            DEV_CHECK(mem.alloc(hkeep[l], (rows * H + 64) * sizeof(float)));
         }
-        DV_CHECK(hipMalloc((void**)&dgates, (rows * 4 * H + 64) * sizeof(float)));
-        for (int i = 0; i < 2; ++i) DV_CHECK(hipMalloc((void**)&dxbuf[i], (rows * H + 64) * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&eraw, (size_t)cap_N * E * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&dpart, (size_t)cap_N * E * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&dz, ((size_t)cap_N * E + 64) * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&dh_last, (size_t)cap_N * H * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&dout, (size_t)cap_B * E * sizeof(float)));
-        for (float** p : {&grads, &adam_m, &adam_v}) { DV_CHECK(hipMalloc((void**)p, (size_t)n_params * sizeof(float))); DV_CHECK(hipMemset(*p, 0, (size_t)n_params * sizeof(float))); }
-        DV_CHECK(hipMalloc((void**)&ones4, (rows * 4 + 64) * sizeof(float)));
+        DEV_CHECK(mem.alloc(dgates, (rows * 4 * H + 64) * sizeof(float)));
+        for (int i = 0; i < 2; ++i) DEV_CHECK(mem.alloc(dxbuf[i], (rows * H + 64) * sizeof(float)));
+        DEV_CHECK(mem.alloc(eraw, (size_t)cap_N * E * sizeof(float)));
+        DEV_CHECK(mem.alloc(dpart, (size_t)cap_N * E * sizeof(float)));
+        DEV_CHECK(mem.alloc(dz, ((size_t)cap_N * E + 64) * sizeof(float)));
+        DEV_CHECK(mem.alloc(dh_last, (size_t)cap_N * H * sizeof(float)));
+        DEV_CHECK(mem.alloc(dout, (size_t)cap_B * E * sizeof(float)));
+        for (float** p : {&grads, &adam_m, &adam_v}) { DEV_CHECK(mem.alloc(*p, (size_t)n_params * sizeof(float))); DEV_CHECK(hipMemset(*p, 0, (size_t)n_params * sizeof(float))); }
+        DEV_CHECK(mem.alloc(ones4, (rows * 4 + 64) * sizeof(float)));
         MTTS_LAUNCH(dv_fill_kernel, dim3(256), dim3(256), stream, ones4, 1.f, (long long)(rows * 4));
-        DV_CHECK(hipMalloc((void**)&sq_partial, 512 * sizeof(float)));
-        DV_CHECK(hipMalloc((void**)&sq_out, 4 * sizeof(float)));
-        DV_CHECK(hipMemset(sq_out, 0, 4 * sizeof(float)));
+        DEV_CHECK(mem.alloc(sq_partial, 512 * sizeof(float)));
+        DEV_CHECK(mem.alloc(sq_out, 4 * sizeof(float)));
+        DEV_CHECK(hipMemset(sq_out, 0, 4 * sizeof(float)));
         train_ready = true;
         return 0;
     }
@@ -308,7 +302,7 @@ public:
         for (auto& t : tensors)
             if (t.name == name) {
                 if (t.numel != numel) { set_error(std::string("size mismatch for ") + name); return -1; }
-                DV_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+                DEV_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
                 dirty = true;
                 return 0;
             }
@@ -325,7 +319,7 @@ public:
                         (const float*)(params + find("lstm.bias_hh_l" + s)), bsum + (long long)l * 4 * H, 4 * H);
         }
         MTTS_LAUNCH(dv_transpose_kernel, dim3(256), dim3(256), stream, (const float*)(params + find("linear.weight")), linT, E, H);
-        DV_CHECK(hipGetLastError());
+        DEV_CHECK(hipGetLastError());
         dirty = false;
         return 0;
     }
@@ -334,9 +328,9 @@ public:
         if (train && !train_ready) { set_error("mtts_dvector_enable_training first"); return -1; }
         if (check_batch(mels_host, N, utt_off, B, out_host) != 0) return -1;
         if (dirty && refresh() != 0) return -1;
-        DV_CHECK(hipMemcpyAsync(mels, mels_host, (size_t)N * T * n_mels * sizeof(float), hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipMemcpyAsync(mels, mels_host, (size_t)N * T * n_mels * sizeof(float), hipMemcpyHostToDevice, stream));
         if (forward(mels, N, utt_off, B, out_host, part_host, train, 0) != 0) return -1;
-        DV_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipStreamSynchronize(stream));
         return 0;
     }
     // The same forward over a partial stack that is already on the device (mels_dev [N][T][n_mels], read in place).  The input
@@ -346,7 +340,7 @@ public:
         if (check_batch(mels_dev, N, utt_off, B, out_host) != 0) return -1;
         if (dirty && refresh() != 0) return -1;
         if (forward(mels_dev, N, utt_off, B, out_host, part_host, false, 64) != 0) return -1;
-        if (sync) DV_CHECK(hipStreamSynchronize(stream));
+        if (sync) DEV_CHECK(hipStreamSynchronize(stream));
         return 0;
     }
     int check_batch(const float* mels_any, int N, const int* utt_off, int B, const float* out_host) {
@@ -359,7 +353,7 @@ public:
     // x0: [N][T][n_mels] on the device; tile: the input projections' GEMM tile code (0: through the launch queue)
     int forward(const float* x0, int N, const int* utt_off, int B, float* out_host, float* part_host, bool train, int tile) {
         const long long rows = (long long)N * T;
-        DV_CHECK(hipMemcpyAsync(off_dev, utt_off, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipMemcpyAsync(off_dev, utt_off, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
         const float* x = x0;
         for (int l = 0; l < layers; ++l) {
             const std::string s = std::to_string(l);
@@ -381,9 +375,9 @@ public:
         if (train) { last_N = N; last_B = B; have_forward = true; }
         MTTS_LAUNCH(dvec_utterance_kernel, dim3((unsigned)B), dim3((unsigned)((E + 63) & ~63)), stream, (const float*)part, (const int*)off_dev, out, E);
         if (gx.error) { set_error(std::string("GEMM launcher: ") + gx.error); gx.error = nullptr; return -1; }
-        DV_CHECK(hipGetLastError());
-        DV_CHECK(hipMemcpyAsync(out_host, out, (size_t)B * E * sizeof(float), hipMemcpyDeviceToHost, stream));
-        if (part_host) DV_CHECK(hipMemcpyAsync(part_host, part, (size_t)N * E * sizeof(float), hipMemcpyDeviceToHost, stream));
+        DEV_CHECK(hipGetLastError());
+        DEV_CHECK(hipMemcpyAsync(out_host, out, (size_t)B * E * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (part_host) DEV_CHECK(hipMemcpyAsync(part_host, part, (size_t)N * E * sizeof(float), hipMemcpyDeviceToHost, stream));
         return 0;
     }
 
@@ -402,8 +396,8 @@ public:
         const int N = last_N, B = last_B;
         const long long rows = (long long)N * T;
         const unsigned eb = (unsigned)((E + 63) & ~63);
-        DV_CHECK(hipMemsetAsync(grads, 0, (size_t)n_params * sizeof(float), stream));
-        DV_CHECK(hipMemcpyAsync(dout, dout_host, (size_t)B * E * sizeof(float), hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipMemsetAsync(grads, 0, (size_t)n_params * sizeof(float), stream));
+        DEV_CHECK(hipMemcpyAsync(dout, dout_host, (size_t)B * E * sizeof(float), hipMemcpyHostToDevice, stream));
         MTTS_LAUNCH(dvec_utterance_bwd_kernel, dim3((unsigned)B), dim3(eb), stream, (const float*)part, (const int*)off_dev, (const float*)dout, dpart, E);
         MTTS_LAUNCH(dvec_head_bwd_kernel, dim3((unsigned)N), dim3(eb), stream, (const float*)eraw, (const float*)dpart,
                     (const float*)(params + find("linear.weight")), dz, dh_last, H, E);
@@ -427,7 +421,7 @@ public:
                 dh_ext = dx;
             }
         }
-        DV_CHECK(hipGetLastError());
+        DEV_CHECK(hipGetLastError());
         have_forward = false;
         return 0;
     }
@@ -444,7 +438,7 @@ public:
         const float bc1 = 1.f - (float)std::pow((double)b1, (double)adam_steps), bc2 = 1.f - (float)std::pow((double)b2, (double)adam_steps);
         MTTS_LAUNCH(adam_clip_kernel, dim3(256), dim3(256), stream, params, (const float*)grads, adam_m, adam_v, n_params / 4, norm_dev,
                     norm_dev ? max_norm : 0.f, lr, b1, b2, eps, bc1, bc2, weight_decay);
-        DV_CHECK(hipGetLastError());
+        DEV_CHECK(hipGetLastError());
         dirty = true;
         return 0;
     }
@@ -456,8 +450,8 @@ public:
         for (auto& t : tensors)
             if (t.name == name) {
                 if (t.numel != numel) { set_error(std::string("size mismatch for ") + name); return -1; }
-                DV_CHECK(hipStreamSynchronize(stream));
-                DV_CHECK(hipMemcpy(out_host, base + t.off, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+                DEV_CHECK(hipStreamSynchronize(stream));
+                DEV_CHECK(hipMemcpy(out_host, base + t.off, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
                 return 0;
             }
         set_error(std::string("unknown d-vector tensor ") + name);
@@ -470,7 +464,7 @@ public:
         for (auto& t : tensors)
             if (t.name == name) {
                 if (t.numel != numel) { set_error(std::string("size mismatch for ") + name); return -1; }
-                DV_CHECK(hipMemcpy(base + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+                DEV_CHECK(hipMemcpy(base + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
                 return 0;
             }
         set_error(std::string("unknown d-vector tensor ") + name);

@@ -77,8 +77,6 @@ struct ParamEntry {
 
 struct TS { float* p; long long ts; };
 
-#define HIP_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return -1; } } while (0)
-
 class Engine {
 public:
     ModelCfg cfg;
@@ -86,6 +84,10 @@ public:
     int capMp, capMf, capMr;
     hipStream_t stream = nullptr;
     std::string last_error;
+    // Every device / pinned block and every single-purpose event of this handle (devres.h).  There is no destroy(): deleting the handle —
+    // mtts_destroy, or a create that failed half way — destroys the lanes below (each drains its stream first) and then this heap,
+    // which is declared before them for that reason.
+    DevHeap mem;
 
     // ---------------- parameter space -------------------------------------------------
     std::vector<ParamEntry> entries;
@@ -202,18 +204,15 @@ public:
     bool shadow_wait = false;                    // an asynchronous refresh is in flight: the next shadow reader waits for ev_shadow
     bool planes_wanted = true;                   // numerics mode 1 (planes) vs 2 (bf16 operands rounded in the staging pass only)
     int defer_tasks = 0;                 // task capacity of the deferred buffers (0: not available)
-    hipStream_t side = nullptr;
     static constexpr int kSideEvents = 32;   // more than the forks of one backward pass (19 at base.yaml): no event is re-recorded while a wait on it can be pending
-    hipEvent_t ev_side[kSideEvents] = {};
-    hipEvent_t ev_join = nullptr;
-    int ev_next = 0;
+    Lane<kSideEvents> side;
     GemmCtx gx_side;
     float* col_partial_side = nullptr;   // the side stream's own scratch of the two-stage column reduction
     // Encoder run-ahead (same regime): a non-adapted encoder does not depend on the fast weights, so the encoder forwards of ALL inner
     // steps (they differ only by their dropout seeds) are enqueued on a second side stream before the inner loop and overlap it; step s
     // waits for its event and reads the kept copy of the encoder output
     static constexpr int kAhead = 8;
-    hipStream_t side2 = nullptr;
+    Lane<kSideEvents> side2;
     hipEvent_t ev_enc[kAhead] = {};
     TS enc_ahead[kAhead];
     GemmCtx gx_side2;
@@ -254,7 +253,6 @@ public:
     struct GradSet { std::vector<LayerKeep> dec; TS dec_top{nullptr, 0}; std::vector<TS> post_cur; TS gRm{nullptr, 0}; };
     GradSet gs_alias;
     std::vector<GradSet> gs_steps;
-    std::vector<char*> gs_mem;
     int gs_bound = -1;                // -1: gs_alias
     GradSet& GK() { return gs_bound < 0 ? gs_alias : gs_steps[gs_bound]; }
     size_t act_bytes = 0;             // leading part of the arena: the activation set (layout_act)
@@ -277,7 +275,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     int site_base = 0;  // set by the caller of fft_* / pred_*: identifies the layer for the mask stream
     bool drop_active(const Pass& ps) const { return dropout_on && ps.train; }
 
-    void set_error(const std::string& s) { last_error = s; }
+    int err(const std::string& s) { last_error = s; return -1; }
+    void set_error(const std::string& s) { err(s); }
 
     // =================================================================================
     // construction
@@ -468,13 +467,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             GradSet g;
             arena_dry = true; arena_off = 0; layout_gradset(g);
             const size_t bytes = arena_off + 256;
-            char* mem = nullptr;
-            bool ok = hipMalloc((void**)&mem, bytes) == hipSuccess;
-            if (ok && hipMemset(mem, 0, bytes) != hipSuccess) { hipFree(mem); ok = false; }
-            if (ok) { arena = mem; arena_dry = false; arena_off = 0; layout_gradset(g); }
+            char* set = nullptr;
+            const bool ok = mem.alloc_zeroed(set, bytes) == hipSuccess;
+            if (ok) { arena = set; arena_dry = false; arena_off = 0; layout_gradset(g); }
             arena = save_arena; arena_off = save_off; arena_dry = save_dry;
-            if (!ok) { (void)hipGetLastError(); return false; }
-            gs_mem.push_back(mem);
+            if (!ok) { mem.give_back(set); return false; }
             gs_steps.push_back(g);
         }
         return true;
@@ -493,8 +490,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     bool ensure_act_sets(int n) {
         while ((int)act_sets.size() < n) {
             char* a = nullptr;
-            if (hipMalloc((void**)&a, act_bytes + 256) != hipSuccess) { (void)hipGetLastError(); return false; }
-            if (hipMemset(a, 0, act_bytes + 256) != hipSuccess) { hipFree(a); (void)hipGetLastError(); return false; }
+            if (mem.alloc_zeroed(a, act_bytes + 256) != hipSuccess) { mem.give_back(a); return false; }
             act_sets.push_back(a);
         }
         return true;
@@ -602,26 +598,26 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         capMf = G + cap_B * (cap_Tc + G);
         capMr = capMf;
         build_param_table();
-        HIP_CHECK(hipMalloc((void**)&theta, n_total * sizeof(float)));
-        HIP_CHECK(hipMalloc((void**)&adam_m, n_total * sizeof(float)));
-        HIP_CHECK(hipMalloc((void**)&adam_v, n_total * sizeof(float)));
+        DEV_CHECK(mem.alloc(theta, n_total * sizeof(float)));
+        DEV_CHECK(mem.alloc(adam_m, n_total * sizeof(float)));
+        DEV_CHECK(mem.alloc(adam_v, n_total * sizeof(float)));
         sync_tail = 8;   // 6 loss scalars (+ 2 pad), then per PostNet layer running mean | running var
         for (int i = 0; i < cfg.postnet_layers; ++i) sync_tail += 2LL * postP[i].cout;
         sync_tail = (sync_tail + 3) & ~3LL;
-        HIP_CHECK(hipMalloc((void**)&outer, (n_total + sync_tail) * sizeof(float)));
-        HIP_CHECK(hipMalloc((void**)&fast, (size_t)std::max<long long>(n_adapt, 4) * cap_tasks * sizeof(float)));
-        HIP_CHECK(hipMalloc((void**)&grad, (size_t)n_total * cap_tasks * sizeof(float)));
-        HIP_CHECK(hipMemset(theta, 0, n_total * sizeof(float)));
-        HIP_CHECK(hipMemset(adam_m, 0, n_total * sizeof(float)));
-        HIP_CHECK(hipMemset(adam_v, 0, n_total * sizeof(float)));
-        HIP_CHECK(hipMemset(outer, 0, (n_total + sync_tail) * sizeof(float)));
-        HIP_CHECK(hipMemset(grad, 0, (size_t)n_total * cap_tasks * sizeof(float)));
+        DEV_CHECK(mem.alloc(outer, (n_total + sync_tail) * sizeof(float)));
+        DEV_CHECK(mem.alloc(fast, (size_t)std::max<long long>(n_adapt, 4) * cap_tasks * sizeof(float)));
+        DEV_CHECK(mem.alloc(grad, (size_t)n_total * cap_tasks * sizeof(float)));
+        DEV_CHECK(hipMemset(theta, 0, n_total * sizeof(float)));
+        DEV_CHECK(hipMemset(adam_m, 0, n_total * sizeof(float)));
+        DEV_CHECK(hipMemset(adam_v, 0, n_total * sizeof(float)));
+        DEV_CHECK(hipMemset(outer, 0, (n_total + sync_tail) * sizeof(float)));
+        DEV_CHECK(hipMemset(grad, 0, (size_t)n_total * cap_tasks * sizeof(float)));
         fast_cur = fast; grad_dst = grad;
-        if (gx.alloc_workspace()) { set_error("hipMalloc failed (split-K workspace)"); return -1; }
+        if (gx.alloc_workspace(mem)) return err("out of device memory (split-K workspace)");
         if (init_defer() != 0) return -1;
         if (upd_setup() < 0) return -1;
-        HIP_CHECK(hipMalloc((void**)&norm_partial, 1024 * sizeof(float)));
-        HIP_CHECK(hipMalloc((void**)&norm_out, 4 * sizeof(float)));
+        DEV_CHECK(mem.alloc(norm_partial, 1024 * sizeof(float)));
+        DEV_CHECK(mem.alloc(norm_out, 4 * sizeof(float)));
         // frozen tables: sinusoid positions (Models.py:10-30, float64 math), linear bins
         pos_rows = std::max(cfg.max_seq_len + 1, std::max(cap_S, cap_T) + 1);
         std::vector<float> pt((size_t)pos_rows * cfg.d_model);
@@ -630,23 +626,23 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                 const double ang = (double)p / std::pow(10000.0, 2.0 * (double)(j / 2) / (double)cfg.d_model);
                 pt[(size_t)p * cfg.d_model + j] = (float)((j % 2 == 0) ? std::sin(ang) : std::cos(ang));
             }
-        HIP_CHECK(hipMalloc((void**)&pos_table, pt.size() * sizeof(float)));
-        HIP_CHECK(hipMemcpy(pos_table, pt.data(), pt.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMalloc((void**)&pitch_bins, cfg.n_bins * sizeof(float)));
-        HIP_CHECK(hipMalloc((void**)&energy_bins, cfg.n_bins * sizeof(float)));
+        DEV_CHECK(mem.alloc(pos_table, pt.size() * sizeof(float)));
+        DEV_CHECK(hipMemcpy(pos_table, pt.data(), pt.size() * sizeof(float), hipMemcpyHostToDevice));
+        DEV_CHECK(mem.alloc(pitch_bins, cfg.n_bins * sizeof(float)));
+        DEV_CHECK(mem.alloc(energy_bins, cfg.n_bins * sizeof(float)));
         set_bins(cfg.pitch_min, cfg.pitch_max, cfg.energy_min, cfg.energy_max);
         bn_rm.resize(cfg.postnet_layers); bn_rv.resize(cfg.postnet_layers); bn_tracked.assign(cfg.postnet_layers, 0);
         for (int i = 0; i < cfg.postnet_layers; ++i) {
             const int cc = postP[i].cout;
-            HIP_CHECK(hipMalloc((void**)&bn_rm[i], cc * sizeof(float)));
-            HIP_CHECK(hipMalloc((void**)&bn_rv[i], cc * sizeof(float)));
+            DEV_CHECK(mem.alloc(bn_rm[i], cc * sizeof(float)));
+            DEV_CHECK(mem.alloc(bn_rv[i], cc * sizeof(float)));
         }
         reset_bn();
         arena_dry = true; arena_off = 0;
         layout();
         arena_bytes = arena_off + 256;
-        HIP_CHECK(hipMalloc((void**)&arena, arena_bytes));
-        HIP_CHECK(hipMemset(arena, 0, arena_bytes));
+        DEV_CHECK(mem.alloc(arena, arena_bytes));
+        DEV_CHECK(hipMemset(arena, 0, arena_bytes));
         arena_dry = false; arena_off = 0;
         layout();
         return init_images();
@@ -678,12 +674,12 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         img.total = o;
         for (int sl = 0; sl < 2; ++sl) {
             Plan& p = plans[sl];
-            HIP_CHECK(hipMalloc((void**)&p.img_dev, img.total));
-            HIP_CHECK(hipMemset(p.img_dev, 0, img.mels));
+            DEV_CHECK(mem.alloc(p.img_dev, img.total));
+            DEV_CHECK(hipMemset(p.img_dev, 0, img.mels));
             for (int b = 0; b < 2; ++b) {
-                HIP_CHECK(hipHostMalloc((void**)&p.img_host[b], img.total));
+                DEV_CHECK(mem.alloc(p.img_host[b], img.total, true));
                 memset(p.img_host[b], 0, img.mels);
-                HIP_CHECK(hipEventCreate(&p.img_done[b]));
+                DEV_CHECK(mem.event(p.img_done[b]));
             }
             p.meta = (int*)(p.img_dev + img.meta);
             p.enc_seqs = (AttnSeq*)(p.img_dev + img.seq_e);
@@ -694,16 +690,6 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             }
         }
         return 0;
-    }
-    void destroy_images() {
-        for (int sl = 0; sl < 2; ++sl) {
-            Plan& p = plans[sl];
-            if (p.img_dev) hipFree(p.img_dev);
-            for (int b = 0; b < 2; ++b) {
-                if (p.img_host[b]) hipHostFree(p.img_host[b]);
-                if (p.img_done[b]) hipEventDestroy(p.img_done[b]);
-            }
-        }
     }
 
     void set_bins(float pmin, float pmax, float emin, float emax) {
@@ -746,9 +732,9 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                              (size_t)defer_tasks * 2 * ((size_t)cfg.enc_layers * ln_chunks(capMp) + (size_t)cfg.dec_layers * ln_chunks(capMf)) * 3 * d * sizeof(float) +
                              (size_t)defer_tasks * 3 * 2 * (size_t)ln_chunks(capMp) * 3 * cfg.vp_filter * sizeof(float) + 64 * 256 +
                              4096;
-        HIP_CHECK(hipMalloc((void**)&arena_defer, bytes));
+        DEV_CHECK(mem.alloc(arena_defer, bytes));
         arena_defer_bytes = bytes;
-        HIP_CHECK(hipMemset(arena_defer, 0, bytes));
+        DEV_CHECK(hipMemset(arena_defer, 0, bytes));
         char* cur = arena_defer;
         auto rows_d = [&](int capM, int C) {   // [defer_tasks][G + capM + G][C], pointer at row 0 (same shape as rows())
             const long long ts = (long long)(capM + 2 * G) * C;
@@ -772,7 +758,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (cap_tasks > defer_tasks && ln_fold_side_on()) {
             const size_t pe = (((size_t)cap_tasks * ln_chunks(capMp) * 3 * d * sizeof(float)) + 255) & ~(size_t)255;
             const size_t pd = (((size_t)cap_tasks * ln_chunks(capMf) * 3 * d * sizeof(float)) + 255) & ~(size_t)255;
-            HIP_CHECK(hipMalloc((void**)&arena_lnpart, 2 * (cfg.enc_layers * pe + cfg.dec_layers * pd) + 256));
+            DEV_CHECK(mem.alloc(arena_lnpart, 2 * (cfg.enc_layers * pe + cfg.dec_layers * pd) + 256));
             char* c2 = (char*)arena_lnpart;
             encLnPart.resize(2 * (size_t)cfg.enc_layers); decLnPart.resize(2 * (size_t)cfg.dec_layers);
             for (auto& q : encLnPart) { q = (float*)c2; c2 += pe; }
@@ -780,8 +766,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         }
         {   // the early predictor backward's buffers: every task of a launch (not only the deferred regime's)
             const long long ts = (long long)(capMp + 2 * G) * d;
-            HIP_CHECK(hipMalloc((void**)&arena_pred, (size_t)(4 + kAhead) * cap_tasks * ts * sizeof(float)));
-            HIP_CHECK(hipMemset(arena_pred, 0, (size_t)(4 + kAhead) * cap_tasks * ts * sizeof(float)));
+            DEV_CHECK(mem.alloc(arena_pred, (size_t)(4 + kAhead) * cap_tasks * ts * sizeof(float)));
+            DEV_CHECK(hipMemset(arena_pred, 0, (size_t)(4 + kAhead) * cap_tasks * ts * sizeof(float)));
             TS* const bufs[4] = {&gPxE, &gPxP, &gPxD, &gPx2};
             for (int i = 0; i < 4; ++i) *bufs[i] = TS{arena_pred + (long long)i * cap_tasks * ts + (long long)G * d, ts};
             for (int i = 0; i < kAhead; ++i) enc_ahead[i] = TS{arena_pred + (long long)(4 + i) * cap_tasks * ts + (long long)G * d, ts};   // (the encoder run-ahead's outputs)
@@ -789,19 +775,17 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         for (auto& pg : predG) { pg.g2a = rows_d(capMp, cfg.vp_filter); pg.g2b = rows_d(capMp, cfg.vp_filter); pg.part2 = part_d(capMp, cfg.vp_filter); pg.part1 = part_d(capMp, cfg.vp_filter); }
         postG.resize(cfg.postnet_layers);
         for (auto& t : postG) t = rows_d(capMr, post_c);
-        HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));   // non-blocking (a blocking stream would serialise with the legacy default stream on every launch)
-        for (auto& e : ev_side) HIP_CHECK(hipEventCreate(&e));
-        HIP_CHECK(hipEventCreate(&ev_join));
-        HIP_CHECK(hipEventCreate(&ev_pred));
-        HIP_CHECK(hipStreamCreateWithFlags(&side2, hipStreamNonBlocking));
-        for (auto& e : ev_enc) HIP_CHECK(hipEventCreate(&e));
+        DEV_CHECK(side.create());
+        DEV_CHECK(mem.event(ev_pred));
+        DEV_CHECK(side2.create());
+        for (auto& e : ev_enc) DEV_CHECK(mem.event(e));
         gx_side2.no_glds = gx_side.no_glds;
-        if (gx_side2.alloc_workspace()) { set_error("hipMalloc failed (split-K workspace of the run-ahead stream)"); return -1; }
+        if (gx_side2.alloc_workspace(mem)) return err("out of device memory (split-K workspace of the run-ahead stream)");
         const int side_chunks = (std::max(std::max(capMp, capMf), capMr) + kRC - 1) / kRC;   // == col_max_chunks (set by layout(), later)
         {   // (sized like col_partial: the early predictor backward runs its LayerNorm reductions through it too)
             const size_t ln_w = (size_t)std::max(cfg.d_model, cfg.vp_filter);
             const size_t per_task = std::max((size_t)side_chunks * 3 * 1024, (size_t)ln_chunks(std::max(std::max(capMp, capMf), capMr)) * 3 * ln_w);
-            HIP_CHECK(hipMalloc((void**)&col_partial_side, (size_t)cap_tasks * per_task * sizeof(float)));
+            DEV_CHECK(mem.alloc(col_partial_side, (size_t)cap_tasks * per_task * sizeof(float)));
         }
         gx_side.no_glds = true;
         // The weight-gradient side stream's launches take the BK = 16 kernels whatever their K (round 6): 20 KB of LDS per workgroup instead of 37, so a
@@ -809,7 +793,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // input gradient: 496 short tiles) no longer queues behind it.  Same k-ordered MFMA chain per tile, results equal to fp32 roundoff (tests/test_gpu_timed_config.py);
         // single-task rank 31.05 -> 30.70 ms, its second order 77.3 -> 76.6 ms, C2 fp32 12.81 -> 12.69 ms, 8-task step unchanged (profiles/r06_ab_log.md).
         { static const int bk16 = [] { const char* e = getenv("MTTS_SIDE_BK16"); return e ? atoi(e) : 1; }(); gx_side.prefer_bk16 = bk16 != 0; }
-        if (gx_side.alloc_workspace()) { set_error("hipMalloc failed (split-K workspace of the side stream)"); return -1; }
+        if (gx_side.alloc_workspace(mem)) return err("out of device memory (split-K workspace of the side stream)");
         return 0;
     }
     // =================================================================================
@@ -839,35 +823,30 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             for (ShadowEnt& e : v) { e.tile0 = t0; t0 += e.k * ((e.cout + 31) / 32) * ((e.cin + 31) / 32); }
             *n = (int)v.size(); *tiles = t0;
             if (v.empty()) return 0;
-            if (hipMalloc((void**)dev, v.size() * sizeof(ShadowEnt)) != hipSuccess) return -1;
+            if (mem.alloc(*dev, v.size() * sizeof(ShadowEnt)) != hipSuccess) return -1;
             return hipMemcpy(*dev, v.data(), v.size() * sizeof(ShadowEnt), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
         };
         if (finish(all, &d_ents_all, &n_ents_all, &tiles_all) || finish(th, &d_ents_theta, &n_ents_theta, &tiles_theta) ||
-            finish(fa, &d_ents_fast, &n_ents_fast, &tiles_fast)) { destroy_planes(); set_error("hipMalloc failed (weight shadow tables)"); return -1; }
+            finish(fa, &d_ents_fast, &n_ents_fast, &tiles_fast)) { destroy_planes(); return err("out of device memory (weight shadow tables)"); }
         // compact shadow vectors (every shadow starts on a multiple of 8 elements: 16-byte loads), one per task for the fast weights
         const size_t th_b = (size_t)(n_shadow + 8) * sizeof(bf16_t), fa_b = (size_t)cap_tasks * (size_t)n_shadow * sizeof(bf16_t) + 16;
-        if (hipMalloc((void**)&sh_theta_f, th_b) != hipSuccess || hipMalloc((void**)&sh_theta_t, th_b) != hipSuccess ||
-            (n_adapt > 0 && (hipMalloc((void**)&sh_fast_f, fa_b) != hipSuccess || hipMalloc((void**)&sh_fast_t, fa_b) != hipSuccess)) ||
-            hipMalloc((void**)&arena_h, arena_bytes / 2 + 64) != hipSuccess ||
-            (arena_defer && hipMalloc((void**)&arena_defer_h, arena_defer_bytes / 2 + 64) != hipSuccess)) {
+        if (mem.alloc(sh_theta_f, th_b) != hipSuccess || mem.alloc(sh_theta_t, th_b) != hipSuccess ||
+            (n_adapt > 0 && (mem.alloc(sh_fast_f, fa_b) != hipSuccess || mem.alloc(sh_fast_t, fa_b) != hipSuccess)) ||
+            mem.alloc(arena_h, arena_bytes / 2 + 64) != hipSuccess ||
+            (arena_defer && mem.alloc(arena_defer_h, arena_defer_bytes / 2 + 64) != hipSuccess)) {
             destroy_planes();
-            set_error("hipMalloc failed (bf16 operand planes: half the activation arena again + the weight shadows)");
-            return -1;
+            return err("out of device memory (bf16 operand planes: half the activation arena again + the weight shadows)");
         }
         hipMemset(arena_h, 0, arena_bytes / 2 + 64);
         if (arena_defer_h) hipMemset(arena_defer_h, 0, arena_defer_bytes / 2 + 64);
-        if (hipEventCreate(&ev_shadow) != hipSuccess) ev_shadow = nullptr;
+        (void)mem.event(ev_shadow);   // (without it the shadows are refreshed on the main stream)
         planes_ready = true;
         return 0;
     }
     void destroy_planes() {
-        for (void* q : {(void*)arena_h, (void*)arena_defer_h, (void*)sh_theta_f, (void*)sh_theta_t, (void*)sh_fast_f, (void*)sh_fast_t,
-                        (void*)d_ents_all, (void*)d_ents_theta, (void*)d_ents_fast})
-            if (q) hipFree(q);
-        if (ev_shadow) hipEventDestroy(ev_shadow);
-        ev_shadow = nullptr;
-        arena_h = arena_defer_h = sh_theta_f = sh_theta_t = sh_fast_f = sh_fast_t = nullptr;
-        d_ents_all = d_ents_theta = d_ents_fast = nullptr;
+        for (bf16_t** q : {&arena_h, &arena_defer_h, &sh_theta_f, &sh_theta_t, &sh_fast_f, &sh_fast_t}) mem.give_back(*q);
+        for (ShadowEnt** q : {&d_ents_all, &d_ents_theta, &d_ents_fast}) mem.give_back(*q);
+        mem.drop_event(ev_shadow);
         shadow_off.clear();
         planes_ready = false;
     }
@@ -883,10 +862,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         hipStream_t st = stream;
         async = async && side2 != nullptr && ev_shadow != nullptr;
         if (async) {
-            hipEvent_t ev = ev_side[ev_next];
-            ev_next = (ev_next + 1) % kSideEvents;
-            hipEventRecord(ev, stream);          // (after whatever last wrote the weights on this stream: the optimizer, the inner update)
-            hipStreamWaitEvent(side2, ev, 0);
+            side2.after(stream);                 // (after whatever last wrote the weights on this stream: the optimizer, the inner update)
             st = side2;
         }
         auto run = [&](const ShadowEnt* ents, int n, int tiles, const float* src, long long src_ts, bf16_t* f, bf16_t* t, long long dst_ts, int nt) {
@@ -933,39 +909,6 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         MTTS_LAUNCH(to_bf16_kernel, dim3((unsigned)std::min<long long>((n8 + 255) / 256, 4096)), dim3(256), stream, (const float*)(x.p - o), h - o, n8);
         return h;
     }
-    void destroy() {
-        ar_destroy();
-        upd_destroy();
-        if (side) { hipStreamSynchronize(side); hipStreamDestroy(side); }
-        for (auto& e : ev_side) if (e) hipEventDestroy(e);
-        if (ev_join) hipEventDestroy(ev_join);
-        if (ev_pred) hipEventDestroy(ev_pred);
-        if (side2) { hipStreamSynchronize(side2); hipStreamDestroy(side2); }
-        for (auto& e : ev_enc) if (e) hipEventDestroy(e);
-        gx_side2.release();
-        gx_side.release();
-        if (arena_defer) hipFree(arena_defer);
-        if (arena_lnpart) hipFree(arena_lnpart);
-        if (arena_pred) hipFree(arena_pred);
-        destroy_planes();
-        if (col_partial_side) hipFree(col_partial_side);
-        for (float* p : {theta, adam_m, adam_v, outer, fast, grad, norm_partial, norm_out, pos_table, pitch_bins, energy_bins})
-            if (p) hipFree(p);
-        for (float* p : bn_rm) hipFree(p);
-        for (float* p : bn_rv) hipFree(p);
-        gx.release();
-        destroy_imaml();
-        destroy_images();
-        if (arena) hipFree(arena);
-        for (char* a : act_sets) if (a) hipFree(a);
-        for (char* a : gs_mem) if (a) hipFree(a);
-        if (arena_so) hipFree(arena_so);
-        if (arena_so_defer) hipFree(arena_so_defer);
-        if (arena_so_defer_post) hipFree(arena_so_defer_post);
-        if (hv) hipFree(hv);
-        if (fast_hist) hipFree(fast_hist);
-    }
-
     // =================================================================================
     // parameter import / export (torch layout <-> internal layout)
     // =================================================================================
@@ -988,7 +931,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         }
         float* dst = which == 0 ? theta : (which == 4 ? adam_m : (which == 5 ? adam_v : nullptr));
         if (!dst) { set_error("bad import selector"); return -1; }
-        HIP_CHECK(hipMemcpy(dst + e.off, src, e.numel * sizeof(float), hipMemcpyHostToDevice));
+        DEV_CHECK(hipMemcpy(dst + e.off, src, e.numel * sizeof(float), hipMemcpyHostToDevice));
         return 0;
     }
 
@@ -1009,9 +952,9 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         else if (which == 5) src = adam_v + e.off;
         else if (which == 6 && hv) src = hv + (long long)task * n_total + e.off;
         else { set_error("bad export selector"); return -1; }
-        HIP_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipStreamSynchronize(stream));
         std::vector<float> tmp(e.numel);
-        HIP_CHECK(hipMemcpy(tmp.data(), src, e.numel * sizeof(float), hipMemcpyDeviceToHost));
+        DEV_CHECK(hipMemcpy(tmp.data(), src, e.numel * sizeof(float), hipMemcpyDeviceToHost));
         if (e.conv) {
             const int co = e.shape[0], ci = e.shape[1], k = e.shape[2];
             for (int o = 0; o < co; ++o)
@@ -1121,7 +1064,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         p.sumMp = p.sumMf = p.sumMr = p.sumLp = p.sumLf = 0;
         const int par = p.img_parity;
         p.img_parity ^= 1;
-        if (p.img_pending[par]) { HIP_CHECK(hipEventSynchronize(p.img_done[par])); p.img_pending[par] = false; }
+        if (p.img_pending[par]) { DEV_CHECK(hipEventSynchronize(p.img_done[par])); p.img_pending[par] = false; }
         char* H = p.img_host[par];
         int* meta = (int*)(H + img.meta);
         PlanTaskHdr* hdr = (PlanTaskHdr*)(H + img.hdr);
@@ -1234,8 +1177,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         }
         // ONE transfer: everything up to the mel area, plus the used part of the mel area
         const size_t bytes = any_mels ? img.mels + (size_t)mel_used * sizeof(float) : img.mels;
-        HIP_CHECK(hipMemcpyAsync(p.img_dev, H, bytes, hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipEventRecord(p.img_done[par], stream));
+        DEV_CHECK(hipMemcpyAsync(p.img_dev, H, bytes, hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipEventRecord(p.img_done[par], stream));
         p.img_pending[par] = true;
         PlanImage im;
         im.hdr = (const PlanTaskHdr*)(p.img_dev + img.hdr);
@@ -1601,7 +1544,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
 #endif
             GemmProfiler& prof = gx.prof;
             hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (prof.enabled) { e0 = prof.get(); e1 = prof.get(); hipEventRecord(e0, stream); }
+            if (prof.enabled) { e0 = prof.get(mem); e1 = prof.get(mem); hipEventRecord(e0, stream); }
             attn_fwd_launch(fa, L, groups, stream);
             if (prof.enabled) {
                 hipEventRecord(e1, stream);
@@ -1750,11 +1693,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // (the same floats are summed by the same collective, in pieces).
     struct ArHook { void* ctx = nullptr; int (*sum)(void*, float*, size_t, hipStream_t) = nullptr; int rank = 0, world = 1; };
     ArHook ar;
-    hipStream_t comm_stream = nullptr;
     static constexpr int kArEvents = 64;   // more than one exchange records (2 per bucket + the tail: 27 at base.yaml): no event is re-recorded while a wait on it can be pending
-    hipEvent_t ev_ar[kArEvents] = {};
-    hipEvent_t ev_ar_done = nullptr;
-    int ev_ar_next = 0;
+    Lane<kArEvents> comm_stream;
     std::vector<std::pair<long long, long long>> ar_buckets;   // [lo, hi) float ranges of outer[], completion order
     bool ar_armed = false, ar_active = false, ar_issued = false, ar_failed = false;
     int ar_next = 0, ar_nt = 0;
@@ -1769,11 +1709,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     int ar_idx_last() const { return 2 + cfg.dec_layers + cfg.enc_layers; }
     // streams / events and the bucket table; 0 when the overlapped exchange is available
     int ar_setup() {
-        if (!comm_stream) {
-            HIP_CHECK(hipStreamCreateWithFlags(&comm_stream, hipStreamNonBlocking));
-            for (auto& e : ev_ar) HIP_CHECK(hipEventCreate(&e));
-            HIP_CHECK(hipEventCreate(&ev_ar_done));
-        }
+        DEV_CHECK(comm_stream.create());
         return build_buckets(ar_buckets);
     }
     // the module buckets of the flat parameter buffer, in backward-completion order; 0 when the architecture has them all
@@ -1816,11 +1752,6 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (covered != n_total) { out.clear(); return 1; }   // (the buckets must tile the whole outer gradient)
         return 0;
     }
-    void ar_destroy() {
-        if (comm_stream) { hipStreamSynchronize(comm_stream); hipStreamDestroy(comm_stream); comm_stream = nullptr; }
-        for (auto& e : ev_ar) if (e) { hipEventDestroy(e); e = nullptr; }
-        if (ev_ar_done) { hipEventDestroy(ev_ar_done); ev_ar_done = nullptr; }
-    }
     // start of an overlapped exchange (the gradient call that fills outer[]): true when armed and possible
     bool ar_begin(int nt, float axpy = 0.f) {
         const bool go = ar_armed && ar.sum != nullptr && comm_stream != nullptr && !ar_buckets.empty();
@@ -1829,17 +1760,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         ar_active = true; ar_failed = false; ar_next = 0; ar_nt = nt; ar_axpy = axpy; ar_launches = 0;
         return true;
     }
-    void ar_wait_for(hipStream_t producer) {
-        hipEvent_t ev = ev_ar[ev_ar_next];
-        ev_ar_next = (ev_ar_next + 1) % kArEvents;
-        hipEventRecord(ev, producer);
-        hipStreamWaitEvent(comm_stream, ev, 0);
-    }
     // the exchange tail (final once the loss of the pass is known): packed on the main stream, reduced on the comm stream
     void ar_tail() {
         const float w = bn_sync_mode == 1 ? 1.f / (float)ar.world : (ar.rank == 0 ? 1.f : 0.f);
         if (sync_pack(w)) { ar_failed = true; return; }
-        ar_wait_for(stream);
+        comm_stream.after(stream);
         if (ar.sum(ar.ctx, outer + n_total, (size_t)sync_tail, comm_stream)) ar_failed = true;
         ++ar_launches;
     }
@@ -1848,8 +1773,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (!ar_active) return;
         if (upto >= (int)ar_buckets.size()) upto = (int)ar_buckets.size() - 1;
         if (ar_next > upto) return;
-        ar_wait_for(stream);
-        if (defer_live && side) ar_wait_for(side);
+        comm_stream.after(stream);
+        if (defer_live && side) comm_stream.after(side);
         for (; ar_next <= upto; ++ar_next) {
             const long long lo = ar_buckets[(size_t)ar_next].first, n = ar_buckets[(size_t)ar_next].second - lo;
             if (ar_axpy != 0.f)
@@ -1870,8 +1795,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     }
     // the main stream waits for the comm stream's collectives (before the clip + Adam reads outer[])
     void ar_join() {
-        hipEventRecord(ev_ar_done, comm_stream);
-        hipStreamWaitEvent(stream, ev_ar_done, 0);
+        comm_stream.join(stream);
         ar_issued = false;
     }
 
@@ -1882,11 +1806,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // runs on `upd_stream` the moment its module's parameter gradients are complete (and its weights have been read for the last time in
     // this backward: a module's input-gradient GEMMs come before its hook), under the matrix-core-bound backward of the modules below it.
     // Same kernel, same floats: bit-identical to the monolithic update (tests/test_deferred_paths.py).  MTTS_UPD_OVERLAP=0: one launch.
-    hipStream_t upd_stream = nullptr;
     static constexpr int kUpdEvents = 64;
-    hipEvent_t ev_upd[kUpdEvents] = {};
-    hipEvent_t ev_upd_done = nullptr;
-    int ev_upd_next = 0;
+    Lane<kUpdEvents> upd_stream;
     std::vector<std::pair<long long, long long>> upd_buckets;
     bool upd_active = false;
     int upd_next = 0, upd_nt = 0, upd_launches = 0;
@@ -1896,28 +1817,13 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         upd_buckets.clear();
         if (!on || n_adapt <= 0 || (adapt_start % 4) != 0 || (n_adapt % 4) != 0) return 1;
         if (build_buckets(upd_buckets)) return 1;
-        if (!upd_stream) {
-            HIP_CHECK(hipStreamCreateWithFlags(&upd_stream, hipStreamNonBlocking));
-            for (auto& e : ev_upd) HIP_CHECK(hipEventCreate(&e));
-            HIP_CHECK(hipEventCreate(&ev_upd_done));
-        }
+        DEV_CHECK(upd_stream.create());
         return 0;
-    }
-    void upd_destroy() {
-        if (upd_stream) { hipStreamSynchronize(upd_stream); hipStreamDestroy(upd_stream); upd_stream = nullptr; }
-        for (auto& e : ev_upd) if (e) { hipEventDestroy(e); e = nullptr; }
-        if (ev_upd_done) { hipEventDestroy(ev_upd_done); ev_upd_done = nullptr; }
     }
     bool upd_begin(int nt, float lr) {
         if (upd_stream == nullptr || upd_buckets.empty() || n_adapt <= 0 || inner_prox > 0.f) return false;
         upd_active = true; upd_next = 0; upd_nt = nt; upd_lr = lr; upd_launches = 0;
         return true;
-    }
-    void upd_wait_for(hipStream_t producer) {
-        hipEvent_t ev = ev_upd[ev_upd_next];
-        ev_upd_next = (ev_upd_next + 1) % kUpdEvents;
-        hipEventRecord(ev, producer);
-        hipStreamWaitEvent(upd_stream, ev, 0);
     }
     // modules 0 .. upto are done: their slices of the fast weights take the step
     void upd_ready(int upto) {
@@ -1929,8 +1835,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             const long long hi = std::min(upd_buckets[(size_t)upd_next].second, adapt_start + n_adapt);
             if (hi <= lo) continue;
             if (!waited) {
-                upd_wait_for(stream);
-                if (defer_live && side) upd_wait_for(side);
+                upd_stream.after(stream);
+                if (defer_live && side) upd_stream.after(side);
                 waited = true;
             }
             MTTS_LAUNCH(sgd_update_kernel, dim3(blocks_for((hi - lo) / 4), 1, upd_nt), dim3(256), upd_stream, fast + (lo - adapt_start),
@@ -1942,8 +1848,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     void upd_end() {
         upd_ready((int)upd_buckets.size() - 1);
         upd_active = false;
-        hipEventRecord(ev_upd_done, upd_stream);
-        hipStreamWaitEvent(stream, ev_upd_done, 0);
+        upd_stream.join(stream);
     }
     void module_done(int idx) { ar_ready(idx); upd_ready(idx); }
 
@@ -1962,17 +1867,13 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
 
     // everything enqueued on the main stream so far happens before what is enqueued on the side stream next
     void fork_side() {
-        hipEvent_t ev = ev_side[ev_next];
-        ev_next = (ev_next + 1) % kSideEvents;
-        hipEventRecord(ev, stream);
-        hipStreamWaitEvent(side, ev, 0);
+        side.after(stream);
         defer_live = true;
     }
     // the main stream waits for the side stream's weight gradients (before anything reads or overwrites what they touch)
     void join_side() {
         if (!defer_live) return;
-        hipEventRecord(ev_join, side);
-        hipStreamWaitEvent(stream, ev_join, 0);
+        side.join(stream);
         defer_live = false;
     }
 
@@ -2080,7 +1981,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         static const int on = [] { const char* e = getenv("MTTS_PRED_EARLY"); return e ? atoi(e) : 1; }();
         if (!on || !side_pred_ok(p) || any_frame_level()) return false;
         fork_side();
-        std::swap(stream, side);
+        std::swap(stream, side.s);
         std::swap(gx, gx_side);
         std::swap(col_partial, col_partial_side);
         site_base = 136; pred_bwd(ps, eneP, eneB, x1, dpred[2], gPxE, SP_P, nullptr, 0);
@@ -2088,7 +1989,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         site_base = 128; pred_bwd(ps, durP, durB, x0, dpred[0], gPxD, SP_P, nullptr, 0);
         std::swap(col_partial, col_partial_side);
         std::swap(gx, gx_side);
-        std::swap(stream, side);
+        std::swap(stream, side.s);
         hipEventRecord(ev_pred, side);
         return true;
     }
@@ -2129,11 +2030,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (query && (!q_on || !ahead_ok(*query) || cfg.enc_layers < 1)) query = nullptr;
         if (query) *query_seed = next_drop_seed();   // (the seed forward() would draw for the query pass: after the inner steps')
         refresh_shadows(Pass{&pl, true, true});   // (bf16 mode: the encoder's weight shadows, before the fork)
-        hipEvent_t ev = ev_side[ev_next];
-        ev_next = (ev_next + 1) % kSideEvents;
-        hipEventRecord(ev, stream);              // the batch image / plan kernels of this plan are on the main stream
-        hipStreamWaitEvent(side2, ev, 0);
-        std::swap(stream, side2);
+        side2.after(stream);                     // the batch image / plan kernels of this plan are on the main stream
+        std::swap(stream, side2.s);
         std::swap(gx, gx_side2);
         for (int s = 0; s < steps; ++s) {
             Pass pe{&pl, true, true};
@@ -2152,7 +2050,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             hipEventRecord(ev_enc[steps], stream);
         } else if (query_seed) *query_seed = 0;
         std::swap(gx, gx_side2);
-        std::swap(stream, side2);
+        std::swap(stream, side2.s);
         return true;
     }
     int forward(const Pass& ps) {
@@ -2200,11 +2098,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             static const bool pred_side = [] { const char* e = getenv("MTTS_PRED_SIDE"); return e ? atoi(e) != 0 : true; }();
             if (pred_side && side_pred_ok(p) && !defer_live) {
                 fork_side();
-                std::swap(stream, side);
+                std::swap(stream, side.s);
                 std::swap(gx, gx_side);
                 pred_fwd3(ps, PP, BB, XX, SS);
                 std::swap(gx, gx_side);
-                std::swap(stream, side);
+                std::swap(stream, side.s);
             } else {
                 pred_fwd3(ps, PP, BB, XX, SS);
             }
@@ -2344,8 +2242,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         MTTS_LAUNCH(plan_gather_durations_kernel, dim3(2, 1, nt), dim3(256), stream, (const int*)p.meta, (const float*)d_rounded.p, d_rounded.ts,
                     p.dur_readback, cap_B, cap_S);
         fr_host.resize((size_t)nt * bs);
-        HIP_CHECK(hipMemcpyAsync(fr_host.data(), p.dur_readback, (size_t)nt * bs * sizeof(float), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpyAsync(fr_host.data(), p.dur_readback, (size_t)nt * bs * sizeof(float), hipMemcpyDeviceToHost, stream));
+        DEV_CHECK(hipStreamSynchronize(stream));
         const int slot = (int)(&p - &plans[0]);
         for (int t = 0; t < nt; ++t) {
             TaskIn& in = p.in[t];
@@ -2701,8 +2599,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // encoder in front of the model back-propagates (speaker_emb: encoder / scratch_encoder)
     int get_speaker_grad(int task, int B, float* out_host) {
         if (task < 0 || task >= cap_tasks || B < 1 || B > cap_B || !out_host) { set_error("bad arguments"); return -1; }
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(out_host, dspk.p + (long long)task * dspk.ts, (size_t)B * cfg.d_model * sizeof(float), hipMemcpyDeviceToHost));
+        DEV_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpy(out_host, dspk.p + (long long)task * dspk.ts, (size_t)B * cfg.d_model * sizeof(float), hipMemcpyDeviceToHost));
         return 0;
     }
     // ---- the exchange step's tail: replicated side state that travels with the outer gradient ------------------------------------
@@ -2733,8 +2631,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         return 0;
     }
     int get_synced_losses(float* out6) {
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(out6, outer + n_total, 6 * sizeof(float), hipMemcpyDeviceToHost));
+        DEV_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpy(out6, outer + n_total, 6 * sizeof(float), hipMemcpyDeviceToHost));
         return 0;
     }
 
@@ -2751,8 +2649,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         MTTS_LAUNCH(adam_clip_kernel, dim3(blocks_for(n_total / 4)), dim3(256), stream, theta, g, adam_m, adam_v, n_total / 4,
                     (const float*)norm_out, max_norm, lr, b1, b2, eps, bc1, bc2, weight_decay);
         if (norm_out_host) {
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(norm_out_host, norm_out, sizeof(float), hipMemcpyDeviceToHost));
+            DEV_CHECK(hipStreamSynchronize(stream));
+            DEV_CHECK(hipMemcpy(norm_out_host, norm_out, sizeof(float), hipMemcpyDeviceToHost));
         }
         return 0;
     }

@@ -21,17 +21,12 @@ int enable_imaml() {
     if (im_ready) return 0;
     if (enable_second_order(1)) return -1;
     if (n_adapt <= 0) { set_error("iMAML needs at least one adapted module"); return -1; }
-    HIP_CHECK(hipMalloc((void**)&im_x, (size_t)n_adapt * cap_tasks * sizeof(float)));
-    HIP_CHECK(hipMalloc((void**)&im_r, (size_t)n_adapt * cap_tasks * sizeof(float)));
-    HIP_CHECK(hipMalloc((void**)&im_scal, (size_t)cap_tasks * IM_STRIDE * sizeof(float)));
-    HIP_CHECK(hipMalloc((void**)&im_partial, (size_t)cap_tasks * kImBlocks * sizeof(float)));
+    DEV_CHECK(mem.alloc(im_x, (size_t)n_adapt * cap_tasks * sizeof(float)));
+    DEV_CHECK(mem.alloc(im_r, (size_t)n_adapt * cap_tasks * sizeof(float)));
+    DEV_CHECK(mem.alloc(im_scal, (size_t)cap_tasks * IM_STRIDE * sizeof(float)));
+    DEV_CHECK(mem.alloc(im_partial, (size_t)cap_tasks * kImBlocks * sizeof(float)));
     im_ready = true;
     return 0;
-}
-void destroy_imaml() {
-    for (float* p : {im_x, im_r, im_scal, im_partial}) if (p) hipFree(p);
-    im_x = im_r = im_scal = im_partial = nullptr;
-    im_ready = false;
 }
 
 // out[task][slot] = sum_i a_i * (ca * b_i + cb * a_i)   (deterministic two-stage reduction)
@@ -52,7 +47,7 @@ int imaml_begin(float* losses_out) {
     if (loss(pq, losses_out ? losses_out : losses)) return -1;
     if (backward(pq, 1.f, encoder_adapted())) return -1;   // a non-adapted encoder's query gradient is not part of the hypergradient (see header)
     const float* b = grad + adapt_start;         // p lives in the per-task gradient buffer: it is what the HVP reads as direction
-    HIP_CHECK(hipMemsetAsync(im_x, 0, (size_t)n_adapt * cap_tasks * sizeof(float), stream));
+    DEV_CHECK(hipMemsetAsync(im_x, 0, (size_t)n_adapt * cap_tasks * sizeof(float), stream));
     MTTS_LAUNCH(copy_tasks_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream, b, n_total, im_r, n_adapt, n_adapt / 4);
     im_dot(im_r, n_adapt, im_r, n_adapt, 1.f, 0.f, IM_RS, nt);
     MTTS_LAUNCH(cg_scalar_kernel, dim3(1), dim3(64), stream, im_scal, nt, 0, 0.f);
@@ -87,13 +82,13 @@ int imaml_finish(float inner_lr, float reg, float grad_scale, float max_norm, fl
     const int nt = sp.tasks;
     im_dot(im_x, n_adapt, im_x, n_adapt, 1.f, 0.f, IM_NORM, nt);
     MTTS_LAUNCH(cg_clip_kernel, dim3(1), dim3(64), stream, im_scal, nt, inner_lr * reg, max_norm, grad_scale);
-    HIP_CHECK(hipMemsetAsync(outer, 0, (size_t)n_total * sizeof(float), stream));
+    DEV_CHECK(hipMemsetAsync(outer, 0, (size_t)n_total * sizeof(float), stream));
     MTTS_LAUNCH(sum_tasks_coef_kernel, dim3(blocks_for(n_adapt / 4)), dim3(256), stream, (const float*)im_x, n_adapt, nt, (const float*)im_scal,
                 (int)IM_STRIDE, (int)IM_COEF, outer + adapt_start, n_adapt / 4);
     if (norms_out_host) {
         std::vector<float> sc((size_t)nt * IM_STRIDE);
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(sc.data(), im_scal, sc.size() * sizeof(float), hipMemcpyDeviceToHost));
+        DEV_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpy(sc.data(), im_scal, sc.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (int t = 0; t < nt; ++t) norms_out_host[t] = sc[(size_t)t * IM_STRIDE + IM_NORM];
     }
     return 0;

@@ -98,17 +98,17 @@ int enable_second_order(int max_steps) {
         char* save_arena = arena; size_t save_off = arena_off; bool save_dry = arena_dry;
         arena_dry = true; arena_off = 0; layout_so();
         const size_t bytes = arena_off + 256;
-        HIP_CHECK(hipMalloc((void**)&arena_so, bytes));
-        HIP_CHECK(hipMemset(arena_so, 0, bytes));
+        DEV_CHECK(mem.alloc(arena_so, bytes));
+        DEV_CHECK(hipMemset(arena_so, 0, bytes));
         arena = arena_so; arena_dry = false; arena_off = 0; layout_so();
         arena = save_arena; arena_off = save_off; arena_dry = save_dry;
-        HIP_CHECK(hipMalloc((void**)&hv, (size_t)n_total * cap_tasks * sizeof(float)));
-        HIP_CHECK(hipMemset(hv, 0, (size_t)n_total * cap_tasks * sizeof(float)));
+        DEV_CHECK(mem.alloc(hv, (size_t)n_total * cap_tasks * sizeof(float)));
+        DEV_CHECK(hipMemset(hv, 0, (size_t)n_total * cap_tasks * sizeof(float)));
         if (defer_tasks > 0 && cfg.dec_layers > 0) {   // per-layer tangent-gradient buffers of the deferred hv(W) products (see TLayerGrad)
             const int d = cfg.d_model;
             const long long per_row = 4LL * d + cfg.d_ff + 3LL * d;
             const size_t bytes = (size_t)defer_tasks * cfg.dec_layers * (size_t)(capMf + 2 * G) * per_row * sizeof(float) + 4096;
-            if (hipMalloc((void**)&arena_so_defer, bytes) == hipSuccess && hipMemset(arena_so_defer, 0, bytes) == hipSuccess) {
+            if (mem.alloc_zeroed(arena_so_defer, bytes) == hipSuccess) {
                 char* cur = arena_so_defer;
                 auto rows_d = [&](int C) {
                     const long long ts = (long long)(capMf + 2 * G) * C;
@@ -119,15 +119,14 @@ int enable_second_order(int max_steps) {
                 tdecG.resize(cfg.dec_layers);
                 for (TLayerGrad& t : tdecG) { t.tdc = rows_d(d); t.tgh = rows_d(cfg.d_ff); t.tda = rows_d(d); t.tgqkv = rows_d(3 * d); t.dc = rows_d(d); t.da = rows_d(d); }
             } else {   // (the device cannot hold them: the hv(W) products stay in the tangent launches)
-                (void)hipGetLastError();
-                if (arena_so_defer) { hipFree(arena_so_defer); arena_so_defer = nullptr; }
+                mem.give_back(arena_so_defer);
                 tdecG.clear();
             }
         }
         if (defer_tasks > 0 && cfg.postnet_layers > 0) {
             const int pc = std::max(cfg.postnet_dim, cfg.n_mel);
             const size_t bytes = (size_t)defer_tasks * cfg.postnet_layers * 2 * (size_t)(capMr + 2 * G) * pc * sizeof(float) + 4096;
-            if (hipMalloc((void**)&arena_so_defer_post, bytes) == hipSuccess && hipMemset(arena_so_defer_post, 0, bytes) == hipSuccess) {
+            if (mem.alloc_zeroed(arena_so_defer_post, bytes) == hipSuccess) {
                 char* cur = arena_so_defer_post;
                 auto rows_r = [&](int C) {
                     const long long ts = (long long)(capMr + 2 * G) * C;
@@ -138,14 +137,13 @@ int enable_second_order(int max_steps) {
                 tpostG.resize(cfg.postnet_layers);
                 for (TPostGrad& t : tpostG) { t.dc = rows_r(pc); t.tdc = rows_r(pc); }
             } else {
-                (void)hipGetLastError();
-                if (arena_so_defer_post) { hipFree(arena_so_defer_post); arena_so_defer_post = nullptr; }
+                mem.give_back(arena_so_defer_post);
                 tpostG.clear();
             }
         }
     }
-    if (fast_hist) hipFree(fast_hist);
-    HIP_CHECK(hipMalloc((void**)&fast_hist, (size_t)std::max<long long>(n_adapt, 4) * cap_tasks * max_steps * sizeof(float)));
+    so_steps_cap = 0;   // (the history goes back to the heap before it is taken again: nothing to replay until the new one is there)
+    DEV_CHECK(mem.alloc(fast_hist, (size_t)std::max<long long>(n_adapt, 4) * cap_tasks * max_steps * sizeof(float)));
     so_steps_cap = max_steps;
     so_ready = true;
     return 0;
@@ -392,7 +390,7 @@ int forward_t(const Pass& ps) {
         MTTS_LAUNCH(speaker_vec_kernel, dim3(p.maxB, 1, nt), dim3(64), stream, (const int*)p.meta, (const float*)ttab.p, ttab.ts,
                     (const int*)p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, t_spk.p, t_spk.ts, d);
     } else {
-        HIP_CHECK(hipMemsetAsync(t_spk.p, 0, (size_t)t_spk.ts * nt * sizeof(float), stream));
+        DEV_CHECK(hipMemsetAsync(t_spk.p, 0, (size_t)t_spk.ts * nt * sizeof(float), stream));
     }
     if (encoder_adapted()) {
         // tangent of the embedding output: the token rows of the word table's tangent (the position table is frozen; invalid rows carry
@@ -741,7 +739,7 @@ int meta_grad_so(int steps, float inner_lr, float grad_scale, float* losses_out,
     unsigned qseed = 0;
     const bool ahead = run_encoder_ahead(sp, steps, ahead_seeds, keep, &qp, &qseed);   // engine.h: the (non-adapted) encoder's forwards of all steps (+ the query pass's), on side2
     for (int s = 0; s < steps; ++s) {
-        HIP_CHECK(hipMemcpyAsync(fast_hist + (long long)s * cap_tasks * hist_ts, fast, (size_t)n_adapt * nt * sizeof(float),
+        DEV_CHECK(hipMemcpyAsync(fast_hist + (long long)s * cap_tasks * hist_ts, fast, (size_t)n_adapt * nt * sizeof(float),
                                  hipMemcpyDeviceToDevice, stream));
         if (keep) bind_act(s + 1);
         gs_bound = keep_grad ? s : -1;

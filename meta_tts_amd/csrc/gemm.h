@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "compat.h"
+#include "devres.h"
 
 namespace mtts {
 
@@ -1080,12 +1081,11 @@ struct GemmProfiler {
     std::vector<hipEvent_t> pool;
     size_t used = 0;
     bool enabled = false;
-    hipEvent_t get() {
-        if (used == pool.size()) { hipEvent_t e; hipEventCreate(&e); pool.push_back(e); }
+    hipEvent_t get(DevHeap& heap) {   // (the pool's events belong to the owner's heap)
+        if (used == pool.size()) { hipEvent_t e = nullptr; heap.event(e); pool.push_back(e); }
         return pool[used++];
     }
     void reset() { recs.clear(); used = 0; }
-    void destroy() { for (hipEvent_t e : pool) hipEventDestroy(e); pool.clear(); recs.clear(); used = 0; }
     // out[kind][4] = launches, total ms, total algorithmic flops, total algorithmic bytes
     void report(double out[GK_COUNT][4]) {
         for (int k = 0; k < GK_COUNT; ++k) out[k][0] = out[k][1] = out[k][2] = out[k][3] = 0.0;
@@ -1121,7 +1121,7 @@ inline int gemm_xcd_swizzle() { return kGemmXcdSwizzle; }
 inline int gemm_default_bk() { return kGemmDefaultBk; }
 inline bool gemm_default_pipe() { return kGemmDefaultPipe; }
 
-// Split-K workspace (partial tiles + tile counters): owned by a GemmCtx, allocated once by its owner's create.
+// Split-K workspace (partial tiles + tile counters): used by one GemmCtx, allocated once from its owner's heap by the owner's create.
 struct GemmWorkspace { float* ws = nullptr; int* ctr = nullptr; };
 constexpr long long kSplitWsFloats = 16ll << 20;  // 64 MB of partial tiles
 constexpr int kSplitCtrs = 1 << 16;
@@ -1151,17 +1151,16 @@ struct GemmCtx {
     bool prefer_bk16 = false;   // multi-problem launches of this context take the BK = 16 kernels (20 KB of LDS per workgroup instead of 37) whatever their K
     int wave_prio = 0;      // GemmArgs::wave_prio of every launch of this context (the engine sets it on the critical stream's context while side streams carry work)
     bool no_glds = false;   // never pick the LDS-DMA kernels (48 KB of LDS per workgroup: a side-stream launch would leave no LDS for the main stream's)
-    int alloc_workspace() {
+    DevHeap* heap = nullptr;   // the owner's: the workspace and the profiler's events come from it and go back with it
+    int alloc_workspace(DevHeap& h) {
+        heap = &h;
         if (wsp.ws) return 0;
-        if (hipMalloc((void**)&wsp.ws, kSplitWsFloats * sizeof(float)) != hipSuccess || hipMalloc((void**)&wsp.ctr, (kSplitCtrs + 16) * sizeof(int)) != hipSuccess ||
-            hipMemset(wsp.ctr, 0, (kSplitCtrs + 16) * sizeof(int)) != hipSuccess) { release(); return -1; }
+        if (h.alloc(wsp.ws, kSplitWsFloats * sizeof(float)) != hipSuccess || h.alloc_zeroed(wsp.ctr, (kSplitCtrs + 16) * sizeof(int)) != hipSuccess) {
+            h.give_back(wsp.ws);
+            h.give_back(wsp.ctr);
+            return -1;
+        }
         return 0;
-    }
-    void release() {
-        if (wsp.ws) hipFree(wsp.ws);
-        if (wsp.ctr) hipFree(wsp.ctr);
-        wsp.ws = nullptr; wsp.ctr = nullptr;
-        prof.destroy();
     }
 };
 // LnFuse (requested by the caller through g.ln.y): can this launch carry it, and its counter slice.  `used` = counters already handed out
@@ -1332,7 +1331,7 @@ inline void gemm_launch(GemmCtx& cx, int form, const GemmArgs& g_in, int max_M, 
     }
     GemmProfiler& prof = cx.prof;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof.enabled) { e0 = prof.get(); e1 = prof.get(); hipEventRecord(e0, stream); }
+    if (prof.enabled) { e0 = prof.get(*cx.heap); e1 = prof.get(*cx.heap); hipEventRecord(e0, stream); }
     int kind = GK_OTHER;
 #define MTTS_GEMM_CASE(F, T)                                                                              \
     if (form == F && tile == T) {                                                                         \
@@ -1497,7 +1496,7 @@ inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream) {
         flops += p.flops; rows += p.rows; bytes += p.bytes;
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof.enabled) { e0 = prof.get(); e1 = prof.get(); hipEventRecord(e0, stream); }
+    if (prof.enabled) { e0 = prof.get(*cx.heap); e1 = prof.get(*cx.heap); hipEventRecord(e0, stream); }
     dim3 block(256), grid((unsigned)mp.start[mp.n], 1, 1);
     // BK = 32 stages K-contiguous operands in full 128-byte lines (half the load instructions, TA transactions and barriers
     // per flop); needs every tapped problem's tap length to be a multiple of 32 and pays off only for long K.  Default since round 3

@@ -135,20 +135,14 @@ public:
     DevBuf<int> melmap;                // inv_mel's row map: the last mel frame of every utterance dropped
     std::vector<int> h_melmap;
 
-    int err(const std::string& s) { return mf->err(s); }   // (MF_CHECK)
-    void destroy() {
-        for (float* p : {invT, win2}) if (p) hipFree(p);
-        invT = win2 = nullptr;
-        for (DevBuf<float>* b : {&frames, &ang, &emel}) b->release();
-        melmap.release();
-    }
+    int err(const std::string& s) { return mf->err(s); }   // (DEV_CHECK)
 
     // inverse_basis: [2F][n_fft] (stft.py:33-45: pinv(scale * fourier_basis).T, float32, x window); window_sq: [n_fft] (window_sumsquare)
     int load(const float* inverse_basis, const float* window_sq) {
         const int n_fft = mf->n_fft, F = mf->F, ld = mf->ld_spec;
         if (!inverse_basis || !window_sq) return err("mtts_stft_load_inverse: NULL inverse basis or squared window");
-        if (!invT && hipMalloc((void**)&invT, (size_t)n_fft * ld * sizeof(float)) != hipSuccess) { invT = nullptr; return err("hipMalloc failed (inverse basis)"); }
-        if (!win2 && hipMalloc((void**)&win2, (size_t)n_fft * sizeof(float)) != hipSuccess) { win2 = nullptr; return err("hipMalloc failed (window)"); }
+        if (!invT && mf->mem.alloc(invT, (size_t)n_fft * ld * sizeof(float)) != hipSuccess) return err("out of device memory (inverse basis)");
+        if (!win2 && mf->mem.alloc(win2, (size_t)n_fft * sizeof(float)) != hipSuccess) return err("out of device memory (window)");
         std::vector<float> t((size_t)n_fft * ld, 0.f);
         for (int c = 0; c < 2 * F; ++c)
             for (int k = 0; k < n_fft; ++k) t[(size_t)k * ld + c] = inverse_basis[(size_t)c * n_fft + k];
@@ -173,9 +167,9 @@ public:
         mf->forward_stft(T, nullptr, 0);
         MTTS_LAUNCH(gl_mag_phase_kernel, dim3(512), dim3(256), st, (const float*)mf->spec, mf->ld_spec, T, F, mf->mag.p, ang.p);
         if (mf->check_launch()) return -1;
-        MF_CHECK(hipMemcpyAsync(mag_host, mf->mag, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipMemcpyAsync(phase_host, ang, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipStreamSynchronize(st));
+        DEV_CHECK(hipMemcpyAsync(mag_host, mf->mag, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipMemcpyAsync(phase_host, ang, (size_t)T * F * sizeof(float), hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipStreamSynchronize(st));
         return T;
     }
 
@@ -185,7 +179,7 @@ public:
         if (!mag_host) return err("mtts_stft_griffin_lim: NULL magnitude");
         if (prepare(n_utts, n_frames, ang_host, n_iters, out_host)) return -1;
         const int F = mf->F;
-        MF_CHECK(hipMemcpyAsync(mf->mag, mag_host, (size_t)mf->n_frames * F * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+        DEV_CHECK(hipMemcpyAsync(mf->mag, mag_host, (size_t)mf->n_frames * F * sizeof(float), hipMemcpyHostToDevice, mf->stream));
         return run(mf->mag, F, n_iters, out_host);
     }
 
@@ -206,8 +200,8 @@ public:
         if (mf->grow(mf->mel, (size_t)mrows * n_mel, "log-mel") || mf->grow(emel, (size_t)mrows * ldm + 64, "exp(mel)") || mf->grow(melmap, (size_t)mrows, "mel row map"))
             return -1;
         hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(mf->mel, log_mel, (size_t)mrows * n_mel * sizeof(float), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(melmap, h_melmap.data(), (size_t)mrows * sizeof(int), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(mf->mel, log_mel, (size_t)mrows * n_mel * sizeof(float), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(melmap, h_melmap.data(), (size_t)mrows * sizeof(int), hipMemcpyHostToDevice, st));
         MTTS_LAUNCH(gl_exp_rows_kernel, dim3(512), dim3(256), st, (const float*)mf->mel, (int)mrows, n_mel, emel.p, ldm);
         {   // magnitude [sum T][F] = 1000 * exp(mel)[sum Tm][n_mel] * mel_basis[n_mel][F], the last frame of each utterance dropped
             GemmArgs g;
@@ -236,7 +230,7 @@ private:
         }
         const size_t rows = (size_t)mf->n_frames;
         if (mf->stage("Griffin-Lim", true) || mf->grow(frames, rows * n_fft + 64, "frames") || mf->grow(ang, rows * F, "angles")) return -1;
-        MF_CHECK(hipMemcpyAsync(ang, ang_host, rows * F * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+        DEV_CHECK(hipMemcpyAsync(ang, ang_host, rows * F * sizeof(float), hipMemcpyHostToDevice, mf->stream));
         return 0;
     }
 
@@ -264,8 +258,8 @@ private:
             MTTS_LAUNCH(gl_phasor_kernel, dim3(1024), dim3(256), st, R, ld, M, ldm, (int)rows, F);
         }
         if (mf->check_launch()) return -1;
-        MF_CHECK(hipMemcpyAsync(out_host, mf->wav, (size_t)mf->n_samples * sizeof(float), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipStreamSynchronize(st));
+        DEV_CHECK(hipMemcpyAsync(out_host, mf->wav, (size_t)mf->n_samples * sizeof(float), hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipStreamSynchronize(st));
         return mf->n_samples;
     }
 };

@@ -14,7 +14,7 @@
 //     at a multiple of hop, so ONE forward GEMM covers all of them, and the rows that straddle two signals are dropped through
 //     GemmArgs::c_rowmap (the spectrum lands compact, [sum T] rows).  A single-utterance entry stages without the map;
 //   * stft_reflect_pad_kernel (clip on or off), forward_stft (the overlapping-row GEMM), mel_from_spectrum (magnitude + energy, mel
-//     GEMM, log-clamp, download), check_launch, and the grow-on-demand workspace (DevBuf): one set of wav / padded signal / spectrum /
+//     GEMM, log-clamp, download), check_launch, and the grow-on-demand workspace (DevBuf, devres.h): one set of wav / padded signal / spectrum /
 //     magnitude / mel / energy buffers per handle, which every entry point may use because each is synchronous on the handle's stream.
 // The workspace is allocated by the first call that needs it, not at create: max_samples only bounds mel_spectrogram's input, and a
 // create with an absurd max_samples succeeds where it used to fail in hipMalloc (the first call that large fails instead).
@@ -81,23 +81,13 @@ __global__ void log_clamp_kernel(float* x, long long n, float clip) {
     }
 }
 
-// A device buffer that grows on demand (MelFront::grow); cap in elements.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    operator T*() const { return p; }
-    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-};
-
-#define MF_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return err(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 class MelFront {
 public:
     int n_fft = 1024, hop = 256, n_mel = 80, F = 513, cap_samples = 0;
     int ld_spec = 0, ld_mag = 0;
     hipStream_t stream = nullptr;
     std::string last_error;
+    DevHeap mem;   // every device block and event of the mtts_stft handle: this front-end's and those of the stages built on it (devres.h)
     GemmCtx gx;
     float *basis = nullptr, *melb = nullptr;   // [2F][n_fft] windowed Fourier basis; [n_mel][ld_mag] mel filter bank (zero padded)
     bool have_basis = false, have_mel = false;
@@ -120,41 +110,26 @@ public:
         F = n_fft / 2 + 1;
         ld_spec = (2 * F + 3) & ~3;
         ld_mag = (F + 3) & ~3;
-        MF_CHECK(hipMalloc((void**)&basis, (size_t)2 * F * n_fft * sizeof(float)));
-        MF_CHECK(hipMalloc((void**)&melb, (size_t)n_mel * ld_mag * sizeof(float)));
-        MF_CHECK(hipMemset(melb, 0, (size_t)n_mel * ld_mag * sizeof(float)));
-        if (gx.alloc_workspace()) return err("hipMalloc failed (split-K workspace)");
+        DEV_CHECK(mem.alloc(basis, (size_t)2 * F * n_fft * sizeof(float)));
+        DEV_CHECK(mem.alloc_zeroed(melb, (size_t)n_mel * ld_mag * sizeof(float)));
+        if (gx.alloc_workspace(mem)) return err("out of device memory (split-K workspace)");
         return 0;
-    }
-    void destroy() {
-        for (float* p : {basis, melb}) if (p) hipFree(p);
-        for (DevBuf<float>* b : {&wav, &xp, &spec, &mag, &mel, &energy}) b->release();
-        rowmap.release();
-        utts.release();
-        gx.release();
     }
     // forward_basis: [2F][n_fft] (stft.py:27-46, window applied); mel_basis: [n_mel][F] (stft.py:143-147)
     int load(const float* forward_basis, const float* mel_basis) {
-        if (forward_basis) { MF_CHECK(hipMemcpy(basis, forward_basis, (size_t)2 * F * n_fft * sizeof(float), hipMemcpyHostToDevice)); have_basis = true; }
+        if (forward_basis) { DEV_CHECK(hipMemcpy(basis, forward_basis, (size_t)2 * F * n_fft * sizeof(float), hipMemcpyHostToDevice)); have_basis = true; }
         if (mel_basis) {
             std::vector<float> padded((size_t)n_mel * ld_mag, 0.f);
             for (int m = 0; m < n_mel; ++m)
                 for (int f = 0; f < F; ++f) padded[(size_t)m * ld_mag + f] = mel_basis[(size_t)m * F + f];
-            MF_CHECK(hipMemcpy(melb, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice));
+            DEV_CHECK(hipMemcpy(melb, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice));
             have_mel = true;
         }
         return 0;
     }
 
     template <class T>
-    int grow(DevBuf<T>& b, size_t need, const char* what) {
-        if (need <= b.cap) return 0;
-        const size_t n = std::max(need + need / 4, (size_t)1024);
-        if (b.p) { hipStreamSynchronize(stream); b.release(); }
-        if (hipMalloc((void**)&b.p, n * sizeof(T)) != hipSuccess) { b.p = nullptr; return err(std::string("hipMalloc failed (STFT workspace: ") + what + ")"); }
-        b.cap = n;
-        return 0;
-    }
+    int grow(DevBuf<T>& b, size_t need, const char* what) { return mtts::grow(mem, b, need, stream, what, last_error); }
     // Launches are asynchronous: what the GEMM launcher refused is in gx.error, what the runtime refused in hipGetLastError().
     int check_launch() {
         if (gx.error) { const std::string e = std::string("GEMM launcher: ") + gx.error; gx.error = nullptr; return err(e); }
@@ -190,14 +165,14 @@ public:
         for (const StftUtt& u : h_utts)
             for (int t = 0; t < u.T; ++t) h_rowmap[(size_t)(u.xp0 / hop + t)] = u.frame0 + t;
         if (grow(rowmap, (size_t)xp_rows, "row map") || grow(utts, h_utts.size(), "utterances")) return -1;
-        MF_CHECK(hipMemcpyAsync(utts, h_utts.data(), h_utts.size() * sizeof(StftUtt), hipMemcpyHostToDevice, stream));
-        MF_CHECK(hipMemcpyAsync(rowmap, h_rowmap.data(), (size_t)xp_rows * sizeof(int), hipMemcpyHostToDevice, stream));
-        MF_CHECK(hipMemsetAsync(xp, 0, xp_len * sizeof(float), stream));
+        DEV_CHECK(hipMemcpyAsync(utts, h_utts.data(), h_utts.size() * sizeof(StftUtt), hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipMemcpyAsync(rowmap, h_rowmap.data(), (size_t)xp_rows * sizeof(int), hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipMemsetAsync(xp, 0, xp_len * sizeof(float), stream));
         return 0;
     }
     // wav_host (the staged call's waveforms one after another) -> the reflect-padded signals
     int pad_waveforms(const float* wav_host, bool clip, bool mapped) {
-        MF_CHECK(hipMemcpyAsync(wav, wav_host, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipMemcpyAsync(wav, wav_host, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, stream));
         const dim3 grid((unsigned)std::min<long long>((max_span + 255) / 256, 1024), (unsigned)h_utts.size());
         MTTS_LAUNCH(stft_reflect_pad_kernel, grid, dim3(256), stream, (const float*)wav, (const StftUtt*)(mapped ? utts.p : nullptr), h_utts[0], n_fft, hop,
                     clip ? 1 : 0, xp.p);
@@ -222,9 +197,9 @@ public:
         }
         MTTS_LAUNCH(log_clamp_kernel, dim3((unsigned)std::min<long long>((T * n_mel + 255) / 256, 1024)), dim3(256), stream, mel.p, T * n_mel, 1e-5f);
         if (check_launch()) return -1;
-        MF_CHECK(hipMemcpyAsync(mel_host, mel, (size_t)T * n_mel * sizeof(float), hipMemcpyDeviceToHost, stream));
-        MF_CHECK(hipMemcpyAsync(energy_host, energy, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, stream));
-        MF_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpyAsync(mel_host, mel, (size_t)T * n_mel * sizeof(float), hipMemcpyDeviceToHost, stream));
+        DEV_CHECK(hipMemcpyAsync(energy_host, energy, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, stream));
+        DEV_CHECK(hipStreamSynchronize(stream));
         return 0;
     }
 

@@ -67,14 +67,15 @@ int mtts_create(const mtts_model_cfg* c, int device, int max_tasks, int max_B, i
     m.energy_min = c->energy_min; m.energy_max = c->energy_max; m.adapt_mask = c->adapt_mask;
     m.enc_dropout = c->enc_dropout; m.dec_dropout = c->dec_dropout; m.vp_dropout = c->vp_dropout;
     m.pitch_frame = c->pitch_frame_level != 0; m.energy_frame = c->energy_frame_level != 0;
+    // (a handle that could not be completed takes everything it got with it: ~Engine)
     if (h->eng.init(m, max_tasks, max_B, max_S, max_T) != 0) {
         g_create_error = h->eng.last_error;
         delete h;
         return -1;
     }
     h->sup_losses_cap = 128;
-    if (hipMalloc((void**)&h->sup_losses_dev, (size_t)h->sup_losses_cap * max_tasks * 6 * sizeof(float)) != hipSuccess) {
-        g_create_error = "hipMalloc failed";
+    if (h->eng.mem.alloc(h->sup_losses_dev, (size_t)h->sup_losses_cap * max_tasks * 6 * sizeof(float)) != hipSuccess) {
+        g_create_error = "out of device memory (support losses)";
         delete h;
         return -1;
     }
@@ -86,8 +87,6 @@ void mtts_destroy(mtts_handle* h) {
     if (!h) return;
     hipDeviceSynchronize();
     h->comm.release();
-    h->eng.destroy();
-    if (h->sup_losses_dev) hipFree(h->sup_losses_dev);
     delete h;
 }
 
@@ -618,14 +617,13 @@ int mtts_vocoder_create(int n_mel, int ngf, int n_res, const int* ratios, int n_
     VocoderCfg c;
     c.n_mel = n_mel; c.ngf = ngf; c.n_res = n_res; c.n_ratios = n_ratios;
     for (int i = 0; i < n_ratios; ++i) c.ratios[i] = ratios[i];
-    if (h->v.init(c, max_B, max_T) != 0) { g_create_error = h->v.last_error; h->v.destroy(); delete h; return -1; }
+    if (h->v.init(c, max_B, max_T) != 0) { g_create_error = h->v.last_error; delete h; return -1; }
     *out = h;
     return 0;
 }
 void mtts_vocoder_destroy(mtts_vocoder* h) {
     if (!h) return;
     hipDeviceSynchronize();
-    h->v.destroy();
     delete h;
 }
 const char* mtts_vocoder_last_error(mtts_vocoder* h) { return h ? h->v.last_error.c_str() : g_create_error.c_str(); }
@@ -653,9 +651,8 @@ int mtts_dvector_create(int n_mels, int hidden, int layers, int emb, int max_par
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
     mtts_dvector* h = new mtts_dvector();
     h->device = device;
-    h->sc.last_error = &h->d.last_error;
-    h->sc.stream = &h->d.stream;
-    if (h->d.init(n_mels, hidden, layers, emb, max_partials, frames, max_utts) != 0) { g_create_error = h->d.last_error; h->d.destroy(); delete h; return -1; }
+    h->sc.dv = &h->d;
+    if (h->d.init(n_mels, hidden, layers, emb, max_partials, frames, max_utts) != 0) { g_create_error = h->d.last_error; delete h; return -1; }
     *out = h;
     return 0;
 }
@@ -663,8 +660,6 @@ int mtts_dvector_set_stream(mtts_dvector* h, void* s) { if (!h) return -1; h->d.
 void mtts_dvector_destroy(mtts_dvector* h) {
     if (!h) return;
     hipDeviceSynchronize();
-    h->sc.destroy();
-    h->d.destroy();
     delete h;
 }
 const char* mtts_dvector_last_error(mtts_dvector* h) { return h ? h->d.last_error.c_str() : g_create_error.c_str(); }
@@ -695,7 +690,7 @@ int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_sampl
     h->pp.mf = &h->m;
     h->se.mf = &h->m;
     h->se.device = device;
-    if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; h->m.destroy(); delete h; return -1; }
+    if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; delete h; return -1; }
     *out = h;
     return 0;
 }
@@ -703,10 +698,6 @@ int mtts_stft_set_stream(mtts_stft* h, void* s) { if (!h) return -1; h->m.stream
 void mtts_stft_destroy(mtts_stft* h) {
     if (!h) return;
     hipDeviceSynchronize();
-    h->gl.destroy();
-    h->pp.destroy();
-    h->se.destroy();
-    h->m.destroy();
     delete h;
 }
 const char* mtts_stft_last_error(mtts_stft* h) { return h ? h->m.last_error.c_str() : g_create_error.c_str(); }

@@ -221,10 +221,7 @@ public:
     std::vector<PpVal> h_val;
     std::vector<double> h_minmax;
 
-    int err(const std::string& s) { return mf->err(s); }   // (MF_CHECK)
-    void destroy() {
-        for (DevBuf<unsigned char>* b : {&vals, &work, &durs, &pos, &outb, &keepb, &parts, &descs}) b->release();
-    }
+    int err(const std::string& s) { return mf->err(s); }   // (DEV_CHECK)
 
     // get_mel_from_wav of n_utts waveforms (packed in wav_host), each truncated to keep_frames[u] frames (< 0: all):
     // mel_host [sum T][n_mel] log-mel, energy_host [sum T]; T_u = min(n_u / hop + 1, keep_u)   (preprocessor.py:227-229)
@@ -276,9 +273,9 @@ public:
             mf->grow(descs, (size_t)n_utts * sizeof(PpSeq), "utterances"))
             return -1;
         hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(vals.p, values, (size_t)nx * esz, hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(durs.p, durations, (size_t)nd * sizeof(int), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(descs.p, h_seq.data(), (size_t)n_utts * sizeof(PpSeq), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(vals.p, values, (size_t)nx * esz, hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(durs.p, durations, (size_t)nd * sizeof(int), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(descs.p, h_seq.data(), (size_t)n_utts * sizeof(PpSeq), hipMemcpyHostToDevice, st));
         if (dtype)
             MTTS_LAUNCH(pp_segment_kernel<double>, dim3((unsigned)n_utts), dim3(kPpThreads), st, (const double*)vals.p, (double*)work.p, (const int*)durs.p,
                         (int*)pos.p, (const PpSeq*)descs.p, (double*)outb.p, interpolate);
@@ -286,8 +283,8 @@ public:
             MTTS_LAUNCH(pp_segment_kernel<float>, dim3((unsigned)n_utts), dim3(kPpThreads), st, (const float*)vals.p, (float*)work.p, (const int*)durs.p,
                         (int*)pos.p, (const PpSeq*)descs.p, (float*)outb.p, interpolate);
         if (mf->check_launch()) return -1;
-        MF_CHECK(hipMemcpyAsync(out_host, outb.p, (size_t)nd * esz, hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipStreamSynchronize(st));
+        DEV_CHECK(hipMemcpyAsync(out_host, outb.p, (size_t)nd * esz, hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipStreamSynchronize(st));
         return 0;
     }
 
@@ -309,8 +306,8 @@ public:
             mf->grow(parts, (size_t)n_utts * 3 * sizeof(double), "partial statistics") || mf->grow(descs, (size_t)n_utts * sizeof(PpVal), "utterances"))
             return -1;
         hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(vals.p, values, (size_t)nx * esz, hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(descs.p, h_val.data(), (size_t)n_utts * sizeof(PpVal), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(vals.p, values, (size_t)nx * esz, hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(descs.p, h_val.data(), (size_t)n_utts * sizeof(PpVal), hipMemcpyHostToDevice, st));
         if (dtype)
             MTTS_LAUNCH(pp_outlier_stats_kernel<double>, dim3((unsigned)n_utts), dim3(kPpThreads), st, (const double*)vals.p, (const PpVal*)descs.p,
                         (unsigned char*)keepb.p, (double*)parts.p);
@@ -318,9 +315,9 @@ public:
             MTTS_LAUNCH(pp_outlier_stats_kernel<float>, dim3((unsigned)n_utts), dim3(kPpThreads), st, (const float*)vals.p, (const PpVal*)descs.p,
                         (unsigned char*)keepb.p, (double*)parts.p);
         if (mf->check_launch()) return -1;
-        MF_CHECK(hipMemcpyAsync(keep_host, keepb.p, (size_t)nx, hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipMemcpyAsync(partials_host, parts.p, (size_t)n_utts * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipStreamSynchronize(st));
+        DEV_CHECK(hipMemcpyAsync(keep_host, keepb.p, (size_t)nx, hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipMemcpyAsync(partials_host, parts.p, (size_t)n_utts * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipStreamSynchronize(st));
         return 0;
     }
 
@@ -355,16 +352,16 @@ public:
             mf->grow(parts, (size_t)blocks * 2 * sizeof(double), "min / max partials"))
             return -1;
         hipStream_t st = mf->stream;
-        MF_CHECK(hipMemcpyAsync(vals.p, values, (size_t)n * esz, hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(vals.p, values, (size_t)n * esz, hipMemcpyHostToDevice, st));
         if (dtype)
             MTTS_LAUNCH(pp_normalize_kernel<double>, dim3((unsigned)blocks), dim3(kPpThreads), st, (const double*)vals.p, n, mean, stdv, (double*)outb.p, (double*)parts.p);
         else
             MTTS_LAUNCH(pp_normalize_kernel<float>, dim3((unsigned)blocks), dim3(kPpThreads), st, (const float*)vals.p, n, mean, stdv, (double*)outb.p, (double*)parts.p);
         if (mf->check_launch()) return -1;
         h_minmax.resize((size_t)blocks * 2);
-        MF_CHECK(hipMemcpyAsync(out_host, outb.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipMemcpyAsync(h_minmax.data(), parts.p, (size_t)blocks * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipStreamSynchronize(st));
+        DEV_CHECK(hipMemcpyAsync(out_host, outb.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipMemcpyAsync(h_minmax.data(), parts.p, (size_t)blocks * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipStreamSynchronize(st));
         double lo = h_minmax[0], hi = h_minmax[1];
         for (int b = 1; b < blocks; ++b) { lo = std::min(lo, h_minmax[(size_t)2 * b]); hi = std::max(hi, h_minmax[(size_t)2 * b + 1]); }
         minmax_host[0] = lo;

@@ -142,13 +142,6 @@ public:
     std::vector<Chunk> chunks;
 
     int err(const std::string& s) { return mf->err(s); }
-    void destroy() {
-        stack.release();
-        win.release();
-        if (ev_front) hipEventDestroy(ev_front);
-        if (ev_enc) hipEventDestroy(ev_enc);
-        ev_front = ev_enc = nullptr;
-    }
 
     // Speaker-encoder mel of the staged call into mf->mel [sum T][n_mel]: forward STFT, power, mel projection (no log, no clamp).
     void power_mel() {
@@ -177,8 +170,8 @@ public:
         if (mf->stage("mtts_stft_power_mel_batch", true) || mf->pad_waveforms(wavs, false, true)) return -1;
         power_mel();
         if (mf->check_launch()) return -1;
-        MF_CHECK(hipMemcpyAsync(mel_host, mf->mel, (size_t)mf->n_frames * mf->n_mel * sizeof(float), hipMemcpyDeviceToHost, mf->stream));
-        MF_CHECK(hipStreamSynchronize(mf->stream));
+        DEV_CHECK(hipMemcpyAsync(mel_host, mf->mel, (size_t)mf->n_frames * mf->n_mel * sizeof(float), hipMemcpyDeviceToHost, mf->stream));
+        DEV_CHECK(hipStreamSynchronize(mf->stream));
         return 0;
     }
 
@@ -217,7 +210,7 @@ public:
         if (total_parts > (1LL << 30) / ((long long)frames * n_mel)) return err(std::string(who) + "too many partial utterances in one call");
         if (dv && dv->dirty && dv->refresh() != 0) return err(std::string(who) + dv->last_error);
         const bool two_streams = dv && dv->stream != mf->stream;
-        if (two_streams && !ev_front) { MF_CHECK(hipEventCreate(&ev_front)); MF_CHECK(hipEventCreate(&ev_enc)); }
+        if (two_streams) { DEV_CHECK(mf->mem.event(ev_front)); DEV_CHECK(mf->mem.event(ev_enc)); }
         h_wav.assign((size_t)total, 0.f);
         {
             long long src = 0, dst = 0;
@@ -269,23 +262,23 @@ public:
             keep_maps.emplace_back(std::move(mf->h_rowmap));
             mf->h_utts.clear();
             mf->h_rowmap.clear();
-            MF_CHECK(hipMemcpyAsync(win.p, wv.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, mf->stream));
-            if (two_streams && c > 0) MF_CHECK(hipStreamWaitEvent(mf->stream, ev_enc, 0));   // the previous chunk's encoder still reads the stack
+            DEV_CHECK(hipMemcpyAsync(win.p, wv.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, mf->stream));
+            if (two_streams && c > 0) DEV_CHECK(hipStreamWaitEvent(mf->stream, ev_enc, 0));   // the previous chunk's encoder still reads the stack
             MTTS_LAUNCH(spk_gather_kernel, dim3((unsigned)N * (unsigned)per), dim3(256), mf->stream, (const float*)mf->mel, (const int*)win.p, n_mel, span4, per,
                         stack.p);
             if (mf->check_launch()) return -1;
             if (slices_out)
-                MF_CHECK(hipMemcpyAsync(slices_out + part0 * span4 * 4, stack.p, (size_t)N * span4 * 4 * sizeof(float), hipMemcpyDeviceToHost, mf->stream));
+                DEV_CHECK(hipMemcpyAsync(slices_out + part0 * span4 * 4, stack.p, (size_t)N * span4 * 4 * sizeof(float), hipMemcpyDeviceToHost, mf->stream));
             if (dv) {
-                if (two_streams) { MF_CHECK(hipEventRecord(ev_front, mf->stream)); MF_CHECK(hipStreamWaitEvent(dv->stream, ev_front, 0)); }
+                if (two_streams) { DEV_CHECK(hipEventRecord(ev_front, mf->stream)); DEV_CHECK(hipStreamWaitEvent(dv->stream, ev_front, 0)); }
                 if (dv->forward_device(stack.p, N, off.data(), u1 - u0, out + (long long)u0 * dv->E, nullptr, false) != 0) return err(std::string(who) + dv->last_error);
-                if (two_streams) MF_CHECK(hipEventRecord(ev_enc, dv->stream));
+                if (two_streams) DEV_CHECK(hipEventRecord(ev_enc, dv->stream));
             }
             for (int u = u0; u < u1; ++u) wav0 += h_ext[(size_t)u];
             part0 += N;
         }
-        if (dv) MF_CHECK(hipStreamSynchronize(dv->stream));
-        MF_CHECK(hipStreamSynchronize(mf->stream));
+        if (dv) DEV_CHECK(hipStreamSynchronize(dv->stream));
+        DEV_CHECK(hipStreamSynchronize(mf->stream));
         return 0;
     }
 };
@@ -295,20 +288,11 @@ class SpeakerScore {
 public:
     DevBuf<float> a, b, o;
     DevBuf<int> ia, ib;
-    std::string* last_error = nullptr;
-    hipStream_t* stream = nullptr;
+    DVector* dv = nullptr;   // the handle it scores on: its stream, its heap, its error string
 
-    int err(const std::string& s) { *last_error = s; return -1; }
-    void destroy() { a.release(); b.release(); o.release(); ia.release(); ib.release(); }
+    int err(const std::string& s) { return dv->err(s); }
     template <class T>
-    int grow(DevBuf<T>& buf, size_t need) {
-        if (need <= buf.cap) return 0;
-        if (buf.p) { hipStreamSynchronize(*stream); buf.release(); }
-        const size_t n = std::max(need + need / 4, (size_t)1024);
-        if (hipMalloc((void**)&buf.p, n * sizeof(T)) != hipSuccess) { buf.p = nullptr; return err("hipMalloc failed (scoring workspace)"); }
-        buf.cap = n;
-        return 0;
-    }
+    int grow(DevBuf<T>& buf, size_t need) { return mtts::grow(dv->mem, buf, need, dv->stream, "scoring workspace", dv->last_error); }
 
     int cosine_indexed(const float* A, int n_a, const float* B, int n_b, int dim, int n, const int* idx_a, const int* idx_b, double eps, float* sim) {
         const char* who = "mtts_dvector_cosine_indexed: ";
@@ -316,16 +300,16 @@ public:
         for (int i = 0; i < n; ++i)
             if (idx_a[i] < 0 || idx_a[i] >= n_a || idx_b[i] < 0 || idx_b[i] >= n_b) return err(std::string(who) + "pair " + std::to_string(i) + ": index out of range");
         if (grow(a, (size_t)n_a * dim) || grow(b, (size_t)n_b * dim) || grow(o, (size_t)n) || grow(ia, (size_t)n) || grow(ib, (size_t)n)) return -1;
-        hipStream_t st = *stream;
-        MF_CHECK(hipMemcpyAsync(a.p, A, (size_t)n_a * dim * sizeof(float), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(b.p, B, (size_t)n_b * dim * sizeof(float), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(ia.p, idx_a, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(ib.p, idx_b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+        hipStream_t st = dv->stream;
+        DEV_CHECK(hipMemcpyAsync(a.p, A, (size_t)n_a * dim * sizeof(float), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(b.p, B, (size_t)n_b * dim * sizeof(float), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(ia.p, idx_a, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(ib.p, idx_b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
         MTTS_LAUNCH(spk_cosine_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), st, (const float*)a.p, (const float*)b.p, (const int*)ia.p, (const int*)ib.p, n, dim,
                     eps, o.p);
-        MF_CHECK(hipGetLastError());
-        MF_CHECK(hipMemcpyAsync(sim, o.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipStreamSynchronize(st));
+        DEV_CHECK(hipGetLastError());
+        DEV_CHECK(hipMemcpyAsync(sim, o.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipStreamSynchronize(st));
         return 0;
     }
 
@@ -337,13 +321,13 @@ public:
             if (offsets[s + 1] < offsets[s]) return err(std::string(who) + "speaker " + std::to_string(s) + ": offsets must not decrease");
         const size_t rows = (size_t)offsets[n_spk];
         if (grow(a, std::max(rows, (size_t)1) * dim) || grow(o, (size_t)n_spk * dim) || grow(ia, (size_t)n_spk + 1)) return -1;
-        hipStream_t st = *stream;
-        MF_CHECK(hipMemcpyAsync(a.p, vecs, rows * dim * sizeof(float), hipMemcpyHostToDevice, st));
-        MF_CHECK(hipMemcpyAsync(ia.p, offsets, ((size_t)n_spk + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+        hipStream_t st = dv->stream;
+        DEV_CHECK(hipMemcpyAsync(a.p, vecs, rows * dim * sizeof(float), hipMemcpyHostToDevice, st));
+        DEV_CHECK(hipMemcpyAsync(ia.p, offsets, ((size_t)n_spk + 1) * sizeof(int), hipMemcpyHostToDevice, st));
         MTTS_LAUNCH(spk_centroid_kernel, dim3((unsigned)n_spk), dim3(256), st, (const float*)a.p, (const int*)ia.p, dim, o.p);
-        MF_CHECK(hipGetLastError());
-        MF_CHECK(hipMemcpyAsync(out, o.p, (size_t)n_spk * dim * sizeof(float), hipMemcpyDeviceToHost, st));
-        MF_CHECK(hipStreamSynchronize(st));
+        DEV_CHECK(hipGetLastError());
+        DEV_CHECK(hipMemcpyAsync(out, o.p, (size_t)n_spk * dim * sizeof(float), hipMemcpyDeviceToHost, st));
+        DEV_CHECK(hipStreamSynchronize(st));
         return 0;
     }
 };

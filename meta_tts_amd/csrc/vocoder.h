@@ -102,8 +102,9 @@ public:
     GemmCtx gx;  // this handle's launcher state (gemm.h)
     Buf b_x[2], b_pad, b_h;
 
-    void set_error(const std::string& s) { last_error = s; }
-#define VOC_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return -1; } } while (0)
+    DevHeap mem;   // every device block of this handle (devres.h)
+    int err(const std::string& s) { last_error = s; return -1; }
+    void set_error(const std::string& s) { err(s); }
 
     int ch(int stage) const { int c = cfg.ngf << cfg.n_ratios; for (int s = 0; s < stage; ++s) c >>= 1; return c; }  // channels after `stage` upsamples
     long long find(const std::string& n) const { for (auto& t : tensors) if (t.name == n) return t.off; return -1; }
@@ -128,9 +129,9 @@ public:
             }
         }
         add("conv_out.w", 7LL * ch(cfg.n_ratios)); add("conv_out.b", 1);
-        if (gx.alloc_workspace()) { set_error("hipMalloc failed (split-K workspace)"); return -1; }
-        VOC_CHECK(hipMalloc((void**)&params, (size_t)n_params * sizeof(float)));
-        VOC_CHECK(hipMemset(params, 0, (size_t)n_params * sizeof(float)));
+        if (gx.alloc_workspace(mem)) return err("out of device memory (split-K workspace)");
+        DEV_CHECK(mem.alloc(params, (size_t)n_params * sizeof(float)));
+        DEV_CHECK(hipMemset(params, 0, (size_t)n_params * sizeof(float)));
         // activations: rows x channels is largest where rows*C peaks; size every buffer for the worst stage (+ pad rows)
         long long worst = (long long)(cap_T + 32) * std::max(cfg.n_mel, c0);
         long long mult = 1;
@@ -139,24 +140,19 @@ public:
         for (int s = 0; s < cfg.n_ratios; ++s) { mult *= cfg.ratios[s]; worst = std::max(worst, ((long long)cap_T * mult + 2 * maxd + 32) * ch(s + 1)); }
         worst = (worst + 63) & ~63LL;
         const long long per = worst;  // per utterance per buffer
-        VOC_CHECK(hipMalloc((void**)&arena, (size_t)per * cap_B * 4 * sizeof(float)));
-        VOC_CHECK(hipMemset(arena, 0, (size_t)per * cap_B * 4 * sizeof(float)));
+        DEV_CHECK(mem.alloc(arena, (size_t)per * cap_B * 4 * sizeof(float)));
+        DEV_CHECK(hipMemset(arena, 0, (size_t)per * cap_B * 4 * sizeof(float)));
         b_x[0] = Buf{0, per}; b_x[1] = Buf{per * cap_B, per}; b_pad = Buf{2 * per * cap_B, per}; b_h = Buf{3 * per * cap_B, per};
-        VOC_CHECK(hipMalloc((void**)&lens_dev, cap_B * sizeof(int)));
-        VOC_CHECK(hipMalloc((void**)&mel_dev, (size_t)cap_B * cap_T * cfg.n_mel * sizeof(float)));
-        VOC_CHECK(hipMalloc((void**)&wav_dev, (size_t)cap_B * cap_T * hop * sizeof(float)));
+        DEV_CHECK(mem.alloc(lens_dev, cap_B * sizeof(int)));
+        DEV_CHECK(mem.alloc(mel_dev, (size_t)cap_B * cap_T * cfg.n_mel * sizeof(float)));
+        DEV_CHECK(mem.alloc(wav_dev, (size_t)cap_B * cap_T * hop * sizeof(float)));
         return 0;
-    }
-    void destroy() {
-        for (void* p : {(void*)params, (void*)arena, (void*)lens_dev, (void*)mel_dev, (void*)wav_dev}) if (p) hipFree(p);
-        params = arena = mel_dev = wav_dev = nullptr; lens_dev = nullptr;
-        gx.release();
     }
     int load(const char* name, const float* host, long long numel) {
         for (auto& t : tensors)
             if (t.name == name) {
                 if (t.numel != numel) { set_error(std::string("size mismatch for ") + name); return -1; }
-                VOC_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+                DEV_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
                 return 0;
             }
         set_error(std::string("unknown vocoder tensor ") + name);
@@ -186,7 +182,7 @@ public:
     int run(const float* mel, int B, int T_max, const int* lens_host, float mel_scale, float* wav, long long wav_gs, long long mel_gs = 0) {
         if (B < 1 || B > cap_B || T_max < 4 || T_max > cap_T) { set_error("vocoder batch exceeds capacity"); return -1; }
         for (int b = 0; b < B; ++b) if (lens_host[b] < 4 || lens_host[b] > T_max) { set_error("mel length out of range (need 4 <= len <= T_max)"); return -1; }
-        VOC_CHECK(hipMemcpyAsync(lens_dev, lens_host, B * sizeof(int), hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipMemcpyAsync(lens_dev, lens_host, B * sizeof(int), hipMemcpyHostToDevice, stream));
         const int nm = cfg.n_mel;
         // conv_in: reflection pad 3 of the scaled mel, k=7 conv
         {
@@ -254,15 +250,14 @@ public:
     // host entry: mel_host [B][T_max][n_mel] -> wav_host [B][T_max * hop] (samples beyond len * hop are left untouched)
     int infer_host(const float* mel_host, int B, int T_max, const int* lens_host, float mel_scale, float* wav_host) {
         if (B < 1 || B > cap_B || T_max < 4 || T_max > cap_T) { set_error("vocoder batch exceeds capacity"); return -1; }
-        VOC_CHECK(hipMemcpyAsync(mel_dev, mel_host, (size_t)B * T_max * cfg.n_mel * sizeof(float), hipMemcpyHostToDevice, stream));
+        DEV_CHECK(hipMemcpyAsync(mel_dev, mel_host, (size_t)B * T_max * cfg.n_mel * sizeof(float), hipMemcpyHostToDevice, stream));
         if (run(mel_dev, B, T_max, lens_host, mel_scale, wav_dev, (long long)T_max * hop) != 0) return -1;
-        VOC_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipStreamSynchronize(stream));
         for (int b = 0; b < B; ++b)
-            VOC_CHECK(hipMemcpy(wav_host + (long long)b * T_max * hop, wav_dev + (long long)b * T_max * hop, (size_t)lens_host[b] * hop * sizeof(float),
+            DEV_CHECK(hipMemcpy(wav_host + (long long)b * T_max * hop, wav_dev + (long long)b * T_max * hop, (size_t)lens_host[b] * hop * sizeof(float),
                                 hipMemcpyDeviceToHost));
         return 0;
     }
-#undef VOC_CHECK
 };
 
 }  // namespace mtts

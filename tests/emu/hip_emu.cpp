@@ -7,6 +7,8 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 thread_local emu_uint3 threadIdx, blockIdx;
@@ -133,13 +135,69 @@ float atomicAdd(float* p, float v) {
 }
 int atomicAdd(int* p, int v) { return reinterpret_cast<std::atomic<int>*>(p)->fetch_add(v); }
 
+namespace {
+struct Ledger {
+    std::mutex mu;
+    std::unordered_map<void*, size_t> allocs;
+    std::unordered_set<void*> streams, events;
+    long long bytes = 0, bad_frees = 0, alloc_calls = 0, fail_in = -1;
+    uintptr_t next_id = 0;
+    void* make(std::unordered_set<void*>& live) {
+        std::lock_guard<std::mutex> lk(mu);
+        void* h = (void*)(++next_id << 4);   // identity only: never dereferenced
+        live.insert(h);
+        return h;
+    }
+    void drop(std::unordered_set<void*>& live, void* h) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!live.erase(h)) ++bad_frees;
+    }
+};
+Ledger& ledger() { static Ledger* l = new Ledger(); return *l; }
+}  // namespace
+
 hipError_t hipMalloc(void** p, size_t n) {
+    Ledger& L = ledger();
+    {
+        std::lock_guard<std::mutex> lk(L.mu);
+        ++L.alloc_calls;
+        if (L.fail_in >= 0 && L.fail_in-- == 0) return 2;
+    }
     void* q = nullptr;
     if (posix_memalign(&q, 256, n ? n : 256) != 0) return 1;
+    std::lock_guard<std::mutex> lk(L.mu);
+    L.allocs[q] = n;
+    L.bytes += (long long)n;
     *p = q;
     return 0;
 }
-hipError_t hipFree(void* p) { free(p); return 0; }
+hipError_t hipFree(void* p) {
+    if (!p) return 0;
+    Ledger& L = ledger();
+    {
+        std::lock_guard<std::mutex> lk(L.mu);
+        const auto it = L.allocs.find(p);
+        if (it == L.allocs.end()) { ++L.bad_frees; return 1; }
+        L.bytes -= (long long)it->second;
+        L.allocs.erase(it);
+    }
+    free(p);
+    return 0;
+}
+hipError_t hipStreamCreate(hipStream_t* s) { *s = ledger().make(ledger().streams); return 0; }
+hipError_t hipStreamDestroy(hipStream_t s) { ledger().drop(ledger().streams, s); return 0; }
+hipError_t hipEventCreate(hipEvent_t* e) { *e = ledger().make(ledger().events); return 0; }
+hipError_t hipEventDestroy(hipEvent_t e) { ledger().drop(ledger().events, e); return 0; }
+
+extern "C" {
+long long emu_live_allocs() { std::lock_guard<std::mutex> lk(ledger().mu); return (long long)ledger().allocs.size(); }
+long long emu_live_bytes() { std::lock_guard<std::mutex> lk(ledger().mu); return ledger().bytes; }
+long long emu_live_streams() { std::lock_guard<std::mutex> lk(ledger().mu); return (long long)ledger().streams.size(); }
+long long emu_live_events() { std::lock_guard<std::mutex> lk(ledger().mu); return (long long)ledger().events.size(); }
+long long emu_bad_frees() { std::lock_guard<std::mutex> lk(ledger().mu); return ledger().bad_frees; }
+long long emu_alloc_calls() { std::lock_guard<std::mutex> lk(ledger().mu); return ledger().alloc_calls; }
+void emu_fail_alloc_after(long long n) { std::lock_guard<std::mutex> lk(ledger().mu); ledger().fail_in = n; }
+}
 
 namespace {
 struct Pool {

@@ -60,21 +60,33 @@ static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); 
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return 0; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 enum { hipStreamNonBlocking = 1 };
-static inline hipError_t hipStreamCreate(hipStream_t* s) { *s = (hipStream_t)1; return 0; }   // launches execute at the call: one in-order "stream"
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)1; return 0; }
-static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)1; return 0; }
+hipError_t hipStreamCreate(hipStream_t* s);   // launches execute at the call: one in-order "stream" (the handle only has identity)
+static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return hipStreamCreate(s); }
+static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { return hipStreamCreate(s); }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = 0; return 0; }
-static inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
+hipError_t hipStreamDestroy(hipStream_t s);
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
 static inline hipError_t hipDeviceSynchronize() { return 0; }
 static inline hipError_t hipGetLastError() { return 0; }
 static inline hipError_t hipSetDevice(int) { return 0; }
 static inline const char* hipGetErrorString(hipError_t) { return "emu"; }
-static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = nullptr; return 0; }
-static inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
+hipError_t hipEventCreate(hipEvent_t* e);
+hipError_t hipEventDestroy(hipEvent_t e);
 static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return 0; }
+
+// Resource accounting for tests/test_handle_resources.py: hipMalloc / hipFree (pinned memory routes through them), streams and events
+// keep tables of what is live; a free / destroy of something that is not live is counted, not performed.
+extern "C" {
+long long emu_live_allocs();
+long long emu_live_bytes();
+long long emu_live_streams();
+long long emu_live_events();
+long long emu_bad_frees();
+long long emu_alloc_calls();            // hipMalloc calls so far, failed ones included
+void emu_fail_alloc_after(long long n);  // one shot: the n-th hipMalloc from now (0 = the next) fails; n < 0 disarms
+}
 
 void emu_launch(dim3 grid, dim3 block, const std::function<void()>& body);
 #define MTTS_LAUNCH(kernel, grid, block, stream, ...) \
