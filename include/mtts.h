@@ -476,8 +476,8 @@ int mtts_stft_normalize(mtts_stft* h, int64_t n, const void* values, int dtype, 
  * Replaces the device-worthy part of the reference's `evaluation/` package (wavs_to_dvector.py: `encoder.embed_utterance(
  * preprocess_wav(path))` one wav at a time on the CPU; pair_similarity.py:68-88, centroid_similarity.py:47-118: cosine similarity;
  * wavs_to_dvector.py:176-183: centroids) and `spk_ref_mel_slices` of preprocessor/preprocessor.py:263-299.  resemblyzer is un-vendored:
- * its front-end is restated from the published recipe.  NOT built: its `preprocess_wav` (resampling, -30 dBFS normalisation, webrtcvad
- * trimming) — waveforms are 16 kHz float32 as they are.
+ * its front-end is restated from the published recipe.  Of its `preprocess_wav`, resampling and -30 dBFS normalisation are the next
+ * section's (opt-in); webrtcvad trimming is NOT built.  In THESE entries waveforms are 16 kHz float32 as they are.
  * power_mel_batch: resemblyzer's `wav_to_mel_spectrogram` of n_utts waveforms packed in `wavs` as they are: mel [sum T][n_mel], T_u =
  * n_samples[u] / hop_length + 1, = mel_basis @ (re^2 + im^2) of the centred, reflect-padded frames (power; no clip, no log, no clamp).
  * An utterance's rows are bit-identical whatever else is in the call.  Errors (before any launch): n_samples[u] <= filter_length / 2.
@@ -508,6 +508,38 @@ int mtts_dvector_embed_wavs(mtts_dvector* h, mtts_stft* stft, int n_utts, const 
 int mtts_dvector_cosine_indexed(mtts_dvector* h, const float* a, int n_a, const float* b, int n_b, int dim, int n, const int* index_a, const int* index_b,
                                 double eps, float* sim);
 int mtts_dvector_centroids(mtts_dvector* h, const float* vectors, const int* offsets, int n_speakers, int dim, float* out);
+
+/* ---- rate conversion and volume normalisation of waveform batches ----------------------------------------
+ * The stage in front of the packed waveform buffer of an mtts_stft handle: what `librosa.load(path, sampling_rate)` does in the
+ * reference's corpus loaders (preprocessor/libritts.py:37, vctk.py:35, preprocessor.py:205) and the first two steps of resemblyzer's
+ * `preprocess_wav` (evaluation/wavs_to_dvector.py:206-296, preprocessor.py:265).  Opt-in: a handle without a resampler behaves as before.
+ * Neither library is vendored; parity with them is UNPINNED.  What is computed, exactly: with up / down = target_sr / orig_sr reduced,
+ *   y[n] = sum_m h[n * down - m * up] x[m]   over |n * down - m * up| <= H, 0 <= m < n_in,   n_out = ceil(n_in * up / down),
+ * for a filter h[-H .. H] on the grid of the up-sampled rate (designed by the caller in float64: meta_tts_amd/audio/resample.py builds
+ * the Kaiser-windowed sinc, sum(h) = up, and equals scipy.signal.resample_poly with that window).  Not built: webrtcvad trimming.
+ * load_resampler: the filter as a polyphase bank, float32 [taps][up], rounded once from float64:
+ *   bank[t][p] = h[((p * down) mod up) + (t - lead) * up]   (0 where that index falls outside -H .. H),
+ * so that y[n] = sum_t bank[t][n mod up] * x[floor(n * down / up) + lead - t], added in tap order in float32 (FMA).  With K =
+ * floor(H / up): lead = K + 1, taps = 2 K + 2 covers every phase.  Column p = n mod up is the fastest index: consecutive outputs read
+ * consecutive addresses.  Replaces a bank loaded before.  Errors: up, down, taps < 1, lead outside 0 .. taps - 1, a bank above 2^22
+ * entries, a ratio so steep that the input span of 256 outputs (255 * down / up + taps + 1 samples) exceeds the 4096 a workgroup stages.
+ * resample_batch: n_utts waveforms packed one after another in `wavs` (n_in[u] source-rate samples each; host) -> out, the resampled
+ * waveforms packed one after another (ceil(n_in[u] * up / down) each; host).  target_dbfs: NaN = no normalisation; else resemblyzer's
+ * normalize_volume(y, target_dbfs, increase_only) per utterance on the RESAMPLED signal: dBFS = 10 log10(mean(y^2)), change =
+ * target_dbfs - dBFS; left as it is when change < 0 and increase_only != 0 (and when y is all zeros), else y *= 10^(change / 20), the
+ * float64 product rounded once.  gains (or NULL): float64 [n_utts], the gain applied (1 where left as it is).  mean(y^2) is a float64
+ * sum in a fixed order (one partial per 256-thread workgroup, then in workgroup order): no atomics.  An utterance's output and gain
+ * are bit-identical alone, in any batch, at any position.  Errors, before any launch: no resampler loaded, n_utts < 1 or > 65535, NULL
+ * pointers, n_in[u] < 1, a resampled length beyond the handle's max_samples.  Synchronous.
+ * embed_wavs_resampled: mtts_dvector_embed_wavs with n_samples[u] counted at the SOURCE rate: every chunk's waveforms are uploaded at
+ * the source rate, resampled (and normalised, target_dbfs / increase_only as above) on the device straight into the packed waveform
+ * buffer, zero-extended there, and go through the same chain (pad, STFT, power mel, gather, encoder); the front-end-rate signal never
+ * visits the host.  The partial rule applies to the resampled length; results are bit-identical to embed_wavs on resample_batch's
+ * output.  Errors: those of both entries, under this entry's name. */
+int mtts_stft_load_resampler(mtts_stft* h, int up, int down, int taps, int lead, const float* bank);
+int mtts_stft_resample_batch(mtts_stft* h, int n_utts, const int* n_in, const float* wavs, double target_dbfs, int increase_only, float* out, double* gains);
+int mtts_dvector_embed_wavs_resampled(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
+                                      double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out);
 
 #ifdef __cplusplus
 }

@@ -173,6 +173,10 @@ public:
     // wav_host (the staged call's waveforms one after another) -> the reflect-padded signals
     int pad_waveforms(const float* wav_host, bool clip, bool mapped) {
         DEV_CHECK(hipMemcpyAsync(wav, wav_host, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, stream));
+        return pad_staged(clip, mapped);
+    }
+    // the same for waveforms an earlier launch on this stream has left in `wav` (resample.h): no upload
+    int pad_staged(bool clip, bool mapped) {
         const dim3 grid((unsigned)std::min<long long>((max_span + 255) / 256, 1024), (unsigned)h_utts.size());
         MTTS_LAUNCH(stft_reflect_pad_kernel, grid, dim3(256), stream, (const float*)wav, (const StftUtt*)(mapped ? utts.p : nullptr), h_utts[0], n_fft, hop,
                     clip ? 1 : 0, xp.p);

@@ -10,6 +10,7 @@
 #include "melfront.h"
 #include "griffin.h"
 #include "preprocess.h"
+#include "resample.h"
 #include "speakereval.h"
 
 using namespace mtts;
@@ -50,6 +51,7 @@ struct mtts_stft {
     GriffinLim gl;
     Preprocess pp;
     SpeakerEval se;
+    Resample rs;
 };
 
 extern "C" {
@@ -689,6 +691,7 @@ int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_sampl
     h->gl.mf = &h->m;
     h->pp.mf = &h->m;
     h->se.mf = &h->m;
+    h->rs.mf = &h->m;
     h->se.device = device;
     if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; delete h; return -1; }
     *out = h;
@@ -738,6 +741,13 @@ int mtts_stft_normalize(mtts_stft* h, int64_t n, const void* values, int dtype, 
     return h ? h->pp.normalize(n, values, dtype, mean, std, out, minmax) : -1;
 }
 
+// ---- rate conversion and volume normalisation in front of the packed waveform buffer (resample.h; reference: librosa.load(path, sr) in
+// the corpus loaders, resemblyzer's preprocess_wav in every speaker-encoder entry) ----
+int mtts_stft_load_resampler(mtts_stft* h, int up, int down, int taps, int lead, const float* bank) { return h ? h->rs.load(up, down, taps, lead, bank) : -1; }
+int mtts_stft_resample_batch(mtts_stft* h, int n_utts, const int* n_in, const float* wavs, double target_dbfs, int increase_only, float* out, double* gains) {
+    return h ? h->rs.resample_batch(n_utts, n_in, wavs, target_dbfs, increase_only, out, gains) : -1;
+}
+
 // ---- speaker-similarity evaluation (speakereval.h; reference evaluation/wavs_to_dvector.py, pair_similarity.py, centroid_similarity.py) ----
 int mtts_stft_power_mel_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, float* mel) {
     return h ? h->se.power_mel_batch(n_utts, n_samples, wavs, mel) : -1;
@@ -750,6 +760,14 @@ int mtts_dvector_embed_wavs(mtts_dvector* h, mtts_stft* stft, int n_utts, const 
     if (!stft) { g_create_error = "mtts_dvector_embed_wavs: NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
     const int rc = stft->se.embed_wavs(h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, partial_frames, frame_step, min_coverage, out,
                                        n_partials_out, slices_out);
+    if (rc != 0 && h) h->d.set_error(stft->m.last_error);
+    return rc;
+}
+int mtts_dvector_embed_wavs_resampled(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
+                                      double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out) {
+    if (!stft) { g_create_error = "mtts_dvector_embed_wavs_resampled: NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
+    const int rc = stft->se.embed_wavs(h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, partial_frames, frame_step, min_coverage, out,
+                                       n_partials_out, slices_out, &stft->rs, target_dbfs, increase_only);
     if (rc != 0 && h) h->d.set_error(stft->m.last_error);
     return rc;
 }

@@ -8,8 +8,9 @@
 // n_fft=400, hop_length=160, n_mels=40).T — centred frames over the reflect-padded signal, POWER spectrum re^2 + im^2, mel
 // projection, no log, no clamp — and `compute_partial_slices`: 160-frame windows every frame_step = round(16000 / rate / 160) frames
 // over ceil((n + 1) / 160) frames, the last one dropped when it covers less than min_coverage of its span and is not the only one,
-// the waveform zero-extended to the end of the last window kept.  `preprocess_wav` (resampling, -30 dBFS normalisation, webrtcvad
-// trimming) is NOT built: inputs are 16 kHz waveforms as they are.
+// the waveform zero-extended to the end of the last window kept.  Of `preprocess_wav`, resampling and -30 dBFS normalisation are
+// resample.h's (embed_wavs with a Resample: the chained entry); webrtcvad trimming is NOT built.  Without a resampler inputs are 16 kHz
+// waveforms as they are.
 //
 // MI355X layout.  All utterances of a chunk share every launch (melfront.h's packing): the reflect-pad kernel, ONE forward-STFT GEMM
 // with the rows between utterances dropped, stft_power_kernel (one wavefront per frame, HBM-bound: 2F floats in, F out), the mel GEMM,
@@ -34,6 +35,7 @@
 
 #include "dvector.h"
 #include "melfront.h"
+#include "resample.h"
 
 namespace mtts {
 
@@ -138,6 +140,8 @@ public:
     std::vector<std::vector<int>> h_win, h_off;   // per chunk (alive until the call's last copy has been enqueued and waited for)
     std::vector<std::vector<StftUtt>> keep_utts;  // MelFront's packing tables of the chunks already enqueued, kept for the same reason
     std::vector<std::vector<int>> keep_maps;
+    std::vector<std::vector<RsUtt>> keep_rs;      // and the resampler's tables (embed_wavs with a resampler)
+    std::vector<long long> h_n;                   // samples per utterance at the front-end's rate
     struct Chunk { int u0, u1, N; };
     std::vector<Chunk> chunks;
 
@@ -177,9 +181,13 @@ public:
 
     // dv != nullptr: out [n_utts][E] d-vectors.  slices_out != nullptr: the partial stacks [sum N][frames][n_mel] (all utterances one
     // after another).  n_partials_out [n_utts].  Everything that can be refused is refused before the first launch.
+    // rs != nullptr (mtts_dvector_embed_wavs_resampled): n_samples counts SOURCE-rate samples; every chunk is resampled (and normalised
+    // to target_dbfs unless that is NaN) by rs straight into mf->wav, zero-extended there, and the front-end rate's signal never
+    // visits the host.  The chunking, the launches behind the waveform buffer and the results are those of the plain entry on the
+    // resampled waveforms.
     int embed_wavs(DVector* dv, int dv_device, int n_utts, const int* n_samples, const float* wavs, int frames, int step, double min_coverage, float* out,
-                   int* n_partials_out, float* slices_out) {
-        const char* who = "mtts_dvector_embed_wavs: ";
+                   int* n_partials_out, float* slices_out, Resample* rs = nullptr, double target_dbfs = 0.0, int increase_only = 0) {
+        const char* who = rs ? "mtts_dvector_embed_wavs_resampled: " : "mtts_dvector_embed_wavs: ";
         const int hop = mf->hop, n_mel = mf->n_mel;
         if (!mf->have_basis || !mf->have_mel) return err(std::string(who) + "STFT bases not loaded");
         if (n_utts < 1 || !n_samples || !wavs || !n_partials_out) return err(std::string(who) + "bad arguments (n_utts < 1 or NULL n_samples / wavs / n_partials_out)");
@@ -193,14 +201,17 @@ public:
                 return err(std::string(who) + "the encoder expects partials of " + std::to_string(dv->T) + " x " + std::to_string(dv->n_mels) + ", the front-end makes " +
                            std::to_string(frames) + " x " + std::to_string(n_mel));
         }
+        if (rs && rs->check_lengths(who, n_utts, n_samples)) return -1;
         h_ext.resize((size_t)n_utts);
         h_cnt.resize((size_t)n_utts);
+        h_n.resize((size_t)n_utts);
         long long total = 0, total_parts = 0;
         for (int u = 0; u < n_utts; ++u) {
             const std::string utt = std::string(who) + "utterance " + std::to_string(u) + ": ";
-            if (n_samples[u] <= mf->n_fft / 2)
+            const long long n = h_n[(size_t)u] = rs ? rs->out_len(n_samples[u]) : n_samples[u];
+            if (n <= mf->n_fft / 2)
                 return err(utt + "waveform too short for the reflection padding (need n_samples > filter_length / 2 = " + std::to_string(mf->n_fft / 2) + ")");
-            h_cnt[(size_t)u] = spk_partial_count(n_samples[u], hop, frames, step, min_coverage, &h_ext[(size_t)u]);
+            h_cnt[(size_t)u] = spk_partial_count(n, hop, frames, step, min_coverage, &h_ext[(size_t)u]);
             if (dv && h_cnt[(size_t)u] > dv->cap_N)
                 return err(utt + std::to_string(h_cnt[(size_t)u]) + " partial utterances exceed the encoder's max_partials = " + std::to_string(dv->cap_N));
             if (h_ext[(size_t)u] > 0x7fffffffLL - hop) return err(utt + "too long");
@@ -211,20 +222,21 @@ public:
         if (dv && dv->dirty && dv->refresh() != 0) return err(std::string(who) + dv->last_error);
         const bool two_streams = dv && dv->stream != mf->stream;
         if (two_streams) { DEV_CHECK(mf->mem.event(ev_front)); DEV_CHECK(mf->mem.event(ev_enc)); }
-        h_wav.assign((size_t)total, 0.f);
-        {
+        if (!rs) {
+            h_wav.assign((size_t)total, 0.f);
             long long src = 0, dst = 0;
             for (int u = 0; u < n_utts; ++u) {
                 std::copy(wavs + src, wavs + src + n_samples[u], h_wav.begin() + dst);
                 src += n_samples[u];
                 dst += h_ext[(size_t)u];
-                n_partials_out[u] = h_cnt[(size_t)u];
             }
         }
+        for (int u = 0; u < n_utts; ++u) n_partials_out[u] = h_cnt[(size_t)u];
         h_win.clear();
         h_off.clear();
         keep_utts.clear();
         keep_maps.clear();
+        keep_rs.clear();
         chunks.clear();
         int max_N = 0;
         for (int u0 = 0; u0 < n_utts;) {   // a chunk: consecutive utterances within the encoder's capacity (front-end only: the whole call)
@@ -238,12 +250,34 @@ public:
         // sized once for the largest chunk, before the first launch: a later, larger chunk must not free the stack the previous chunk's
         // encoder still reads on the other stream
         if (mf->grow(stack, (size_t)max_N * span4 * 4 + 64, "partial utterances") || mf->grow(win, (size_t)max_N, "windows")) return -1;
-        long long wav0 = 0, part0 = 0;
+        if (rs) {   // the same for the resampler's buffers: the largest chunk's source samples, slots and utterances
+            long long max_src = 0, max_slots = 0;
+            size_t max_utts = 0;
+            for (const Chunk& c : chunks) {
+                long long n_src = 0, slots = 0;
+                for (int u = c.u0; u < c.u1; ++u) { n_src += n_samples[u]; slots += (h_n[(size_t)u] + rs->run - 1) / rs->run; }
+                max_src = std::max(max_src, n_src);
+                max_slots = std::max(max_slots, slots);
+                max_utts = std::max(max_utts, (size_t)(c.u1 - c.u0));
+            }
+            if (max_src > (1LL << 31) - 1) return err(std::string(who) + "too many samples in one chunk");
+            if (rs->reserve(max_src, max_slots, max_utts)) return -1;
+        }
+        long long wav0 = 0, src0 = 0, part0 = 0;
         for (size_t c = 0; c < chunks.size(); ++c) {
             const int u0 = chunks[c].u0, u1 = chunks[c].u1, N = chunks[c].N;
             mf->pack_begin();
             for (int u = u0; u < u1; ++u) mf->pack_add(h_ext[(size_t)u], mf->frames_of((int)h_ext[(size_t)u]));
-            if (mf->stage("mtts_dvector_embed_wavs", true) || mf->pad_waveforms(h_wav.data() + wav0, false, true)) return -1;
+            if (mf->stage("mtts_dvector_embed_wavs", true)) return -1;
+            if (rs) {   // source-rate samples up, resampled into mf->wav over zeros (the zero-extension to the last window's end)
+                DEV_CHECK(hipMemsetAsync(mf->wav.p, 0, (size_t)mf->n_samples * sizeof(float), mf->stream));
+                rs->table_begin();
+                for (int u = u0; u < u1; ++u) rs->table_add(n_samples[u], mf->h_utts[(size_t)(u - u0)].wav0);
+                if (rs->launch(wavs + src0, target_dbfs, increase_only != 0) || mf->pad_staged(false, true)) return -1;
+                keep_rs.emplace_back(std::move(rs->h_utts));
+                rs->h_utts.clear();
+                src0 += rs->n_src;
+            } else if (mf->pad_waveforms(h_wav.data() + wav0, false, true)) return -1;
             power_mel();
             h_win.emplace_back();
             h_off.emplace_back(1, 0);

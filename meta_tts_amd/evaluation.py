@@ -9,9 +9,11 @@ centroids are device kernels too (index arrays in place of the reference's np.re
 are a few hundred scores and run on the host in numpy (sklearn's det_curve / roc_curve / auc restated; sklearn is not imported).
 
 resemblyzer is not vendored by the reference and not part of this project: its `wav_to_mel_spectrogram` and
-`VoiceEncoder.compute_partial_slices` are restated here from the published recipe.  Its `preprocess_wav` (resampling to 16 kHz,
--30 dBFS volume normalisation, webrtcvad silence trimming) is NOT built: every waveform handed to this module is taken as 16 kHz
-float32 as it is.  Figures (the reference's matplotlib / seaborn plots) are out of scope."""
+`VoiceEncoder.compute_partial_slices` are restated here from the published recipe.  Of its `preprocess_wav`, resampling to 16 kHz and
+the -30 dBFS volume normalisation run on the device when asked for (`embed_utterances(source_rate=, normalize_dbfs=)`,
+`WavsToDvector(resample=True)`; audio/resample.py, csrc/resample.h); webrtcvad silence trimming is NOT built.  Without those arguments
+every waveform handed to this module is taken as 16 kHz float32 as it is.  Figures (the reference's matplotlib / seaborn plots) are
+out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -66,7 +68,7 @@ class SpeakerEmbedder:
     """The speaker encoder end to end on the device.  `state_dict`: the resemblyzer `VoiceEncoder` weights in torch's names
     (lstm.weight_ih_l0 ... linear.bias; None: deterministic synthetic weights, for tests and benchmarks); `encoder=False` builds the
     front-end only (`reference_mel_slices` for preprocessing).  Waveforms are 16 kHz float32 and are NOT resampled, normalised or
-    trimmed (resemblyzer's `preprocess_wav` is not part of this project)."""
+    trimmed unless `embed_utterances` is given `source_rate` (resemblyzer's silence trimming is not part of this project)."""
 
     def __init__(self, state_dict=None, max_partials: int = 2048, max_utts: int = 256, hidden: int = HIDDEN, emb: int = EMBED, layers: int = LAYERS,
                  rate: float = 1.3, min_coverage: float = 0.75, device: int = 0, lib_path=None, encoder: bool = True):
@@ -79,6 +81,7 @@ class SpeakerEmbedder:
         self._dev.check(self.lib.mtts_stft_load(self._dev.h, _ptr(self.forward_basis), _ptr(self.mel_basis)))
         self.encoder = DVectorEncoder(state_dict, max_partials=max_partials, max_utts=max_utts, hidden=hidden, emb=emb, layers=layers, device=device,
                                       lib_path=lib_path) if encoder else None
+        self._resamplers = {}   # source rate -> audio.resample.Resampler on this front-end's handle (embed_utterances(source_rate=))
 
     def set_streams(self, stft_stream: int, encoder_stream: Optional[int] = None):
         """HIP streams of the two handles (the stages are ordered by events when they differ)."""
@@ -107,25 +110,49 @@ class SpeakerEmbedder:
         self._dev.check(self.lib.mtts_stft_power_mel_batch(self._dev.h, len(ws), _ptr(n), _ptr(packed), _ptr(mel)))
         return np.split(mel, np.cumsum(T)[:-1])
 
-    def _run(self, wavs, want_vectors: bool, want_slices: bool):
+    def resampler(self, source_rate: int, preset: str = "kaiser_best"):
+        """The resampler source_rate -> 16 kHz on this front-end's handle (built on first use; 16 kHz itself: the identity)."""
+        from .audio.resample import Resampler
+        key = (int(source_rate), preset)
+        if key not in self._resamplers:
+            self._resamplers[key] = Resampler(int(source_rate), SAMPLING_RATE, preset, _handle=self._dev)
+        return self._resamplers[key]
+
+    def _run(self, wavs, want_vectors: bool, want_slices: bool, source_rate=None, normalize_dbfs=None, increase_only=True):
         ws, n, packed = self._pack(wavs)
-        counts = np.asarray([len(compute_partial_slices(int(k), self.rate, self.min_coverage)[1]) for k in n], np.int32)
+        rs = None
+        if source_rate is not None:
+            rs = self.resampler(source_rate)
+            if getattr(self._dev, "_resampler_key", None) != rs._key:
+                rs.load()
+        elif normalize_dbfs is not None:
+            raise ValueError("normalize_dbfs needs source_rate (16000 for waveforms that are at the encoder's rate already)")
+        counts = np.asarray([len(compute_partial_slices(rs.output_length(int(k)) if rs else int(k), self.rate, self.min_coverage)[1]) for k in n], np.int32)
         got = np.empty(len(ws), np.int32)
         out = np.empty((len(ws), self.emb), np.float32) if want_vectors else None
         slices = np.empty((int(counts.sum()), PARTIAL_FRAMES, MEL_N_CHANNELS), np.float32) if want_slices else None
         enc = self.encoder.h if want_vectors else None
-        self._dev.check(self.lib.mtts_dvector_embed_wavs(enc, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step,
-                                                         float(self.min_coverage), _ptr(out) if want_vectors else None, _ptr(got),
-                                                         _ptr(slices) if want_slices else None))
+        outs = (_ptr(out) if want_vectors else None, _ptr(got), _ptr(slices) if want_slices else None)
+        if rs is None:
+            self._dev.check(self.lib.mtts_dvector_embed_wavs(enc, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step,
+                                                             float(self.min_coverage), *outs))
+        else:   # resampled (and normalised) on the device, chunk by chunk, into the packed waveform buffer
+            self._dev.check(self.lib.mtts_dvector_embed_wavs_resampled(enc, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step,
+                                                                       float(self.min_coverage), float("nan") if normalize_dbfs is None else float(normalize_dbfs),
+                                                                       int(bool(increase_only)), *outs))
         assert np.array_equal(got, counts), (got, counts)   # the device entry and compute_partial_slices state the same rule
         return out, (np.split(slices, np.cumsum(counts)[:-1]) if want_slices else None)
 
-    def embed_utterances(self, wavs, return_slices: bool = False):
+    def embed_utterances(self, wavs, return_slices: bool = False, source_rate: Optional[int] = None, normalize_dbfs: Optional[float] = None,
+                         increase_only: bool = True):
         """`VoiceEncoder.embed_utterance` (rate 1.3, min_coverage 0.75) of a list of 16 kHz float32 waveforms -> (B, emb) float32, every
-        row L2-normalised.  One chain of launches per chunk of utterances (as many as fit the encoder's max_partials)."""
+        row L2-normalised.  One chain of launches per chunk of utterances (as many as fit the encoder's max_partials).
+        source_rate: the waveforms are at that rate and are resampled to 16 kHz on the device in front of the same chain (the 16 kHz
+        signal never visits the host); normalize_dbfs: and normalised to that level (resemblyzer: -30, increase_only) — the result
+        equals `embed_utterances(Resampler.resample_batch(wavs, normalize_dbfs))` bit for bit."""
         if self.encoder is None:
             raise MttsError("SpeakerEmbedder(encoder=False) has no encoder")
-        out, slices = self._run(wavs, True, return_slices)
+        out, slices = self._run(wavs, True, return_slices, source_rate, normalize_dbfs, increase_only)
         return (out, slices) if return_slices else out
 
     def embed_utterance(self, wav):
@@ -199,11 +226,16 @@ def _testing_dir(data_dir: str) -> str:
 class WavsToDvector:
     """wavs_to_dvector.py: every wav of a test run -> d-vectors, saved as npy/<corpus>/<mode>_dvector.npy (an existing file is loaded
     instead, as in the reference).  `wav_loader(path) -> 16 kHz float32 waveform` (default: `read_wav_16k`).  All wavs of a mode go to
-    the device in one `embed_utterances` call."""
+    the device in one `embed_utterances` call.  resample=True: files of any rate (a result tree's 22 050 Hz wavs) are read with
+    `preprocessor.read_wav`, grouped by rate, and each group is resampled to 16 kHz and normalised to `normalize_dbfs` (resemblyzer's
+    `preprocess_wav` without its silence trimming; None: not normalised) on the device in front of the encoder, one call per group."""
 
     def __init__(self, config: EvalConfig, embedder: SpeakerEmbedder, wav_loader: Optional[Callable[[str], np.ndarray]] = None, pair_list=None,
-                 rng: Optional[random.Random] = None, run: bool = True):
+                 rng: Optional[random.Random] = None, run: bool = True, resample: bool = False, normalize_dbfs: Optional[float] = -30.0):
         self.config, self.embedder = config, embedder
+        self.resample, self.normalize_dbfs = bool(resample), normalize_dbfs
+        if resample and wav_loader is not None:
+            raise ValueError("WavsToDvector(resample=True) reads the files itself: wav_loader must be None")
         self.corpus, self.data_dir_dict = config.corpus, config.data_dir_dict
         self.n_sample, self.n_speaker, self.mode_step_list = config.n_sample, config.n_speaker, config.mode_step_list
         self.wav_loader = wav_loader or read_wav_16k
@@ -225,7 +257,21 @@ class WavsToDvector:
             self.dvector_list_dict = self.get_dvector()
 
     def files_to_dvectors(self, paths: Sequence[str]) -> np.ndarray:
-        return self.embedder.embed_utterances([self.wav_loader(p) for p in paths])
+        if not self.resample:
+            return self.embedder.embed_utterances([self.wav_loader(p) for p in paths])
+        from .preprocessor import read_wav
+        by_rate: Dict[int, List[int]] = {}
+        wavs = []
+        for i, p in enumerate(paths):
+            wav, rate = read_wav(p)
+            wavs.append(wav)
+            by_rate.setdefault(int(rate), []).append(i)
+        if not wavs:
+            raise MttsError("no waveforms")
+        out = np.empty((len(wavs), self.embedder.emb), np.float32)
+        for rate, idx in sorted(by_rate.items()):
+            out[idx] = self.embedder.embed_utterances([wavs[i] for i in idx], source_rate=rate, normalize_dbfs=self.normalize_dbfs)
+        return out
 
     def get_speaker_id_map(self):
         fwd, inv = {}, {}

@@ -6,7 +6,8 @@ with the partial statistics, and the normalisation with its min / max (csrc/prep
 every utterance of a call shares every launch.  The host does what is text or file handling: the TextGrid reader, `get_alignment`,
 the walk over the corpus, the `.npy` files.  Two third-party steps are injected, not restated: pitch extraction (`f0_fn`; the default calls pyworld's DIO + StoneMask as
 the reference does and raises when pyworld is missing) and the speaker-encoder reference mels (`spk_ref_fn`; skipped when absent).
-Wavs are read with scipy.io.wavfile (or an injected loader) and are NOT resampled: a file whose rate differs from the config's raises.
+Wavs are read with scipy.io.wavfile (or an injected loader); a file whose rate differs from the config's raises unless
+`build_from_path(resample=True)`, which resamples each batch's wavs on the device (audio/resample.py; librosa.load's role in the reference).
 
 Deliberate differences from the reference's `build_from_path`: directory listings are sorted (the reference takes `os.listdir`
 order), and an utterance without a TextGrid is skipped (the reference re-fits the previous utterance's values in that case)."""
@@ -130,6 +131,7 @@ class Preprocessor(_OnHandle):
                                  pp["audio"]["sampling_rate"], pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"], max_samples=max_samples, device=device,
                                  lib_path=lib_path)
         self._dev = self.STFT._dev   # the TacotronSTFT's handle: this class's device steps run on it
+        self._resamplers = {}   # file rate -> audio.resample.Resampler on this handle (build_from_path(resample=True))
         self.train_set = self.val_set = self.test_set = None
         if "subsets" in config:
             self.train_set = config["subsets"].get("train", None)
@@ -309,11 +311,28 @@ class Preprocessor(_OnHandle):
             return embedder.reference_mel_slices(np.asarray(wav, np.float32))
         return spk_ref_fn
 
-    def build_from_path(self, f0_fn=None, batch_utterances=32, wav_loader=None, spk_ref_fn=None):
+    def resample_to_config_rate(self, wavs, rates, preset="kaiser_best"):
+        """The waveforms whose rate differs from the config's, resampled on the device: one `resample_batch` call per distinct rate."""
+        from .audio.resample import Resampler
+        out = [np.asarray(w, np.float32) for w in wavs]
+        by_rate = {}
+        for i, r in enumerate(rates):
+            if int(r) != int(self.sampling_rate):
+                by_rate.setdefault(int(r), []).append(i)
+        for rate, idx in sorted(by_rate.items()):
+            if (rate, preset) not in self._resamplers:
+                self._resamplers[(rate, preset)] = Resampler(rate, int(self.sampling_rate), preset, _handle=self._dev)
+            for i, w in zip(idx, self._resamplers[(rate, preset)].resample_batch([out[i] for i in idx])):
+                out[i] = w
+        return out
+
+    def build_from_path(self, f0_fn=None, batch_utterances=32, wav_loader=None, spk_ref_fn=None, resample=False):
         """preprocessor.py:60-185.  f0_fn(wav, sampling_rate, hop_length) -> float64[T] (default: pyworld); wav_loader(path) -> (float32
         wav, rate) (default: scipy.io.wavfile); spk_ref_fn(speaker, basename) -> the spk_ref_mel_slices array (default: not written;
         `speaker_reference_fn` makes one on the device).
-        `batch_utterances` utterances share each device call.  Returns {subset: [metadata lines]}."""
+        `batch_utterances` utterances share each device call.  resample=True: a file at another rate than the config's is not an error;
+        the wavs of a batch are resampled to the config's rate in one device call per distinct rate (kaiser_best) before they are cut
+        to the alignment's [start, end) and handed to f0_fn.  Returns {subset: [metadata lines]}."""
         f0_fn = f0_fn or pyworld_f0
         wav_loader = wav_loader or read_wav
         for kind in ("mel", "pitch", "energy", "duration"):
@@ -330,7 +349,16 @@ class Preprocessor(_OnHandle):
 
         def flush(pending, out):
             nonlocal n_frames
-            for r in self.process_utterances(pending, spk_ref_fn=spk_ref_fn):
+            # pending: (speaker, basename, whole wav, its rate, phones, durations, start, end, raw_text)
+            wavs = [p[2] for p in pending]
+            if resample:
+                wavs = self.resample_to_config_rate(wavs, [p[3] for p in pending])
+            items = []
+            for (speaker, basename, _, _, phones, durations, start, end, raw_text), wav in zip(pending, wavs):
+                wav = np.asarray(wav, np.float32)[int(self.sampling_rate * start): int(self.sampling_rate * end)]
+                f0 = np.asarray(f0_fn(wav, self.sampling_rate, self.hop_length), np.float64)
+                items.append((speaker, basename, wav, phones, durations, f0, raw_text))
+            for r in self.process_utterances(items, spk_ref_fn=spk_ref_fn):
                 if r is None:
                     continue
                 out.append(r.info)
@@ -355,13 +383,11 @@ class Preprocessor(_OnHandle):
                     if start >= end:
                         continue
                     wav, sr = wav_loader(os.path.join(dset_dir, speaker, wav_name))
-                    if int(sr) != int(self.sampling_rate):
-                        raise MttsError(f"{wav_name}: sampling rate {sr} differs from the config's {self.sampling_rate} (no resampling here)")
-                    wav = np.asarray(wav, np.float32)[int(self.sampling_rate * start): int(self.sampling_rate * end)]
+                    if int(sr) != int(self.sampling_rate) and not resample:
+                        raise MttsError(f"{wav_name}: sampling rate {sr} differs from the config's {self.sampling_rate} (no resampling here: pass resample=True)")
                     with open(os.path.join(dset_dir, speaker, f"{basename}.lab")) as f:
                         raw_text = f.readline().strip("\n")
-                    f0 = np.asarray(f0_fn(wav, self.sampling_rate, self.hop_length), np.float64)
-                    pending.append((speaker, basename, wav, phones, durations, f0, raw_text))
+                    pending.append((speaker, basename, wav, int(sr), phones, durations, start, end, raw_text))
                     if len(pending) >= batch_utterances:
                         flush(pending, out)
                 i += 1
