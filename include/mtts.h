@@ -541,6 +541,29 @@ int mtts_stft_resample_batch(mtts_stft* h, int n_utts, const int* n_in, const fl
 int mtts_dvector_embed_wavs_resampled(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
                                       double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out);
 
+/* ---- fundamental frequency of waveform batches --------------------------------------------------------------
+ * The pitch feature of the preprocessing stage, on the packed waveform buffer of an mtts_stft handle.  The reference calls pyworld's
+ * DIO + StoneMask (preprocessor/preprocessor.py:214-220); pyworld is not vendored and NOT restated: parity with it is UNPINNED.  What is
+ * computed is YIN (de Cheveigne & Kawahara 2002) on DIO's frame grid.  Opt-in: a handle without a pitch configuration behaves as before.
+ * load_pitch: tau_max = ceil(sampling_rate / f0_floor), tau_min = floor(sampling_rate / f0_ceil), W = the smallest multiple of 64 that
+ * is >= 1.5 tau_max (512 at 22 050 Hz and 71 Hz), L = W + tau_max; the hop is the handle's hop_length.  Replaces a configuration loaded
+ * before.  Errors: f0_ceil <= f0_floor, tau_min < 2, fewer than two lags in [tau_min, tau_max), non-finite or non-positive arguments
+ * (silence_rms may be 0), a frame span W + tau_max beyond what a workgroup stages in LDS (about 4700 samples).
+ * f0_batch: n_utts waveforms packed one after another in `wavs` (float32, n_samples[u] each; host) -> f0 (float64) and aperiodicity
+ * (float32, or NULL), packed one after another, T_u = n_samples[u] / hop_length + 1 values per utterance (mel_batch's and DIO's frame
+ * count).  Frame t reads s = x[t hop - L / 2 .. + L), zeros outside its utterance (never a neighbouring utterance's samples):
+ *   d(tau)  = sum_{j < W} (s[j] - s[j + tau])^2 for tau = 0 .. tau_max, float32 FMAs in ascending j;
+ *   d'(0) = 1, d'(tau) = d(tau) tau / sum_{k = 1 .. tau} d(k) in float32 (1 where the running sum is 0);
+ *   f0 = 0 if mean(s[0 : W]^2) < silence_rms^2, or if no tau in [tau_min, tau_max) has d'(tau) < threshold; else tau = the smallest
+ *   such lag, moved forward while d'(tau + 1) < d'(tau) (within the range), and f0 = sampling_rate / (tau + off), off = 0.5 (y0 - y2) /
+ *   (y0 - 2 y1 + y2) over y = d'(tau - 1 .. tau + 1) in float64 (0 when the denominator is 0, and at tau = tau_min or tau_max - 1).
+ *   aperiodicity = the chosen d'(tau), 1 for an unvoiced frame.
+ * A frame's values depend on its utterance's samples and the configuration only: bit-identical alone, in any batch, at any position.
+ * Returns the total number of frames, < 0 on error.  Errors, before any launch: no configuration loaded, n_utts < 1 or > 65535, NULL
+ * n_samples / wavs / f0, n_samples[u] < 1 or beyond the handle's max_samples.  Synchronous. */
+int mtts_stft_load_pitch(mtts_stft* h, int sampling_rate, double f0_floor, double f0_ceil, double threshold, double silence_rms);
+int64_t mtts_stft_f0_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, double* f0, float* aperiodicity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,7 @@ class _Handle:
         if self.lib.mtts_stft_create(filter_length, hop_length, n_mel, max_samples, device, C.byref(h)) != 0:
             raise MttsError(self.lib.mtts_stft_last_error(None).decode())
         self.h = h
+        self.hop_length = int(hop_length)
 
     def check(self, rc):
         if rc < 0:

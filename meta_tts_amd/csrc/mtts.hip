@@ -11,6 +11,7 @@
 #include "griffin.h"
 #include "preprocess.h"
 #include "resample.h"
+#include "pitch.h"
 #include "speakereval.h"
 
 using namespace mtts;
@@ -52,6 +53,7 @@ struct mtts_stft {
     Preprocess pp;
     SpeakerEval se;
     Resample rs;
+    Pitch pt;
 };
 
 extern "C" {
@@ -692,6 +694,7 @@ int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_sampl
     h->pp.mf = &h->m;
     h->se.mf = &h->m;
     h->rs.mf = &h->m;
+    h->pt.mf = &h->m;
     h->se.device = device;
     if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; delete h; return -1; }
     *out = h;
@@ -746,6 +749,15 @@ int mtts_stft_normalize(mtts_stft* h, int64_t n, const void* values, int dtype, 
 int mtts_stft_load_resampler(mtts_stft* h, int up, int down, int taps, int lead, const float* bank) { return h ? h->rs.load(up, down, taps, lead, bank) : -1; }
 int mtts_stft_resample_batch(mtts_stft* h, int n_utts, const int* n_in, const float* wavs, double target_dbfs, int increase_only, float* out, double* gains) {
     return h ? h->rs.resample_batch(n_utts, n_in, wavs, target_dbfs, increase_only, out, gains) : -1;
+}
+
+// ---- fundamental frequency of waveform batches (pitch.h: YIN; the reference calls pyworld's DIO + StoneMask, preprocessor/preprocessor.py:214-220,
+// which is not restated) ----
+int mtts_stft_load_pitch(mtts_stft* h, int sampling_rate, double f0_floor, double f0_ceil, double threshold, double silence_rms) {
+    return h ? h->pt.load(sampling_rate, f0_floor, f0_ceil, threshold, silence_rms) : -1;
+}
+int64_t mtts_stft_f0_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, double* f0, float* aperiodicity) {
+    return h ? h->pt.f0_batch(n_utts, n_samples, wavs, f0, aperiodicity) : -1;
 }
 
 // ---- speaker-similarity evaluation (speakereval.h; reference evaluation/wavs_to_dvector.py, pair_similarity.py, centroid_similarity.py) ----

@@ -6,6 +6,8 @@ with the partial statistics, and the normalisation with its min / max (csrc/prep
 every utterance of a call shares every launch.  The host does what is text or file handling: the TextGrid reader, `get_alignment`,
 the walk over the corpus, the `.npy` files.  Two third-party steps are injected, not restated: pitch extraction (`f0_fn`; the default calls pyworld's DIO + StoneMask as
 the reference does and raises when pyworld is missing) and the speaker-encoder reference mels (`spk_ref_fn`; skipped when absent).
+`f0_fn="device"` needs no injected pitch: the batched YIN estimator of audio/pitch.py (csrc/pitch.h; NOT a DIO / StoneMask clone, parity
+with pyworld unpinned) takes all waveforms of a batch in one call.
 Wavs are read with scipy.io.wavfile (or an injected loader); a file whose rate differs from the config's raises unless
 `build_from_path(resample=True)`, which resamples each batch's wavs on the device (audio/resample.py; librosa.load's role in the reference).
 
@@ -132,6 +134,7 @@ class Preprocessor(_OnHandle):
                                  lib_path=lib_path)
         self._dev = self.STFT._dev   # the TacotronSTFT's handle: this class's device steps run on it
         self._resamplers = {}   # file rate -> audio.resample.Resampler on this handle (build_from_path(resample=True))
+        self._pitch = None      # audio.pitch.PitchExtractor on this handle, made by the first f0_batch call
         self.train_set = self.val_set = self.test_set = None
         if "subsets" in config:
             self.train_set = config["subsets"].get("train", None)
@@ -187,6 +190,14 @@ class Preprocessor(_OnHandle):
         self._check(self.lib.mtts_stft_mel_batch(self.h, len(wavs), _ptr(n), _ptr(keep), _ptr(packed), _ptr(mel), _ptr(energy)))
         cuts = np.cumsum(T)[:-1]
         return np.split(mel, cuts), np.split(energy, cuts)
+
+    def f0_batch(self, wavs):
+        """YIN F0 of every waveform in one device call on this preprocessor's handle (audio/pitch.py at its defaults: 71 .. 800 Hz,
+        threshold 0.15).  Returns ([f0 (T_u,) float64, 0 = unvoiced], [aperiodicity (T_u,) float32]), T_u = len(wav) // hop_length + 1."""
+        if self._pitch is None:
+            from .audio.pitch import PitchExtractor
+            self._pitch = PitchExtractor(self.sampling_rate, self.hop_length, _handle=self._dev)
+        return self._pitch.f0_batch(wavs)
 
     def phoneme_average(self, values, durations, interpolate=False):
         """preprocessor.py:231-261 for a list of frame-level arrays (all float64, or all float32) and their duration lists."""
@@ -327,12 +338,15 @@ class Preprocessor(_OnHandle):
         return out
 
     def build_from_path(self, f0_fn=None, batch_utterances=32, wav_loader=None, spk_ref_fn=None, resample=False):
-        """preprocessor.py:60-185.  f0_fn(wav, sampling_rate, hop_length) -> float64[T] (default: pyworld); wav_loader(path) -> (float32
+        """preprocessor.py:60-185.  f0_fn(wav, sampling_rate, hop_length) -> float64[T] (default: pyworld), or the string "device": one
+        `f0_batch` call (YIN on the device) for all cut waveforms of a batch; wav_loader(path) -> (float32
         wav, rate) (default: scipy.io.wavfile); spk_ref_fn(speaker, basename) -> the spk_ref_mel_slices array (default: not written;
         `speaker_reference_fn` makes one on the device).
         `batch_utterances` utterances share each device call.  resample=True: a file at another rate than the config's is not an error;
         the wavs of a batch are resampled to the config's rate in one device call per distinct rate (kaiser_best) before they are cut
         to the alignment's [start, end) and handed to f0_fn.  Returns {subset: [metadata lines]}."""
+        if isinstance(f0_fn, str) and f0_fn != "device":
+            raise MttsError(f"build_from_path: f0_fn={f0_fn!r} (a callable, None for pyworld, or \"device\")")
         f0_fn = f0_fn or pyworld_f0
         wav_loader = wav_loader or read_wav
         for kind in ("mel", "pitch", "energy", "duration"):
@@ -353,11 +367,9 @@ class Preprocessor(_OnHandle):
             wavs = [p[2] for p in pending]
             if resample:
                 wavs = self.resample_to_config_rate(wavs, [p[3] for p in pending])
-            items = []
-            for (speaker, basename, _, _, phones, durations, start, end, raw_text), wav in zip(pending, wavs):
-                wav = np.asarray(wav, np.float32)[int(self.sampling_rate * start): int(self.sampling_rate * end)]
-                f0 = np.asarray(f0_fn(wav, self.sampling_rate, self.hop_length), np.float64)
-                items.append((speaker, basename, wav, phones, durations, f0, raw_text))
+            cut = [np.asarray(wav, np.float32)[int(self.sampling_rate * p[6]): int(self.sampling_rate * p[7])] for p, wav in zip(pending, wavs)]
+            f0s = self.f0_batch(cut)[0] if f0_fn == "device" else [np.asarray(f0_fn(wav, self.sampling_rate, self.hop_length), np.float64) for wav in cut]
+            items = [(p[0], p[1], wav, p[4], p[5], f0, p[8]) for p, wav, f0 in zip(pending, cut, f0s)]
             for r in self.process_utterances(items, spk_ref_fn=spk_ref_fn):
                 if r is None:
                     continue

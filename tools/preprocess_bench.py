@@ -4,7 +4,11 @@ phoneme-level pitch and energy, no file I/O): utterances/s and audio-seconds/s o
   new          the batched device path (meta_tts_amd/preprocessor.py: mel_batch, phoneme_average x 2, outlier_stats x 2, merge_stats,
                normalize_values x 2 — all utterances share every launch);
   device_loop  the route before it: one get_mel_from_wav call per utterance on the device, the remaining steps in numpy;
-  cpu          the torch / numpy restatement (oracle/stft_oracle.py + the same numpy steps) on 16 threads.
+  cpu          the torch / numpy restatement (oracle/stft_oracle.py + the same numpy steps) on 16 threads;
+  new_f0       `new` with the pitch computed too: one f0_batch call (csrc/pitch.h, YIN) in front, its output fed to the pitch steps;
+  f0           that f0_batch call alone;
+  f0_host      the same F0 definition in float64 numpy (tests/f0_oracle.py), utterances spread over 16 threads.
+The first three legs take an injected f0 (pitch extraction is not part of their numbers).
 Each leg runs in a child process of its own under a time limit, after warm-up, as the median wall time of repeated calls that end in
 a device synchronise (every entry point is synchronous); a leg that fails ends the run.  Writes profiles/preprocess_bench.json and
 prints it.  Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/preprocess_bench.py --leg new` run."""
@@ -97,7 +101,16 @@ def leg(name, a):
     data = corpus(a.utts, a.secs)
     wavs, durs, f0s = [d[0] for d in data], [d[1] for d in data], [d[2] for d in data]
     keep = [sum(d) for d in durs]
-    if name == "cpu":
+    if name == "f0_host":
+        from concurrent.futures import ThreadPoolExecutor
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import f0_oracle
+        pool = ThreadPoolExecutor(16)
+
+        def call():
+            f0 = list(pool.map(lambda w: f0_oracle.yin(w, SR, HOP)[0], wavs))
+            return {"pitch": [min(f.min() for f in f0), max(f.max() for f in f0), float(np.mean([f.mean() for f in f0])), float(np.mean([(f > 0).mean() for f in f0]))]}
+    elif name == "cpu":
         import torch
         from meta_tts_amd.audio.stft import mel_filterbank
         from oracle import stft_oracle as orc
@@ -113,14 +126,19 @@ def leg(name, a):
         from meta_tts_amd.audio import tools
         from meta_tts_amd.preprocessor import Preprocessor
         pp = Preprocessor(CFG, max_samples=int(SR * a.secs) + 37 * a.utts + 64)
-        if name == "device_loop":
+        if name == "f0":
+            def call():
+                f0 = pp.f0_batch(wavs)[0]
+                return {"pitch": [min(f.min() for f in f0), max(f.max() for f in f0), float(np.mean([f.mean() for f in f0])), float(np.mean([(f > 0).mean() for f in f0]))]}
+        elif name == "device_loop":
             def call():
                 en = [tools.get_mel_from_wav(w, pp.STFT)[1] for w in wavs]
                 return host_steps(en, f0s, durs)
         else:
             def call():
+                f0 = pp.f0_batch(wavs)[0] if name == "new_f0" else f0s
                 _, en = pp.mel_batch(wavs, keep)
-                p = pp.phoneme_average([f[:k] for f, k in zip(f0s, keep)], durs, interpolate=True)
+                p = pp.phoneme_average([f[:k] for f, k in zip(f0, keep)], durs, interpolate=True)
                 e = pp.phoneme_average(en, durs)
                 stats = {}
                 for k, v in (("pitch", p), ("energy", e)):
@@ -148,7 +166,7 @@ def main():
     ap.add_argument("--secs", type=float, default=5.0)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--leg", default="all", choices=["all", "new", "device_loop", "cpu"])
+    ap.add_argument("--leg", default="all", choices=["all", "new", "device_loop", "cpu", "new_f0", "f0", "f0_host"])
     ap.add_argument("--timeout", type=int, default=240, help="seconds per leg")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "preprocess_bench.json"))
     a = ap.parse_args()
@@ -156,7 +174,7 @@ def main():
         print(json.dumps(leg(a.leg, a)))
         return
     res = {"utts": a.utts, "secs": a.secs, "warmup": a.warmup, "reps": a.reps, "config": "LibriTTS 1024/256/1024, 80 mels, 22050 Hz, phoneme level"}
-    for name in ("new", "device_loop", "cpu"):
+    for name in ("new", "device_loop", "cpu", "new_f0", "f0", "f0_host"):
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", name, "--utts", str(a.utts), "--secs", str(a.secs), "--warmup", str(a.warmup),
                             "--reps", str(a.reps)], capture_output=True, text=True, timeout=a.timeout)
         if r.returncode != 0:
@@ -165,6 +183,7 @@ def main():
         res[name] = json.loads(r.stdout.strip().splitlines()[-1])
     res["speedup_vs_device_loop"] = round(res["device_loop"]["ms_per_call"] / res["new"]["ms_per_call"], 2)
     res["speedup_vs_cpu"] = round(res["cpu"]["ms_per_call"] / res["new"]["ms_per_call"], 2)
+    res["f0_speedup_vs_host"] = round(res["f0_host"]["ms_per_call"] / res["f0"]["ms_per_call"], 2)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
