@@ -335,6 +335,32 @@ int mtts_length_regulate_bwd(int n_phonemes, int C, const float* dout, const int
 int mtts_layernorm_jvp(int rows, int C, const float* ta, const float* tres, const float* z, const float* stats, const float* gamma, const float* tgamma,
                        const float* tbeta, const unsigned char* mask, float* ty, void* ws, void* hip_stream);
 int mtts_softmax_jvp(int n_mat, int L, const float* P, float* tS, void* ws, void* hip_stream);
+/* The rest of the second-order row kernels (csrc/tangent.h; ColArgs modes 5 and 6 of csrc/rowops.h), one entry per kernel.  "t" prefixes
+ * the tangent of a forward value, "tg" the tangent of a gradient, "h" a tangent parameter gradient (= Hessian-vector product row).
+ * layernorm_jvp_full: layernorm_jvp that also keeps tz_out [rows][C] = ta + tres and tstats_out [rows][2] (either may be NULL).
+ * layernorm_jvp_bwd: primal dz and tangent tgz of the LayerNorm backward, hgamma / hbeta [C]; relu_on_z multiplies both by [z > 0];
+ *   two_launch 0: hgamma / hbeta from the kernel's own 8-row partials, 1: from a column reduction of its own (another summation order).
+ * softmax_jvp_bwd: in place, dP -> dS = alpha P (dP - c), tgP -> tg_S; pad columns [L, ldS) are zeroed.
+ * batchnorm_jvp: tsum [2C] = [sum tx xhat | sum tx] over the inrect rows and ta = tangent of y; y / stats from mtts_batchnorm_fwd.
+ * batchnorm_jvp_bwd: dx, tdx, hgamma, hbeta; dgamma / dbeta from mtts_batchnorm_bwd, tsum / ta from mtts_batchnorm_jvp.
+ * rowdot_jvp: tout [rows] = valid ? tx . w + x . tw + tb : 0 (tb: one float);  rowdot_jvp_bwd: dx = dout w, tdx = tgout w + dout tw.
+ * tgamma / tbeta / tw / tb / mask may be NULL. */
+int mtts_layernorm_jvp_full(int rows, int C, const float* ta, const float* tres, const float* z, const float* stats, const float* gamma,
+                            const float* tgamma, const float* tbeta, const unsigned char* mask, float* ty, float* tz_out, float* tstats_out, void* ws,
+                            void* hip_stream);
+int mtts_layernorm_jvp_bwd(int rows, int C, const float* dy, const float* tgy, const float* z, const float* stats, const float* tz, const float* tstats,
+                           const float* gamma, const float* tgamma, const unsigned char* mask, int relu_on_z, int two_launch, float* dz, float* tgz,
+                           float* hgamma, float* hbeta, void* ws, void* hip_stream);
+int mtts_softmax_jvp_bwd(int n_mat, int L, const float* P, const float* tP, float* dP, float* tgP, float alpha, void* ws, void* hip_stream);
+int mtts_batchnorm_jvp(int rows, int n_in, int C, const float* x, const float* tx, const float* stats, const float* gamma, const float* tgamma,
+                       const float* tbeta, const float* y, const unsigned char* inrect, int do_tanh, float* tsum, float* ta, void* ws, void* hip_stream);
+int mtts_batchnorm_jvp_bwd(int rows, int n_in, int C, const float* dy, const float* tgy, const float* y, const float* ta, const float* x, const float* tx,
+                           const float* stats, const float* tsum, const float* gamma, const float* tgamma, const float* dgamma, const float* dbeta,
+                           const unsigned char* inrect, int do_tanh, float* dx, float* tdx, float* hgamma, float* hbeta, void* ws, void* hip_stream);
+int mtts_rowdot_jvp(int rows, int C, const float* x, const float* tx, const float* w, const float* tw, const float* tb, const unsigned char* valid,
+                    float* tout, void* ws, void* hip_stream);
+int mtts_rowdot_jvp_bwd(int rows, int C, const float* dout, const float* tgout, const float* w, const float* tw, float* dx, float* tdx, void* ws,
+                        void* hip_stream);
 
 /* ---- MelGAN generator: mel -> waveform --------------------------------------------
  * Replaces `LightningMelGAN.inverse / infer`, lightning/utils.py:8-30 (vocoder.mel2wav of torch.hub

@@ -121,6 +121,13 @@ EXPORTS = {
     "mtts_length_regulate_bwd": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mtts_layernorm_jvp": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 11),
     "mtts_softmax_jvp": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_layernorm_jvp_full": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 13),
+    "mtts_layernorm_jvp_bwd": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "mtts_softmax_jvp_bwd": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "mtts_batchnorm_jvp": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 4),
+    "mtts_batchnorm_jvp_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13 + [C.c_int] + [C.c_void_p] * 6),
+    "mtts_rowdot_jvp": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 9),
+    "mtts_rowdot_jvp_bwd": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 8),
     "mtts_dvector_create": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_void_p)]),
     "mtts_dvector_destroy": (None, [C.c_void_p]),
     "mtts_dvector_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -204,22 +204,117 @@ int mtts_length_regulate_bwd(int n_phonemes, int C, const float* dout, const int
 // Forward-mode twins used by the second-order path (tangent.h).  layernorm_jvp: tangent of y = mask * (gamma * xhat + beta) for the
 // input tangent ta (+ tres), parameter tangents tgamma / tbeta (null: 0), on the z / stats saved by mtts_layernorm_fwd.
 // softmax_jvp: tS -> tP = P (tS - sum_j P_j tS_j), in place.
-int mtts_layernorm_jvp(int rows, int C, const float* ta, const float* tres, const float* z, const float* stats, const float* gamma, const float* tgamma,
-                       const float* tbeta, const unsigned char* mask, float* ty, void* ws, void* stream) {
+// layernorm_jvp_full: the same launch with the kernel's two by-products kept — tz_out [rows][C] = ta + tres and tstats_out [rows][2] = (m1, m2),
+// what the tangent backward reads (either may be null: tstats then goes to scratch).
+int mtts_layernorm_jvp_full(int rows, int C, const float* ta, const float* tres, const float* z, const float* stats, const float* gamma,
+                            const float* tgamma, const float* tbeta, const unsigned char* mask, float* ty, float* tz_out, float* tstats_out, void* ws,
+                            void* stream) {
     if (bad_rows(rows, C) || !ta || !z || !stats || !gamma || !ty || !ws) return -1;
     const KernelWs k = carve(ws, rows, 0);
     if (put_meta(k, rows, rows)) return -1;
-    float* tstats = k.col_partial;   // per-row (m1, m2), scratch here
-    if ((long long)rows * 2 > (long long)k.chunks * 3 * 1024) return -1;
+    float* tstats = tstats_out ? tstats_out : k.col_partial;   // per-row (m1, m2), scratch when the caller keeps none
+    if (!tstats_out && (long long)rows * 2 > (long long)k.chunks * 3 * 1024) return -1;
     MTTS_LAUNCH_LN(ln_jvp_fwd_kernel, C, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, ta, (long long)0, tres,
                 (long long)0, z, (long long)0, stats, (long long)0, gamma, (long long)0, tgamma, tbeta, (long long)0, mask, (long long)0,
-                (float*)nullptr, (long long)0, ty, (long long)0, tstats, (long long)0, C, DropSpec(), DropSpec());
+                tz_out, (long long)0, ty, (long long)0, tstats, (long long)0, C, DropSpec(), DropSpec());
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int mtts_layernorm_jvp(int rows, int C, const float* ta, const float* tres, const float* z, const float* stats, const float* gamma, const float* tgamma,
+                       const float* tbeta, const unsigned char* mask, float* ty, void* ws, void* stream) {
+    return mtts_layernorm_jvp_full(rows, C, ta, tres, z, stats, gamma, tgamma, tbeta, mask, ty, nullptr, nullptr, ws, stream);
 }
 int mtts_softmax_jvp(int n_mat, int L, const float* P, float* tS, void* ws, void* stream) {
     if (n_mat < 1 || L < 1 || !P || !tS || !ws) return -1;
     const KernelWs k = carve(ws, 1, n_mat);
     if (put_seqs(k, n_mat, L)) return -1;
     MTTS_LAUNCH(softmax_jvp_fwd_kernel, dim3((L + 3) / 4, 1, n_mat), dim3(256), (hipStream_t)stream, (const AttnSeq*)k.seqs, P, tS);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Tangent backward twins (tangent.h), primal + tangent in one pass, on what the forward entries above saved.
+// layernorm_jvp_bwd: dy / tgy -> dz / tgz and hv(gamma) = sum_rows (tgy xhat + dy t_xhat), hv(beta) = sum_rows tgy over the unmasked rows.
+// two_launch = 0: the kernel's own 8-row partials, folded by colfinal (the engine's default); 1: the ColArgs mode-5 reduction in front of
+// a kernel launch without partials (the engine under MTTS_SO_LN_PART=0).
+int mtts_layernorm_jvp_bwd(int rows, int C, const float* dy, const float* tgy, const float* z, const float* stats, const float* tz, const float* tstats,
+                           const float* gamma, const float* tgamma, const unsigned char* mask, int relu_on_z, int two_launch, float* dz, float* tgz,
+                           float* hgamma, float* hbeta, void* ws, void* stream) {
+    if (bad_rows(rows, C) || !dy || !tgy || !z || !stats || !tz || !tstats || !gamma || !dz || !tgz || !hgamma || !hbeta || !ws) return -1;
+    const KernelWs k = carve(ws, rows, 0);
+    if (put_meta(k, rows, rows)) return -1;
+    if (two_launch) {
+        ColArgs a;
+        a.X = tgy; a.X2 = dy; a.Z = z; a.stats = stats; a.Z2 = tz; a.stats2 = tstats; a.mask = mask; a.C = C; a.mode = 5; a.mfield = META_MP;
+        col_reduce(k, a, hgamma, hbeta, rows, (hipStream_t)stream);
+    }
+    const int ln_chunks = (rows + kLnRows - 1) / kLnRows;
+    MTTS_LAUNCH_LN(ln_jvp_bwd_kernel, C, row2_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, dy, (long long)0, tgy,
+                (long long)0, z, (long long)0, stats, (long long)0, tz, (long long)0, tstats, (long long)0, gamma, (long long)0, tgamma, (long long)0,
+                mask, (long long)0, dz, (long long)0, tgz, (long long)0, C, relu_on_z, (float*)nullptr, (long long)0, (float*)nullptr, (long long)0,
+                DropSpec(), DropSpec(), two_launch ? (float*)nullptr : k.col_partial, ln_chunks);
+    if (!two_launch)
+        MTTS_LAUNCH(colfinal_kernel, dim3(colfinal_blocks(C), 1, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, 1,
+                    (const float*)k.col_partial, ln_chunks, C, hgamma, hbeta, (long long)0, 1e-5f, 0, (int)kLnRows);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// in place: dP -> dS = alpha P (dP - c), tgP -> tg_S = alpha [tP (dP - c) + P (tgP - cdot)]; the pad columns [L, ldS) of both are zeroed
+int mtts_softmax_jvp_bwd(int n_mat, int L, const float* P, const float* tP, float* dP, float* tgP, float alpha, void* ws, void* stream) {
+    if (n_mat < 1 || L < 1 || !P || !tP || !dP || !tgP || !ws) return -1;
+    const KernelWs k = carve(ws, 1, n_mat);
+    if (put_seqs(k, n_mat, L)) return -1;
+    MTTS_LAUNCH(softmax_jvp_bwd_kernel, dim3((L + 3) / 4, 1, n_mat), dim3(256), (hipStream_t)stream, (const AttnSeq*)k.seqs, P, tP, dP, tgP, alpha);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// batchnorm_jvp: tangent of y = [tanh](gamma xhat + beta) for the input tangent tx on the stats / y of mtts_batchnorm_fwd: tsum [2C] =
+// [S1 | S0] = [sum tx xhat | sum tx] over the inrect rows (kept: the backward reads it), then ta; rows outside inrect give 0.
+int mtts_batchnorm_jvp(int rows, int n_in, int C, const float* x, const float* tx, const float* stats, const float* gamma, const float* tgamma,
+                       const float* tbeta, const float* y, const unsigned char* inrect, int do_tanh, float* tsum, float* ta, void* ws, void* stream) {
+    if (bad_rows(rows, C) || n_in < 1 || !x || !tx || !stats || !gamma || !y || !inrect || !tsum || !ta || !ws) return -1;
+    const KernelWs k = carve(ws, rows, 0);
+    if (put_meta(k, rows, n_in)) return -1;
+    ColArgs ca;
+    ca.X = tx; ca.Z = x; ca.stats = stats; ca.mask = inrect; ca.C = C; ca.mode = 3; ca.do_tanh = 0; ca.mfield = META_MR;
+    col_reduce(k, ca, tsum, tsum + C, rows, (hipStream_t)stream);
+    MTTS_LAUNCH(bn_jvp_apply_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, x, (long long)0, tx, (long long)0, stats,
+                (long long)0, (const float*)tsum, (const float*)(tsum + C), (long long)0, gamma, (long long)0, tgamma, tbeta, (long long)0, y,
+                (long long)0, inrect, (long long)0, do_tanh, ta, (long long)0, C, 1.f, DropSpec());
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// batchnorm_jvp_bwd: dy / tgy -> dx / tdx and hv(gamma), hv(beta) (the ColArgs mode-6 reduction); dgamma / dbeta are mtts_batchnorm_bwd's
+int mtts_batchnorm_jvp_bwd(int rows, int n_in, int C, const float* dy, const float* tgy, const float* y, const float* ta, const float* x, const float* tx,
+                           const float* stats, const float* tsum, const float* gamma, const float* tgamma, const float* dgamma, const float* dbeta,
+                           const unsigned char* inrect, int do_tanh, float* dx, float* tdx, float* hgamma, float* hbeta, void* ws, void* stream) {
+    if (bad_rows(rows, C) || n_in < 1 || !dy || !tgy || !y || !ta || !x || !tx || !stats || !tsum || !gamma || !dgamma || !dbeta || !inrect || !dx ||
+        !tdx || !hgamma || !hbeta || !ws)
+        return -1;
+    const KernelWs k = carve(ws, rows, 0);
+    if (put_meta(k, rows, n_in)) return -1;
+    ColArgs cb;
+    cb.X = tgy; cb.X2 = dy; cb.Y = y; cb.Y2 = ta; cb.Z = x; cb.Z2 = tx; cb.stats = stats; cb.stats2 = tsum; cb.mask = inrect; cb.C = C;
+    cb.mode = 6; cb.do_tanh = do_tanh; cb.mfield = META_MR;
+    col_reduce(k, cb, hgamma, hbeta, rows, (hipStream_t)stream);
+    MTTS_LAUNCH(bn_jvp_bwd_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, dy, (long long)0, tgy, (long long)0, y,
+                (long long)0, ta, (long long)0, x, (long long)0, tx, (long long)0, stats, (long long)0, tsum, (const float*)(tsum + C), (long long)0,
+                gamma, (long long)0, tgamma, (long long)0, dgamma, dbeta, (long long)0, (const float*)hgamma, (const float*)hbeta, (long long)0,
+                inrect, (long long)0, do_tanh, dx, (long long)0, tdx, (long long)0, C, 1.f, DropSpec());
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// rowdot (the variance predictors' 256 -> 1 projection): tout[row] = valid ? dot(tx, w) + dot(x, tw) + tb : 0; bwd: dx = dout w,
+// tdx = tgout w + dout tw.  tw / tb may be null (a projection that is not adapted).
+int mtts_rowdot_jvp(int rows, int C, const float* x, const float* tx, const float* w, const float* tw, const float* tb, const unsigned char* valid,
+                    float* tout, void* ws, void* stream) {
+    if (bad_rows(rows, C) || !x || !tx || !w || !valid || !tout || !ws) return -1;
+    const KernelWs k = carve(ws, rows, 0);
+    if (put_meta(k, rows, rows)) return -1;
+    MTTS_LAUNCH(rowdot_jvp_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, x, (long long)0, tx, (long long)0,
+                w, (long long)0, tw, tb, (long long)0, valid, (long long)0, tout, (long long)0, C);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int mtts_rowdot_jvp_bwd(int rows, int C, const float* dout, const float* tgout, const float* w, const float* tw, float* dx, float* tdx, void* ws,
+                        void* stream) {
+    if (bad_rows(rows, C) || !dout || !tgout || !w || !dx || !tdx || !ws) return -1;
+    const KernelWs k = carve(ws, rows, 0);
+    if (put_meta(k, rows, rows)) return -1;
+    MTTS_LAUNCH(rowdot_jvp_bwd_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, dout, tgout, (long long)0, w,
+                (long long)0, tw, (long long)0, dx, (long long)0, tdx, (long long)0, C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

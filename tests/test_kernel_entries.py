@@ -56,7 +56,8 @@ def dev(request):
     return Dev(request.param)
 
 
-@pytest.mark.parametrize("rows,Cc,with_res,with_mask", [(37, 256, True, True), (8, 32, False, False), (203, 1024, True, False), (5, 48, False, True)])
+@pytest.mark.parametrize("rows,Cc,with_res,with_mask", [(37, 256, True, True), (8, 32, False, False), (203, 1024, True, False), (5, 48, False, True),
+                                                        (419, 32, True, True)])   # 53 partial chunks: the four-deep loop of colfinal_fold
 def test_layernorm_fwd_bwd(dev, rows, Cc, with_res, with_mask):
     g = np.random.RandomState(rows + Cc)
     a, res = g.standard_normal((rows, Cc)).astype(np.float32), g.standard_normal((rows, Cc)).astype(np.float32)
@@ -120,7 +121,9 @@ def test_sdpa_and_softmax(dev, n_mat, L, dk):
     np.testing.assert_allclose(dev.get(dPd)[:, :, :L], ts.grad.numpy(), atol=3e-6)
 
 
-@pytest.mark.parametrize("B,T,Cc,do_tanh", [(3, 21, 48, 1), (2, 40, 512, 1), (1, 9, 80, 0)])
+@pytest.mark.parametrize("B,T,Cc,do_tanh", [(3, 21, 48, 1), (2, 40, 512, 1), (1, 9, 80, 0),
+                                            (2, 300, 16, 1),     # 612 rows, 20 chunks: the unrolled pair merge of the statistics fold (mode 2)
+                                            (2, 800, 16, 1)])    # 1612 rows, 51 chunks: the four-deep loop of the backward's fold
 def test_batchnorm_fwd_bwd_over_padded_rectangle(dev, B, T, Cc, do_tanh):
     """rows = G + B * (T + G) with 4 guard rows between sequences (engine.h row space R); the statistics run over all B * T in-rect
     rows, padded frames included, as nn.BatchNorm1d over (B, C, T_max) does in the reference."""
