@@ -218,7 +218,7 @@ int mtts_allreduce_outer(mtts_handle* h);
  * communication stream of the handle the moment the backward has completed the module — behind events of the main and the
  * weight-gradient side stream — while the main stream continues; the exchange tail goes out first.  The following mtts_allreduce_outer
  * only makes the handle's stream wait for those collectives (its time is the EXPOSED part of the exchange).  One-shot: disarmed by
- * the gradient call.  Returns 0 when armed, 1 when the overlapped path is not available (no communicator, MTTS_AR_OVERLAP=0, an
+ * the gradient call.  Returns 0 when armed, 1 when the overlapped path is not available (no communicator, an
  * architecture whose modules are not contiguous runs of the flat buffer) — mtts_allreduce_outer then reduces the whole buffer as before.
  * Results equal the one-shot exchange's (the same floats, the same collective, in pieces).  mtts_allreduce_launches: collectives the
  * last overlapped exchange issued (buckets + tail). */

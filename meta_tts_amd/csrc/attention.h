@@ -36,8 +36,8 @@ struct AttnFwdArgs {
     float scale;
     int dk;                          // head width: multiple of 8, <= 128
     int prio;                        // > 0: the wavefronts raise their issue priority (the critical stream's launches beside side-stream work; gemm.h: GemmArgs::wave_prio)
-    int rot;                         // 1: the key chunks of phase A start at wavefront (blockIdx.x + blockIdx.z) & 3 instead of 0 — with nkc % 4 != 0 the first
-                                     // wavefronts carry one chunk more, and wavefront w of every workgroup sits on SIMD w: unrotated, SIMDs 0-1 of every CU carry the kernel
+    int rot;                         // always 0 (a retired A/B arm rotated the wavefronts' first key chunk of phase A): a dead argument — without it and its select below the
+                                     // NJ = 8 / 16 instantiations allocate 2 VGPRs more (profiles/knob_table_ab.md)
 #if defined(MTTS_ATTN_DIAG)
     int diag;                        // diagnostic builds only (tools/attn_phases.sh; WRONG results, timing of the phases): bit 0 / 1 / 2 = skip phase A / B / C,
                                      // bit 3 = every lane of phase A reads its chunk's FIRST key row (one cache line per load instruction), bit 4 = no score stores
@@ -45,7 +45,6 @@ struct AttnFwdArgs {
 };
 
 constexpr int kAttnQ = 32;           // query rows per workgroup
-inline int attn_rot_default() { static const int r = [] { const char* e = getenv("MTTS_ATTN_ROT"); return e ? atoi(e) : 0; }(); return r; }
 
 // NJ = dk / 8: a compile-time head width keeps every fragment load unconditional (a load behind a run-time "j < dk / 8" test, or a prefetch
 // behind "is there a next chunk", makes hipcc drain vmcnt(0) in front of the MFMAs that follow: the whole L2 latency exposed per chunk —

@@ -716,12 +716,10 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         }
     }
 
-    static bool ln_fold_side_on() { static const int on = [] { const char* e = getenv("MTTS_LN_FOLD_SIDE"); return e ? atoi(e) : 1; }(); return on != 0; }
     // buffers, stream and events of the deferred weight-gradient path (see LayerGrad)
     int init_defer() {
-        static const int max_defer_tasks = [] { const char* e = getenv("MTTS_DEFER_TASKS"); return e ? atoi(e) : 2; }();   // (A/B runs: 4 / 8)
-        defer_tasks = std::min(cap_tasks, max_defer_tasks);
-        if (defer_tasks < 1) { defer_tasks = 0; return 0; }
+        constexpr int kDeferTasks = 2;   // (measured: 4 tasks per launch slower, profiles/r06_ab_log.md)
+        defer_tasks = std::min(cap_tasks, kDeferTasks);   // >= 1: mtts_create refuses max_tasks < 1
         const int d = cfg.d_model;
         const long long per_row = 2LL * d + cfg.d_ff + 3LL * d;
         const int post_c = std::max(cfg.postnet_dim, cfg.n_mel);
@@ -755,7 +753,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         };
         mk(encG, cfg.enc_layers, capMp);
         mk(decG, cfg.dec_layers, capMf);
-        if (cap_tasks > defer_tasks && ln_fold_side_on()) {
+        if (cap_tasks > defer_tasks && knobs().ln_fold_side) {
             const size_t pe = (((size_t)cap_tasks * ln_chunks(capMp) * 3 * d * sizeof(float)) + 255) & ~(size_t)255;
             const size_t pd = (((size_t)cap_tasks * ln_chunks(capMf) * 3 * d * sizeof(float)) + 255) & ~(size_t)255;
             DEV_CHECK(mem.alloc(arena_lnpart, 2 * (cfg.enc_layers * pe + cfg.dec_layers * pd) + 256));
@@ -792,7 +790,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // 752-workgroup weight-gradient batch leaves room for TWO main-stream workgroups per CU instead of one — the critical stream's next launch (w_2's
         // input gradient: 496 short tiles) no longer queues behind it.  Same k-ordered MFMA chain per tile, results equal to fp32 roundoff (tests/test_gpu_timed_config.py);
         // single-task rank 31.05 -> 30.70 ms, its second order 77.3 -> 76.6 ms, C2 fp32 12.81 -> 12.69 ms, 8-task step unchanged (profiles/r06_ab_log.md).
-        { static const int bk16 = [] { const char* e = getenv("MTTS_SIDE_BK16"); return e ? atoi(e) : 1; }(); gx_side.prefer_bk16 = bk16 != 0; }
+        gx_side.prefer_bk16 = knobs().side_bk16 != 0;
         if (gx_side.alloc_workspace(mem)) return err("out of device memory (split-K workspace of the side stream)");
         return 0;
     }
@@ -850,10 +848,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         shadow_off.clear();
         planes_ready = false;
     }
-    bool planes_on() const {
-        static const int on = [] { const char* e = getenv("MTTS_BF16_PLANES"); return e ? atoi(e) : 1; }();
-        return on && planes_ready && planes_wanted && gx.bf16;
-    }
+    bool planes_on() const { return planes_ready && planes_wanted && gx.bf16; }
     // the weights this pass reads -> their shadows
     // async: on the second side stream (idle outside an encoder run-ahead), beside the pass's first kernels; the first conv that reads a
     // shadow waits for it (shadow_wait)
@@ -1161,8 +1156,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // batch order the last dispatch round of the fused forward (1.1 k workgroups on 512 slots at 8 tasks) and of the backward's grouped GEMMs is
         // whatever pairs happen to come last; sorted, the long pairs start first and the short ones fill the tail.  Every table entry carries its own
         // offsets, so the order is free; the sort is stable (the heads of a sequence stay neighbours).  MTTS_ATTN_SORT=0: batch order.
-        static const bool attn_sort = [] { const char* e = getenv("MTTS_ATTN_SORT"); return e ? atoi(e) != 0 : true; }();
-        for (int which = 0; attn_sort && which < 2; ++which) {
+        for (int which = 0; knobs().attn_sort && which < 2; ++which) {
             const int n = nseq[which];
             if (n < 2) continue;
             std::vector<int> idx((size_t)n);
@@ -1312,18 +1306,16 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                     4.0 * (alg_rows(p, s) * (nsrc * cin + cout) + nsrc * (double)p.tasks * cout * k * cin));
     }
     // sublayer GEMM + `LayerNorm(dropout(.) + residual)` (SubLayers.py:54-55,90-91): the GEMM followed by layernorm_fwd_kernel — or, with
-    // MTTS_LN_FUSE=1, ONE launch when the GEMM can carry the row-complete epilogue (fp32 mode, C <= 256, a launcher context with counters).
-    // Built and measured in round 5, bit-identical results, but SLOWER: 8-task step 157.3 -> 158.8 ms, single-task rank
-    // 32.5 -> 34.2 ms, second order 81.4 -> 83.1 ms (profiles/r05_ab_log.md) — the write-through stores, the drain + counter rendezvous and the
-    // one-workgroup-per-m-tile tail cost more than the 5-17 us launch they replace — so it stays opt-in.
+    // MTTS_LN_FUSE=1, ONE launch when the GEMM can carry the row-complete epilogue (fp32 mode, C <= 256, a launcher context with counters): bit-identical,
+    // but measured SLOWER (profiles/r05_ab_log.md: the write-through stores, the drain + counter rendezvous and the one-workgroup-per-m-tile tail
+    // cost more than the 5-17 us launch they replace), so it stays opt-in.
     // z receives the sublayer output a, then (in place) a' = dropout(a) + res — what the backward keeps; y the normalised rows.
     void ln_fused_fwd(const Pass& ps, Space s, TS x, int cin, int k, TS w, TS b, TS z, TS res, long long g_off, long long b_off,
                       const unsigned char* mask, TS y, TS st, int C, DropSpec din, bool x_plane, bool y_twin) {
-        static const bool fuse_on = [] { const char* e = getenv("MTTS_LN_FUSE"); return e ? atoi(e) != 0 : false; }();
         const Plan& p = *ps.pl;
         GemmArgs probe;
         probe.N = C;
-        if (fuse_on && !ablate_ln() && !gx.batch.open && gemm_ln_fusable(gx, GEMM_NT, probe, maxM(p, s), p.tasks)) {
+        if (knobs().ln_fuse && !ablate_ln() && !gx.batch.open && gemm_ln_fusable(gx, GEMM_NT, probe, maxM(p, s), p.tasks)) {
             LnFuse f;
             TS gm = W(ps, g_off), bt = W(ps, b_off);
             f.res = res.p; f.res_gs = res.ts;
@@ -1436,16 +1428,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         a.C = C; a.mode = 0; a.mfield = mfield(s);
         colreduce(p, a, out.p, nullptr, out.ts, maxM(p, s), on_side);
     }
-    // MEASUREMENT ONLY (results are wrong): MTTS_ABLATE_LN=1 drops every LayerNorm forward / backward launch of the FFT blocks and predictors, which
-    // bounds from above what folding bias + dropout + residual + LayerNorm into the producing GEMM's epilogue (and the LayerNorm backward into
-    // the consuming GEMM's prologue) could save — a timing run, never a result (profiles/r05_ab_log.md; bench.py refuses to gate parity on it)
-    // The switch only exists in a library built with -DMTTS_ABLATE (a diagnostic build: `hipcc ... -DMTTS_ABLATE`); the shipped libmtts.so has no
-    // way to skip a LayerNorm, whatever its environment holds.
+    // MEASUREMENT ONLY (results are wrong): MTTS_ABLATE_LN=1 drops every LayerNorm forward / backward launch of the FFT blocks and predictors — the
+    // upper bound of what folding LayerNorm into the neighbouring GEMMs could save (profiles/r05_ab_log.md; bench.py refuses to gate parity on it).
+    // Only in a diagnostic build (`hipcc ... -DMTTS_ABLATE`): the shipped libmtts.so has no way to skip a LayerNorm, whatever its environment holds.
 #if defined(MTTS_ABLATE)
-    static bool ablate_ln() {
-        static const bool on = [] { const char* e = getenv("MTTS_ABLATE_LN"); return e && atoi(e) != 0; }();
-        return on;
-    }
+    static bool ablate_ln() { return knobs().ablate_ln != 0; }
 #else
     static constexpr bool ablate_ln() { return false; }
 #endif
@@ -1530,15 +1517,14 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // between Q K^T, the softmax and P V; the probabilities go to HBM once, for the backward.  MTTS_FUSED_ATTN=0 (A/B runs), the bf16
         // numerics mode (measured on C2: 7.28 ms with this fp32 kernel, 7.15 ms with bf16 grouped GEMMs around the softmax kernel) and
         // sequences beyond 1024 keys take the three-launch form: grouped GEMM, softmax kernel, grouped GEMM.
-        static const bool fused_attn = [] { const char* e = getenv("MTTS_FUSED_ATTN"); return e ? atoi(e) != 0 : true; }();
-        if (fused_attn && !gx.bf16 && attn_fused_ok(L, dk) && groups > 0) {
+        if (knobs().fused_attn && !gx.bf16 && attn_fused_ok(L, dk) && groups > 0) {
             AttnFwdArgs fa;
             fa.seqs = seqs;
             fa.tab_qk = (s == SP_P) ? p.enc_tab[TAB_QK] : p.dec_tab[TAB_QK];
             fa.tab_pv = (s == SP_P) ? p.enc_tab[TAB_PV] : p.dec_tab[TAB_PV];
             fa.Q = fa.K = fa.V = b.qkv.p; fa.ld_q = fa.ld_k = fa.ld_v = 3 * d;
             fa.P = b.P.p; fa.O = b.O.p; fa.ld_o = d;
-            fa.scale = 1.f / sqrtf((float)dk); fa.dk = dk; fa.rot = attn_rot_default(); fa.prio = gx.wave_prio;
+            fa.scale = 1.f / sqrtf((float)dk); fa.dk = dk; fa.rot = 0; fa.prio = gx.wave_prio;
 #if defined(MTTS_ATTN_DIAG)
             fa.diag = 0;
 #endif
@@ -1665,9 +1651,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // weight gradients may be deferred to the side stream for this plan (under-filled launches; the bias
     // gradient rides on the GEMM — the separate column reduction would run on the main stream)
     bool defer_ok(const Plan& p) const {
-        static const int on = [] { const char* e = getenv("MTTS_DEFER_WGRAD"); return e ? atoi(e) : 1; }();
-        static const long long max_rows = [] { const char* e = getenv("MTTS_DEFER_MAX_ROWS"); return e ? atoll(e) : 16000LL; }();   // beyond this the launches fill the chip and the wgrad + dgrad pairing wins (measured: 4 / 8 tasks per rank neutral / -1 %)
-        return on && defer_tasks > 0 && p.tasks <= defer_tasks && p.sumMf <= max_rows && side != nullptr;
+        constexpr long long kDeferMaxRows = 16000;   // beyond this the launches fill the chip and the wgrad + dgrad pairing wins (measured: 4 / 8 tasks per rank neutral / -1 %)
+        return knobs().defer_wgrad && defer_tasks > 0 && p.tasks <= defer_tasks && p.sumMf <= kDeferMaxRows && side != nullptr;
     }
     // call-site class of the GEMM launches issued from here on (the profiler's per-launch records carry it: GemmProfiler::tag)
     void set_tag(int t) { gx.prof.tag = gx_side.prof.tag = gx_side2.prof.tag = t; }
@@ -1679,8 +1664,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // the variance predictors on the side stream (forward: beside the decoder; backward: under the PostNet / decoder backward) — needs no
     // deferred-gradient buffer, so it also serves launches of more tasks than the deferred regime takes
     bool side_pred_ok(const Plan& p) const {
-        static const int all = [] { const char* e = getenv("MTTS_SIDE_PRED_ALL"); return e ? atoi(e) : 1; }();
-        return side != nullptr && arena_pred != nullptr && p.tasks <= cap_tasks && (all || defer_ok(p));
+        return side != nullptr && arena_pred != nullptr && p.tasks <= cap_tasks && (knobs().side_pred_all || defer_ok(p));
     }
     // ---- bucketed exchange, overlapped with the backward that produces the outer gradient (main.py:30-38: DDP's bucketed gradient
     // all-reduce) ------------------------------------------------------------------------------------------------
@@ -1813,9 +1797,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     int upd_next = 0, upd_nt = 0, upd_launches = 0;
     float upd_lr = 0.f;
     int upd_setup() {
-        static const int on = [] { const char* e = getenv("MTTS_UPD_OVERLAP"); return e ? atoi(e) : 1; }();
         upd_buckets.clear();
-        if (!on || n_adapt <= 0 || (adapt_start % 4) != 0 || (n_adapt % 4) != 0) return 1;
+        if (!knobs().upd_overlap || n_adapt <= 0 || (adapt_start % 4) != 0 || (n_adapt % 4) != 0) return 1;
         if (build_buckets(upd_buckets)) return 1;
         DEV_CHECK(upd_stream.create());
         return 0;
@@ -1852,8 +1835,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     }
     void module_done(int idx) { ar_ready(idx); upd_ready(idx); }
 
-    // kernel-family choice of the pass's main-stream GEMM launches (gemm.h: gemm_glds_mode): the LDS-DMA family only when MTTS_GLDS=1 asks for it
-    // per pass: the LDS-DMA family switch, and the critical stream's wavefront priority — in the deferred regime (weight gradients, run-ahead and
+    // per pass: the LDS-DMA family switch (gemm.h: gemm_glds_mode, only when MTTS_GLDS=1 asks for it), and the critical stream's wavefront priority — in the deferred regime (weight gradients, run-ahead and
     // predictors on side streams beside an under-filled critical chain) the main stream's GEMM wavefronts issue at priority 3 (s_setprio), the
     // side streams' at the default 0: single-task rank 30.89 -> 30.39 ms, two tasks per rank 47.2 -> 46.8 ms; the 8-task step is unchanged with or without,
     // and a deferred launch of 6 750 frame rows (C2, batch 16) LOSES 1.1 % (fp32) / 2.4 % (bf16) — there the side stream's weight gradients are the
@@ -1861,7 +1843,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     static constexpr long long kPrioMaxRows = 5200;
     void set_regime(const Plan& p) {
         gx.no_glds = gemm_glds_mode() == 0;
-        static const int mp = [] { const char* e = getenv("MTTS_MAIN_PRIO"); return e ? atoi(e) : 1; }();
+        const int mp = knobs().main_prio;
         gx.wave_prio = (mp == 2 || (mp == 1 && defer_ok(p) && p.sumMf <= kPrioMaxRows)) ? 1 : 0;
     }
 
@@ -1978,8 +1960,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // runs on the side stream under the PostNet / decoder backward, each predictor's input gradient into a buffer of its own (gPxE / gPxP / gPxD).
     bool pred_bwd_early(const Pass& ps) {
         const Plan& p = *ps.pl;
-        static const int on = [] { const char* e = getenv("MTTS_PRED_EARLY"); return e ? atoi(e) : 1; }();
-        if (!on || !side_pred_ok(p) || any_frame_level()) return false;
+        if (!knobs().pred_early || !side_pred_ok(p) || any_frame_level()) return false;
         fork_side();
         std::swap(stream, side.s);
         std::swap(gx, gx_side);
@@ -2020,14 +2001,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // query (optional): the query pass's encoder forward runs ahead too, after the inner steps' — into the arena's own activation set,
     // where its backward will find the activations; *query_seed receives its dropout seed, ev_enc[steps] its completion
     bool run_encoder_ahead(Plan& pl, int steps, unsigned* seeds, bool per_step_sets = false, Plan* query = nullptr, unsigned* query_seed = nullptr) {
-        static const int on = [] { const char* e = getenv("MTTS_ENC_AHEAD"); return e ? atoi(e) : 1; }();
-        static const int all = [] { const char* e = getenv("MTTS_ENC_AHEAD_ALL"); return e ? atoi(e) : 1; }();   // also launches beyond the deferred regime
-        auto ahead_ok = [&](const Plan& q) { return arena_pred != nullptr && q.tasks <= cap_tasks && (all || defer_ok(q)); };
+        auto ahead_ok = [&](const Plan& q) { return arena_pred != nullptr && q.tasks <= cap_tasks && (knobs().enc_ahead_all || defer_ok(q)); };
         if (query && steps + 1 > kAhead) { query = nullptr; if (query_seed) *query_seed = 0; }   // no slot left for the query pass: the inner steps still run ahead
-        if (!on || steps < 1 || steps > kAhead || encoder_adapted() || !ahead_ok(pl) || side2 == nullptr) return false;
+        if (!knobs().enc_ahead || steps < 1 || steps > kAhead || encoder_adapted() || !ahead_ok(pl) || side2 == nullptr) return false;
         for (int s = 0; s < steps; ++s) seeds[s] = next_drop_seed();
-        static const int q_on = [] { const char* e = getenv("MTTS_ENC_AHEAD_QUERY"); return e ? atoi(e) : 1; }();
-        if (query && (!q_on || !ahead_ok(*query) || cfg.enc_layers < 1)) query = nullptr;
+        if (query && (!knobs().enc_ahead_query || !ahead_ok(*query) || cfg.enc_layers < 1)) query = nullptr;
         if (query) *query_seed = next_drop_seed();   // (the seed forward() would draw for the query pass: after the inner steps')
         refresh_shadows(Pass{&pl, true, true});   // (bf16 mode: the encoder's weight shadows, before the fork)
         side2.after(stream);                     // the batch image / plan kernels of this plan are on the main stream
@@ -2079,8 +2057,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         TS pe = W(ps, pitch_emb), ee = W(ps, energy_emb);
         const bool tf = p.has_targets;
         TS xp = x0;
-        static const bool pred_batch = [] { const char* e = getenv("MTTS_PRED_BATCH"); return e ? atoi(e) != 0 : true; }();
-        if (tf && pred_batch && !any_frame_level() && p.sumMp <= 2048) {   // (measured neutral once the launches fill the chip: 8-task meta-batches)
+        if (tf && knobs().pred_batch && !any_frame_level() && p.sumMp <= 2048) {   // (measured neutral once the launches fill the chip: 8-task meta-batches)
             // teacher-forced: both embeddings come from the targets, so x1 / x2 do not wait for a predictor — embed first, then the three
             // predictors side by side
             MTTS_LAUNCH(bucket_embed_add_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)x0.p, x0.ts,
@@ -2095,8 +2072,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             const int SS[3] = {128, 132, 136};
             // teacher-forced: nothing downstream in the forward reads the predictions (the decoder input uses the TARGET embeddings); with
             // an idle side stream the predictors overlap the decoder and are joined at the end of forward()
-            static const bool pred_side = [] { const char* e = getenv("MTTS_PRED_SIDE"); return e ? atoi(e) != 0 : true; }();
-            if (pred_side && side_pred_ok(p) && !defer_live) {
+            if (knobs().pred_side && side_pred_ok(p) && !defer_live) {
                 fork_side();
                 std::swap(stream, side.s);
                 std::swap(gx, gx_side);

@@ -194,7 +194,7 @@ void ln_fwd_t(const Pass& ps, Space s, TS ta, TS tres, TS z, TS st, long long g_
 }
 // the dropout launches of the tangent FFT blocks (two in front of the forward's LayerNorm tangents, four behind the backward's) ride in the LayerNorm
 // tangent kernels — the same masks on the same values: bit-identical.  MTTS_SO_FUSE_DROP=0: launches of their own again.
-static bool so_fuse_drop() { static const int on = [] { const char* e = getenv("MTTS_SO_FUSE_DROP"); return e ? atoi(e) : 1; }(); return on != 0; }
+static bool so_fuse_drop() { return knobs().so_fuse_drop != 0; }
 // primal dz + tangent tgz, and hv(gamma), hv(beta); dz_drop / tgz_drop (optional): dropout(dz) / dropout(tgz) with the forward site's mask dd
 void ln_bwd_t(const Pass& ps, Space s, TS dy, TS tgy, TS z, TS st, TS tz, TS tst, long long g_off, long long b_off,
               const unsigned char* mask, TS dz, TS tgz, int C, int relu_on_z, TS dz_drop = TS{nullptr, 0}, TS tgz_drop = TS{nullptr, 0},
@@ -208,7 +208,7 @@ void ln_bwd_t(const Pass& ps, Space s, TS dy, TS tgy, TS z, TS st, TS tz, TS tst
     a.C = C; a.mode = 5; a.mfield = mfield(s); a.xdrop = din;
     // stage 1 of hv(gamma) / hv(beta) rides in the tangent kernel (8-row partials, folded by one colfinal launch); MTTS_SO_LN_PART=0: the two-launch
     // reduction over the same arrays in front of it (ColArgs mode 5) — another summation order, equal to fp32 roundoff
-    static const bool emit = [] { const char* e = getenv("MTTS_SO_LN_PART"); return e ? atoi(e) != 0 : true; }();
+    const bool emit = knobs().so_ln_part != 0;
     if (!emit) colreduce(p, a, hg.p, hb.p, hg.ts, maxM(p, s));
     const int chunks = ln_chunks(maxM(p, s));
     MTTS_LAUNCH_LN(ln_jvp_bwd_kernel, C, row2_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
@@ -354,8 +354,7 @@ void pred_bwd_t(const Pass& ps, const PredP& P, PredBuf& b, PredBuf& t, TS xin, 
     // hv of the 256 -> 1 projection (three reductions over arrays nothing in this pass writes again — the activations n2 / t_n2 and the loss's gradients
     // dout / tgout): on the side stream when there is one (six launches per predictor and reverse step leave the critical stream; joined with the
     // pass's other side-stream work).  MTTS_SO_PRED_SIDE=0: on the critical stream.
-    static const bool hv_side = [] { const char* e = getenv("MTTS_SO_PRED_SIDE"); return e ? atoi(e) != 0 : true; }();
-    const bool os = hv_side && side != nullptr && col_partial_side != nullptr;
+    const bool os = knobs().so_pred_side && side != nullptr && col_partial_side != nullptr;
     if (os) fork_side();
     colsum(ps, s, tgout, 1, nullptr, none, Gd(P.lb), os);
     colsum(ps, s, b.n2, f, nullptr, tgout, Gd(P.lw), os);
@@ -507,11 +506,6 @@ int forward_t(const Pass& ps) {
 // ---- combined backward: primal activation gradients + tangents; tangent parameter gradients -> Gd() (= hv) ----
 // skip_primal: the bound gradient set (engine.h: GK()) holds the primal gradients of this very pass from an earlier backward() — the
 // decoder's, the PostNet's and mel_linear's primal input-gradient GEMMs are not repeated (meta_grad_so's reverse sweep).
-static bool so_defer_post() {
-    static const bool on = [] { const char* e = getenv("MTTS_SO_DEFER_POST"); return e ? atoi(e) != 0 : true; }();
-    static const bool all = [] { const char* e = getenv("MTTS_DEFER_WGRAD"); return e ? atoi(e) != 0 : true; }();
-    return on && all;
-}
 int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
     const Plan& p = *ps.pl;
     set_regime(p);
@@ -563,7 +557,7 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
         TS gm = W(ps, P.g), tgm = Wt(P.g);
         // under-filled plans: the layer's hv(W) product leaves the tangent launch for the side stream (as the decoder layers' do: TLayerGrad);
         // the BatchNorm backward then writes into buffers of the layer's own, which outlive the shared scratch the next layer reuses
-        const bool dfp = so_defer_post() && !tpostG.empty() && defer_ok(p) && p.tasks <= defer_tasks;
+        const bool dfp = knobs().so_defer_post && !tpostG.empty() && defer_ok(p) && p.tasks <= defer_tasks;
         const TS gR0 = dfp ? TS{tpostG[i].dc.p, tpostG[i].dc.ts} : this->gR0, tgR0 = dfp ? TS{tpostG[i].tdc.p, tpostG[i].tdc.ts} : this->tgR0;
         MTTS_LAUNCH(bn_jvp_bwd_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (const float*)cur.p, cur.ts,
                     (const float*)tcur.p, tcur.ts, (const float*)b.a.p, b.a.ts, (const float*)t.a.p, t.a.ts, (const float*)b.c.p, b.c.ts,
@@ -606,8 +600,7 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
     for (int l = cfg.dec_layers - 1; l >= 0; --l) {
         TS xin = l == 0 ? dec_in : decB[l - 1].y2, txin = l == 0 ? t_dec_in : tdecB[l - 1].y2;
         site_base = 64 + 2 * l;
-        static const int so_defer = [] { const char* e = getenv("MTTS_DEFER_WGRAD"); return e ? atoi(e) : 1; }();
-        TLayerGrad* tl = (so_defer && sk && !tdecG.empty() && defer_ok(p)) ? &tdecG[l] : nullptr;
+        TLayerGrad* tl = (sk && !tdecG.empty() && defer_ok(p)) ? &tdecG[l] : nullptr;
         fft_bwd_t(ps, SP_F, cfg.dec_heads, decP[l], decB[l], tdecB[l], xin, txin, l == cfg.dec_layers - 1 ? K.dec_top : K.dec[l + 1].g0, tgF0,
                   K.dec[l], sk, this->gF0, this->gF1, tgF1, tgFqkv, tgFh, dSf, tdSf, tl);
         ar_ready(ar_idx_dec(l));
@@ -693,9 +686,8 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
 // launches that follow on the critical stream (the predictors' input gradients), so the side stream reads a copy (`snap`, a buffer of the early predictor backward,
 // idle during the tangent backward; one 5 us copy launch stays on the critical stream).  MTTS_SO_TABLE_SIDE=0: on the critical stream.  Bit-identical either way.
 void table_hv(const Plan& p, TS g, TS snap, const int* idx, int n_rows, int skip_row, long long emb_off, bool snapshot) {
-    static const bool on = [] { const char* e = getenv("MTTS_SO_TABLE_SIDE"); return e ? atoi(e) != 0 : true; }();
     const int d = cfg.d_model, nt = p.tasks;
-    if (!on || side == nullptr || (snapshot && (arena_pred == nullptr || snap.p == nullptr))) {
+    if (!knobs().so_table_side || side == nullptr || (snapshot && (arena_pred == nullptr || snap.p == nullptr))) {
         MTTS_LAUNCH(table_grad_kernel, dim3(n_rows, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)g.p, g.ts, idx, row_ts_p, skip_row,
                     Gd(emb_off).p, n_total, d);
         return;
@@ -729,12 +721,10 @@ int meta_grad_so(int steps, float inner_lr, float grad_scale, float* losses_out,
     // Inner step s keeps its activations in a set of its own (288 GB of HBM: ~0.65 GB per full-size task and step), so the reverse
     // sweep below goes straight to the tangent passes instead of replaying the forward of every step first (one forward of the eight
     // forward-equivalents a reverse step costs).  MTTS_SO_KEEP_ACT=0, or a device that cannot hold the sets: the replay.
-    static const bool keep_on = [] { const char* e = getenv("MTTS_SO_KEEP_ACT"); return e ? atoi(e) != 0 : true; }();
-    const bool keep = keep_on && steps >= 1 && ensure_act_sets(steps);
+    const bool keep = knobs().so_keep_act && steps >= 1 && ensure_act_sets(steps);
     // ... and the gradients its backward leaves (engine.h: GradSet), so the tangent backward of step s does not repeat the primal
     // input-gradient GEMMs either (another forward-equivalent per step; ~0.3 GB per full-size task and step).  MTTS_SO_KEEP_GRAD=0: recompute.
-    static const bool keep_grad_on = [] { const char* e = getenv("MTTS_SO_KEEP_GRAD"); return e ? atoi(e) != 0 : true; }();
-    const bool keep_grad = keep && keep_grad_on && ensure_grad_sets(steps);
+    const bool keep_grad = keep && knobs().so_keep_grad && ensure_grad_sets(steps);
     struct Rebind { Engine* e; ~Rebind() { e->bind_act(0); e->gs_bound = -1; } } rebind{this};
     unsigned qseed = 0;
     const bool ahead = run_encoder_ahead(sp, steps, ahead_seeds, keep, &qp, &qseed);   // engine.h: the (non-adapted) encoder's forwards of all steps (+ the query pass's), on side2

@@ -38,6 +38,7 @@
 
 #include "compat.h"
 #include "devres.h"
+#include "knobs.h"
 
 namespace mtts {
 
@@ -231,7 +232,7 @@ inline int gemm_keff(const GemmArgs& g) { return g.A2 ? 2 * g.K : g.K; }
 // consecutive tiles instead: with G = tiles_n (x split-K factor) one m-tile's n-tiles share an XCD while every XCD still
 // receives every eighth workgroup — no imbalance (a contiguous eighth of the grid per XCD measured -3 % on the ragged
 // 8-task launches).  PMC: L2-miss traffic of the multi-problem launches 454 -> 286 MB per launch; time neutral (the kernels
-// are MFMA-, not fetch-bound).  MTTS_XCD_GROUP=0 restores the natural order.
+// are MFMA-, not fetch-bound).
 __device__ __forceinline__ int xcd_group_size(int tiles_n, int splitk) {
     const int G = tiles_n * (splitk > 1 ? splitk : 1);
     return G < 64 ? G : 64;
@@ -1089,6 +1090,7 @@ struct GemmProfiler {
     // out[kind][4] = launches, total ms, total algorithmic flops, total algorithmic bytes
     void report(double out[GK_COUNT][4]) {
         for (int k = 0; k < GK_COUNT; ++k) out[k][0] = out[k][1] = out[k][2] = out[k][3] = 0.0;
+        // (read here, not in knobs.h: bench.py sets and clears the variable between reports of one process)
         FILE* dump = (getenv("MTTS_GEMM_DUMP") && !recs.empty()) ? fopen(getenv("MTTS_GEMM_DUMP"), "a") : nullptr;  // per-launch CSV (tools/gemm_sites.py); appended: a handle reports its three launch contexts one after the other
         if (dump && ftell(dump) == 0) fprintf(dump, "kind,form,tile,N,K,rows,groups,splitk,us,gflop,site,ctx\n");
         for (auto& r : recs) {
@@ -1104,13 +1106,7 @@ struct GemmProfiler {
 constexpr int kGemmXcdSwizzle = 1;     // XCD-grouped tile order of the plain grids (xcd_group_remap)
 constexpr int kGemmDefaultBk = 16;     // K-slice of the register-staged kernels (32 for long K-contiguous panels, see gemm_launch)
 constexpr bool kGemmDefaultPipe = true;  // software-pipelined K-loop
-// K-loop variant of the pipelined 64x64 kernels (gemm_f32_kloop: KL).  MTTS_KLOOP=0 / 1 / 4 picks one for A/B runs
-// (profiles/r05_kloop_ab.md); results are bit-identical across variants (same k order in every accumulator chain).
-constexpr int kGemmDefaultKloop = 4;
-inline int gemm_kloop_variant() {
-    static const int v = [] { const char* e = getenv("MTTS_KLOOP"); const int x = e ? atoi(e) : kGemmDefaultKloop; return (x == 0 || x == 1 || x == 4) ? x : kGemmDefaultKloop; }();
-    return v;
-}
+inline int gemm_kloop_variant() { return knobs().kloop; }   // K-loop variant of the pipelined 64x64 kernels (gemm_f32_kloop: KL): same k order in every accumulator chain, bit-identical
 // The KL >= 1 loops step their operand pointers by loop-invariant distances, which needs conv taps that are whole multiples of the K-slice
 // (every channel count of the model is a multiple of 16; anything else keeps the generic KL = 0 loop)
 inline int gemm_kloop_for(const GemmArgs& g, int bk) {
@@ -1185,16 +1181,10 @@ inline bool gemm_ln_bind(GemmCtx& cx, int form, GemmArgs& g, int max_M, int grou
 inline void gemm_batch_begin(GemmCtx& cx) { cx.batch.open = true; }
 inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream);
 
-// LDS-DMA kernel family (gemm_glds.h, device builds only)
-// LDS-DMA family (gemm_glds.h).  Round 5: with the interleaved K-loop (KL = 4) the register-staged kernels beat it in the latency regime it
-// was built for (single-task rank 33.5 -> 32.0 ms first order, 83.9 -> 79.3 ms second order; the 8-task step is indifferent: 158.0 vs
-// 157.4 ms, profiles/r05_kloop_ab.md), so the automatic tile choice no longer takes it.  MTTS_GLDS=1 restores the round 3-4 rule (launches
-// of <= 768 workgroups) for A/B runs — GemmCtx::no_glds (engine.h: set_regime) can then still veto it per pass; tile code 4064 selects
-// the family explicitly (kernel tests, micro-benchmarks).
-inline int gemm_glds_mode() {
-    static const int m = [] { const char* e = getenv("MTTS_GLDS"); return e ? (atoi(e) != 0 ? 1 : 0) : 0; }();
-    return m;
-}
+// LDS-DMA kernel family (gemm_glds.h, device builds only).  Round 5: with the interleaved K-loop (KL = 4) the register-staged kernels beat it in the
+// latency regime it was built for (profiles/r05_kloop_ab.md), so the automatic tile choice takes it only under MTTS_GLDS=1 (knobs.h) — GemmCtx::no_glds
+// (engine.h: set_regime) can then still veto it per pass; tile code 4064 selects the family explicitly (kernel tests, micro-benchmarks).
+inline int gemm_glds_mode() { return knobs().glds; }
 inline bool gemm_use_glds() { return gemm_glds_mode() != 0; }
 inline bool gemm_glds_ok(const GemmArgs& g) { return !(g.taps > 1 && g.tap_k % 32 != 0); }
 // n-tiles of a problem's grid: the tiles of C plus the column-sum tile (GemmArgs::colsum)
@@ -1220,18 +1210,15 @@ inline int gemm_bf16_tile(double rows, int tiles_n128) { return std::ceil(rows /
 
 // Task-per-XCD schedule (XcdSched) of a problem: exactly 8 groups whose sizes the caller knows on the host, whole tiles.  MTTS_XCD_SCHED=0: off.
 inline bool gemm_xcd_sched_for(GemmArgs& g, int max_M, int max_N, int groups, int S, int tile) {
-    static const bool on = [] { const char* e = getenv("MTTS_XCD_SCHED"); return e ? atoi(e) != 0 : true; }();
     g.xs.on = 0;
-    static const int min_groups = [] { const char* e = getenv("MTTS_XCD_SCHED_MIN_GROUPS"); return e ? atoi(e) : 8; }();   // 2 / 4: also the launches of a 4- / 2-rank job's ranks
-    if (!on || (groups != 8 && groups != 4 && groups != 2) || groups < min_groups || !g.host_dims || !g.dimptr || g.table || S != 1) return false;
+    if (!knobs().xcd_sched || (groups != 8 && groups != 4 && groups != 2) || groups < knobs().xcd_sched_min_groups || !g.host_dims || !g.dimptr || g.table || S != 1) return false;
     int dims[8] = {0};
     for (int z = 0; z < groups; ++z) dims[z] = g.host_dims[z] * g.dim_mult;
     const int tn = gemm_tiles_n(g, max_N, tile);
     if (g.dim_sel == 0) xcd_sched_build(g.xs, dims, 1, tn, 0, tile, groups);
     else xcd_sched_build(g.xs, dims, 2, 1, ((max_M + tile - 1) / tile) * tn, 64, groups);
     if (g.xs.maxlen <= 0) g.xs.on = 0;
-    static const bool dbg = getenv("MTTS_XCD_SCHED_DEBUG") != nullptr;   // one line per scheduled problem (tests: the schedule really is in use)
-    if (dbg && g.xs.on) fprintf(stderr, "xcd_sched cls %d tn %d maxlen %d pool %d\n", g.xs.on, g.xs.tn, g.xs.maxlen, g.xs.P[8]);
+    if (knobs().xcd_sched_debug && g.xs.on) fprintf(stderr, "xcd_sched cls %d tn %d maxlen %d pool %d\n", g.xs.on, g.xs.tn, g.xs.maxlen, g.xs.P[8]);
     return g.xs.on != 0;
 }
 inline long gemm_xcd_sched_slots(const XcdSched& s) { return 8L * s.maxlen * (s.on == 1 ? s.tn : 1); }
@@ -1240,8 +1227,7 @@ inline long gemm_xcd_sched_slots(const XcdSched& s) { return 8L * s.maxlen * (s.
 // m-tile-major grouping, which keeps an m-tile's A panel in one L2, is already the right one.  Measured (profiles/r04_ab_log.md): the
 // k = 9 input gradient of a single-task rank 212 -> 194 us, its step 35.17 -> 34.73 ms.  MTTS_PANEL_ORDER=0: off (A/B runs).
 inline bool gemm_panel_order_for(const GemmArgs& g, int form, double rows, int max_M, int max_N, int groups) {
-    static const bool on = [] { const char* e = getenv("MTTS_PANEL_ORDER"); return e ? atoi(e) != 0 : true; }();
-    if (!on || g.table || groups >= 8 || groups < 1) return false;
+    if (!knobs().panel_order || g.table || groups >= 8 || groups < 1) return false;
     if (std::ceil(rows / 64.0) * gemm_tiles_n(g, max_N, 64) > (double)gemm_glds_max_wgs()) return false;   // chip-filling launches: measured slightly worse (C2: +1 %)
     const double K = (double)gemm_keff(g);
     const double a_bytes = form == GEMM_TN ? rows * max_M : rows / groups * (g.lda > 0 ? g.lda : K);   // unique bytes behind the A operand (per group)
@@ -1405,8 +1391,7 @@ inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream) {
     GemmProfiler& prof = cx.prof;
     // a single queued problem normally takes the stand-alone launcher; in the latency regime it stays here, where the long-chain
     // split-K rule applies (the k=9 dgrad of a single-task rank is 124 tiles x 288 slices: alone it would run at one tile per CU)
-    static const int single_multi = [] { const char* e = getenv("MTTS_SINGLE_MULTI"); return e ? atoi(e) : 1; }();
-    bool solo = b.q.size() == 1 && (!single_multi || batch_full_regime(b.q));
+    bool solo = b.q.size() == 1 && (!knobs().single_multi || batch_full_regime(b.q));
     bool any_dual = false;   // dual-source problems (GemmArgs::A2) exist in the multi-problem kernels only
     for (const GemmPending& p : b.q) any_dual = any_dual || p.g.A2 != nullptr;
     if (any_dual) solo = false;
@@ -1467,8 +1452,7 @@ inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream) {
         int S = 1;
         const int nch = (gemm_keff(p.g) + 15) / 16;
         constexpr double ratio = 1.5;
-        static const int split_on = [] { const char* e = getenv("MTTS_BATCH_SPLITK"); return e ? atoi(e) : 1; }();   // 0: never cut K (an arm of tools/so_tolerance_bisect.py)
-        if (split_on && small_batch && T == 64 && !p.g.table && !p.g.colsum && !p.g.ln.y && nch > per_cu / ratio) {
+        if (knobs().batch_splitk && small_batch && T == 64 && !p.g.table && !p.g.colsum && !p.g.ln.y && nch > per_cu / ratio) {
             S = (int)std::min<double>(std::min<double>(std::ceil(nch / std::max(per_cu / ratio, 1.0)), nch / 16), 8);
             const long long slots = (long long)tiles * p.groups;
             if (S >= 2 && ((ws_off + slots * S * 4096) > kSplitWsFloats || ctr_off + slots > kSplitCtrs - kLnCtrs)) S = 1;

@@ -107,14 +107,13 @@ int mtts_sdpa_fwd(int n_mat, int L, int dk, const float* q, const float* kk, con
     }
     if (hipMemcpy(k.tab[0], t0.data(), t0.size() * sizeof(GemmGroupDesc), hipMemcpyHostToDevice) != hipSuccess) return -1;
     if (hipMemcpy(k.tab[1], t1.data(), t1.size() * sizeof(GemmGroupDesc), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    static const bool fused_attn = [] { const char* e = getenv("MTTS_FUSED_ATTN"); return e ? atoi(e) != 0 : true; }();
-    if (fused_attn && attn_fused_ok(L, dk)) {   // the fused kernel the engine uses (attention.h)
+    if (knobs().fused_attn && attn_fused_ok(L, dk)) {   // the fused kernel the engine uses (attention.h)
         AttnFwdArgs fa;
         fa.seqs = (const AttnSeq*)k.seqs; fa.tab_qk = k.tab[0]; fa.tab_pv = k.tab[1];
         fa.Q = q; fa.K = kk; fa.V = v; fa.ld_q = fa.ld_k = fa.ld_v = dk;
-        fa.P = P; fa.O = o; fa.ld_o = dk; fa.scale = 1.f / sqrtf((float)dk); fa.dk = dk; fa.rot = attn_rot_default(); fa.prio = 0;
+        fa.P = P; fa.O = o; fa.ld_o = dk; fa.scale = 1.f / sqrtf((float)dk); fa.dk = dk; fa.rot = 0; fa.prio = 0;
 #if defined(MTTS_ATTN_DIAG)
-        { const char* e = getenv("MTTS_ATTN_DIAG_MASK"); fa.diag = e ? atoi(e) : 0; }
+        fa.diag = knobs().attn_diag_mask;
 #endif
         attn_fwd_launch(fa, L, n_mat, (hipStream_t)stream);
         return hipGetLastError() == hipSuccess ? 0 : -1;

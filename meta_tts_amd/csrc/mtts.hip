@@ -406,8 +406,7 @@ int mtts_disarm_allreduce_overlap(mtts_handle* h) {
 int mtts_arm_allreduce_overlap(mtts_handle* h) {
     if (!h) return -1;
     Engine& e = h->eng;
-    static const int on = [] { const char* v = getenv("MTTS_AR_OVERLAP"); return v ? atoi(v) : 1; }();
-    if (!on || !h->comm.comm || e.ar.sum == nullptr || e.comm_stream == nullptr || e.ar_buckets.empty()) return 1;
+    if (!h->comm.comm || e.ar.sum == nullptr || e.comm_stream == nullptr || e.ar_buckets.empty()) return 1;
     e.ar_armed = true;
     return 0;
 }
