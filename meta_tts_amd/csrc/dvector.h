@@ -410,8 +410,7 @@ public:
             const float* x = l == 0 ? mels : hkeep[l - 1];
             wgrad(dgates, 4 * H, x, in_dim(l), rows, grads + find("lstm.weight_ih_l" + s), grads + find("lstm.bias_ih_l" + s));
             wgrad(dgates, 4 * H, hprev[l], H, rows, grads + find("lstm.weight_hh_l" + s), nullptr);
-            MTTS_LAUNCH(copy_tasks_kernel, dim3(4), dim3(256), stream, (const float*)(grads + find("lstm.bias_ih_l" + s)), (long long)0,
-                        grads + find("lstm.bias_hh_l" + s), (long long)0, (long long)H);   // 4H floats = H float4: d b_hh == d b_ih
+            launch_copy_tasks(TS{grads + find("lstm.bias_ih_l" + s), 0}, TS{grads + find("lstm.bias_hh_l" + s), 0}, (long long)H, 1, stream, 4);   // 4H floats = H float4: d b_hh == d b_ih
             if (l > 0) {   // gradient reaching the layer below: dx = dgates W_ih  ([rows][4H] x [4H][H])
                 float* dx = dxbuf[l & 1];
                 GemmArgs g;
@@ -427,7 +426,7 @@ public:
     }
     // device scalar: sum of squares of the parameter gradients (a term of the joint clip_grad_norm_, main.py:61)
     const float* grad_sumsq() {
-        MTTS_LAUNCH(sumsq_partial_kernel, dim3(64), dim3(256), stream, (const float*)grads, n_params / 4, sq_partial);
+        launch_sumsq_partial(grads, n_params / 4, sq_partial, 64, stream);
         MTTS_LAUNCH(dv_sum_partials_kernel, dim3(1), dim3(64), stream, (const float*)sq_partial, 64, sq_out);
         return sq_out;
     }
@@ -436,8 +435,7 @@ public:
         if (!train_ready) { set_error("mtts_dvector_enable_training first"); return -1; }
         ++adam_steps;
         const float bc1 = 1.f - (float)std::pow((double)b1, (double)adam_steps), bc2 = 1.f - (float)std::pow((double)b2, (double)adam_steps);
-        MTTS_LAUNCH(adam_clip_kernel, dim3(256), dim3(256), stream, params, (const float*)grads, adam_m, adam_v, n_params / 4, norm_dev,
-                    norm_dev ? max_norm : 0.f, lr, b1, b2, eps, bc1, bc2, weight_decay);
+        launch_adam_clip(params, grads, adam_m, adam_v, n_params / 4, norm_dev, norm_dev ? max_norm : 0.f, lr, b1, b2, eps, bc1, bc2, weight_decay, stream, 256);
         DEV_CHECK(hipGetLastError());
         dirty = true;
         return 0;

@@ -75,8 +75,6 @@ struct ParamEntry {
     int module = 0;
 };
 
-struct TS { float* p; long long ts; };
-
 class Engine {
 public:
     ModelCfg cfg;
@@ -239,7 +237,6 @@ public:
     float *loss_partial = nullptr, *losses = nullptr, *col_partial = nullptr;
     int col_max_chunks = 0;
     long long col_partial_ts = 0;                 // floats per task of col_partial
-    static int ln_chunks(int rows) { return (rows + kLnRows - 1) / kLnRows; }   // partial chunks of the LayerNorm backward (rowops.h)
     long long S_ts_p = 0, S_ts_f = 0;
 
     char* arena = nullptr;
@@ -901,7 +898,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         bf16_t* h = H(x.p);
         if (!h || (x.ts % 8) != 0 || (((long long)G * C) % 8) != 0) return nullptr;
         const long long n8 = x.ts * nt / 8, o = (long long)G * C;
-        MTTS_LAUNCH(to_bf16_kernel, dim3((unsigned)std::min<long long>((n8 + 255) / 256, 4096)), dim3(256), stream, (const float*)(x.p - o), h - o, n8);
+        launch_to_bf16(x.p - o, h - o, n8, stream);
         return h;
     }
     // =================================================================================
@@ -1226,6 +1223,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     TS Gd(long long off) const { return TS{grad_dst + off, n_total}; }
     int mfield(Space s) const { return s == SP_P ? META_MP : (s == SP_F ? META_MF : META_MR); }
     int maxM(const Plan& p, Space s) const { return s == SP_P ? p.maxMp : (s == SP_F ? p.maxMf : p.maxMr); }
+    long long row_ts(Space s) const { return s == SP_P ? row_ts_p : (s == SP_F ? row_ts_f : row_ts_r); }
+    // what a rowops.h / tangent.h launcher needs to know about a row space of a plan (mask: the row mask the kernel applies, if any)
+    RowLaunch on_rows(const Plan& p, Space s, hipStream_t st, const unsigned char* mask = nullptr) const {
+        return RowLaunch{p.meta, mfield(s), maxM(p, s), p.tasks, mask, row_ts(s), st};
+    }
     // [row][4] float image of one of the plan's byte masks
     const float* mask_w(const Plan& p, const unsigned char* m) const {
         if (m == p.p_valid) return p.p_valid_w;
@@ -1239,7 +1241,6 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     const unsigned char* inrect_mask(const Plan& p, Space s) const { return s == SP_P ? p.p_inrect : (s == SP_F ? p.f_valid : p.r_inrect); }
     long long sumM(const Plan& p, Space s) const { return s == SP_P ? p.sumMp : (s == SP_F ? p.sumMf : p.sumMr); }
     double alg_rows(const Plan& p, Space s) const { return s == SP_P ? p.sum_nP : p.sum_nF; }
-    long long row_ts(Space s) const { return s == SP_P ? row_ts_p : (s == SP_F ? row_ts_f : row_ts_r); }
 
     // dst = dropout(src) with the mask stream (plan seed, site); no-op alias when dropout is off
     TS drop(const Pass& ps, Space s, TS src, TS dst, int C, float prob, int site) {
@@ -1405,28 +1406,18 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (b_off >= 0 && !fused) colsum(ps, s, dy, cout, bias_mask, TS{nullptr, 0}, Gd(b_off));   // (main stream: never reached on the deferred path)
     }
     // two-stage deterministic column reduction (rowops.h colpart/colfinal)
-    void colreduce(const Plan& p, ColArgs a, float* out0, float* out1, long long out_ts, int maxM, bool on_side = false) {
-        if (on_side) {   // the deferred path's reductions: side stream, its own partial buffer, plain two-stage form
-            const int chunks_s = (maxM + kRC - 1) / kRC;
-            MTTS_LAUNCH(colpart_kernel, dim3((a.C + 127) / 128, chunks_s, p.tasks), dim3(256), side, (const int*)p.meta, a, col_partial_side, col_max_chunks);
-            MTTS_LAUNCH(colfinal_kernel, dim3(colfinal_blocks(a.C), 1, p.tasks), dim3(256), side, (const int*)p.meta, a.mfield, a.mode,
-                        (const float*)col_partial_side, col_max_chunks, a.C, out0, out1, out_ts, 1e-5f, a.accumulate, (int)kRC);
-            return;
-        }
+    void colreduce(const Plan& p, ColArgs a, float* out0, float* out1, long long out_ts, Space s, bool on_side = false) {
+        // on_side: the deferred path's reductions — side stream, its own partial buffer
         // (single-launch variants were built and measured slower in rounds 2-3: a workgroup per 32-column stripe walking all rows is latency-
         // bound, +10 % on the 8-task step; a last-arriver fold needs an agent-scope release / acquire amid the GEMMs' dirty L2 lines, +10 %)
-        const int chunks = (maxM + kRC - 1) / kRC;
-        MTTS_LAUNCH(colpart_kernel, dim3((a.C + 127) / 128, chunks, p.tasks), dim3(256), stream, (const int*)p.meta, a, col_partial,
-                    col_max_chunks);
-        MTTS_LAUNCH(colfinal_kernel, dim3(colfinal_blocks(a.C), 1, p.tasks), dim3(256), stream, (const int*)p.meta, a.mfield, a.mode,
-                    (const float*)col_partial, col_max_chunks, a.C, out0, out1, out_ts, 1e-5f, a.accumulate, (int)kRC);
+        launch_colreduce(on_rows(p, s, on_side ? (hipStream_t)side : stream, a.mask), a, on_side ? col_partial_side : col_partial, col_max_chunks, out0, out1, out_ts);
     }
     void colsum(const Pass& ps, Space s, TS x, int C, const unsigned char* mask, TS roww, TS out, bool on_side = false) {
         const Plan& p = *ps.pl;
         ColArgs a;
         a.X = x.p; a.x_ts = x.ts; a.mask = mask; a.mask_ts = row_ts(s); a.roww = roww.p; a.roww_ts = roww.ts;
         a.C = C; a.mode = 0; a.mfield = mfield(s);
-        colreduce(p, a, out.p, nullptr, out.ts, maxM(p, s), on_side);
+        colreduce(p, a, out.p, nullptr, out.ts, s, on_side);
     }
     // MEASUREMENT ONLY (results are wrong): MTTS_ABLATE_LN=1 drops every LayerNorm forward / backward launch of the FFT blocks and predictors — the
     // upper bound of what folding LayerNorm into the neighbouring GEMMs could save (profiles/r05_ab_log.md; bench.py refuses to gate parity on it).
@@ -1441,10 +1432,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // y_twin: bf16 mode — also write y's operand plane (H(y)): the next conv reads it instead of a conversion pass
         if (ablate_ln()) return;
         const Plan& p = *ps.pl;
-        TS gm = W(ps, g_off), bt = W(ps, b_off);
-        MTTS_LAUNCH_LN(layernorm_fwd_kernel, C, row2_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                    (const float*)a.p, a.ts, (const float*)res.p, res.ts, (const float*)gm.p, (const float*)bt.p, gm.ts, mask,
-                    row_ts(s), zout.p, zout.ts, y.p, y.ts, st.p, st.ts, C, 1e-5f, din, dout, y_twin ? H(y.p) : (bf16_t*)nullptr);
+        launch_layernorm_fwd(on_rows(p, s, stream, mask), a, res, W(ps, g_off), W(ps, b_off), zout, y, st, C, din, dout, y_twin ? H(y.p) : (bf16_t*)nullptr);
     }
     // dz = LayerNorm backward (masked); parameter grads into the per-task grad buffer
     // dz_drop: second output = dropout(dz) with the forward site's mask; copy_always: written even when dropout is off (a plain copy)
@@ -1458,27 +1446,15 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // twin_sel: bf16 mode — also write the operand plane of dz (1) or of dz_drop (2)
         if (ablate_ln()) return;
         const Plan& p = *ps.pl;
-        TS gm = W(ps, g_off);
-        const int chunks = ln_chunks(maxM(p, s));
-        float* pbuf = part ? part : col_partial;
         bf16_t* twin = twin_sel == 1 ? H(dz.p) : (twin_sel == 2 ? H(dz_drop.p) : nullptr);
         if (!twin) twin_sel = 0;
-        MTTS_LAUNCH_LN(layernorm_bwd_kernel, C, row2_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                    (const float*)dy.p, dy.ts, (const float*)z.p, z.ts, (const float*)st.p, st.ts, (const float*)gm.p, gm.ts,
-                    mask, row_ts(s), dz.p, dz.ts, C, relu_on_z, (dd.thr16 || copy_always) ? dz_drop.p : nullptr, dz_drop.ts, dd,
-                    din, pbuf, chunks, twin, twin_sel);
-        if (!part) ln_fold(p, s, pbuf, chunks, g_off, b_off, C, stream);
-    }
-    // stage 2 of a LayerNorm's gamma / beta reduction: fold the backward kernel's partial rows
-    void ln_fold(const Plan& p, Space s, const float* part, int chunks, long long g_off, long long b_off, int C, hipStream_t st) {
-        TS gg = Gd(g_off), gb = Gd(b_off);
-        MTTS_LAUNCH(colfinal_kernel, dim3(colfinal_blocks(C), 1, p.tasks), dim3(256), st, (const int*)p.meta, mfield(s), 1, part, chunks, C,
-                    gg.p, gb.p, gg.ts, 1e-5f, 0, (int)kLnRows);
+        if (!(dd.thr16 || copy_always)) dz_drop.p = nullptr;
+        launch_layernorm_bwd(on_rows(p, s, stream, mask), dy, z, st, W(ps, g_off), dz, C, relu_on_z, dz_drop, dd, din, part ? part : col_partial, !part,
+                             Gd(g_off), Gd(b_off), twin, twin_sel);
     }
     // the LayerNorm gamma / beta gradients of a deferred layer, from the partials its backward kernel left, on the side stream
     void ln_param_grads_side(const Pass& ps, Space s, const float* part, long long g_off, long long b_off, int C) {
-        const Plan& p = *ps.pl;
-        ln_fold(p, s, part, ln_chunks(maxM(p, s)), g_off, b_off, C, side);
+        launch_ln_fold(on_rows(*ps.pl, s, side), part, C, Gd(g_off), Gd(b_off));
     }
     void attn_gemm(const Pass& ps, Space s, int which, int form, const float* A, int lda, const float* B, int ldb,
                    float* C, int ldc, float alpha, int heads, int flags = 0, const float* A2 = nullptr, const float* B2 = nullptr) {
@@ -1544,7 +1520,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         } else {
             attn_gemm(ps, s, TAB_QK, GEMM_NT, b.qkv.p, 3 * d, b.qkv.p, 3 * d, b.P.p, 0, 1.f / sqrtf((float)dk), heads);
             if (groups > 0 && L > 0)
-                MTTS_LAUNCH(softmax_fwd_kernel, dim3((L + 3) / 4, 1, groups), dim3(256), stream, seqs, b.P.p);
+                launch_softmax_fwd(seqs, L, groups, b.P.p, stream);
             attn_gemm(ps, s, TAB_PV, GEMM_NN, b.P.p, 0, b.qkv.p, 3 * d, b.O.p, d, 1.f, heads);
         }
         // self.dropout(self.fc(output)) + residual -> LayerNorm (SubLayers.py:54-55): in the fc GEMM's launch (row-complete epilogue), or
@@ -1616,8 +1592,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             attn_gemm(ps, s, TAB_DV, GEMM_TN, b.P.p, 0, g1.p, d, gqkv.p, 3 * d, 1.f, heads);
         }
         if (groups > 0 && L > 0)
-            MTTS_LAUNCH(softmax_bwd_kernel, dim3((L + 3) / 4, 1, groups), dim3(256), stream, seqs, (const float*)b.P.p, dS.p,
-                        1.f / sqrtf((float)dk));
+            launch_softmax_bwd(seqs, L, groups, b.P.p, dS.p, 1.f / sqrtf((float)dk), stream);
         {
             GemmBatchScope pair(gx, stream);
             attn_gemm(ps, s, TAB_DQ, GEMM_NN, dS.p, 0, b.qkv.p, 3 * d, gqkv.p, 3 * d, 1.f, heads);
@@ -1762,9 +1737,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         for (; ar_next <= upto; ++ar_next) {
             const long long lo = ar_buckets[(size_t)ar_next].first, n = ar_buckets[(size_t)ar_next].second - lo;
             if (ar_axpy != 0.f)
-                MTTS_LAUNCH(axpy_kernel, dim3(blocks_for(n / 4), 1, ar_nt), dim3(256), comm_stream, grad + lo, n_total, (const float*)(hv + lo), n_total, ar_axpy, n / 4);
-            MTTS_LAUNCH(sum_tasks_kernel, dim3(blocks_for(n / 4)), dim3(256), comm_stream, (const float*)(grad + lo), n_total, ar_nt, 1.f, outer + lo, n / 4,
-                        (int)outer_accumulate);
+                launch_axpy(TS{grad + lo, n_total}, TS{hv + lo, n_total}, ar_axpy, n / 4, ar_nt, comm_stream);
+            launch_sum_tasks(TS{grad + lo, n_total}, ar_nt, 1.f, outer + lo, n / 4, (int)outer_accumulate, comm_stream);
             if (ar.sum(ar.ctx, outer + lo, (size_t)n, comm_stream)) ar_failed = true;
             ++ar_launches;
         }
@@ -1822,8 +1796,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                 if (defer_live && side) upd_stream.after(side);
                 waited = true;
             }
-            MTTS_LAUNCH(sgd_update_kernel, dim3(blocks_for((hi - lo) / 4), 1, upd_nt), dim3(256), upd_stream, fast + (lo - adapt_start),
-                        (const float*)(grad + lo), (hi - lo) / 4, upd_lr, n_adapt, n_total);
+            launch_sgd_update(TS{fast + (lo - adapt_start), n_adapt}, TS{grad + lo, n_total}, (hi - lo) / 4, upd_lr, upd_nt, upd_stream);
             ++upd_launches;
         }
     }
@@ -1873,9 +1846,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         conv_fwd(ps, s, b.n1, f, k, W(ps, P.c2w), W(ps, P.c2b), f, b.r2, GEMM_RELU, im);
         ln_fwd(ps, s, b.r2, none, P.l2g, P.l2b, im, none, b.n2, b.st2, f, DropSpec(), drop_spec(ps, cfg.vp_dropout, site_base + 1));
         TS w = W(ps, P.lw), bb = W(ps, P.lb);
-        MTTS_LAUNCH(rowdot_kernel, row_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                    (const float*)b.n2.p, b.n2.ts, (const float*)w.p, (const float*)bb.p, w.ts, valid_mask(p, s),
-                    row_ts(s), b.out.p, b.out.ts, f);
+        launch_rowdot(on_rows(p, s, stream, valid_mask(p, s)), b.n2, w, bb, b.out, f);
     }
     // The three predictors of a teacher-forced pass are independent (their inputs come from the TARGET embeddings): run them stage by
     // stage so that the three conv1 (then the three conv2) GEMMs — 28 workgroups each on a single-task rank — go out as ONE
@@ -1900,8 +1871,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             ln_fwd(ps, SP_P, b[i]->r2, none, P[i]->l2g, P[i]->l2b, im, none, b[i]->n2, b[i]->st2, f, DropSpec(), drop_spec(ps, cfg.vp_dropout, sites[i] + 1));
         for (int i = 0; i < 3; ++i) {
             TS w = W(ps, P[i]->lw), bb = W(ps, P[i]->lb);
-            MTTS_LAUNCH(rowdot_kernel, row_grid(p.maxMp, p.tasks), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)b[i]->n2.p,
-                        b[i]->n2.ts, (const float*)w.p, (const float*)bb.p, w.ts, valid_mask(p, SP_P), row_ts_p, b[i]->out.p, b[i]->out.ts, f);
+            launch_rowdot(on_rows(p, SP_P, stream, valid_mask(p, SP_P)), b[i]->n2, w, bb, b[i]->out, f);
         }
     }
     // dout: [Mp] gradient of the prediction (0 on masked rows); dx accumulates the input gradient
@@ -1917,8 +1887,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         TS none{nullptr, 0};
         if (pg) {
             TS w = W(ps, P.lw);
-            MTTS_LAUNCH(rowdot_bwd_kernel, row_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                        (const float*)dout.p, dout.ts, (const float*)w.p, w.ts, g1.p, g1.ts, f);
+            launch_rowdot_bwd(on_rows(p, s, stream), dout, w, g1, f);
             // (the backward of the dropout behind each LayerNorm rides in the LayerNorm backward's load of its incoming gradient)
             ln_bwd(ps, s, g1, b.r2, b.st2, P.l2g, P.l2b, im, pg->g2a, f, 1, none, DropSpec(), false, pg->part2, drop_spec(ps, cfg.vp_dropout, site_base + 1));
             conv_dgrad(ps, s, pg->g2a, f, k, W(ps, P.c2w), f, g1, 0, im);
@@ -1940,8 +1909,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         colsum(ps, s, dout, 1, nullptr, none, Gd(P.lb));
         colsum(ps, s, b.n2, f, nullptr, dout, Gd(P.lw));
         TS w = W(ps, P.lw);
-        MTTS_LAUNCH(rowdot_bwd_kernel, row_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                    (const float*)dout.p, dout.ts, (const float*)w.p, w.ts, g1.p, g1.ts, f);
+        launch_rowdot_bwd(on_rows(p, s, stream), dout, w, g1, f);
         ln_bwd(ps, s, g1, b.r2, b.st2, P.l2g, P.l2b, im, g2, f, 1, none, DropSpec(), false, nullptr, drop_spec(ps, cfg.vp_dropout, site_base + 1));       // g2 = d conv2 out
         {
             GemmBatchScope pair(gx, stream);
@@ -1988,9 +1956,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         const Plan& p = *ps.pl;
         TS none{nullptr, 0};
         TS we = W(ps, word_emb);
-        MTTS_LAUNCH(embed_pos_kernel, row_grid(p.maxMp, p.tasks), dim3(256), stream, (const int*)p.meta, (int)META_MP, emb_out.p,
-                    emb_out.ts, (const float*)we.p, we.ts, (const float*)pos_table, (const int*)p.p_tok, (const int*)p.p_row_t,
-                    (const unsigned char*)p.p_valid, row_ts_p, cfg.d_model);
+        launch_embed_pos(on_rows(p, SP_P, stream, p.p_valid), emb_out, we, pos_table, p.p_tok, p.p_row_t, cfg.d_model);
         TS x = emb_out;
         for (int l = 0; l < cfg.enc_layers; ++l) { site_base = 2 * l; fft_fwd(ps, SP_P, cfg.enc_heads, encP[l], encB[l], x, none); x = encB[l].y2; }
         return x;
@@ -2016,8 +1982,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             pl.drop_seed = seeds[s];
             if (per_step_sets) bind_act(s + 1);
             TS x = encoder_fwd(pe);
-            MTTS_LAUNCH(copy_tasks_kernel, dim3((unsigned)std::min<long long>(((long long)pl.maxMp * cfg.d_model / 4 + 255) / 256, 1024), 1, pl.tasks), dim3(256),
-                        stream, (const float*)x.p, x.ts, enc_ahead[s].p, enc_ahead[s].ts, (long long)pl.maxMp * cfg.d_model / 4);
+            launch_copy_tasks(x, enc_ahead[s], (long long)pl.maxMp * cfg.d_model / 4, pl.tasks, stream);
             hipEventRecord(ev_enc[s], stream);
         }
         if (per_step_sets) bind_act(0);
@@ -2043,14 +2008,10 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // speaker vector, added on every position of the phoneme rectangle
         TS tb = W(ps, spk_table);
         if (p.ext_spk)   // the batch's own embeddings (speaker_encoder.py:71-76 computed by the d-vector encoder): rows of the image
-            MTTS_LAUNCH(copy_tasks_kernel, dim3((unsigned)(((long long)p.maxB * d / 4 + 255) / 256), 1, nt), dim3(256), stream,
-                        (const float*)(p.img_dev + img.spk_emb), (long long)cap_B * d, spk.p, spk.ts, (long long)p.maxB * d / 4);
+            launch_copy_tasks(TS{(float*)(p.img_dev + img.spk_emb), (long long)cap_B * d}, spk, (long long)p.maxB * d / 4, nt, stream, ~0u);
         else
-        MTTS_LAUNCH(speaker_vec_kernel, dim3(p.maxB, 1, nt), dim3(64), stream, (const int*)p.meta, (const float*)tb.p, tb.ts,
-                    (const int*)p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, spk.p, spk.ts, d);
-        MTTS_LAUNCH(add_rowvec_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP,
-                    (const float*)x.p, x.ts, (const float*)spk.p, spk.ts, (const int*)p.p_row_b, (const unsigned char*)p.p_inrect,
-                    row_ts_p, x0.p, x0.ts, d);
+        launch_speaker_vec(on_rows(p, SP_P, stream), p.maxB, tb, p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, spk, d);
+        launch_add_rowvec(on_rows(p, SP_P, stream, p.p_inrect), x, spk, p.p_row_b, x0, d);
         // variance adaptor: targets select the embeddings when given, else the (controlled) predictions.  A phoneme-level feature
         // (modules.py:118-127) is handled on the phoneme rectangle before the length regulator, a frame-level one (:139-148) on the
         // frame rectangle after it.
@@ -2060,12 +2021,10 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (tf && knobs().pred_batch && !any_frame_level() && p.sumMp <= 2048) {   // (measured neutral once the launches fill the chip: 8-task meta-batches)
             // teacher-forced: both embeddings come from the targets, so x1 / x2 do not wait for a predictor — embed first, then the three
             // predictors side by side
-            MTTS_LAUNCH(bucket_embed_add_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)x0.p, x0.ts,
-                        (const float*)p.p_pitch_t, row_ts_p, 1.f, (const float*)pitch_bins, cfg.n_bins - 1, (const float*)pe.p, pe.ts,
-                        (const unsigned char*)p.p_inrect, row_ts_p, pidx, x1.p, x1.ts, d);
-            MTTS_LAUNCH(bucket_embed_add_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)x1.p, x1.ts,
-                        (const float*)p.p_energy_t, row_ts_p, 1.f, (const float*)energy_bins, cfg.n_bins - 1, (const float*)ee.p, ee.ts,
-                        (const unsigned char*)p.p_inrect, row_ts_p, eidx, x2.p, x2.ts, d);
+            launch_bucket_embed_add(on_rows(p, SP_P, stream, p.p_inrect), x0, TS{(float*)p.p_pitch_t, row_ts_p}, 1.f, pitch_bins, cfg.n_bins - 1, pe, pidx, x1,
+                                    d);
+            launch_bucket_embed_add(on_rows(p, SP_P, stream, p.p_inrect), x1, TS{(float*)p.p_energy_t, row_ts_p}, 1.f, energy_bins, cfg.n_bins - 1, ee, eidx,
+                                    x2, d);
             const PredP* const PP[3] = {&durP, &pitP, &eneP};
             PredBuf* const BB[3] = {&durB, &pitB, &eneB};
             const TS XX[3] = {x0, x0, x1};
@@ -2087,18 +2046,14 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         site_base = 128; pred_fwd(ps, durP, durB, x0);
         if (!cfg.pitch_frame) {
             site_base = 132; pred_fwd(ps, pitP, pitB, xp);
-            MTTS_LAUNCH(bucket_embed_add_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP,
-                        (const float*)xp.p, xp.ts, tf ? (const float*)p.p_pitch_t : (const float*)pitB.out.p, tf ? row_ts_p : pitB.out.ts,
-                        tf ? 1.f : ps.p_control, (const float*)pitch_bins, cfg.n_bins - 1, (const float*)pe.p, pe.ts,
-                        (const unsigned char*)p.p_inrect, row_ts_p, pidx, x1.p, x1.ts, d);
+            launch_bucket_embed_add(on_rows(p, SP_P, stream, p.p_inrect), xp, tf ? TS{(float*)p.p_pitch_t, row_ts_p} : pitB.out, tf ? 1.f : ps.p_control,
+                                    pitch_bins, cfg.n_bins - 1, pe, pidx, x1, d);
             xp = x1;
         }
         if (!cfg.energy_frame) {
             site_base = 136; pred_fwd(ps, eneP, eneB, xp);
-            MTTS_LAUNCH(bucket_embed_add_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP,
-                        (const float*)xp.p, xp.ts, tf ? (const float*)p.p_energy_t : (const float*)eneB.out.p, tf ? row_ts_p : eneB.out.ts,
-                        tf ? 1.f : ps.e_control, (const float*)energy_bins, cfg.n_bins - 1, (const float*)ee.p, ee.ts,
-                        (const unsigned char*)p.p_inrect, row_ts_p, eidx, x2.p, x2.ts, d);
+            launch_bucket_embed_add(on_rows(p, SP_P, stream, p.p_inrect), xp, tf ? TS{(float*)p.p_energy_t, row_ts_p} : eneB.out, tf ? 1.f : ps.e_control,
+                                    energy_bins, cfg.n_bins - 1, ee, eidx, x2, d);
             xp = x2;
         }
         }
@@ -2106,33 +2061,24 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (!tf && frames_from_predictions_impl(ps)) return -1;
         if (!any_frame_level()) {
             // length regulator + speaker + decoder positions
-            MTTS_LAUNCH(length_regulate_fwd_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (const float*)xp.p,
-                        xp.ts, (const int*)p.f_src, (const int*)p.f_row_b, (const int*)p.f_row_t, row_ts_f, (const float*)spk.p, spk.ts,
-                        (const float*)pos_table, dec_in.p, dec_in.ts, d);
+            launch_length_regulate_fwd(on_rows(p, SP_F, stream), xp, p.f_src, p.f_row_b, p.f_row_t, spk, pos_table, dec_in, d);
         } else {
-            MTTS_LAUNCH(length_regulate_rect_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (const float*)xp.p, xp.ts,
-                        (const int*)p.f_src, row_ts_f, (const int*)p.r2f, row_ts_r, xr0.p, xr0.ts, d);
+            launch_length_regulate_rect(on_rows(p, SP_R, stream), xp, p.f_src, row_ts_f, p.r2f, xr0, d);
             TS xr = xr0;
             if (cfg.pitch_frame) {
                 site_base = 132; pred_fwd(ps, pitP, pitR, xr, SP_R);
-                MTTS_LAUNCH(bucket_embed_add_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR,
-                            (const float*)xr.p, xr.ts, tf ? (const float*)p.r_pitch_t : (const float*)pitR.out.p, tf ? row_ts_r : pitR.out.ts,
-                            tf ? 1.f : ps.p_control, (const float*)pitch_bins, cfg.n_bins - 1, (const float*)pe.p, pe.ts,
-                            (const unsigned char*)p.r_inrect, row_ts_r, pidx_r, xr1.p, xr1.ts, d);
+                launch_bucket_embed_add(on_rows(p, SP_R, stream, p.r_inrect), xr, tf ? TS{(float*)p.r_pitch_t, row_ts_r} : pitR.out, tf ? 1.f : ps.p_control,
+                                        pitch_bins, cfg.n_bins - 1, pe, pidx_r, xr1, d);
                 xr = xr1;
             }
             if (cfg.energy_frame) {
                 site_base = 136; pred_fwd(ps, eneP, eneR, xr, SP_R);
-                MTTS_LAUNCH(bucket_embed_add_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR,
-                            (const float*)xr.p, xr.ts, tf ? (const float*)p.r_energy_t : (const float*)eneR.out.p, tf ? row_ts_r : eneR.out.ts,
-                            tf ? 1.f : ps.e_control, (const float*)energy_bins, cfg.n_bins - 1, (const float*)ee.p, ee.ts,
-                            (const unsigned char*)p.r_inrect, row_ts_r, eidx_r, xr2.p, xr2.ts, d);
+                launch_bucket_embed_add(on_rows(p, SP_R, stream, p.r_inrect), xr, tf ? TS{(float*)p.r_energy_t, row_ts_r} : eneR.out, tf ? 1.f : ps.e_control,
+                                        energy_bins, cfg.n_bins - 1, ee, eidx_r, xr2, d);
                 xr = xr2;
             }
             // packed decoder input = rectangle rows of the valid frames + speaker + positions
-            MTTS_LAUNCH(length_regulate_fwd_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (const float*)xr.p,
-                        xr.ts, (const int*)p.f2r, (const int*)p.f_row_b, (const int*)p.f_row_t, row_ts_f, (const float*)spk.p, spk.ts,
-                        (const float*)pos_table, dec_in.p, dec_in.ts, d);
+            launch_length_regulate_fwd(on_rows(p, SP_F, stream), xr, p.f2r, p.f_row_b, p.f_row_t, spk, pos_table, dec_in, d);
         }
         x = dec_in;
         for (int l = 0; l < cfg.dec_layers; ++l) { site_base = 64 + 2 * l; fft_fwd(ps, SP_F, cfg.dec_heads, decP[l], decB[l], x, none); x = decB[l].y2; }
@@ -2148,9 +2094,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             g.c_rowmap = p.f2r; g.c_rowmap_gs = row_ts_f;
             gemm_launch(gx, GEMM_NT, g, p.maxMf, cfg.n_mel, nt, stream, 0, 2.0 * p.sum_nF * cfg.n_mel * d, p.sumMf,
                         4.0 * (p.sum_nF * (d + cfg.n_mel) + (double)nt * cfg.n_mel * d));
-            MTTS_LAUNCH(fill_padded_rows_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, mel.p, mel.ts,
-                        (const float*)b.p, b.ts, (const unsigned char*)p.r_inrect, (const unsigned char*)p.r_valid, row_ts_r,
-                        cfg.n_mel);
+            launch_fill_padded_rows(on_rows(p, SP_R, stream, p.r_inrect), mel, b, p.r_valid, cfg.n_mel);
         }
         // PostNet
         TS cur = mel;
@@ -2164,7 +2108,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                 ColArgs ca;
                 ca.X = b.c.p; ca.x_ts = b.c.ts; ca.mask = p.r_inrect; ca.mask_ts = row_ts_r; ca.C = P.cout; ca.mode = 2;
                 ca.mfield = META_MR;
-                colreduce(p, ca, b.stats.p, nullptr, b.stats.ts, p.maxMr);
+                colreduce(p, ca, b.stats.p, nullptr, b.stats.ts, SP_R);
                 if (ps.update_bn && cfg.postnet_layers > kBnRunMax) {
                     MTTS_LAUNCH(bn_running_update_kernel, dim3((P.cout + 63) / 64), dim3(64), stream, (const float*)b.stats.p,
                                 b.stats.ts, nt, bn_rm[i], bn_rv[i], P.cout, 0.1f);
@@ -2175,11 +2119,9 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                             (const float*)bn_rv[i], b.stats.p, b.stats.ts, nt, P.cout, 1e-5f);
             }
             TS gm = W(ps, P.g), bt = W(ps, P.beta);
-            MTTS_LAUNCH(bn_apply_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (const float*)b.c.p, b.c.ts,
-                        (const float*)b.stats.p, b.stats.ts, (const float*)gm.p, (const float*)bt.p, gm.ts,
-                        (const unsigned char*)p.r_inrect, row_ts_r, (int)(i < cfg.postnet_layers - 1), b.a.p, b.a.ts, P.cout,
-                        drop_spec(ps, cfg.postnet_dropout, 192 + i),   // F.dropout(..., 0.5, self.training), Layers.py:133-134, in passing
-                        i + 1 < cfg.postnet_layers ? H(b.a.p) : (bf16_t*)nullptr);
+            launch_bn_apply(on_rows(p, SP_R, stream, p.r_inrect), b.c, b.stats, gm, bt, (int)(i < cfg.postnet_layers - 1), b.a, P.cout,
+                            drop_spec(ps, cfg.postnet_dropout, 192 + i),   // F.dropout(..., 0.5, self.training), Layers.py:133-134, in passing
+                            i + 1 < cfg.postnet_layers ? H(b.a.p) : (bf16_t*)nullptr);
             cur = b.a;
         }
         set_tag(0);
@@ -2199,8 +2141,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             const float* base_a = cur.p - (long long)G * cfg.n_mel;
             const float* base_b = mel.p - (long long)G * cfg.n_mel;
             float* base_o = mel_post.p - (long long)G * cfg.n_mel;
-            MTTS_LAUNCH(add2_kernel, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 2048)), dim3(256), stream, base_a, base_b,
-                        base_o, n4);
+            launch_add2(base_a, base_b, base_o, n4, stream);
         }
         join_side();   // (the predictors of a teacher-forced pass may have run on the side stream)
         return 0;
@@ -2295,8 +2236,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         GradSet& K = GK();   // where the gradients a second-order reverse sweep reads again go (default: the shared scratch)
         const TS gRm = K.gRm;
         // prediction strides in the phoneme space: the [Mp] vectors were allocated as rows(capMp, 1)
-        MTTS_LAUNCH(loss_grad_kernel, dim3(kLossBlocks, 1, nt), dim3(256), stream, (const int*)p.meta, a, scale, gRm.p, gRp.p,
-                    dpred[1].p, dpred[2].p, dpred[0].p, dpred_r[0].p, dpred_r[1].p);
+        launch_loss_grad(p.meta, nt, a, scale, gRm.p, gRp.p, dpred[1].p, dpred[2].p, dpred[0].p, dpred_r[0].p, dpred_r[1].p, stream);
         const bool pred_early = pred_bwd_early(ps);
         // ---- PostNet: cur = dL/d(a_i), starts as dL/d(mel_post); dc -> gR0, layer-input grad -> gR1
         TS cur = gRp;
@@ -2313,14 +2253,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             ca.X = cur.p; ca.x_ts = cur.ts; ca.Y = b.a.p; ca.y_ts = b.a.ts; ca.Z = b.c.p; ca.z_ts = b.c.ts;
             ca.stats = b.stats.p; ca.st_ts = b.stats.ts; ca.mask = p.r_inrect; ca.mask_ts = row_ts_r; ca.C = P.cout;
             ca.mode = 3; ca.do_tanh = act; ca.mfield = META_MR;
-            colreduce(p, ca, dgm.p, dbt.p, dgm.ts, p.maxMr);
+            colreduce(p, ca, dgm.p, dbt.p, dgm.ts, SP_R);
             TS gm = W(ps, P.g);
             const bool dfp = defer_ok(p);
             TS dc = dfp ? postG[i] : gR0;  // [rows][Cout] inside a scratch sized for max(postnet_dim, n_mel) channels (deferred: a buffer of the layer's own)
-            MTTS_LAUNCH(bn_bwd_apply_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (const float*)cur.p,
-                        cur.ts, (const float*)b.a.p, b.a.ts, (const float*)b.c.p, b.c.ts, (const float*)b.stats.p, b.stats.ts,
-                        (const float*)gm.p, gm.ts, (const float*)dgm.p, (const float*)dbt.p, dgm.ts,
-                        (const unsigned char*)p.r_inrect, row_ts_r, act, dc.p, dc.ts, P.cout, ysc, pdrop, H(dc.p));
+            launch_bn_bwd_apply(on_rows(p, SP_R, stream, p.r_inrect), cur, b.a, b.c, b.stats, gm, dgm, dbt, act, dc, P.cout, ysc, pdrop, H(dc.p));
             TS xin = (i == 0) ? mel : postB[i - 1].a;
             if (dfp) {   // this layer's weight gradient on the side stream, overlapping the rest of the backward chain
                 fork_side();
@@ -2337,9 +2274,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             } else {
                 // dL/d(mel) total = direct L1 term + residual path + PostNet input gradient
                 const long long n4 = (gRm.ts * nt) / 4;
-                MTTS_LAUNCH(add2_kernel, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 2048)), dim3(256), stream,
-                            (const float*)(gRm.p - (long long)G * nm), (const float*)(gRp.p - (long long)G * nm),
-                            gRm.p - (long long)G * nm, n4);
+                launch_add2(gRm.p - (long long)G * nm, gRp.p - (long long)G * nm, gRm.p - (long long)G * nm, n4, stream);
                 conv_dgrad(ps, SP_R, dc, P.cout, cfg.postnet_kernel, W(ps, P.w), P.cin, gRm, GEMM_ACCUM, p.r_inrect, TS{nullptr, 0}, TS{nullptr, 0},
                            TS{nullptr, 0}, true, false);
             }
@@ -2350,8 +2285,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         module_done(ar_idx_postnet());
         const bool dfm = defer_ok(p);   // gRm / gMelF are final from here on: their parameter gradients can run on the side stream
         if (!dfm) colsum(ps, SP_R, gRm, nm, nullptr, none, Gd(mel_b));
-        MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (int)META_MF,
-                    (const float*)gRm.p, gRm.ts, (const int*)p.f2r, row_ts_f, gMelF.p, gMelF.ts, nm);
+        launch_gather_rows(on_rows(p, SP_F, stream), gRm, p.f2r, gMelF, nm);
         TS dec_out = cfg.dec_layers ? decB[cfg.dec_layers - 1].y2 : dec_in;
         if (dfm) {
             fork_side();
@@ -2381,30 +2315,24 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // segment sums, the speaker table's and the bucket tables' gradients go to the side stream)
         const bool spk_side = pred_early && !need_encoder;
         if (!spk_side)
-        MTTS_LAUNCH(segsum_rows_kernel, dim3((d + 63) / 64, p.maxB, nt), dim3(256), stream, (const int*)p.meta, (const float*)gF0.p,
-                    gF0.ts, (const int*)p.f_seg_start, (const int*)p.f_seg_len, (long long)cap_B, dspk.p, dspk.ts, d, 0);
+        launch_segsum_rows(on_rows(p, SP_F, stream), p.maxB, gF0, p.f_seg_start, p.f_seg_len, (long long)cap_B, dspk, d, 0);
         // ---- frame-level half of the variance adaptor (frame rectangle), then the length regulator -> gP0 = dL/d(va_out) --------
         TS gLR = gF0;
         if (any_frame_level()) {
-            MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR, (const float*)gF0.p,
-                        gF0.ts, (const int*)p.r2f, row_ts_r, gRx.p, gRx.ts, d);          // dL/d(xr_last): 0 on padded frames
+            launch_gather_rows(on_rows(p, SP_R, stream), gF0, p.r2f, gRx, d);          // dL/d(xr_last): 0 on padded frames
             if (cfg.energy_frame) {
-                MTTS_LAUNCH(table_grad_kernel, dim3(cfg.n_bins, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR,
-                            (const float*)gRx.p, gRx.ts, (const int*)eidx_r, row_ts_r, -1, Gd(energy_emb).p, n_total, d);
+                launch_table_grad(on_rows(p, SP_R, stream), cfg.n_bins, gRx, eidx_r, -1, Gd(energy_emb), d);
                 site_base = 136; pred_bwd(ps, eneP, eneR, cfg.pitch_frame ? xr1 : xr0, dpred_r[1], gRx, SP_R);
             }
             if (cfg.pitch_frame) {
-                MTTS_LAUNCH(table_grad_kernel, dim3(cfg.n_bins, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR,
-                            (const float*)gRx.p, gRx.ts, (const int*)pidx_r, row_ts_r, -1, Gd(pitch_emb).p, n_total, d);
+                launch_table_grad(on_rows(p, SP_R, stream), cfg.n_bins, gRx, pidx_r, -1, Gd(pitch_emb), d);
                 site_base = 132; pred_bwd(ps, pitP, pitR, xr0, dpred_r[0], gRx, SP_R);
             }
-            MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (int)META_MF, (const float*)gRx.p,
-                        gRx.ts, (const int*)p.f2r, row_ts_f, gFx.p, gFx.ts, d);
+            launch_gather_rows(on_rows(p, SP_F, stream), gRx, p.f2r, gFx, d);
             gLR = gFx;
         }
         const TS gLRo = pred_early ? gPx2 : gP0;
-        MTTS_LAUNCH(length_regulate_bwd_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (const float*)gLR.p,
-                    gLR.ts, (const int*)p.p_first, (const int*)p.p_count, row_ts_p, gLRo.p, gLRo.ts, d, 0);
+        launch_length_regulate_bwd(on_rows(p, SP_P, stream), gLR, p.p_first, p.p_count, gLRo, d, 0);
         // ---- phoneme-level half of the variance adaptor ---------------------------------------------------------------------
         if (pred_early) {
             // the predictors' input gradients are waiting in gPxE / gPxP / gPxD (pred_bwd_early): dL/d(x2) = gPx2 (just written),
@@ -2413,23 +2341,19 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             const long long n4 = (gP0.ts * nt) / 4, o = (long long)G * d;
             const dim3 ag((unsigned)std::min<long long>((n4 + 255) / 256, 2048));
             hipStreamWaitEvent(stream, ev_pred, 0);
-            MTTS_LAUNCH(add2_kernel, ag, dim3(256), stream, (const float*)(gPx2.p - o), (const float*)(gPxE.p - o), gPxE.p - o, n4);
+            launch_add2(gPx2.p - o, gPxE.p - o, gPxE.p - o, n4, stream);
             MTTS_LAUNCH(add3_kernel, ag, dim3(256), stream, (const float*)(gPxE.p - o), (const float*)(gPxP.p - o), (const float*)(gPxD.p - o),
                         gP0.p - o, n4);
             fork_side();
-            MTTS_LAUNCH(table_grad_kernel, dim3(cfg.n_bins, 1, nt), dim3(256), side, (const int*)p.meta, (int)META_MP,
-                        (const float*)gPx2.p, gPx2.ts, (const int*)eidx, row_ts_p, -1, Gd(energy_emb).p, n_total, d);
-            MTTS_LAUNCH(table_grad_kernel, dim3(cfg.n_bins, 1, nt), dim3(256), side, (const int*)p.meta, (int)META_MP,
-                        (const float*)gPxE.p, gPxE.ts, (const int*)pidx, row_ts_p, -1, Gd(pitch_emb).p, n_total, d);
+            launch_table_grad(on_rows(p, SP_P, side), cfg.n_bins, gPx2, eidx, -1, Gd(energy_emb), d);
+            launch_table_grad(on_rows(p, SP_P, side), cfg.n_bins, gPxE, pidx, -1, Gd(pitch_emb), d);
         } else {
         if (!cfg.energy_frame) {
-            MTTS_LAUNCH(table_grad_kernel, dim3(cfg.n_bins, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP,
-                        (const float*)gP0.p, gP0.ts, (const int*)eidx, row_ts_p, -1, Gd(energy_emb).p, n_total, d);
+            launch_table_grad(on_rows(p, SP_P, stream), cfg.n_bins, gP0, eidx, -1, Gd(energy_emb), d);
             site_base = 136; pred_bwd(ps, eneP, eneB, cfg.pitch_frame ? x0 : x1, dpred[2], gP0, SP_P, defer_ok(p) ? &predG[2] : nullptr);
         }
         if (!cfg.pitch_frame) {
-            MTTS_LAUNCH(table_grad_kernel, dim3(cfg.n_bins, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP,
-                        (const float*)gP0.p, gP0.ts, (const int*)pidx, row_ts_p, -1, Gd(pitch_emb).p, n_total, d);
+            launch_table_grad(on_rows(p, SP_P, stream), cfg.n_bins, gP0, pidx, -1, Gd(pitch_emb), d);
             site_base = 132; pred_bwd(ps, pitP, pitB, x0, dpred[1], gP0, SP_P, defer_ok(p) ? &predG[1] : nullptr);
         }
         site_base = 128; pred_bwd(ps, durP, durB, x0, dpred[0], gP0, SP_P, defer_ok(p) ? &predG[0] : nullptr);
@@ -2437,14 +2361,10 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         // speaker vector gradient, part 2: every position of the phoneme rectangle
         const hipStream_t sst = spk_side ? side : stream;
         if (spk_side)   // (after the fork above: gF0 and gP0 are final)
-        MTTS_LAUNCH(segsum_rows_kernel, dim3((d + 63) / 64, p.maxB, nt), dim3(256), sst, (const int*)p.meta, (const float*)gF0.p,
-                    gF0.ts, (const int*)p.f_seg_start, (const int*)p.f_seg_len, (long long)cap_B, dspk.p, dspk.ts, d, 0);
-        MTTS_LAUNCH(segsum_rows_kernel, dim3((d + 63) / 64, p.maxB, nt), dim3(256), sst, (const int*)p.meta, (const float*)gP0.p,
-                    gP0.ts, (const int*)p.p_seg_start, (const int*)p.p_seg_len, (long long)cap_B, dspk.p, dspk.ts, d, 1);
+        launch_segsum_rows(on_rows(p, SP_F, sst), p.maxB, gF0, p.f_seg_start, p.f_seg_len, (long long)cap_B, dspk, d, 0);
+        launch_segsum_rows(on_rows(p, SP_P, sst), p.maxB, gP0, p.p_seg_start, p.p_seg_len, (long long)cap_B, dspk, d, 1);
         if (!p.ext_spk)
-        MTTS_LAUNCH(speaker_table_grad_kernel, dim3(cfg.n_speaker, 1, nt), dim3(64), sst, (const int*)p.meta,
-                    (const float*)dspk.p, dspk.ts, (const int*)p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk,
-                    Gd(spk_table).p, n_total, d);
+        launch_speaker_table_grad(on_rows(p, SP_P, sst), cfg.n_speaker, dspk, p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, Gd(spk_table), d);
         module_done(ar_idx_spk());        // variance adaptor + speaker table
         if (!need_encoder) return 0;
         // ---- encoder ------------------------------------------------------------------------
@@ -2457,8 +2377,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         }
         // word embedding (padding row 0 keeps a zero gradient); p_tok is 0 on invalid rows, and
         // gP0 is only meaningful on valid rows -> scan with the token ids masked by validity
-        MTTS_LAUNCH(table_grad_kernel, dim3(cfg.vocab, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP,
-                    (const float*)gP0.p, gP0.ts, (const int*)p.p_tok, row_ts_p, 0, Gd(word_emb).p, n_total, d);
+        launch_table_grad(on_rows(p, SP_P, stream), cfg.vocab, gP0, p.p_tok, 0, Gd(word_emb), d);
         return 0;
     }
 
@@ -2472,8 +2391,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             MTTS_LAUNCH(sgd_prox_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream, fast, (const float*)(grad + adapt_start),
                         (const float*)(theta + adapt_start), n_adapt / 4, inner_lr, inner_prox, n_adapt, n_total);
         else
-            MTTS_LAUNCH(sgd_update_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream, fast, (const float*)(grad + adapt_start),
-                        n_adapt / 4, inner_lr, n_adapt, n_total);
+            launch_sgd_update(TS{fast, n_adapt}, TS{grad + adapt_start, n_total}, n_adapt / 4, inner_lr, nt, stream);
     }
     // backward of an inner step + its SGD step (the step overlapped module by module when upd_setup made that possible)
     int inner_backward_update(const Pass& ps, int nt, float inner_lr) {
@@ -2498,8 +2416,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (sp.tasks != qp.tasks || sp.tasks < 1) { set_error("support/query plans not set"); return -1; }
         const int nt = sp.tasks;
         if (n_adapt > 0)
-            MTTS_LAUNCH(broadcast_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream,
-                        (const float*)(theta + adapt_start), fast, n_adapt / 4, n_adapt);
+            launch_broadcast(theta + adapt_start, TS{fast, n_adapt}, n_adapt / 4, nt, stream);
         Pass ps{&sp, true, true};
         unsigned seeds[kAhead], qseed = 0;
         const bool ahead = run_encoder_ahead(sp, steps, seeds, false, &qp, &qseed);
@@ -2524,8 +2441,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         const int rc = backward(pq, grad_scale, true);
         if (overlap) { if (ar_end() || rc) return -1; return 0; }
         if (rc) return -1;
-        MTTS_LAUNCH(sum_tasks_kernel, dim3(blocks_for(n_total / 4)), dim3(256), stream, (const float*)grad, n_total, nt, 1.f, outer,
-                    n_total / 4, (int)outer_accumulate);
+        launch_sum_tasks(TS{grad, n_total}, nt, 1.f, outer, n_total / 4, (int)outer_accumulate, stream);
         return 0;
     }
 
@@ -2536,8 +2452,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (sp.tasks < 1 || !sp.has_targets) { set_error("support plan not set"); return -1; }
         const int nt = sp.tasks;
         if (reset && n_adapt > 0)
-            MTTS_LAUNCH(broadcast_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream,
-                        (const float*)(theta + adapt_start), fast, n_adapt / 4, n_adapt);
+            launch_broadcast(theta + adapt_start, TS{fast, n_adapt}, n_adapt / 4, nt, stream);
         Pass ps{&sp, true, true};
         unsigned seeds[kAhead];
         const bool ahead = run_encoder_ahead(sp, steps, seeds);
@@ -2564,8 +2479,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         const int rc = backward(ps, grad_scale, true);
         if (overlap) { if (ar_end() || rc) return -1; return 0; }
         if (rc) return -1;
-        MTTS_LAUNCH(sum_tasks_kernel, dim3(blocks_for(n_total / 4)), dim3(256), stream, (const float*)grad, n_total, p.tasks, 1.f,
-                    outer, n_total / 4, (int)outer_accumulate);
+        launch_sum_tasks(TS{grad, n_total}, p.tasks, 1.f, outer, n_total / 4, (int)outer_accumulate, stream);
         return 0;
     }
 
@@ -2617,13 +2531,12 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         const int nb = 512;
         if (ar_issued) ar_join();  // (an overlapped exchange nobody joined with mtts_allreduce_outer: the clip must still see the reduced buffer)
         shadows_current = false;   // theta is about to move
-        MTTS_LAUNCH(sumsq_partial_kernel, dim3(nb), dim3(256), stream, g, n_total / 4, norm_partial);
+        launch_sumsq_partial(g, n_total / 4, norm_partial, nb, stream);
         MTTS_LAUNCH(sumsq_final_kernel, dim3(1), dim3(64), stream, (const float*)norm_partial, nb, norm_out, extra_sumsq);
         ++adam_step_count;
         const float bc1 = 1.f - (float)std::pow((double)b1, (double)adam_step_count);
         const float bc2 = 1.f - (float)std::pow((double)b2, (double)adam_step_count);
-        MTTS_LAUNCH(adam_clip_kernel, dim3(blocks_for(n_total / 4)), dim3(256), stream, theta, g, adam_m, adam_v, n_total / 4,
-                    (const float*)norm_out, max_norm, lr, b1, b2, eps, bc1, bc2, weight_decay);
+        launch_adam_clip(theta, g, adam_m, adam_v, n_total / 4, norm_out, max_norm, lr, b1, b2, eps, bc1, bc2, weight_decay, stream);
         if (norm_out_host) {
             DEV_CHECK(hipStreamSynchronize(stream));
             DEV_CHECK(hipMemcpy(norm_out_host, norm_out, sizeof(float), hipMemcpyDeviceToHost));

@@ -46,11 +46,11 @@ int imaml_begin(float* losses_out) {
     if (forward(pq)) return -1;
     if (loss(pq, losses_out ? losses_out : losses)) return -1;
     if (backward(pq, 1.f, encoder_adapted())) return -1;   // a non-adapted encoder's query gradient is not part of the hypergradient (see header)
-    const float* b = grad + adapt_start;         // p lives in the per-task gradient buffer: it is what the HVP reads as direction
+    // b = p lives in the per-task gradient buffer (grad + adapt_start): it is what the HVP reads as direction
     DEV_CHECK(hipMemsetAsync(im_x, 0, (size_t)n_adapt * cap_tasks * sizeof(float), stream));
-    MTTS_LAUNCH(copy_tasks_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream, b, n_total, im_r, n_adapt, n_adapt / 4);
+    launch_copy_tasks(TS{grad + adapt_start, n_total}, TS{im_r, n_adapt}, n_adapt / 4, nt, stream, 4096);
     im_dot(im_r, n_adapt, im_r, n_adapt, 1.f, 0.f, IM_RS, nt);
-    MTTS_LAUNCH(cg_scalar_kernel, dim3(1), dim3(64), stream, im_scal, nt, 0, 0.f);
+    launch_cg_scalar(im_scal, nt, 0, 0.f, stream);
     return 0;
 }
 
@@ -64,11 +64,11 @@ int imaml_cg_step(float inner_lr, float reg, float tol) {
     const float* Hp = hv + adapt_start;
     // pAp = sum p * a (Hp + lambda p)
     im_dot(p, n_total, Hp, n_total, inner_lr, inner_lr * reg, IM_PAP, nt);
-    MTTS_LAUNCH(cg_scalar_kernel, dim3(1), dim3(64), stream, im_scal, nt, 1, tol);   // alpha = rs / pAp
+    launch_cg_scalar(im_scal, nt, 1, tol, stream);   // alpha = rs / pAp
     MTTS_LAUNCH(cg_update_r_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream, im_r, n_adapt, (const float*)p, Hp, n_total,
                 inner_lr, inner_lr * reg, (const float*)im_scal, (int)IM_STRIDE, n_adapt / 4);
     im_dot(im_r, n_adapt, im_r, n_adapt, 1.f, 0.f, IM_RSNEW, nt);
-    MTTS_LAUNCH(cg_scalar_kernel, dim3(1), dim3(64), stream, im_scal, nt, 2, tol);   // converged? else beta = rs_new / rs, rs = rs_new
+    launch_cg_scalar(im_scal, nt, 2, tol, stream);   // converged? else beta = rs_new / rs, rs = rs_new
     MTTS_LAUNCH(cg_update_xp_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream, im_x, n_adapt, p, n_total, (const float*)im_r,
                 (const float*)im_scal, (int)IM_STRIDE, n_adapt / 4);
     return 0;

@@ -186,11 +186,7 @@ void conv_bwd_t(const Pass& ps, Space s, TS dy, TS tdy, int cout, int k, TS x, T
 void ln_fwd_t(const Pass& ps, Space s, TS ta, TS tres, TS z, TS st, long long g_off, long long b_off, const unsigned char* mask,
               TS tz_out, TS ty, TS tst, int C, DropSpec din = DropSpec(), DropSpec dout = DropSpec()) {
     const Plan& p = *ps.pl;
-    TS gm = W(ps, g_off), tgm = Wt(g_off), tbt = Wt(b_off);
-    MTTS_LAUNCH_LN(ln_jvp_fwd_kernel, C, row_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                (const float*)ta.p, ta.ts, (const float*)tres.p, tres.ts, (const float*)z.p, z.ts, (const float*)st.p, st.ts,
-                (const float*)gm.p, gm.ts, (const float*)tgm.p, (const float*)tbt.p, tgm.ts, mask, row_ts(s), tz_out.p, tz_out.ts,
-                ty.p, ty.ts, tst.p, tst.ts, C, din, dout);
+    launch_ln_jvp_fwd(on_rows(p, s, stream, mask), ta, tres, z, st, W(ps, g_off), Wt(g_off), Wt(b_off), tz_out, ty, tst, C, din, dout);
 }
 // the dropout launches of the tangent FFT blocks (two in front of the forward's LayerNorm tangents, four behind the backward's) ride in the LayerNorm
 // tangent kernels — the same masks on the same values: bit-identical.  MTTS_SO_FUSE_DROP=0: launches of their own again.
@@ -200,22 +196,10 @@ void ln_bwd_t(const Pass& ps, Space s, TS dy, TS tgy, TS z, TS st, TS tz, TS tst
               const unsigned char* mask, TS dz, TS tgz, int C, int relu_on_z, TS dz_drop = TS{nullptr, 0}, TS tgz_drop = TS{nullptr, 0},
               DropSpec dd = DropSpec(), DropSpec din = DropSpec()) {   // din: dropout applied to dy and tgy on load (both kernels)
     const Plan& p = *ps.pl;
-    TS gm = W(ps, g_off), tgm = Wt(g_off);
-    TS hg = Gd(g_off), hb = Gd(b_off);
-    ColArgs a;
-    a.X = tgy.p; a.x_ts = tgy.ts; a.X2 = dy.p; a.x2_ts = dy.ts; a.Z = z.p; a.z_ts = z.ts; a.stats = st.p; a.st_ts = st.ts;
-    a.Z2 = tz.p; a.z2_ts = tz.ts; a.stats2 = tst.p; a.st2_ts = tst.ts; a.mask = mask; a.mask_ts = row_ts(s);
-    a.C = C; a.mode = 5; a.mfield = mfield(s); a.xdrop = din;
     // stage 1 of hv(gamma) / hv(beta) rides in the tangent kernel (8-row partials, folded by one colfinal launch); MTTS_SO_LN_PART=0: the two-launch
     // reduction over the same arrays in front of it (ColArgs mode 5) — another summation order, equal to fp32 roundoff
-    const bool emit = knobs().so_ln_part != 0;
-    if (!emit) colreduce(p, a, hg.p, hb.p, hg.ts, maxM(p, s));
-    const int chunks = ln_chunks(maxM(p, s));
-    MTTS_LAUNCH_LN(ln_jvp_bwd_kernel, C, row2_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                (const float*)dy.p, dy.ts, (const float*)tgy.p, tgy.ts, (const float*)z.p, z.ts, (const float*)st.p, st.ts,
-                (const float*)tz.p, tz.ts, (const float*)tst.p, tst.ts, (const float*)gm.p, gm.ts, (const float*)tgm.p, tgm.ts,
-                mask, row_ts(s), dz.p, dz.ts, tgz.p, tgz.ts, C, relu_on_z, dz_drop.p, dz_drop.ts, tgz_drop.p, tgz_drop.ts, dd, din, emit ? col_partial : (float*)nullptr, chunks);
-    if (emit) ln_fold(p, s, col_partial, chunks, g_off, b_off, C, stream);
+    launch_ln_jvp_bwd(on_rows(p, s, stream, mask), dy, tgy, z, st, tz, tst, W(ps, g_off), Wt(g_off), dz, tgz, C, relu_on_z, dz_drop, tgz_drop, dd, din,
+                      col_partial, knobs().so_ln_part != 0, col_max_chunks, Gd(g_off), Gd(b_off));
 }
 
 // ---- FFT block ----------------------------------------------------------------------------------------
@@ -232,7 +216,7 @@ void fft_fwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, L
     const int L = (s == SP_P) ? p.enc_maxL : p.dec_maxL;
     const AttnSeq* seqs = (s == SP_P) ? p.enc_seqs : p.dec_seqs;
     if (groups > 0 && L > 0)
-        MTTS_LAUNCH(softmax_jvp_fwd_kernel, dim3((L + 3) / 4, 1, groups), dim3(256), stream, seqs, (const float*)b.P.p, t.P.p);
+        launch_softmax_jvp_fwd(seqs, L, groups, b.P.p, t.P.p, stream);
     attn_gemm(ps, s, TAB_PV, GEMM_NN, t.P.p, 0, b.qkv.p, 3 * d, t.O.p, d, 1.f, heads, 0, b.P.p, t.qkv.p);
     conv_fwd_t(ps, s, b.O, t.O, d, 1, P.wfc, P.bfc, d, t.z1, nullptr);
     const bool fuse = so_fuse_drop();
@@ -271,8 +255,7 @@ void fft_bwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, L
     auto masked = [&](TS src, TS shared, TS own, int site) {
         if (!df) return drop(ps, s, src, shared, d, block_dropout(s), site);
         if (drop_active(ps) && block_dropout(s) > 0.f) return drop(ps, s, src, own, d, block_dropout(s), site);
-        MTTS_LAUNCH(copy_tasks_kernel, dim3((unsigned)std::min<long long>(((long long)maxM(p, s) * d / 4 + 255) / 256, 1024), 1, p.tasks), dim3(256), stream,
-                    (const float*)src.p, src.ts, own.p, own.ts, (long long)maxM(p, s) * d / 4);
+        launch_copy_tasks(src, own, (long long)maxM(p, s) * d / 4, p.tasks, stream);
         return own;
     };
     TS dc = fuse2 ? (df ? tl->dc : gm) : masked(dz2, gm, df ? tl->dc : gm, site_base + 1), tdc = fuse2 ? (df ? tl->tdc : tgm) : masked(tg1, tgm, df ? tl->tdc : tgm, site_base + 1);
@@ -295,8 +278,7 @@ void fft_bwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, L
         attn_gemm(ps, s, TAB_DV, GEMM_TN, t.P.p, 0, g1.p, d, tgqkv.p, 3 * d, 1.f, heads, 0, b.P.p, tg1.p);
     }
     if (groups > 0 && L > 0)
-        MTTS_LAUNCH(softmax_jvp_bwd_kernel, dim3((L + 3) / 4, 1, groups), dim3(256), stream, seqs, (const float*)b.P.p,
-                    (const float*)t.P.p, dS.p, tdS.p, 1.f / sqrtf((float)dk));
+        launch_softmax_jvp_bwd(seqs, L, groups, b.P.p, t.P.p, dS.p, tdS.p, 1.f / sqrtf((float)dk), stream);
     // dQ = dS K ; tg_Q = tg_S K + dS tK
     // dK = dS^T Q ; tg_K = tg_S^T Q + dS^T tQ
     {
@@ -336,9 +318,7 @@ void pred_fwd_t(const Pass& ps, const PredP& P, PredBuf& b, PredBuf& t, TS xin, 
     ln_fwd_t(ps, s, t.r2, none, b.r2, b.st2, P.l2g, P.l2b, im, none, t.n2, t.st2, f, DropSpec(), fuse ? drop_spec(ps, cfg.vp_dropout, site_base + 1) : DropSpec());
     if (!fuse) drop(ps, s, t.n2, t.n2, f, cfg.vp_dropout, site_base + 1);
     TS w = W(ps, P.lw), tw = Wt(P.lw), tbb = Wt(P.lb);
-    MTTS_LAUNCH(rowdot_jvp_kernel, row_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                (const float*)b.n2.p, b.n2.ts, (const float*)t.n2.p, t.n2.ts, (const float*)w.p, w.ts, (const float*)tw.p,
-                (const float*)tbb.p, tw.ts, valid_mask(p, s), row_ts(s), t.out.p, t.out.ts, f);
+    launch_rowdot_jvp(on_rows(p, s, stream, valid_mask(p, s)), b.n2, t.n2, w, tw, tbb, t.out, f);
 }
 // dout / tgout: gradient of the prediction and its tangent; tdx accumulates the tangent of the input gradient, dx (optional: only an
 // adapted encoder upstream needs it) the primal input gradient
@@ -362,12 +342,10 @@ void pred_bwd_t(const Pass& ps, const PredP& P, PredBuf& b, PredBuf& t, TS xin, 
         ColArgs a;
         a.X = t.n2.p; a.x_ts = t.n2.ts; a.roww = dout.p; a.roww_ts = dout.ts; a.C = f; a.mode = 0; a.mfield = mfield(s); a.accumulate = 1;
         TS o = Gd(P.lw);
-        colreduce(p, a, o.p, nullptr, o.ts, maxM(p, s), os);
+        colreduce(p, a, o.p, nullptr, o.ts, s, os);
     }
     TS w = W(ps, P.lw), tw = Wt(P.lw);
-    MTTS_LAUNCH(rowdot_jvp_bwd_kernel, row_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s),
-                (const float*)dout.p, (const float*)tgout.p, dout.ts, (const float*)w.p, w.ts, (const float*)tw.p, tw.ts,
-                g1.p, g1.ts, tg1.p, tg1.ts, f);
+    launch_rowdot_jvp_bwd(on_rows(p, s, stream), dout, tgout, w, tw, g1, tg1, f);
     // the dropout behind each LayerNorm masks both incoming gradients: on load in the two kernels of ln_bwd_t (so_fuse_drop), or by launches of their own
     const bool fuse = so_fuse_drop();
     if (!fuse) { drop(ps, s, g1, g1, f, cfg.vp_dropout, site_base + 1); drop(ps, s, tg1, tg1, f, cfg.vp_dropout, site_base + 1); }
@@ -386,8 +364,7 @@ int forward_t(const Pass& ps) {
     TS none{nullptr, 0};
     TS ttab = Wt(spk_table);
     if (ttab.p && !p.ext_spk) {   // external speaker embeddings (speaker_emb: dvec) are inputs of the batch: no tangent
-        MTTS_LAUNCH(speaker_vec_kernel, dim3(p.maxB, 1, nt), dim3(64), stream, (const int*)p.meta, (const float*)ttab.p, ttab.ts,
-                    (const int*)p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, t_spk.p, t_spk.ts, d);
+        launch_speaker_vec(on_rows(p, SP_P, stream), p.maxB, ttab, p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, t_spk, d);
     } else {
         DEV_CHECK(hipMemsetAsync(t_spk.p, 0, (size_t)t_spk.ts * nt * sizeof(float), stream));
     }
@@ -395,19 +372,16 @@ int forward_t(const Pass& ps) {
         // tangent of the embedding output: the token rows of the word table's tangent (the position table is frozen; invalid rows carry
         // token 0 = the padding row, whose tangent is 0 as its gradient is), then the encoder blocks, then + the speaker vector's tangent
         TS twe = Wt(word_emb);
-        MTTS_LAUNCH(embed_add_idx_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)nullptr,
-                    0LL, (const float*)twe.p, twe.ts, (const int*)p.p_tok, row_ts_p, t_emb.p, t_emb.ts, d);
+        launch_embed_add_idx(on_rows(p, SP_P, stream), TS{nullptr, 0}, twe, p.p_tok, t_emb, d);
         TS xe = emb_out, txe = t_emb;
         for (int l = 0; l < cfg.enc_layers; ++l) {
             site_base = 2 * l;
             fft_fwd_t(ps, SP_P, cfg.enc_heads, encP[l], encB[l], tencB[l], xe, txe);
             xe = encB[l].y2; txe = tencB[l].y2;
         }
-        MTTS_LAUNCH(add_rowvec_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)txe.p, txe.ts,
-                    (const float*)t_spk.p, t_spk.ts, (const int*)p.p_row_b, (const unsigned char*)p.p_inrect, row_ts_p, t_x0.p, t_x0.ts, d);
+        launch_add_rowvec(on_rows(p, SP_P, stream, p.p_inrect), txe, t_spk, p.p_row_b, t_x0, d);
     } else
-    MTTS_LAUNCH(bcast_rowvec_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP,
-                (const float*)t_spk.p, t_spk.ts, (const int*)p.p_row_b, (const unsigned char*)p.p_inrect, row_ts_p, t_x0.p, t_x0.ts, d);
+    launch_bcast_rowvec(on_rows(p, SP_P, stream, p.p_inrect), t_spk, p.p_row_b, t_x0, d);
     // variance adaptor (teacher-forced: the embeddings are looked up at the TARGET buckets, so only the table tangents flow through them);
     // a phoneme-level feature sits on the phoneme rectangle before the length regulator, a frame-level one on the frame rectangle after it
     // (engine.h: forward)
@@ -416,39 +390,30 @@ int forward_t(const Pass& ps) {
     site_base = 128; pred_fwd_t(ps, durP, durB, tdurB, x0, t_x0);
     if (!cfg.pitch_frame) {
         site_base = 132; pred_fwd_t(ps, pitP, pitB, tpitB, xp, txp);
-        MTTS_LAUNCH(embed_add_idx_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)txp.p,
-                    txp.ts, (const float*)tpe.p, tpe.ts, (const int*)pidx, row_ts_p, t_x1.p, t_x1.ts, d);
+        launch_embed_add_idx(on_rows(p, SP_P, stream), txp, tpe, pidx, t_x1, d);
         xp = x1; txp = t_x1;
     }
     if (!cfg.energy_frame) {
         site_base = 136; pred_fwd_t(ps, eneP, eneB, teneB, xp, txp);
-        MTTS_LAUNCH(embed_add_idx_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)txp.p,
-                    txp.ts, (const float*)tee.p, tee.ts, (const int*)eidx, row_ts_p, t_x2.p, t_x2.ts, d);
+        launch_embed_add_idx(on_rows(p, SP_P, stream), txp, tee, eidx, t_x2, d);
         xp = x2; txp = t_x2;
     }
     if (!any_frame_level()) {
-        MTTS_LAUNCH(length_regulate_fwd_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (const float*)txp.p,
-                    txp.ts, (const int*)p.f_src, (const int*)p.f_row_b, (const int*)p.f_row_t, row_ts_f, (const float*)t_spk.p, t_spk.ts,
-                    (const float*)nullptr, t_dec_in.p, t_dec_in.ts, d);
+        launch_length_regulate_fwd(on_rows(p, SP_F, stream), txp, p.f_src, p.f_row_b, p.f_row_t, t_spk, nullptr, t_dec_in, d);
     } else {
-        MTTS_LAUNCH(length_regulate_rect_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (const float*)txp.p, txp.ts,
-                    (const int*)p.f_src, row_ts_f, (const int*)p.r2f, row_ts_r, t_xr0.p, t_xr0.ts, d);
+        launch_length_regulate_rect(on_rows(p, SP_R, stream), txp, p.f_src, row_ts_f, p.r2f, t_xr0, d);
         TS xr = xr0, txr = t_xr0;
         if (cfg.pitch_frame) {
             site_base = 132; pred_fwd_t(ps, pitP, pitR, tpitR, xr, txr, SP_R);
-            MTTS_LAUNCH(embed_add_idx_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR, (const float*)txr.p,
-                        txr.ts, (const float*)tpe.p, tpe.ts, (const int*)pidx_r, row_ts_r, t_xr1.p, t_xr1.ts, d);
+            launch_embed_add_idx(on_rows(p, SP_R, stream), txr, tpe, pidx_r, t_xr1, d);
             xr = xr1; txr = t_xr1;
         }
         if (cfg.energy_frame) {
             site_base = 136; pred_fwd_t(ps, eneP, eneR, teneR, xr, txr, SP_R);
-            MTTS_LAUNCH(embed_add_idx_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR, (const float*)txr.p,
-                        txr.ts, (const float*)tee.p, tee.ts, (const int*)eidx_r, row_ts_r, t_xr2.p, t_xr2.ts, d);
+            launch_embed_add_idx(on_rows(p, SP_R, stream), txr, tee, eidx_r, t_xr2, d);
             xr = xr2; txr = t_xr2;
         }
-        MTTS_LAUNCH(length_regulate_fwd_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (const float*)txr.p,
-                    txr.ts, (const int*)p.f2r, (const int*)p.f_row_b, (const int*)p.f_row_t, row_ts_f, (const float*)t_spk.p, t_spk.ts,
-                    (const float*)nullptr, t_dec_in.p, t_dec_in.ts, d);
+        launch_length_regulate_fwd(on_rows(p, SP_F, stream), txr, p.f2r, p.f_row_b, p.f_row_t, t_spk, nullptr, t_dec_in, d);
     }
     TS x = dec_in, tx = t_dec_in;
     for (int l = 0; l < cfg.dec_layers; ++l) {
@@ -472,11 +437,9 @@ int forward_t(const Pass& ps) {
                         4.0 * (p.sum_nF * ((dual ? 2 : 1) * d + cfg.n_mel) + (dual ? 2.0 : 1.0) * nt * cfg.n_mel * d));
         }
         if (tb.p) {
-            MTTS_LAUNCH(fill_padded_rows_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, t_mel.p, t_mel.ts,
-                        (const float*)tb.p, tb.ts, (const unsigned char*)p.r_inrect, (const unsigned char*)p.r_valid, row_ts_r, cfg.n_mel);
+            launch_fill_padded_rows(on_rows(p, SP_R, stream, p.r_inrect), t_mel, tb, p.r_valid, cfg.n_mel);
         } else {  // zero bias tangent: padded + guard rows are 0 — valid rows were just written
-            MTTS_LAUNCH(fill_padded_rows_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, t_mel.p, t_mel.ts,
-                        (const float*)tgRz.p, 0LL, (const unsigned char*)p.r_inrect, (const unsigned char*)p.r_valid, row_ts_r, cfg.n_mel);
+            launch_fill_padded_rows(on_rows(p, SP_R, stream, p.r_inrect), t_mel, TS{(float*)tgRz.p, 0}, p.r_valid, cfg.n_mel);
         }
     }
     TS cur = mel, tcur = t_mel;
@@ -489,14 +452,10 @@ int forward_t(const Pass& ps) {
         ColArgs ca;  // S1 = sum tc*xhat, S0 = sum tc
         ca.X = t.c.p; ca.x_ts = t.c.ts; ca.Z = b.c.p; ca.z_ts = b.c.ts; ca.stats = b.stats.p; ca.st_ts = b.stats.ts;
         ca.mask = p.r_inrect; ca.mask_ts = row_ts_r; ca.C = P.cout; ca.mode = 3; ca.do_tanh = 0; ca.mfield = META_MR;
-        colreduce(p, ca, t.stats.p, t.stats.p + P.cout, t.stats.ts, p.maxMr);
+        colreduce(p, ca, t.stats.p, t.stats.p + P.cout, t.stats.ts, SP_R);
         TS gm = W(ps, P.g), tgm = Wt(P.g), tbt = Wt(P.beta);
-        MTTS_LAUNCH(bn_jvp_apply_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (const float*)b.c.p, b.c.ts,
-                    (const float*)t.c.p, t.c.ts, (const float*)b.stats.p, b.stats.ts, (const float*)t.stats.p,
-                    (const float*)(t.stats.p + P.cout), t.stats.ts, (const float*)gm.p, gm.ts, (const float*)tgm.p, (const float*)tbt.p,
-                    tgm.ts, (const float*)b.a.p, b.a.ts, (const unsigned char*)p.r_inrect, row_ts_r,
-                    (int)(i < cfg.postnet_layers - 1), t.a.p, t.a.ts, P.cout, drop_active(ps) ? 1.f - cfg.postnet_dropout : 1.f,
-                    so_fuse_drop() ? drop_spec(ps, cfg.postnet_dropout, 192 + i) : DropSpec());
+        launch_bn_jvp_apply(on_rows(p, SP_R, stream, p.r_inrect), b.c, t.c, b.stats, t.stats, gm, tgm, tbt, b.a, (int)(i < cfg.postnet_layers - 1), t.a, P.cout,
+                            drop_active(ps) ? 1.f - cfg.postnet_dropout : 1.f, so_fuse_drop() ? drop_spec(ps, cfg.postnet_dropout, 192 + i) : DropSpec());
         if (!so_fuse_drop()) drop(ps, SP_R, t.a, t.a, P.cout, cfg.postnet_dropout, 192 + i);
         cur = b.a; tcur = t.a;
     }
@@ -516,8 +475,7 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
     const TS gRm = K.gRm;                              // final mel gradient (kept, or built below)
     const TS gRm_direct = sk ? this->gRm : K.gRm;      // where the loss kernel puts the direct L1 term (scratch when the final one is kept)
     LossArgs a = loss_args(p);
-    MTTS_LAUNCH(loss_grad_kernel, dim3(kLossBlocks, 1, nt), dim3(256), stream, (const int*)p.meta, a, scale, gRm_direct.p, gRp.p,
-                dpred[1].p, dpred[2].p, dpred[0].p, dpred_r[0].p, dpred_r[1].p);
+    launch_loss_grad(p.meta, nt, a, scale, gRm_direct.p, gRp.p, dpred[1].p, dpred[2].p, dpred[0].p, dpred_r[0].p, dpred_r[1].p, stream);
     MTTS_LAUNCH(loss_tangent_kernel, dim3(4, 1, nt), dim3(256), stream, (const int*)p.meta, (const float*)tpitB.out.p,
                 (const float*)teneB.out.p, (const float*)tdurB.out.p, tpitB.out.ts, (const unsigned char*)p.p_valid, row_ts_p, scale,
                 tdpred[1].p, tdpred[2].p, tdpred[0].p, cfg.pitch_frame, cfg.energy_frame);
@@ -545,7 +503,7 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
         ca.X = cur.p; ca.x_ts = cur.ts; ca.Y = b.a.p; ca.y_ts = b.a.ts; ca.Z = b.c.p; ca.z_ts = b.c.ts;
         ca.stats = b.stats.p; ca.st_ts = b.stats.ts; ca.mask = p.r_inrect; ca.mask_ts = row_ts_r; ca.C = P.cout;
         ca.mode = 3; ca.do_tanh = act; ca.mfield = META_MR;
-        colreduce(p, ca, b.dgamma_tmp.p, b.dgamma_tmp.p + P.cout, b.dgamma_tmp.ts, p.maxMr);
+        colreduce(p, ca, b.dgamma_tmp.p, b.dgamma_tmp.p + P.cout, b.dgamma_tmp.ts, SP_R);
         TS hg = Gd(P.g), hb = Gd(P.beta);
         ColArgs cb;  // tangent sums = hv(gamma), hv(beta)
         cb.yscale = ysc; cb.xdrop = pdrop;
@@ -553,18 +511,14 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
         cb.Z = b.c.p; cb.z_ts = b.c.ts; cb.Z2 = t.c.p; cb.z2_ts = t.c.ts; cb.stats = b.stats.p; cb.st_ts = b.stats.ts;
         cb.stats2 = t.stats.p; cb.st2_ts = t.stats.ts; cb.mask = p.r_inrect; cb.mask_ts = row_ts_r; cb.C = P.cout;
         cb.mode = 6; cb.do_tanh = act; cb.mfield = META_MR;
-        colreduce(p, cb, hg.p, hb.p, hg.ts, p.maxMr);
+        colreduce(p, cb, hg.p, hb.p, hg.ts, SP_R);
         TS gm = W(ps, P.g), tgm = Wt(P.g);
         // under-filled plans: the layer's hv(W) product leaves the tangent launch for the side stream (as the decoder layers' do: TLayerGrad);
         // the BatchNorm backward then writes into buffers of the layer's own, which outlive the shared scratch the next layer reuses
         const bool dfp = knobs().so_defer_post && !tpostG.empty() && defer_ok(p) && p.tasks <= defer_tasks;
         const TS gR0 = dfp ? TS{tpostG[i].dc.p, tpostG[i].dc.ts} : this->gR0, tgR0 = dfp ? TS{tpostG[i].tdc.p, tpostG[i].tdc.ts} : this->tgR0;
-        MTTS_LAUNCH(bn_jvp_bwd_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (const float*)cur.p, cur.ts,
-                    (const float*)tcur.p, tcur.ts, (const float*)b.a.p, b.a.ts, (const float*)t.a.p, t.a.ts, (const float*)b.c.p, b.c.ts,
-                    (const float*)t.c.p, t.c.ts, (const float*)b.stats.p, b.stats.ts, (const float*)t.stats.p,
-                    (const float*)(t.stats.p + P.cout), t.stats.ts, (const float*)gm.p, gm.ts, (const float*)tgm.p, tgm.ts,
-                    (const float*)b.dgamma_tmp.p, (const float*)(b.dgamma_tmp.p + P.cout), b.dgamma_tmp.ts, (const float*)hg.p,
-                    (const float*)hb.p, hg.ts, (const unsigned char*)p.r_inrect, row_ts_r, act, gR0.p, gR0.ts, tgR0.p, tgR0.ts, P.cout, ysc, pdrop);
+        launch_bn_jvp_bwd(on_rows(p, SP_R, stream, p.r_inrect), cur, tcur, b.a, t.a, b.c, t.c, b.stats, t.stats, gm, tgm, b.dgamma_tmp,
+                          TS{b.dgamma_tmp.p + P.cout, b.dgamma_tmp.ts}, hg, hb, act, gR0, tgR0, P.cout, ysc, pdrop);
         TS xin = (i == 0) ? mel : postB[i - 1].a, txin = (i == 0) ? t_mel : tpostB[i - 1].a;
         if (i > 0) {
             conv_bwd_t(ps, SP_R, gR0, tgR0, P.cout, cfg.postnet_kernel, xin, txin, P.cin, P.w, P.b, p.r_inrect, sk ? none : K.post_cur[i - 1], 0, tgR1, false, p.r_inrect,
@@ -573,9 +527,7 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
         } else {
             const long long n4 = (gRm.ts * nt) / 4;
             if (!sk)
-                MTTS_LAUNCH(add2_kernel, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 2048)), dim3(256), stream,
-                            (const float*)(gRm.p - (long long)G * nm), (const float*)(gRp.p - (long long)G * nm),
-                            gRm.p - (long long)G * nm, n4);
+                launch_add2(gRm.p - (long long)G * nm, gRp.p - (long long)G * nm, gRm.p - (long long)G * nm, n4, stream);
             conv_bwd_t(ps, SP_R, gR0, tgR0, P.cout, cfg.postnet_kernel, xin, txin, P.cin, P.w, P.b, p.r_inrect, sk ? none : gRm, GEMM_ACCUM, tgRm, false, p.r_inrect,
                        TS{nullptr, 0}, dfp);
         }
@@ -590,10 +542,8 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
     ar_ready(ar_idx_postnet());   // (overlapped exchange of the last reverse step, engine.h)
     // mel_linear
     colsum(ps, SP_R, tgRm, nm, nullptr, none, Gd(mel_b));
-    MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (int)META_MF, (const float*)gRm.p,
-                gRm.ts, (const int*)p.f2r, row_ts_f, gMelF.p, gMelF.ts, nm);
-    MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (int)META_MF, (const float*)tgRm.p,
-                tgRm.ts, (const int*)p.f2r, row_ts_f, tgMelF.p, tgMelF.ts, nm);
+    launch_gather_rows(on_rows(p, SP_F, stream), gRm, p.f2r, gMelF, nm);
+    launch_gather_rows(on_rows(p, SP_F, stream), tgRm, p.f2r, tgMelF, nm);
     TS dec_out = cfg.dec_layers ? decB[cfg.dec_layers - 1].y2 : dec_in;
     TS tdec_out = cfg.dec_layers ? tdecB[cfg.dec_layers - 1].y2 : t_dec_in;
     conv_bwd_t(ps, SP_F, gMelF, tgMelF, nm, 1, dec_out, tdec_out, d, mel_w, -1, nullptr, sk ? none : K.dec_top, 0, tgF0, false, nullptr);
@@ -614,39 +564,30 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
         // frame-level half of the variance adaptor on the frame rectangle (engine.h: backward_impl), tangent and — for an adapted encoder —
         // primal input gradients
         TS dxr = enc_t ? gRx : none;
-        MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR, (const float*)tgF0.p,
-                    tgF0.ts, (const int*)p.r2f, row_ts_r, tgRx.p, tgRx.ts, d);
+        launch_gather_rows(on_rows(p, SP_R, stream), tgF0, p.r2f, tgRx, d);
         if (enc_t)
-            MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMr, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR, (const float*)gF0.p,
-                        gF0.ts, (const int*)p.r2f, row_ts_r, gRx.p, gRx.ts, d);
+            launch_gather_rows(on_rows(p, SP_R, stream), gF0, p.r2f, gRx, d);
         if (cfg.energy_frame) {
-            MTTS_LAUNCH(table_grad_kernel, dim3(cfg.n_bins, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR, (const float*)tgRx.p,
-                        tgRx.ts, (const int*)eidx_r, row_ts_r, -1, Gd(energy_emb).p, n_total, d);
+            launch_table_grad(on_rows(p, SP_R, stream), cfg.n_bins, tgRx, eidx_r, -1, Gd(energy_emb), d);
             site_base = 136;
             pred_bwd_t(ps, eneP, eneR, teneR, cfg.pitch_frame ? xr1 : xr0, cfg.pitch_frame ? t_xr1 : t_xr0, dpred_r[1], tdpred_r[1], tgRx, dxr, SP_R);
         }
         if (cfg.pitch_frame) {
-            MTTS_LAUNCH(table_grad_kernel, dim3(cfg.n_bins, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MR, (const float*)tgRx.p,
-                        tgRx.ts, (const int*)pidx_r, row_ts_r, -1, Gd(pitch_emb).p, n_total, d);
+            launch_table_grad(on_rows(p, SP_R, stream), cfg.n_bins, tgRx, pidx_r, -1, Gd(pitch_emb), d);
             site_base = 132;
             pred_bwd_t(ps, pitP, pitR, tpitR, xr0, t_xr0, dpred_r[0], tdpred_r[0], tgRx, dxr, SP_R);
         }
-        MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (int)META_MF, (const float*)tgRx.p,
-                    tgRx.ts, (const int*)p.f2r, row_ts_f, tgFx.p, tgFx.ts, d);
+        launch_gather_rows(on_rows(p, SP_F, stream), tgRx, p.f2r, tgFx, d);
         tgLR = tgFx;
         if (enc_t) {
-            MTTS_LAUNCH(gather_rows_kernel, row_grid(p.maxMf, nt), dim3(256), stream, (const int*)p.meta, (int)META_MF, (const float*)gRx.p,
-                        gRx.ts, (const int*)p.f2r, row_ts_f, gFx.p, gFx.ts, d);
+            launch_gather_rows(on_rows(p, SP_F, stream), gRx, p.f2r, gFx, d);
             gLR = gFx;
         }
     }
-    MTTS_LAUNCH(length_regulate_bwd_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (const float*)tgLR.p,
-                tgLR.ts, (const int*)p.p_first, (const int*)p.p_count, row_ts_p, tgP0.p, tgP0.ts, d, 0);
+    launch_length_regulate_bwd(on_rows(p, SP_P, stream), tgLR, p.p_first, p.p_count, tgP0, d, 0);
     if (enc_t)
-        MTTS_LAUNCH(length_regulate_bwd_kernel, row_grid(p.maxMp, nt), dim3(256), stream, (const int*)p.meta, (const float*)gLR.p,
-                    gLR.ts, (const int*)p.p_first, (const int*)p.p_count, row_ts_p, gP0.p, gP0.ts, d, 0);
-    MTTS_LAUNCH(segsum_rows_kernel, dim3((d + 63) / 64, p.maxB, nt), dim3(256), stream, (const int*)p.meta, (const float*)tgF0.p,
-                tgF0.ts, (const int*)p.f_seg_start, (const int*)p.f_seg_len, (long long)cap_B, tdspk.p, tdspk.ts, d, 0);
+        launch_length_regulate_bwd(on_rows(p, SP_P, stream), gLR, p.p_first, p.p_count, gP0, d, 0);
+    launch_segsum_rows(on_rows(p, SP_F, stream), p.maxB, tgF0, p.f_seg_start, p.f_seg_len, (long long)cap_B, tdspk, d, 0);
     if (!cfg.energy_frame) {
         table_hv(p, tgP0, gPxE, eidx, cfg.n_bins, -1, energy_emb, true);
         site_base = 136;
@@ -657,11 +598,9 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
         site_base = 132; pred_bwd_t(ps, pitP, pitB, tpitB, x0, t_x0, dpred[1], tdpred[1], tgP0, dxp);
     }
     site_base = 128; pred_bwd_t(ps, durP, durB, tdurB, x0, t_x0, dpred[0], tdpred[0], tgP0, dxp);
-    MTTS_LAUNCH(segsum_rows_kernel, dim3((d + 63) / 64, p.maxB, nt), dim3(256), stream, (const int*)p.meta, (const float*)tgP0.p,
-                tgP0.ts, (const int*)p.p_seg_start, (const int*)p.p_seg_len, (long long)cap_B, tdspk.p, tdspk.ts, d, 1);
+    launch_segsum_rows(on_rows(p, SP_P, stream), p.maxB, tgP0, p.p_seg_start, p.p_seg_len, (long long)cap_B, tdspk, d, 1);
     if (!p.ext_spk)
-    MTTS_LAUNCH(speaker_table_grad_kernel, dim3(cfg.n_speaker, 1, nt), dim3(64), stream, (const int*)p.meta, (const float*)tdspk.p,
-                tdspk.ts, (const int*)p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, Gd(spk_table).p, n_total, d);
+    launch_speaker_table_grad(on_rows(p, SP_P, stream), cfg.n_speaker, tdspk, p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, Gd(spk_table), d);
     ar_ready(ar_idx_spk());
     // a non-adapted encoder carries no forward tangent, so the tangent of its gradients is its ordinary backward applied to tgP0; an
     // adapted one goes through the primal + tangent backward like the decoder
@@ -688,19 +627,16 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
 void table_hv(const Plan& p, TS g, TS snap, const int* idx, int n_rows, int skip_row, long long emb_off, bool snapshot) {
     const int d = cfg.d_model, nt = p.tasks;
     if (!knobs().so_table_side || side == nullptr || (snapshot && (arena_pred == nullptr || snap.p == nullptr))) {
-        MTTS_LAUNCH(table_grad_kernel, dim3(n_rows, 1, nt), dim3(256), stream, (const int*)p.meta, (int)META_MP, (const float*)g.p, g.ts, idx, row_ts_p, skip_row,
-                    Gd(emb_off).p, n_total, d);
+        launch_table_grad(on_rows(p, SP_P, stream), n_rows, g, idx, skip_row, Gd(emb_off), d);
         return;
     }
     TS src = g;
     if (snapshot) {
-        MTTS_LAUNCH(copy_tasks_kernel, dim3((unsigned)std::min<long long>(((long long)p.maxMp * d / 4 + 255) / 256, 1024), 1, nt), dim3(256), stream,
-                    (const float*)g.p, g.ts, snap.p, snap.ts, (long long)p.maxMp * d / 4);
+        launch_copy_tasks(g, snap, (long long)p.maxMp * d / 4, nt, stream);
         src = snap;
     }
     fork_side();
-    MTTS_LAUNCH(table_grad_kernel, dim3(n_rows, 1, nt), dim3(256), side, (const int*)p.meta, (int)META_MP, (const float*)src.p, src.ts, idx, row_ts_p, skip_row,
-                Gd(emb_off).p, n_total, d);
+    launch_table_grad(on_rows(p, SP_P, side), n_rows, src, idx, skip_row, Gd(emb_off), d);
 }
 
 // ---- second-order meta-gradient ---------------------------------------------------------------------------
@@ -713,8 +649,7 @@ int meta_grad_so(int steps, float inner_lr, float grad_scale, float* losses_out,
     const int nt = sp.tasks;
     const long long hist_ts = n_adapt;             // [step][task][n_adapt]
     if (n_adapt > 0)
-        MTTS_LAUNCH(broadcast_kernel, dim3(blocks_for(n_adapt / 4), 1, nt), dim3(256), stream, (const float*)(theta + adapt_start),
-                    fast, n_adapt / 4, n_adapt);
+        launch_broadcast(theta + adapt_start, TS{fast, n_adapt}, n_adapt / 4, nt, stream);
     Pass ps{&sp, true, true};
     std::vector<unsigned> step_seeds(std::max(steps, 1), 0u);
     unsigned ahead_seeds[kAhead];
@@ -774,12 +709,10 @@ int meta_grad_so(int steps, float inner_lr, float grad_scale, float* losses_out,
         gs_bound = -1;
         if (overlap) { if (ar_end() || rc) return -1; return 0; }
         if (rc) return -1;
-        MTTS_LAUNCH(axpy_kernel, dim3(blocks_for(n_total / 4), 1, nt), dim3(256), stream, grad, n_total, (const float*)hv, n_total,
-                    -inner_lr, n_total / 4);
+        launch_axpy(TS{grad, n_total}, TS{hv, n_total}, -inner_lr, n_total / 4, nt, stream);
     }
     ar_armed = false;   // (steps == 0: nothing to overlap with)
-    MTTS_LAUNCH(sum_tasks_kernel, dim3(blocks_for(n_total / 4)), dim3(256), stream, (const float*)grad, n_total, nt, 1.f, outer,
-                n_total / 4, (int)outer_accumulate);
+    launch_sum_tasks(TS{grad, n_total}, nt, 1.f, outer, n_total / 4, (int)outer_accumulate, stream);
     return 0;
 }
 

@@ -32,11 +32,13 @@ inline int put_meta(const KernelWs& k, int rows, int n_in) {
     m[META_B] = 1; m[META_SMAX] = rows; m[META_TCAP] = n_in; m[META_MP] = rows; m[META_MF] = rows; m[META_MR] = rows; m[META_NP] = rows; m[META_NF] = rows;
     return hipMemcpy(k.meta, m, sizeof(m), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
 }
-inline void col_reduce(const KernelWs& k, ColArgs a, float* out0, float* out1, int rows, hipStream_t s) {
-    MTTS_LAUNCH(colpart_kernel, dim3((a.C + 127) / 128, k.chunks, 1), dim3(256), s, (const int*)k.meta, a, k.col_partial, k.chunks);
-    MTTS_LAUNCH(colfinal_kernel, dim3(colfinal_blocks(a.C), 1, 1), dim3(256), s, (const int*)k.meta, a.mfield, a.mode, (const float*)k.col_partial, k.chunks,
-                a.C, out0, out1, (long long)0, 1e-5f, 0, (int)kRC);
-    (void)rows;
+// the launchers' view of the scratch block: one task of `rows` rows (every row-count field of the meta table holds it), strides 0
+inline RowLaunch one_task(const KernelWs& k, int rows, int mfield, const unsigned char* mask, void* stream) {
+    return RowLaunch{k.meta, mfield, rows, 1, mask, 0, (hipStream_t)stream};
+}
+inline TS T0(const float* p) { return TS{const_cast<float*>(p), 0}; }   // a one-task array
+inline void col_reduce(const KernelWs& k, const RowLaunch& r, const ColArgs& a, float* out0, float* out1) {
+    launch_colreduce(r, a, k.col_partial, k.chunks, out0, out1, 0);
 }
 inline bool bad_rows(int rows, int C) { return rows < 1 || C < 4 || (C & 3) || C > 1024; }
 }  // namespace
@@ -48,9 +50,7 @@ int mtts_layernorm_fwd(int rows, int C, const float* a, const float* res, const 
     if (bad_rows(rows, C) || !a || !gamma || !beta || !y || !stats || !ws) return -1;
     const KernelWs k = carve(ws, rows, 0);
     if (put_meta(k, rows, rows)) return -1;
-    MTTS_LAUNCH_LN(layernorm_fwd_kernel, C, row2_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, a, (long long)0, res,
-                (long long)0, gamma, beta, (long long)0, mask, (long long)0, z, (long long)0, y, (long long)0, stats, (long long)0, C, 1e-5f,
-                DropSpec(), DropSpec(), (bf16_t*)nullptr);
+    launch_layernorm_fwd(one_task(k, rows, META_MP, mask, stream), T0(a), T0(res), T0(gamma), T0(beta), T0(z), T0(y), T0(stats), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -60,12 +60,8 @@ int mtts_layernorm_bwd(int rows, int C, const float* dy, const float* z, const f
     const KernelWs k = carve(ws, rows, 0);
     if (put_meta(k, rows, rows)) return -1;
     // stage 1 of the gamma / beta reduction happens inside the backward kernel (8-row partials), colfinal folds them
-    const int ln_chunks = (rows + kLnRows - 1) / kLnRows;
-    MTTS_LAUNCH_LN(layernorm_bwd_kernel, C, row2_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, dy, (long long)0, z,
-                (long long)0, stats, (long long)0, gamma, (long long)0, mask, (long long)0, dz, (long long)0, C, 0, (float*)nullptr, (long long)0,
-                DropSpec(), DropSpec(), k.col_partial, ln_chunks, (bf16_t*)nullptr, 0);
-    MTTS_LAUNCH(colfinal_kernel, dim3(colfinal_blocks(C), 1, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, 1, (const float*)k.col_partial,
-                ln_chunks, C, dgamma, dbeta, (long long)0, 1e-5f, 0, (int)kLnRows);
+    launch_layernorm_bwd(one_task(k, rows, META_MP, mask, stream), T0(dy), T0(z), T0(stats), T0(gamma), T0(dz), C, 0, T0(nullptr), DropSpec(), DropSpec(),
+                         k.col_partial, true, T0(dgamma), T0(dbeta));
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -81,7 +77,7 @@ int mtts_softmax_fwd(int n_mat, int L, float* S, void* ws, void* stream) {
     if (n_mat < 1 || L < 1 || !S || !ws) return -1;
     const KernelWs k = carve(ws, 1, n_mat);
     if (put_seqs(k, n_mat, L)) return -1;
-    MTTS_LAUNCH(softmax_fwd_kernel, dim3((L + 3) / 4, 1, n_mat), dim3(256), (hipStream_t)stream, (const AttnSeq*)k.seqs, S);
+    launch_softmax_fwd(k.seqs, L, n_mat, S, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // dP -> dS in place: dS = alpha * P o (dP - rowsum(dP o P))
@@ -89,7 +85,7 @@ int mtts_softmax_bwd(int n_mat, int L, const float* P, float* dP, float alpha, v
     if (n_mat < 1 || L < 1 || !P || !dP || !ws) return -1;
     const KernelWs k = carve(ws, 1, n_mat);
     if (put_seqs(k, n_mat, L)) return -1;
-    MTTS_LAUNCH(softmax_bwd_kernel, dim3((L + 3) / 4, 1, n_mat), dim3(256), (hipStream_t)stream, (const AttnSeq*)k.seqs, P, dP, alpha);
+    launch_softmax_bwd(k.seqs, L, n_mat, P, dP, alpha, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // ScaledDotProductAttention.forward (transformer/Modules.py:14-25) for n_mat independent (sequence, head) pairs of equal length:
@@ -122,7 +118,7 @@ int mtts_sdpa_fwd(int n_mat, int L, int dk, const float* q, const float* kk, con
     GemmArgs g;
     g.table = k.tab[0]; g.A = q; g.B = kk; g.C = P; g.alpha = 1.f / sqrtf((float)dk); g.K = dk;
     gemm_launch(cx, GEMM_NT, g, L, L, n_mat, (hipStream_t)stream);
-    MTTS_LAUNCH(softmax_fwd_kernel, dim3((L + 3) / 4, 1, n_mat), dim3(256), (hipStream_t)stream, (const AttnSeq*)k.seqs, P);
+    launch_softmax_fwd(k.seqs, L, n_mat, P, (hipStream_t)stream);
     GemmArgs h;
     h.table = k.tab[1]; h.A = P; h.B = v; h.C = o; h.K = L;
     gemm_launch(cx, GEMM_NN, h, L, dk, n_mat, (hipStream_t)stream);
@@ -139,9 +135,9 @@ int mtts_batchnorm_fwd(int rows, int C, const float* x, const unsigned char* inr
     if (put_meta(k, rows, rows)) return -1;
     ColArgs ca;
     ca.X = x; ca.mask = inrect; ca.C = C; ca.mode = 2; ca.mfield = META_MR;
-    col_reduce(k, ca, stats, nullptr, rows, (hipStream_t)stream);
-    MTTS_LAUNCH(bn_apply_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, x, (long long)0, (const float*)stats, (long long)0,
-                gamma, beta, (long long)0, inrect, (long long)0, do_tanh, y, (long long)0, C, DropSpec(), (bf16_t*)nullptr);
+    const RowLaunch r = one_task(k, rows, META_MR, inrect, stream);
+    col_reduce(k, r, ca, stats, nullptr);
+    launch_bn_apply(r, T0(x), T0(stats), T0(gamma), T0(beta), do_tanh, T0(y), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // backward of the above: dy -> dx, dgamma, dbeta (n_in = number of rows with inrect != 0)
@@ -152,10 +148,9 @@ int mtts_batchnorm_bwd(int rows, int n_in, int C, const float* dy, const float* 
     if (put_meta(k, rows, n_in)) return -1;
     ColArgs ca;
     ca.X = dy; ca.Y = y; ca.Z = x; ca.stats = stats; ca.mask = inrect; ca.C = C; ca.mode = 3; ca.do_tanh = do_tanh; ca.mfield = META_MR;
-    col_reduce(k, ca, dgamma, dbeta, rows, (hipStream_t)stream);
-    MTTS_LAUNCH(bn_bwd_apply_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, dy, (long long)0, y, (long long)0, x,
-                (long long)0, stats, (long long)0, gamma, (long long)0, (const float*)dgamma, (const float*)dbeta, (long long)0, inrect, (long long)0,
-                do_tanh, dx, (long long)0, C, 1.f, DropSpec(), (bf16_t*)nullptr);
+    const RowLaunch r = one_task(k, rows, META_MR, inrect, stream);
+    col_reduce(k, r, ca, dgamma, dbeta);
+    launch_bn_bwd_apply(r, T0(dy), T0(y), T0(x), T0(stats), T0(gamma), T0(dgamma), T0(dbeta), do_tanh, T0(dx), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -166,8 +161,7 @@ int mtts_table_grad(int rows, int C, int V, const float* dx, const int* idx, int
     if (bad_rows(rows, C) || V < 1 || !dx || !idx || !dtable || !ws) return -1;
     const KernelWs k = carve(ws, rows, 0);
     if (put_meta(k, rows, rows)) return -1;
-    MTTS_LAUNCH(table_grad_kernel, dim3(V, 1, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, dx, (long long)0, idx, (long long)0,
-                skip_row, dtable, (long long)0, C);
+    launch_table_grad(one_task(k, rows, META_MP, nullptr, stream), V, T0(dx), idx, skip_row, T0(dtable), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -185,9 +179,8 @@ int mtts_length_regulate_fwd(int n_frames, int C, const float* x, const int* src
     float* zeros_f = k.col_partial + n_frames;   // needs n_frames ints + C floats <= chunks * 3072 floats (chunks = ceil(rows / kRC))
     if ((long long)n_frames + C > (long long)k.chunks * 3 * 1024) return -1;
     if (hipMemsetAsync(k.col_partial, 0, ((size_t)n_frames + C) * sizeof(float), (hipStream_t)stream) != hipSuccess) return -1;
-    MTTS_LAUNCH(length_regulate_fwd_kernel, row_grid(n_frames, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, x, (long long)0, src,
-                (const int*)zeros_i, row_t ? row_t : (const int*)zeros_i, (long long)0, spk ? spk : (const float*)zeros_f, (long long)0, pos, out,
-                (long long)0, C);
+    launch_length_regulate_fwd(one_task(k, n_frames, META_MF, nullptr, stream), T0(x), src, zeros_i, row_t ? row_t : (const int*)zeros_i, T0(spk ? spk : zeros_f),
+                               pos, T0(out), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int mtts_length_regulate_bwd(int n_phonemes, int C, const float* dout, const int* first, const int* count, float* dx, int accumulate, void* ws,
@@ -195,8 +188,7 @@ int mtts_length_regulate_bwd(int n_phonemes, int C, const float* dout, const int
     if (bad_rows(n_phonemes, C) || !dout || !first || !count || !dx || !ws) return -1;
     const KernelWs k = carve(ws, n_phonemes, 0);
     if (put_meta(k, n_phonemes, n_phonemes)) return -1;
-    MTTS_LAUNCH(length_regulate_bwd_kernel, row_grid(n_phonemes, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, dout, (long long)0, first, count,
-                (long long)0, dx, (long long)0, C, accumulate);
+    launch_length_regulate_bwd(one_task(k, n_phonemes, META_MP, nullptr, stream), T0(dout), first, count, T0(dx), C, accumulate);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -213,9 +205,8 @@ int mtts_layernorm_jvp_full(int rows, int C, const float* ta, const float* tres,
     if (put_meta(k, rows, rows)) return -1;
     float* tstats = tstats_out ? tstats_out : k.col_partial;   // per-row (m1, m2), scratch when the caller keeps none
     if (!tstats_out && (long long)rows * 2 > (long long)k.chunks * 3 * 1024) return -1;
-    MTTS_LAUNCH_LN(ln_jvp_fwd_kernel, C, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, ta, (long long)0, tres,
-                (long long)0, z, (long long)0, stats, (long long)0, gamma, (long long)0, tgamma, tbeta, (long long)0, mask, (long long)0,
-                tz_out, (long long)0, ty, (long long)0, tstats, (long long)0, C, DropSpec(), DropSpec());
+    launch_ln_jvp_fwd(one_task(k, rows, META_MP, mask, stream), T0(ta), T0(tres), T0(z), T0(stats), T0(gamma), T0(tgamma), T0(tbeta), T0(tz_out), T0(ty),
+                      T0(tstats), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int mtts_layernorm_jvp(int rows, int C, const float* ta, const float* tres, const float* z, const float* stats, const float* gamma, const float* tgamma,
@@ -226,7 +217,7 @@ int mtts_softmax_jvp(int n_mat, int L, const float* P, float* tS, void* ws, void
     if (n_mat < 1 || L < 1 || !P || !tS || !ws) return -1;
     const KernelWs k = carve(ws, 1, n_mat);
     if (put_seqs(k, n_mat, L)) return -1;
-    MTTS_LAUNCH(softmax_jvp_fwd_kernel, dim3((L + 3) / 4, 1, n_mat), dim3(256), (hipStream_t)stream, (const AttnSeq*)k.seqs, P, tS);
+    launch_softmax_jvp_fwd(k.seqs, L, n_mat, P, tS, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -240,19 +231,8 @@ int mtts_layernorm_jvp_bwd(int rows, int C, const float* dy, const float* tgy, c
     if (bad_rows(rows, C) || !dy || !tgy || !z || !stats || !tz || !tstats || !gamma || !dz || !tgz || !hgamma || !hbeta || !ws) return -1;
     const KernelWs k = carve(ws, rows, 0);
     if (put_meta(k, rows, rows)) return -1;
-    if (two_launch) {
-        ColArgs a;
-        a.X = tgy; a.X2 = dy; a.Z = z; a.stats = stats; a.Z2 = tz; a.stats2 = tstats; a.mask = mask; a.C = C; a.mode = 5; a.mfield = META_MP;
-        col_reduce(k, a, hgamma, hbeta, rows, (hipStream_t)stream);
-    }
-    const int ln_chunks = (rows + kLnRows - 1) / kLnRows;
-    MTTS_LAUNCH_LN(ln_jvp_bwd_kernel, C, row2_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, dy, (long long)0, tgy,
-                (long long)0, z, (long long)0, stats, (long long)0, tz, (long long)0, tstats, (long long)0, gamma, (long long)0, tgamma, (long long)0,
-                mask, (long long)0, dz, (long long)0, tgz, (long long)0, C, relu_on_z, (float*)nullptr, (long long)0, (float*)nullptr, (long long)0,
-                DropSpec(), DropSpec(), two_launch ? (float*)nullptr : k.col_partial, ln_chunks);
-    if (!two_launch)
-        MTTS_LAUNCH(colfinal_kernel, dim3(colfinal_blocks(C), 1, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, 1,
-                    (const float*)k.col_partial, ln_chunks, C, hgamma, hbeta, (long long)0, 1e-5f, 0, (int)kLnRows);
+    launch_ln_jvp_bwd(one_task(k, rows, META_MP, mask, stream), T0(dy), T0(tgy), T0(z), T0(stats), T0(tz), T0(tstats), T0(gamma), T0(tgamma), T0(dz), T0(tgz), C,
+                      relu_on_z, T0(nullptr), T0(nullptr), DropSpec(), DropSpec(), k.col_partial, !two_launch, k.chunks, T0(hgamma), T0(hbeta));
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // in place: dP -> dS = alpha P (dP - c), tgP -> tg_S = alpha [tP (dP - c) + P (tgP - cdot)]; the pad columns [L, ldS) of both are zeroed
@@ -260,7 +240,7 @@ int mtts_softmax_jvp_bwd(int n_mat, int L, const float* P, const float* tP, floa
     if (n_mat < 1 || L < 1 || !P || !tP || !dP || !tgP || !ws) return -1;
     const KernelWs k = carve(ws, 1, n_mat);
     if (put_seqs(k, n_mat, L)) return -1;
-    MTTS_LAUNCH(softmax_jvp_bwd_kernel, dim3((L + 3) / 4, 1, n_mat), dim3(256), (hipStream_t)stream, (const AttnSeq*)k.seqs, P, tP, dP, tgP, alpha);
+    launch_softmax_jvp_bwd(k.seqs, L, n_mat, P, tP, dP, tgP, alpha, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // batchnorm_jvp: tangent of y = [tanh](gamma xhat + beta) for the input tangent tx on the stats / y of mtts_batchnorm_fwd: tsum [2C] =
@@ -272,10 +252,9 @@ int mtts_batchnorm_jvp(int rows, int n_in, int C, const float* x, const float* t
     if (put_meta(k, rows, n_in)) return -1;
     ColArgs ca;
     ca.X = tx; ca.Z = x; ca.stats = stats; ca.mask = inrect; ca.C = C; ca.mode = 3; ca.do_tanh = 0; ca.mfield = META_MR;
-    col_reduce(k, ca, tsum, tsum + C, rows, (hipStream_t)stream);
-    MTTS_LAUNCH(bn_jvp_apply_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, x, (long long)0, tx, (long long)0, stats,
-                (long long)0, (const float*)tsum, (const float*)(tsum + C), (long long)0, gamma, (long long)0, tgamma, tbeta, (long long)0, y,
-                (long long)0, inrect, (long long)0, do_tanh, ta, (long long)0, C, 1.f, DropSpec());
+    const RowLaunch r = one_task(k, rows, META_MR, inrect, stream);
+    col_reduce(k, r, ca, tsum, tsum + C);
+    launch_bn_jvp_apply(r, T0(x), T0(tx), T0(stats), T0(tsum), T0(gamma), T0(tgamma), T0(tbeta), T0(y), do_tanh, T0(ta), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // batchnorm_jvp_bwd: dy / tgy -> dx / tdx and hv(gamma), hv(beta) (the ColArgs mode-6 reduction); dgamma / dbeta are mtts_batchnorm_bwd's
@@ -290,11 +269,10 @@ int mtts_batchnorm_jvp_bwd(int rows, int n_in, int C, const float* dy, const flo
     ColArgs cb;
     cb.X = tgy; cb.X2 = dy; cb.Y = y; cb.Y2 = ta; cb.Z = x; cb.Z2 = tx; cb.stats = stats; cb.stats2 = tsum; cb.mask = inrect; cb.C = C;
     cb.mode = 6; cb.do_tanh = do_tanh; cb.mfield = META_MR;
-    col_reduce(k, cb, hgamma, hbeta, rows, (hipStream_t)stream);
-    MTTS_LAUNCH(bn_jvp_bwd_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, dy, (long long)0, tgy, (long long)0, y,
-                (long long)0, ta, (long long)0, x, (long long)0, tx, (long long)0, stats, (long long)0, tsum, (const float*)(tsum + C), (long long)0,
-                gamma, (long long)0, tgamma, (long long)0, dgamma, dbeta, (long long)0, (const float*)hgamma, (const float*)hbeta, (long long)0,
-                inrect, (long long)0, do_tanh, dx, (long long)0, tdx, (long long)0, C, 1.f, DropSpec());
+    const RowLaunch r = one_task(k, rows, META_MR, inrect, stream);
+    col_reduce(k, r, cb, hgamma, hbeta);
+    launch_bn_jvp_bwd(r, T0(dy), T0(tgy), T0(y), T0(ta), T0(x), T0(tx), T0(stats), T0(tsum), T0(gamma), T0(tgamma), T0(dgamma), T0(dbeta), T0(hgamma), T0(hbeta),
+                      do_tanh, T0(dx), T0(tdx), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // rowdot (the variance predictors' 256 -> 1 projection): tout[row] = valid ? dot(tx, w) + dot(x, tw) + tb : 0; bwd: dx = dout w,
@@ -304,8 +282,7 @@ int mtts_rowdot_jvp(int rows, int C, const float* x, const float* tx, const floa
     if (bad_rows(rows, C) || !x || !tx || !w || !valid || !tout || !ws) return -1;
     const KernelWs k = carve(ws, rows, 0);
     if (put_meta(k, rows, rows)) return -1;
-    MTTS_LAUNCH(rowdot_jvp_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, x, (long long)0, tx, (long long)0,
-                w, (long long)0, tw, tb, (long long)0, valid, (long long)0, tout, (long long)0, C);
+    launch_rowdot_jvp(one_task(k, rows, META_MP, valid, stream), T0(x), T0(tx), T0(w), T0(tw), T0(tb), T0(tout), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int mtts_rowdot_jvp_bwd(int rows, int C, const float* dout, const float* tgout, const float* w, const float* tw, float* dx, float* tdx, void* ws,
@@ -313,7 +290,6 @@ int mtts_rowdot_jvp_bwd(int rows, int C, const float* dout, const float* tgout, 
     if (bad_rows(rows, C) || !dout || !tgout || !w || !dx || !tdx || !ws) return -1;
     const KernelWs k = carve(ws, rows, 0);
     if (put_meta(k, rows, rows)) return -1;
-    MTTS_LAUNCH(rowdot_jvp_bwd_kernel, row_grid(rows, 1), dim3(256), (hipStream_t)stream, (const int*)k.meta, (int)META_MP, dout, tgout, (long long)0, w,
-                (long long)0, tw, (long long)0, dx, (long long)0, tdx, (long long)0, C);
+    launch_rowdot_jvp_bwd(one_task(k, rows, META_MP, nullptr, stream), T0(dout), T0(tgout), T0(w), T0(tw), T0(dx), T0(tdx), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

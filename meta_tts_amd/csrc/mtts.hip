@@ -565,7 +565,7 @@ int mtts_gemm_bf16(int form, int M, int N, int K, const float* A, int lda, const
 int mtts_to_bf16(const float* src, unsigned short* dst, long long n, void* stream) {
     if (!src || !dst || n < 0 || n % 8 != 0) return -1;
     if (n == 0) return 0;
-    MTTS_LAUNCH(to_bf16_kernel, dim3((unsigned)std::min<long long>((n / 8 + 255) / 256, 4096)), dim3(256), (hipStream_t)stream, src, (bf16_t*)dst, n / 8);
+    launch_to_bf16(src, (bf16_t*)dst, n / 8, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

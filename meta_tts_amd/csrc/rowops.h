@@ -29,6 +29,23 @@ enum { META_B = 0, META_SMAX, META_TCAP, META_MP, META_MF, META_MR, META_NP, MET
 
 inline dim3 row_grid(int max_rows, int tasks) { return dim3((unsigned)((max_rows + 3) / 4), 1, (unsigned)tasks); }
 
+// Host vocabulary of the launchers below (every kernel of this file and of tangent.h is launched from ONE place: the inline launch_* function
+// behind it; the engine and the raw C entries of kernel_api.inc both call that).
+struct TS { float* p; long long ts; };   // a per-task array: pointer + task stride (elements)
+// a launch over a row space: rows < meta[task][mfield] <= max_rows for each of `tasks` tasks; mask (optional) / row_ts: the row mask the kernel
+// applies and the task stride of every per-row array of the space (masks, index lists)
+struct RowLaunch {
+    const int* meta; int mfield, max_rows, tasks;
+    const unsigned char* mask; long long row_ts;
+    hipStream_t stream;
+};
+inline dim3 row_grid(const RowLaunch& r) { return row_grid(r.max_rows, r.tasks); }
+// workgroups of a grid-stride kernel over n4 float4 of a flat array (per task)
+inline unsigned flat_blocks(long long n4, unsigned max_blocks = 4096) {
+    const long long b = (n4 + 255) / 256;
+    return (unsigned)(b < 1 ? 1 : (b > (long long)max_blocks ? max_blocks : b));
+}
+
 // ------------------------------------------------------------------------------------------
 // encoder input: word embedding (padding row 0) + sinusoid positions (transformer/Models.py:89-91)
 // ------------------------------------------------------------------------------------------
@@ -46,6 +63,10 @@ __global__ void embed_pos_kernel(const int* meta, int mfield, float* out, long l
         if (v) { const float4 x = ld4(e + c), y = ld4(p + c); a = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w); }
         st4(o + c, a);
     }
+}
+inline void launch_embed_pos(const RowLaunch& r, TS out, TS emb, const float* pos, const int* tok, const int* row_t, int C) {
+    MTTS_LAUNCH(embed_pos_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, out.p, out.ts, (const float*)emb.p, emb.ts, pos, tok, row_t,
+                r.mask, r.row_ts, C);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -80,6 +101,7 @@ __device__ __forceinline__ void st4_bf16(bf16_t* p, float4 v) {
 }
 
 inline dim3 row2_grid(int max_rows, int tasks) { return dim3((unsigned)((max_rows + 7) / 8), 1, (unsigned)tasks); }
+inline dim3 row2_grid(const RowLaunch& r) { return row2_grid(r.max_rows, r.tasks); }
 
 // NV = float4 a lane holds per row (1: C <= 256, 4: C <= 1024): a compile-time bound keeps the row in VGPRs (with a runtime
 // trip count the arrays below are indexed dynamically and live in scratch memory)
@@ -158,6 +180,13 @@ __global__ void layernorm_fwd_kernel(const int* meta, int mfield, const float* a
             st[1] = rstd[q];
         }
     }
+}
+// gamma / beta share a stride; the row mask (optional) is r.mask
+inline void launch_layernorm_fwd(const RowLaunch& r, TS a, TS res, TS gamma, TS beta, TS z_out, TS y, TS stats, int C, DropSpec din = DropSpec(),
+                                 DropSpec dout = DropSpec(), bf16_t* yh = nullptr) {
+    MTTS_LAUNCH_LN(layernorm_fwd_kernel, C, row2_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)a.p, a.ts, (const float*)res.p, res.ts,
+                   (const float*)gamma.p, (const float*)beta.p, gamma.ts, r.mask, r.row_ts, z_out.p, z_out.ts, y.p, y.ts, stats.p, stats.ts, C, 1e-5f,
+                   din, dout, yh);
 }
 
 // dz = mask ? rstd * (g - mean(g) - xhat * mean(g * xhat)) : 0, g = dy * gamma
@@ -510,6 +539,29 @@ __global__ void colfinal_kernel(const int* meta, int mfield, int mode, const flo
                                 float* out0, float* out1, long long out_ts, float eps, int accumulate, int rows_per_chunk) {
     colfinal_fold(meta, mfield, mode, partial, max_chunks, C, out0, out1, out_ts, eps, accumulate, blockIdx.x * kCfCols, rows_per_chunk);
 }
+inline void launch_colfinal(const RowLaunch& r, int mode, const float* partial, int max_chunks, int C, float* out0, float* out1, long long out_ts,
+                            int accumulate, int rows_per_chunk) {
+    MTTS_LAUNCH(colfinal_kernel, dim3(colfinal_blocks(C), 1, r.tasks), dim3(256), r.stream, r.meta, r.mfield, mode, partial, max_chunks, C, out0, out1,
+                out_ts, 1e-5f, accumulate, rows_per_chunk);
+}
+// the two-stage column reduction: colpart over kRC-row chunks into `partial` ([tasks][max_chunks][3][C]), colfinal folds them
+inline void launch_colreduce(const RowLaunch& r, const ColArgs& a, float* partial, int max_chunks, float* out0, float* out1, long long out_ts) {
+    MTTS_LAUNCH(colpart_kernel, dim3((a.C + 127) / 128, (r.max_rows + kRC - 1) / kRC, r.tasks), dim3(256), r.stream, r.meta, a, partial, max_chunks);
+    launch_colfinal(r, a.mode, partial, max_chunks, a.C, out0, out1, out_ts, a.accumulate, kRC);
+}
+// LayerNorm backward.  `partial` ([tasks][ln_chunks(r.max_rows)][3][C]) receives the kernel's 8-row gamma / beta partials; fold: launch_ln_fold
+// follows on the same stream (else the caller folds later, from a stream of its choice)
+inline int ln_chunks(int max_rows) { return (max_rows + kLnRows - 1) / kLnRows; }
+inline void launch_ln_fold(const RowLaunch& r, const float* partial, int C, TS dgamma, TS dbeta) {
+    launch_colfinal(r, 1, partial, ln_chunks(r.max_rows), C, dgamma.p, dbeta.p, dgamma.ts, 0, kLnRows);
+}
+inline void launch_layernorm_bwd(const RowLaunch& r, TS dy, TS z, TS stats, TS gamma, TS dz, int C, int relu_on_z, TS dz_drop, DropSpec dd, DropSpec din,
+                                 float* partial, bool fold, TS dgamma, TS dbeta, bf16_t* twin = nullptr, int twin_sel = 0) {
+    MTTS_LAUNCH_LN(layernorm_bwd_kernel, C, row2_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)dy.p, dy.ts, (const float*)z.p, z.ts,
+                   (const float*)stats.p, stats.ts, (const float*)gamma.p, gamma.ts, r.mask, r.row_ts, dz.p, dz.ts, C, relu_on_z, dz_drop.p, dz_drop.ts,
+                   dd, din, partial, ln_chunks(r.max_rows), twin, twin_sel);
+    if (fold) launch_ln_fold(r, partial, C, dgamma, dbeta);
+}
 
 // ------------------------------------------------------------------------------------------
 // attention softmax over per-(task, sequence, head) score matrices (Modules.py:16-22).  Only the
@@ -549,6 +601,10 @@ __global__ void softmax_fwd_kernel(const AttnSeq* seqs, float* S) {
     const float inv = 1.f / s;
     for (int c = lane; c < q.ldS; c += 64) p[c] = (c < q.L) ? p[c] * inv : 0.f;
 }
+// `groups` score matrices of at most L rows
+inline void launch_softmax_fwd(const AttnSeq* seqs, int L, int groups, float* S, hipStream_t st) {
+    MTTS_LAUNCH(softmax_fwd_kernel, dim3((L + 3) / 4, 1, groups), dim3(256), st, seqs, S);
+}
 
 // in place on dP: dS = alpha * P * (dP - sum_j dP_j P_j); pad columns zeroed
 __global__ void softmax_bwd_kernel(const AttnSeq* seqs, const float* P, float* dP, float alpha) {
@@ -577,6 +633,9 @@ __global__ void softmax_bwd_kernel(const AttnSeq* seqs, const float* P, float* d
     s = wave_sum(s);
     for (int c = lane; c < q.ldS; c += 64) d[c] = (c < q.L) ? alpha * p[c] * (d[c] - s) : 0.f;
 }
+inline void launch_softmax_bwd(const AttnSeq* seqs, int L, int groups, const float* P, float* dP, float alpha, hipStream_t st) {
+    MTTS_LAUNCH(softmax_bwd_kernel, dim3((L + 3) / 4, 1, groups), dim3(256), st, seqs, P, dP, alpha);
+}
 
 // ------------------------------------------------------------------------------------------
 // speaker vectors (speaker_encoder.py:62-65; base_adaptor.py:64-70 mean over the support ids)
@@ -602,6 +661,10 @@ __global__ void speaker_vec_kernel(const int* meta, const float* table, long lon
         o[c] = v;
     }
 }
+inline void launch_speaker_vec(const RowLaunch& r, int maxB, TS table, const int* ids, long long ids_ts, int n_ids_max, int average, TS spk, int C) {
+    MTTS_LAUNCH(speaker_vec_kernel, dim3(maxB, 1, r.tasks), dim3(64), r.stream, r.meta, (const float*)table.p, table.ts, ids, ids_ts, n_ids_max, average,
+                spk.p, spk.ts, C);
+}
 
 // out[row] = inrect ? x[row] + vec[row_b[row]] : 0      (fastspeech2.py:65-68)
 __global__ void add_rowvec_kernel(const int* meta, int mfield, const float* x, long long x_ts, const float* vec,
@@ -618,6 +681,10 @@ __global__ void add_rowvec_kernel(const int* meta, int mfield, const float* x, l
         if (in) { const float4 a = ld4(px + c), b = ld4(pv + c); o = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
         st4(po + c, o);
     }
+}
+inline void launch_add_rowvec(const RowLaunch& r, TS x, TS vec, const int* row_b, TS out, int C) {   // r.mask: inrect
+    MTTS_LAUNCH(add_rowvec_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)x.p, x.ts, (const float*)vec.p, vec.ts, row_b, r.mask,
+                r.row_ts, out.p, out.ts, C);
 }
 
 // torch.bucketize(v, bins) (right=False): number of boundaries strictly below v (modules.py:83,94)
@@ -646,6 +713,10 @@ __global__ void bucket_embed_add_kernel(const int* meta, int mfield, const float
         st4(po + c, o);
     }
 }
+inline void launch_bucket_embed_add(const RowLaunch& r, TS x, TS val, float control, const float* bins, int nb, TS table, int* idx_out, TS out, int C) {   // r.mask: inrect
+    MTTS_LAUNCH(bucket_embed_add_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)x.p, x.ts, (const float*)val.p, val.ts, control,
+                bins, nb, (const float*)table.p, table.ts, r.mask, r.row_ts, idx_out, out.p, out.ts, C);
+}
 
 // out[row] = valid ? dot(x[row], w) + b : 0       (modules.py:244-248 linear_layer + masked_fill)
 __global__ void rowdot_kernel(const int* meta, int mfield, const float* x, long long x_ts, const float* w,
@@ -662,6 +733,10 @@ __global__ void rowdot_kernel(const int* meta, int mfield, const float* x, long 
     s = wave_sum(s);
     if (lane == 0) out[(long long)z * out_ts + row] = valid[(long long)z * row_ts + row] ? s + b[(long long)z * par_ts] : 0.f;
 }
+inline void launch_rowdot(const RowLaunch& r, TS x, TS w, TS b, TS out, int C) {   // r.mask: valid; w / b share a stride
+    MTTS_LAUNCH(rowdot_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)x.p, x.ts, (const float*)w.p, (const float*)b.p, w.ts, r.mask,
+                r.row_ts, out.p, out.ts, C);
+}
 
 // dx[row] = dout[row] * w
 __global__ void rowdot_bwd_kernel(const int* meta, int mfield, const float* dout, long long dout_ts, const float* w,
@@ -674,6 +749,9 @@ __global__ void rowdot_bwd_kernel(const int* meta, int mfield, const float* dout
         const float4 ww = ld4(pw + c);
         st4(pd + c, make_float4(d * ww.x, d * ww.y, d * ww.z, d * ww.w));
     }
+}
+inline void launch_rowdot_bwd(const RowLaunch& r, TS dout, TS w, TS dx, int C) {
+    MTTS_LAUNCH(rowdot_bwd_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)dout.p, dout.ts, (const float*)w.p, w.ts, dx.p, dx.ts, C);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -697,6 +775,11 @@ __global__ void length_regulate_fwd_kernel(const int* meta, const float* x, long
         st4(po + c, make_float4(a.x + b.x + d.x, a.y + b.y + d.y, a.z + b.z + d.z, a.w + b.w + d.w));
     }
 }
+// r: the packed frame space; src / row_b / row_t: per-frame arrays of stride r.row_ts; pos may be null
+inline void launch_length_regulate_fwd(const RowLaunch& r, TS x, const int* src, const int* row_b, const int* row_t, TS spk, const float* pos, TS out, int C) {
+    MTTS_LAUNCH(length_regulate_fwd_kernel, row_grid(r), dim3(256), r.stream, r.meta, (const float*)x.p, x.ts, src, row_b, row_t, r.row_ts, (const float*)spk.p,
+                spk.ts, pos, out.p, out.ts, C);
+}
 
 // frame-level features: the length regulator's output on the zero-padded frame RECTANGLE (modules.py:128-137 + pad), before the
 // frame-level pitch / energy predictors: out[rr] = x[f_src[r2f[rr]]] on valid frames, 0 elsewhere
@@ -708,6 +791,10 @@ __global__ void length_regulate_rect_kernel(const int* meta, const float* x, lon
     float* po = out + (long long)z * out_ts + (long long)row * C;
     const float* px = s >= 0 ? x + (long long)z * x_ts + (long long)s * C : nullptr;
     for (int c = lane * 4; c < C; c += 256) st4(po + c, px ? ld4(px + c) : zero4());
+}
+// r: the frame rectangle (r2f has stride r.row_ts); f_src: per packed frame, stride f_ts
+inline void launch_length_regulate_rect(const RowLaunch& r, TS x, const int* f_src, long long f_ts, const int* r2f, TS out, int C) {
+    MTTS_LAUNCH(length_regulate_rect_kernel, row_grid(r), dim3(256), r.stream, r.meta, (const float*)x.p, x.ts, f_src, f_ts, r2f, r.row_ts, out.p, out.ts, C);
 }
 
 // dx[p] (+)= sum_{r in [first[p], first[p]+count[p])} dout[r]   (rows of the phoneme space)
@@ -727,6 +814,11 @@ __global__ void length_regulate_bwd_kernel(const int* meta, const float* dout, l
         }
         st4(po + c, s);
     }
+}
+// r: the phoneme space (first / count have stride r.row_ts)
+inline void launch_length_regulate_bwd(const RowLaunch& r, TS dout, const int* first, const int* count, TS dx, int C, int accumulate) {
+    MTTS_LAUNCH(length_regulate_bwd_kernel, row_grid(r), dim3(256), r.stream, r.meta, (const float*)dout.p, dout.ts, first, count, r.row_ts, dx.p, dx.ts, C,
+                accumulate);
 }
 
 // out[b][c] (+)= sum over rows [start[b], start[b]+len[b]) of X   (speaker-vector gradient)
@@ -754,6 +846,10 @@ __global__ void segsum_rows_kernel(const int* meta, const float* X, long long x_
     float s = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
     if (accumulate) s += out[(long long)z * out_ts + (long long)b * C + c];
     out[(long long)z * out_ts + (long long)b * C + c] = s;
+}
+inline void launch_segsum_rows(const RowLaunch& r, int maxB, TS X, const int* start, const int* len, long long seg_ts, TS out, int C, int accumulate) {
+    MTTS_LAUNCH(segsum_rows_kernel, dim3((C + 63) / 64, maxB, r.tasks), dim3(256), r.stream, r.meta, (const float*)X.p, X.ts, start, len, seg_ts, out.p, out.ts,
+                C, accumulate);
 }
 
 // Deterministic embedding-table gradient: one workgroup per table row scans the index list in
@@ -822,6 +918,11 @@ __global__ void table_grad_kernel(const int* meta, int mfield, const float* dx, 
 #pragma unroll
     for (int k = 0; k < 16; ++k) { const int c = lane + 64 * k; if (c < C) po[c] = s[k]; }
 }
+// one workgroup of four wavefronts per table row; idx has stride r.row_ts
+inline void launch_table_grad(const RowLaunch& r, int n_rows, TS dx, const int* idx, int skip_row, TS dtable, int C) {
+    MTTS_LAUNCH(table_grad_kernel, dim3(n_rows, 1, r.tasks), dim3(256), r.stream, r.meta, r.mfield, (const float*)dx.p, dx.ts, idx, r.row_ts, skip_row, dtable.p,
+                dtable.ts, C);
+}
 
 // speaker table gradient from per-utterance vector grads (table path; averaged path divides by
 // the number of support ids and gives every support id the summed gradient)
@@ -849,6 +950,10 @@ __global__ void speaker_table_grad_kernel(const int* meta, const float* dspk, lo
         }
         po[c] = s;
     }
+}
+inline void launch_speaker_table_grad(const RowLaunch& r, int n_speaker, TS dspk, const int* ids, long long ids_ts, int n_ids_max, int average, TS dtable, int C) {
+    MTTS_LAUNCH(speaker_table_grad_kernel, dim3(n_speaker, 1, r.tasks), dim3(64), r.stream, r.meta, (const float*)dspk.p, dspk.ts, ids, ids_ts, n_ids_max,
+                average, dtable.p, dtable.ts, C);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -923,6 +1028,11 @@ __global__ void bn_apply_kernel(const int* meta, const float* X, long long x_ts,
         if (Yh) st4_bf16(Yh + (long long)z * y_ts + (long long)row * C + c, o);
     }
 }
+// r: the frame rectangle, r.mask: inrect; gamma / beta share a stride
+inline void launch_bn_apply(const RowLaunch& r, TS X, TS stats, TS gamma, TS beta, int do_tanh, TS Y, int C, DropSpec dout = DropSpec(), bf16_t* Yh = nullptr) {
+    MTTS_LAUNCH(bn_apply_kernel, row_grid(r), dim3(256), r.stream, r.meta, (const float*)X.p, X.ts, (const float*)stats.p, stats.ts, (const float*)gamma.p,
+                (const float*)beta.p, gamma.ts, r.mask, r.row_ts, do_tanh, Y.p, Y.ts, C, dout, Yh);
+}
 
 // backward pass 2: dx = gamma * rstd * (dpre - dbeta/n - xhat * dgamma/n) on in-rect rows
 __global__ void bn_bwd_apply_kernel(const int* meta, const float* dY, long long dy_ts, const float* Yact,
@@ -969,6 +1079,13 @@ __global__ void bn_bwd_apply_kernel(const int* meta, const float* dY, long long 
         if (pdh) st4_bf16(pdh + c, make_float4(o[0], o[1], o[2], o[3]));
     }
 }
+// dgamma / dbeta share a stride
+inline void launch_bn_bwd_apply(const RowLaunch& r, TS dY, TS Yact, TS X, TS stats, TS gamma, TS dgamma, TS dbeta, int do_tanh, TS dX, int C, float yscale = 1.f,
+                                DropSpec din = DropSpec(), bf16_t* dXh = nullptr) {
+    MTTS_LAUNCH(bn_bwd_apply_kernel, row_grid(r), dim3(256), r.stream, r.meta, (const float*)dY.p, dY.ts, (const float*)Yact.p, Yact.ts, (const float*)X.p, X.ts,
+                (const float*)stats.p, stats.ts, (const float*)gamma.p, gamma.ts, (const float*)dgamma.p, (const float*)dbeta.p, dgamma.ts, r.mask, r.row_ts,
+                do_tanh, dX.p, dX.ts, C, yscale, din, dXh);
+}
 
 // mel rectangle: padded in-rect rows carry mel_linear.bias (decoder output is zero there);
 // guard rows are re-zeroed (the previous batch plan may have had frames there)
@@ -982,6 +1099,10 @@ __global__ void fill_padded_rows_kernel(const int* meta, float* X, long long x_t
     const float* b = bias + (long long)z * par_ts;
     for (int c = lane * 4; c < C; c += 256) st4(px + c, in ? ld4(b + c) : zero4());
 }
+// r: the frame rectangle, r.mask: inrect
+inline void launch_fill_padded_rows(const RowLaunch& r, TS X, TS bias, const unsigned char* valid, int C) {
+    MTTS_LAUNCH(fill_padded_rows_kernel, row_grid(r), dim3(256), r.stream, r.meta, X.p, X.ts, (const float*)bias.p, bias.ts, r.mask, valid, r.row_ts, C);
+}
 
 // out[r] = rowmap[r] >= 0 ? src[rowmap[r]] : 0   (row gather between row spaces)
 __global__ void gather_rows_kernel(const int* meta, int mfield, const float* src, long long src_ts, const int* rowmap,
@@ -991,6 +1112,10 @@ __global__ void gather_rows_kernel(const int* meta, int mfield, const float* src
     float* po = out + (long long)z * out_ts + (long long)row * C;
     const float* ps = src + (long long)z * src_ts + (long long)(s < 0 ? 0 : s) * C;
     for (int c = lane * 4; c < C; c += 256) st4(po + c, s < 0 ? zero4() : ld4(ps + c));
+}
+// r: the space of `out`; rowmap has stride r.row_ts
+inline void launch_gather_rows(const RowLaunch& r, TS src, const int* rowmap, TS out, int C) {
+    MTTS_LAUNCH(gather_rows_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)src.p, src.ts, rowmap, r.row_ts, out.p, out.ts, C);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1022,6 +1147,9 @@ __global__ void add2_kernel(const float* a, const float* b, float* out, long lon
         st4(out + i * 4, make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w));
     }
 }
+inline void launch_add2(const float* a, const float* b, float* out, long long n4, hipStream_t st) {
+    MTTS_LAUNCH(add2_kernel, dim3(flat_blocks(n4, 2048)), dim3(256), st, a, b, out, n4);
+}
 
 // out = (a + b) + c, in that order (the order in which three accumulating GEMM epilogues would have added them)
 __global__ void add3_kernel(const float* a, const float* b, const float* c, float* out, long long n4) {
@@ -1043,6 +1171,9 @@ __global__ void to_bf16_kernel(const float* src, bf16_t* dst, long long n8) {
         o.v[4] = f32_to_bf16(b.x); o.v[5] = f32_to_bf16(b.y); o.v[6] = f32_to_bf16(b.z); o.v[7] = f32_to_bf16(b.w);
         *reinterpret_cast<decltype(o)*>(dst + i * 8) = o;
     }
+}
+inline void launch_to_bf16(const float* src, bf16_t* dst, long long n8, hipStream_t st) {
+    MTTS_LAUNCH(to_bf16_kernel, dim3(flat_blocks(n8)), dim3(256), st, src, dst, n8);
 }
 
 // The bf16 shadows of the Conv1d / Linear weights, refreshed once per pass from the fp32 masters: `fwd` keeps the [Cout][k][Cin] layout
@@ -1086,6 +1217,9 @@ __global__ void broadcast_kernel(const float* src, float* dst, long long n4, lon
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x)
         st4(d + i * 4, ld4(src + i * 4));
 }
+inline void launch_broadcast(const float* src, TS dst, long long n4, int tasks, hipStream_t st) {
+    MTTS_LAUNCH(broadcast_kernel, dim3(flat_blocks(n4), 1, tasks), dim3(256), st, src, dst.p, n4, dst.ts);
+}
 
 // MAML inner update  theta' = theta - lr * g   (learn2learn maml_update via systems/utils.py:39-47)
 __global__ void sgd_update_kernel(float* w, const float* g, long long n4, float lr, long long w_ts, long long g_ts) {
@@ -1097,6 +1231,9 @@ __global__ void sgd_update_kernel(float* w, const float* g, long long n4, float 
         x.x -= lr * d.x; x.y -= lr * d.y; x.z -= lr * d.z; x.w -= lr * d.w;
         st4(pw + i * 4, x);
     }
+}
+inline void launch_sgd_update(TS w, TS g, long long n4, float lr, int tasks, hipStream_t st) {
+    MTTS_LAUNCH(sgd_update_kernel, dim3(flat_blocks(n4), 1, tasks), dim3(256), st, w.p, (const float*)g.p, n4, lr, w.ts, g.ts);
 }
 
 // out[i] (+)= scale * sum_t g[t][i]   (fixed task order; accumulate: gradient accumulation over several batches, main.py:62)
@@ -1111,6 +1248,9 @@ __global__ void sum_tasks_kernel(const float* g, long long g_ts, int tasks, floa
         if (accumulate) { const float4 p = ld4(out + i * 4); o = make_float4(o.x + p.x, o.y + p.y, o.z + p.z, o.w + p.w); }
         st4(out + i * 4, o);
     }
+}
+inline void launch_sum_tasks(TS g, int tasks, float scale, float* out, long long n4, int accumulate, hipStream_t st) {
+    MTTS_LAUNCH(sum_tasks_kernel, dim3(flat_blocks(n4)), dim3(256), st, (const float*)g.p, g.ts, tasks, scale, out, n4, accumulate);
 }
 
 // The exchange step's tail (engine.h: sync_pack / sync_unpack): what DDP moves between ranks besides the gradient — the 6 loss scalars
@@ -1152,6 +1292,9 @@ __global__ void sumsq_partial_kernel(const float* g, long long n4, float* partia
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
+inline void launch_sumsq_partial(const float* g, long long n4, float* partial, int n_partials, hipStream_t st) {   // one partial per workgroup
+    MTTS_LAUNCH(sumsq_partial_kernel, dim3(n_partials), dim3(256), st, g, n4, partial);
+}
 
 // extra (optional): a device scalar holding the squared gradient norm of parameters that live outside this buffer (a co-trained
 // speaker encoder) — clip_grad_norm_ takes the norm over ALL parameters of the model (main.py:61)
@@ -1185,6 +1328,10 @@ __global__ void adam_clip_kernel(float* w, const float* g, float* m, float* v, l
         st4(m + i * 4, make_float4(ms[0], ms[1], ms[2], ms[3]));
         st4(v + i * 4, make_float4(vs[0], vs[1], vs[2], vs[3]));
     }
+}
+inline void launch_adam_clip(float* w, const float* g, float* m, float* v, long long n4, const float* norm, float max_norm, float lr, float b1, float b2,
+                             float eps, float bc1, float bc2, float weight_decay, hipStream_t st, unsigned max_blocks = 4096) {
+    MTTS_LAUNCH(adam_clip_kernel, dim3(flat_blocks(n4, max_blocks)), dim3(256), st, w, g, m, v, n4, norm, max_norm, lr, b1, b2, eps, bc1, bc2, weight_decay);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1313,6 +1460,10 @@ __global__ void loss_grad_kernel(const int* meta, LossArgs a, float scale, float
             if (a.energy_frame) dep_r[q] = rv[r] ? wR * (a.ep_r[q] - a.e_tgt_r[qt]) : 0.f;
         }
     }
+}
+inline void launch_loss_grad(const int* meta, int tasks, const LossArgs& a, float scale, float* dmel, float* dpost, float* dpp, float* dep, float* dlogd,
+                             float* dpp_r, float* dep_r, hipStream_t st) {
+    MTTS_LAUNCH(loss_grad_kernel, dim3(kLossBlocks, 1, tasks), dim3(256), st, meta, a, scale, dmel, dpost, dpp, dep, dlogd, dpp_r, dep_r);
 }
 
 // free-running durations (modules.py:132-136): clamp(round(exp(logd) - 1) * d_control, min 0)

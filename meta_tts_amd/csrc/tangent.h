@@ -80,6 +80,13 @@ __global__ void ln_jvp_fwd_kernel(const int* meta, int mfield, const float* ta, 
         ts[1] = m2;
     }
 }
+// tgamma / tbeta (either may be null) share a stride
+inline void launch_ln_jvp_fwd(const RowLaunch& r, TS ta, TS tres, TS z, TS stats, TS gamma, TS tgamma, TS tbeta, TS tz_out, TS ty, TS tstats, int C,
+                              DropSpec din = DropSpec(), DropSpec dout = DropSpec()) {
+    MTTS_LAUNCH_LN(ln_jvp_fwd_kernel, C, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)ta.p, ta.ts, (const float*)tres.p, tres.ts,
+                   (const float*)z.p, z.ts, (const float*)stats.p, stats.ts, (const float*)gamma.p, gamma.ts, (const float*)tgamma.p, (const float*)tbeta.p,
+                   tgamma.ts, r.mask, r.row_ts, tz_out.p, tz_out.ts, ty.p, ty.ts, tstats.p, tstats.ts, C, din, dout);
+}
 
 // backward, primal + tangent in one pass:
 //   g = dy*gamma, a1 = mean(g), a2 = mean(g xhat):          dz    = r (g - a1 - xhat a2)
@@ -198,6 +205,23 @@ __global__ __launch_bounds__(256) void ln_jvp_bwd_kernel(const int* meta, int mf
         out[(long long)k * C + c] = (red[0][k][c] + red[1][k][c]) + (red[2][k][c] + red[3][k][c]);
     }
 }
+// hv(gamma) / hv(beta) by one of two routes.  own_partials: the kernel's 8-row partials in `partial` ([tasks][ln_chunks][3][C]) + one colfinal launch;
+// else the ColArgs mode-5 reduction (`partial`: [tasks][max_chunks][3][C] of kRC-row chunks) in front of a kernel launch without partials
+inline void launch_ln_jvp_bwd(const RowLaunch& r, TS dy, TS tgy, TS z, TS stats, TS tz, TS tstats, TS gamma, TS tgamma, TS dz, TS tgz, int C, int relu_on_z,
+                              TS dz_drop, TS tgz_drop, DropSpec dd, DropSpec din, float* partial, bool own_partials, int max_chunks, TS hgamma, TS hbeta) {
+    if (!own_partials) {
+        ColArgs a;
+        a.X = tgy.p; a.x_ts = tgy.ts; a.X2 = dy.p; a.x2_ts = dy.ts; a.Z = z.p; a.z_ts = z.ts; a.stats = stats.p; a.st_ts = stats.ts;
+        a.Z2 = tz.p; a.z2_ts = tz.ts; a.stats2 = tstats.p; a.st2_ts = tstats.ts; a.mask = r.mask; a.mask_ts = r.row_ts;
+        a.xdrop = din; a.C = C; a.mode = 5; a.mfield = r.mfield;
+        launch_colreduce(r, a, partial, max_chunks, hgamma.p, hbeta.p, hgamma.ts);
+    }
+    MTTS_LAUNCH_LN(ln_jvp_bwd_kernel, C, row2_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)dy.p, dy.ts, (const float*)tgy.p, tgy.ts,
+                   (const float*)z.p, z.ts, (const float*)stats.p, stats.ts, (const float*)tz.p, tz.ts, (const float*)tstats.p, tstats.ts, (const float*)gamma.p,
+                   gamma.ts, (const float*)tgamma.p, tgamma.ts, r.mask, r.row_ts, dz.p, dz.ts, tgz.p, tgz.ts, C, relu_on_z, dz_drop.p, dz_drop.ts, tgz_drop.p,
+                   tgz_drop.ts, dd, din, own_partials ? partial : (float*)nullptr, ln_chunks(r.max_rows));
+    if (own_partials) launch_ln_fold(r, partial, C, hgamma, hbeta);
+}
 
 // ---- softmax ----------------------------------------------------------------------------------
 // in place on tS: tP = P (tS - sum_j P_j tS_j)
@@ -211,6 +235,9 @@ __global__ void softmax_jvp_fwd_kernel(const AttnSeq* seqs, const float* P, floa
     for (int c = lane; c < q.L; c += 64) s += p[c] * t[c];
     s = wave_sum(s);
     for (int c = lane; c < q.ldS; c += 64) t[c] = (c < q.L) ? p[c] * (t[c] - s) : 0.f;
+}
+inline void launch_softmax_jvp_fwd(const AttnSeq* seqs, int L, int groups, const float* P, float* tS, hipStream_t st) {
+    MTTS_LAUNCH(softmax_jvp_fwd_kernel, dim3((L + 3) / 4, 1, groups), dim3(256), st, seqs, P, tS);
 }
 
 // in place: dP -> dS = alpha P (dP - c), tgP -> tg_S = alpha [tP (dP - c) + P (tgP - cdot)],
@@ -237,6 +264,9 @@ __global__ void softmax_jvp_bwd_kernel(const AttnSeq* seqs, const float* P, cons
         d[c] = o0;
         tg[c] = o1;
     }
+}
+inline void launch_softmax_jvp_bwd(const AttnSeq* seqs, int L, int groups, const float* P, const float* tP, float* dP, float* tgP, float alpha, hipStream_t st) {
+    MTTS_LAUNCH(softmax_jvp_bwd_kernel, dim3((L + 3) / 4, 1, groups), dim3(256), st, seqs, P, tP, dP, tgP, alpha);
 }
 
 // ---- BatchNorm (+tanh) ------------------------------------------------------------------------
@@ -282,6 +312,13 @@ __global__ void bn_jvp_apply_kernel(const int* meta, const float* X, long long x
         if (dout.thr16) o4 = drop4(dout, z, row, C, c, o4);
         st4(po + c, o4);
     }
+}
+// tsum = [S1 | S0] ([2C] per task); tgamma / tbeta (either may be null) share a stride; r.mask: inrect
+inline void launch_bn_jvp_apply(const RowLaunch& r, TS X, TS tX, TS stats, TS tsum, TS gamma, TS tgamma, TS tbeta, TS A, int do_tanh, TS tA, int C,
+                                float yscale = 1.f, DropSpec dout = DropSpec()) {
+    MTTS_LAUNCH(bn_jvp_apply_kernel, row_grid(r), dim3(256), r.stream, r.meta, (const float*)X.p, X.ts, (const float*)tX.p, tX.ts, (const float*)stats.p, stats.ts,
+                (const float*)tsum.p, (const float*)(tsum.p + C), tsum.ts, (const float*)gamma.p, gamma.ts, (const float*)tgamma.p, (const float*)tbeta.p,
+                tgamma.ts, (const float*)A.p, A.ts, r.mask, r.row_ts, do_tanh, tA.p, tA.ts, C, yscale, dout);
 }
 
 // backward, primal + tangent.  Per channel inputs: primal sums dgamma = sum g xhat, dbeta = sum g
@@ -343,6 +380,15 @@ __global__ void bn_jvp_bwd_kernel(const int* meta, const float* dY, long long dy
         st4(ptd + c, f4(o1[0], o1[1], o1[2], o1[3]));
     }
 }
+// tsum = [S1 | S0]; dgamma / dbeta and tA0 / tA1 (= hv(gamma), hv(beta)) each share a stride
+inline void launch_bn_jvp_bwd(const RowLaunch& r, TS dY, TS tgY, TS A, TS tA, TS X, TS tX, TS stats, TS tsum, TS gamma, TS tgamma, TS dgamma, TS dbeta, TS tA0,
+                              TS tA1, int do_tanh, TS dX, TS tdX, int C, float yscale = 1.f, DropSpec din = DropSpec()) {
+    MTTS_LAUNCH(bn_jvp_bwd_kernel, row_grid(r), dim3(256), r.stream, r.meta, (const float*)dY.p, dY.ts, (const float*)tgY.p, tgY.ts, (const float*)A.p, A.ts,
+                (const float*)tA.p, tA.ts, (const float*)X.p, X.ts, (const float*)tX.p, tX.ts, (const float*)stats.p, stats.ts, (const float*)tsum.p,
+                (const float*)(tsum.p + C), tsum.ts, (const float*)gamma.p, gamma.ts, (const float*)tgamma.p, tgamma.ts, (const float*)dgamma.p,
+                (const float*)dbeta.p, dgamma.ts, (const float*)tA0.p, (const float*)tA1.p, tA0.ts, r.mask, r.row_ts, do_tanh, dX.p, dX.ts, tdX.p, tdX.ts, C,
+                yscale, din);
+}
 
 // ---- 256 -> 1 projection ------------------------------------------------------------------------
 // tout[row] = valid ? dot(tx, w) + dot(x, tw) + tb : 0
@@ -366,6 +412,11 @@ __global__ void rowdot_jvp_kernel(const int* meta, int mfield, const float* x, l
         tout[(long long)z * out_ts + row] = valid[(long long)z * row_ts + row] ? s + b : 0.f;
     }
 }
+// tw / tb (either may be null) share a stride; r.mask: valid
+inline void launch_rowdot_jvp(const RowLaunch& r, TS x, TS tx, TS w, TS tw, TS tb, TS tout, int C) {
+    MTTS_LAUNCH(rowdot_jvp_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)x.p, x.ts, (const float*)tx.p, tx.ts, (const float*)w.p, w.ts,
+                (const float*)tw.p, (const float*)tb.p, tw.ts, r.mask, r.row_ts, tout.p, tout.ts, C);
+}
 
 // dx = dout w (primal) ; tdx = tgout w + dout tw
 __global__ void rowdot_jvp_bwd_kernel(const int* meta, int mfield, const float* dout, const float* tgout, long long dout_ts,
@@ -383,6 +434,11 @@ __global__ void rowdot_jvp_bwd_kernel(const int* meta, int mfield, const float* 
         st4(pd + c, f4(d * ww.x, d * ww.y, d * ww.z, d * ww.w));
         st4(pt + c, f4(td * ww.x + d * t.x, td * ww.y + d * t.y, td * ww.z + d * t.z, td * ww.w + d * t.w));
     }
+}
+// dout / tgout share a stride
+inline void launch_rowdot_jvp_bwd(const RowLaunch& r, TS dout, TS tgout, TS w, TS tw, TS dx, TS tdx, int C) {
+    MTTS_LAUNCH(rowdot_jvp_bwd_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)dout.p, (const float*)tgout.p, dout.ts, (const float*)w.p,
+                w.ts, (const float*)tw.p, tw.ts, dx.p, dx.ts, tdx.p, tdx.ts, C);
 }
 
 // ---- loss: tangent of the prediction gradients (MSE terms; the L1 terms have zero second derivative) ----
@@ -425,6 +481,9 @@ __global__ void axpy_kernel(float* dst, long long dst_ts, const float* src, long
         st4(d + i * 4, x);
     }
 }
+inline void launch_axpy(TS dst, TS src, float alpha, long long n4, int tasks, hipStream_t st) {
+    MTTS_LAUNCH(axpy_kernel, dim3(flat_blocks(n4), 1, tasks), dim3(256), st, dst.p, dst.ts, (const float*)src.p, src.ts, alpha, n4);
+}
 
 // out[row] = (x ? x[row] : 0) + (table && idx[row] >= 0 ? table[idx[row]] : 0)   (tangent of x + emb[bucket])
 __global__ void embed_add_idx_kernel(const int* meta, int mfield, const float* x, long long x_ts, const float* table,
@@ -440,6 +499,11 @@ __global__ void embed_add_idx_kernel(const int* meta, int mfield, const float* x
         st4(po + c, o);
     }
 }
+// x / table may be null; idx has stride r.row_ts
+inline void launch_embed_add_idx(const RowLaunch& r, TS x, TS table, const int* idx, TS out, int C) {
+    MTTS_LAUNCH(embed_add_idx_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)x.p, x.ts, (const float*)table.p, table.ts, idx, r.row_ts,
+                out.p, out.ts, C);
+}
 
 // out[row] = inrect ? vec[row_b[row]] : 0   (tangent of enc_out + spk: the encoder carries no tangent)
 __global__ void bcast_rowvec_kernel(const int* meta, int mfield, const float* vec, long long vec_ts, const int* row_b,
@@ -451,8 +515,12 @@ __global__ void bcast_rowvec_kernel(const int* meta, int mfield, const float* ve
     float* po = out + (long long)z * out_ts + (long long)row * C;
     for (int c = lane * 4; c < C; c += 256) st4(po + c, in ? ld4(pv + c) : zero4());
 }
+inline void launch_bcast_rowvec(const RowLaunch& r, TS vec, const int* row_b, TS out, int C) {   // r.mask: inrect
+    MTTS_LAUNCH(bcast_rowvec_kernel, row_grid(r), dim3(256), r.stream, r.meta, r.mfield, (const float*)vec.p, vec.ts, row_b, r.mask, r.row_ts, out.p, out.ts, C);
+}
 
 // row-space copy: out[r] = in[r] for r < M (all channels)
+// (no launch site: nothing copies a row space at present)
 __global__ void copy_rows_kernel(const int* meta, int mfield, const float* in, long long in_ts, float* out, long long out_ts, int C) {
     ROW_PROLOGUE(mfield)
     const float* pi = in + (long long)z * in_ts + (long long)row * C;
@@ -479,6 +547,9 @@ __global__ void copy_tasks_kernel(const float* src, long long src_ts, float* dst
     const float* s = src + (long long)blockIdx.z * src_ts;
     float* d = dst + (long long)blockIdx.z * dst_ts;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) st4(d + i * 4, ld4(s + i * 4));
+}
+inline void launch_copy_tasks(TS src, TS dst, long long n4, int tasks, hipStream_t st, unsigned max_blocks = 1024) {
+    MTTS_LAUNCH(copy_tasks_kernel, dim3(flat_blocks(n4, max_blocks), 1, tasks), dim3(256), st, (const float*)src.p, src.ts, dst.p, dst.ts, n4);
 }
 // partial[task][block] = sum over this block's elements of a * (ca * b + cb * a)
 __global__ void dot_partial_kernel(const float* a, long long a_ts, const float* b, long long b_ts, float ca, float cb, long long n4, float* partial,
@@ -514,6 +585,9 @@ __global__ void cg_scalar_kernel(float* scal, int tasks, int mode, float tol) {
     if (sqrtf(s[4]) < tol) { s[5] = 0.f; s[3] = 0.f; return; }
     s[3] = s[4] / s[0];
     s[0] = s[4];
+}
+inline void launch_cg_scalar(float* scal, int tasks, int mode, float tol, hipStream_t st) {
+    MTTS_LAUNCH(cg_scalar_kernel, dim3(1), dim3(64), st, scal, tasks, mode, tol);
 }
 // r -= alpha * (ca * Hp + cb * p)
 __global__ void cg_update_r_kernel(float* r, long long r_ts, const float* p, const float* Hp, long long p_ts, float ca, float cb,

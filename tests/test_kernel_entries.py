@@ -57,7 +57,8 @@ def dev(request):
 
 
 @pytest.mark.parametrize("rows,Cc,with_res,with_mask", [(37, 256, True, True), (8, 32, False, False), (203, 1024, True, False), (5, 48, False, True),
-                                                        (419, 32, True, True)])   # 53 partial chunks: the four-deep loop of colfinal_fold
+                                                        (419, 32, True, True),    # 53 partial chunks: the four-deep loop of colfinal_fold
+                                                        (1, 48, False, True), (9, 32, True, True)])   # one row; one row past an 8-row workgroup (a partial last chunk of the fold)
 def test_layernorm_fwd_bwd(dev, rows, Cc, with_res, with_mask):
     g = np.random.RandomState(rows + Cc)
     a, res = g.standard_normal((rows, Cc)).astype(np.float32), g.standard_normal((rows, Cc)).astype(np.float32)
@@ -163,7 +164,7 @@ def test_batchnorm_fwd_bwd_over_padded_rectangle(dev, B, T, Cc, do_tanh):
     np.testing.assert_allclose(dev.get(dbt), tb.grad.numpy(), rtol=1e-4, atol=2e-5)
 
 
-@pytest.mark.parametrize("rows,Cc,V,skip", [(150, 32, 20, 0), (300, 256, 361, 0), (64, 16, 7, -1)])
+@pytest.mark.parametrize("rows,Cc,V,skip", [(150, 32, 20, 0), (300, 256, 361, 0), (64, 16, 7, -1), (9, 32, 20, 0)])
 def test_table_grad_matches_embedding_backward(dev, rows, Cc, V, skip):
     g = np.random.RandomState(rows + V)
     idx = g.randint(0, V, rows).astype(np.int32)
@@ -187,7 +188,7 @@ def test_bad_arguments_are_rejected(dev):
     assert dev.lib.mtts_kernel_ws_bytes(100, 4) > dev.lib.mtts_kernel_ws_bytes(10, 0) > 0
 
 
-@pytest.mark.parametrize("S,Cc,with_extras", [(13, 256, True), (40, 32, False)])
+@pytest.mark.parametrize("S,Cc,with_extras", [(13, 256, True), (40, 32, False), (9, 32, True)])   # 9 phonemes: one row past two 4-row workgroups of the backward
 def test_length_regulate_fwd_bwd(dev, S, Cc, with_extras):
     """modules.py:167-190: expand every phoneme row by its duration (zero durations drop the phoneme), and the transpose."""
     g = np.random.RandomState(S + Cc)

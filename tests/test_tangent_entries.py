@@ -42,6 +42,8 @@ LN_CASES = [  # rows, C, mask, tgamma (and tbeta), relu_on_z, two_launch
     (19, 260, 1, 1, 1, 0), (19, 260, 0, 0, 0, 1),
     (11, 1024, 0, 1, 1, 1), (11, 1024, 1, 0, 0, 0),
     (419, 32, 1, 1, 0, 0), (419, 32, 1, 1, 1, 1), (419, 32, 0, 0, 0, 1),
+    (1, 48, 1, 1, 0, 0), (1, 48, 0, 0, 1, 1), (1, 48, 0, 1, 0, 0),   # one row: masked, live on the two-launch route, live on the kernel's own partials
+    (9, 32, 1, 1, 1, 0), (9, 32, 0, 0, 0, 1),          # one row past an 8-row workgroup: a partial last chunk of the fold
 ]
 
 
@@ -52,7 +54,7 @@ def _ln_case(rows, Cc, with_mask, with_tg, relu):
     i = dict(a=_randn(g, rows, Cc) + off[:, None], ta=_randn(g, rows, Cc), tres=_randn(g, rows, Cc),
              gamma=(1 + 0.1 * g.standard_normal(Cc)).astype(F32), beta=(0.1 * g.standard_normal(Cc)).astype(F32),
              tgamma=_randn(g, Cc), tbeta=_randn(g, Cc), mask=(g.rand(rows) > 0.3).astype(np.uint8), dy=_randn(g, rows, Cc), tgy=_randn(g, rows, Cc))
-    i["mask"][1] = 0
+    i["mask"][min(1, rows - 1)] = 0   # one masked row for sure (rows = 1: the only row, when the case uses the mask)
     i["tz"] = i["ta"] + i["tres"]   # float32 sum: what the kernel stores (asserted bit-exact) and differentiates along
     args = (i["a"], i["tz"], i["gamma"], i["beta"], i["tgamma"] if with_tg else None, i["tbeta"] if with_tg else None,
             i["mask"] if with_mask else None, i["dy"], i["tgy"], relu)
