@@ -503,7 +503,8 @@ int mtts_stft_normalize(mtts_stft* h, int64_t n, const void* values, int dtype, 
  * preprocess_wav(path))` one wav at a time on the CPU; pair_similarity.py:68-88, centroid_similarity.py:47-118: cosine similarity;
  * wavs_to_dvector.py:176-183: centroids) and `spk_ref_mel_slices` of preprocessor/preprocessor.py:263-299.  resemblyzer is un-vendored:
  * its front-end is restated from the published recipe.  Of its `preprocess_wav`, resampling and -30 dBFS normalisation are the next
- * section's (opt-in); webrtcvad trimming is NOT built.  In THESE entries waveforms are 16 kHz float32 as they are.
+ * section's and silence trimming the one after (both opt-in; the detector there is this project's own: parity with webrtcvad is
+ * UNPINNED).  In THESE entries waveforms are 16 kHz float32 as they are.
  * power_mel_batch: resemblyzer's `wav_to_mel_spectrogram` of n_utts waveforms packed in `wavs` as they are: mel [sum T][n_mel], T_u =
  * n_samples[u] / hop_length + 1, = mel_basis @ (re^2 + im^2) of the centred, reflect-padded frames (power; no clip, no log, no clamp).
  * An utterance's rows are bit-identical whatever else is in the call.  Errors (before any launch): n_samples[u] <= filter_length / 2.
@@ -542,7 +543,7 @@ int mtts_dvector_centroids(mtts_dvector* h, const float* vectors, const int* off
  * Neither library is vendored; parity with them is UNPINNED.  What is computed, exactly: with up / down = target_sr / orig_sr reduced,
  *   y[n] = sum_m h[n * down - m * up] x[m]   over |n * down - m * up| <= H, 0 <= m < n_in,   n_out = ceil(n_in * up / down),
  * for a filter h[-H .. H] on the grid of the up-sampled rate (designed by the caller in float64: meta_tts_amd/audio/resample.py builds
- * the Kaiser-windowed sinc, sum(h) = up, and equals scipy.signal.resample_poly with that window).  Not built: webrtcvad trimming.
+ * the Kaiser-windowed sinc, sum(h) = up, and equals scipy.signal.resample_poly with that window).  Silence trimming: the section after next.
  * load_resampler: the filter as a polyphase bank, float32 [taps][up], rounded once from float64:
  *   bank[t][p] = h[((p * down) mod up) + (t - lead) * up]   (0 where that index falls outside -H .. H),
  * so that y[n] = sum_t bank[t][n mod up] * x[floor(n * down / up) + lead - t], added in tap order in float32 (FMA).  With K =
@@ -589,6 +590,52 @@ int mtts_dvector_embed_wavs_resampled(mtts_dvector* h, mtts_stft* stft, int n_ut
  * n_samples / wavs / f0, n_samples[u] < 1 or beyond the handle's max_samples.  Synchronous. */
 int mtts_stft_load_pitch(mtts_stft* h, int sampling_rate, double f0_floor, double f0_ceil, double threshold, double silence_rms);
 int64_t mtts_stft_f0_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, double* f0, float* aperiodicity);
+
+/* ---- silence trimming of waveform batches: the last step of `preprocess_wav` -----------------------------------
+ * resemblyzer's `trim_long_silences` asks webrtcvad for a voiced / unvoiced decision per 30 ms window and post-processes the flags.
+ * webrtcvad's GMM decision is third party and NOT restated: parity with it is UNPINNED.  Everything around that decision is restated
+ * exactly, and a caller who owns webrtcvad injects its decisions through flags_in.  Opt-in: a handle without a VAD configuration
+ * behaves as before and allocates nothing for this stage.
+ * load_vad: resemblyzer's values are sampling_rate 16000, window_ms 30, ma_width 8, max_silence 6.  floor_db, noise_quantile and
+ * margin_db (the Python layer: -50, 0.1, 10) are this project's choice and have not been tuned against webrtcvad.  Replaces a
+ * configuration loaded before.  Errors: sampling_rate or window_ms < 1, window_ms * sampling_rate not a multiple of 1000, ma_width or
+ * max_silence outside 1 .. 64, noise_quantile outside [0, 1], non-finite thresholds.
+ * Per utterance of n samples:
+ *   1. windows: W = window_ms * sampling_rate / 1000 (480), n_w = floor(n / W); the last n mod W samples are dropped.
+ *   2. e[w] = mean of x^2 over window w: every product float32 x float32 held exactly in float64, the sum in float64 in a fixed order
+ *      (a lane's samples w W + lane, + 64, ... ascending, then a fixed tree over the 64 lanes); no atomics.
+ *   3. noise = the k-th smallest e[w] of this utterance, k = floor(noise_quantile * (n_w - 1)): an order statistic, no interpolation.
+ *   4. raw[w] = (e[w] >= max(10^(floor_db / 10), noise * 10^(margin_db / 10))).  With flags_in (one byte per window, packed over the
+ *      utterances, nonzero = voiced) steps 2 to 4 are skipped and raw = flags_in.
+ *   5. moving average of width ma_width over raw, zero padded by (ma_width - 1) / 2 on the left and ma_width / 2 on the right, rounded
+ *      half to even to bool: smooth[w] = (2 * count > ma_width).  At width 8: at least 5 of raw[w - 3 .. w + 4]; 4 of 8 round to 0.
+ *   6. binary dilation by a centred structure of max_silence + 1 ones: mask[w] = any of smooth[w - max_silence / 2 .. w + (max_silence
+ *      + 1) / 2] (w - 3 .. w + 3 at max_silence 6).
+ *   7. out = the samples of the kept windows in order, n_out = W * (kept windows).  When the mask keeps no window (n < W, digital
+ *      silence) the utterance passes through AS IT IS, all n samples with the tail, and n_voiced_out = 0 reports it (resemblyzer would
+ *      hand an empty array to the next stage).
+ * An utterance's result depends on its samples and the configuration only: bit-identical alone, in any batch, at any position.
+ * trim_batch: n_utts waveforms packed one after another in `wavs` (n_samples[u] each; host) -> out, the trimmed ones packed one after
+ * another (room for sum n_samples), n_out [n_utts]; optional: n_voiced_out [n_utts] kept windows, mask_out [sum n_w] bytes, energy_out
+ * [sum n_w] float64 (not written when flags_in is given).  Returns the total number of output samples, < 0 on error.
+ * embed_wavs_preprocessed: all of `preprocess_wav` chained in front of mtts_dvector_embed_wavs: every chunk's waveforms are resampled
+ * when a resampler is loaded (n_samples[u] then counts SOURCE-rate samples) and normalised (target_dbfs, increase_only as in
+ * resample_batch; NaN: not; without a resampler target_dbfs must be NaN), trimmed, and compacted into the packed waveform buffer over
+ * zeros; then the pad / STFT / power mel / gather / encoder chain.  The front-end-rate signal never visits the host.  The partial rule
+ * applies to the TRIMMED length: n_partials_out and slices_out count the trimmed utterances' partials, n_trimmed_out [n_utts] (or NULL)
+ * the trimmed lengths.  Chunks are planned from the untrimmed lengths (trimming only shortens, so every capacity check holds before
+ * any launch); the host reads a chunk's trimmed lengths back once.  Results are bit-identical under any chunking, and to embed_wavs on
+ * trim_batch's output of resample_batch's output.  The VAD window must be longer than filter_length / 2.
+ * Errors of both entries, before any launch (the chained entry: in both handles' last_error, with those of embed_wavs_resampled): no
+ * VAD configuration loaded, NULL pointers, n_utts < 1 or > 65535, n_samples[u] < 1 or (at the detector's rate) beyond max_samples, more
+ * than 4096 windows in one utterance.  Synchronous, on the handle's stream. */
+int mtts_stft_load_vad(mtts_stft* h, int sampling_rate, int window_ms, int ma_width, int max_silence, double floor_db, double noise_quantile,
+                       double margin_db);
+int64_t mtts_stft_trim_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, const unsigned char* flags_in, float* out, int* n_out,
+                             int* n_voiced_out, unsigned char* mask_out, double* energy_out);
+int mtts_dvector_embed_wavs_preprocessed(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames,
+                                         int frame_step, double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out,
+                                         float* slices_out, int* n_trimmed_out);
 
 #ifdef __cplusplus
 }

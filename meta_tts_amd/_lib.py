@@ -172,6 +172,10 @@ EXPORTS = {
     "mtts_stft_resample_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
     "mtts_dvector_embed_wavs_resampled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_stft_load_vad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "mtts_stft_trim_batch": (C.c_int64, [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    "mtts_dvector_embed_wavs_preprocessed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_stft_load_pitch": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
     "mtts_stft_f0_batch": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_vocoder_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,

@@ -12,6 +12,7 @@
 #include "preprocess.h"
 #include "resample.h"
 #include "pitch.h"
+#include "vad.h"
 #include "speakereval.h"
 
 using namespace mtts;
@@ -54,6 +55,7 @@ struct mtts_stft {
     SpeakerEval se;
     Resample rs;
     Pitch pt;
+    Vad vad;
 };
 
 extern "C" {
@@ -694,6 +696,7 @@ int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_sampl
     h->se.mf = &h->m;
     h->rs.mf = &h->m;
     h->pt.mf = &h->m;
+    h->vad.mf = &h->m;
     h->se.device = device;
     if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; delete h; return -1; }
     *out = h;
@@ -759,6 +762,16 @@ int64_t mtts_stft_f0_batch(mtts_stft* h, int n_utts, const int* n_samples, const
     return h ? h->pt.f0_batch(n_utts, n_samples, wavs, f0, aperiodicity) : -1;
 }
 
+// ---- silence trimming of waveform batches (vad.h: an energy detector with resemblyzer's trim_long_silences post-processing; webrtcvad's
+// decision is not restated) ----
+int mtts_stft_load_vad(mtts_stft* h, int sampling_rate, int window_ms, int ma_width, int max_silence, double floor_db, double noise_quantile, double margin_db) {
+    return h ? h->vad.load(sampling_rate, window_ms, ma_width, max_silence, floor_db, noise_quantile, margin_db) : -1;
+}
+int64_t mtts_stft_trim_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, const unsigned char* flags_in, float* out, int* n_out,
+                             int* n_voiced_out, unsigned char* mask_out, double* energy_out) {
+    return h ? h->vad.trim_batch(n_utts, n_samples, wavs, flags_in, out, n_out, n_voiced_out, mask_out, energy_out) : -1;
+}
+
 // ---- speaker-similarity evaluation (speakereval.h; reference evaluation/wavs_to_dvector.py, pair_similarity.py, centroid_similarity.py) ----
 int mtts_stft_power_mel_batch(mtts_stft* h, int n_utts, const int* n_samples, const float* wavs, float* mel) {
     return h ? h->se.power_mel_batch(n_utts, n_samples, wavs, mel) : -1;
@@ -779,6 +792,15 @@ int mtts_dvector_embed_wavs_resampled(mtts_dvector* h, mtts_stft* stft, int n_ut
     if (!stft) { g_create_error = "mtts_dvector_embed_wavs_resampled: NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
     const int rc = stft->se.embed_wavs(h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, partial_frames, frame_step, min_coverage, out,
                                        n_partials_out, slices_out, &stft->rs, target_dbfs, increase_only);
+    if (rc != 0 && h) h->d.set_error(stft->m.last_error);
+    return rc;
+}
+int mtts_dvector_embed_wavs_preprocessed(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
+                                         double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out,
+                                         int* n_trimmed_out) {
+    if (!stft) { g_create_error = "mtts_dvector_embed_wavs_preprocessed: NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
+    const int rc = stft->se.embed_wavs(h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, partial_frames, frame_step, min_coverage, out,
+                                       n_partials_out, slices_out, stft->rs.loaded() ? &stft->rs : nullptr, target_dbfs, increase_only, &stft->vad, n_trimmed_out);
     if (rc != 0 && h) h->d.set_error(stft->m.last_error);
     return rc;
 }

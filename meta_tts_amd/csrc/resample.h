@@ -6,7 +6,7 @@
 // is vendored; what is built is stated in include/mtts.h: an exact polyphase evaluation of
 //     y[n] = sum_m h[n * down - m * up] x[m],   |n * down - m * up| <= H,  0 <= m < n_in,   n_out = ceil(n_in * up / down)
 // for a Kaiser-windowed sinc h designed on the host in float64 (meta_tts_amd/audio/resample.py), and
-// normalize_volume(wav, target, increase_only): gain = 10^((target - 10 log10(mean(y^2))) / 20).  VAD trimming is not built.
+// normalize_volume(wav, target, increase_only): gain = 10^((target - 10 log10(mean(y^2))) / 20).  Silence trimming follows in vad.h.
 //
 // MI355X layout.  The phase of output n is (n * down) mod up, which has period `up` in n, so the fp32 coefficient bank is stored
 // [tap][n mod up]: the 64 lanes of a wavefront, which hold consecutive outputs, read consecutive addresses for every tap (the bank is
@@ -153,16 +153,18 @@ public:
                mf->grow(gains, n_utts_, "gains") || mf->grow(utts, n_utts_, "resampler utterances") ? -1 : 0;
     }
     // The tabled utterances, packed in src_host, -> mf->wav at their dst0 (the caller has sized mf->wav), then the gain.  Asynchronous on
-    // mf->stream; h_utts and src_host must stay as they are until the stream has been synchronised.
-    int launch(const float* src_host, double target_dbfs, bool increase_only) {
+    // mf->stream; h_utts and src_host must stay as they are until the stream has been synchronised.  dst: another buffer than mf->wav
+    // (vad.h's staging buffer, when silence trimming follows and fills mf->wav itself).
+    int launch(const float* src_host, double target_dbfs, bool increase_only, float* dst = nullptr) {
+        if (!dst) dst = mf->wav.p;
         DEV_CHECK(hipMemcpyAsync(src.p, src_host, (size_t)n_src * sizeof(float), hipMemcpyHostToDevice, mf->stream));
         DEV_CHECK(hipMemcpyAsync(utts.p, h_utts.data(), h_utts.size() * sizeof(RsUtt), hipMemcpyHostToDevice, mf->stream));
         const unsigned n_utts = (unsigned)h_utts.size();
         MTTS_LAUNCH(resample_polyphase_kernel, dim3((unsigned)((max_out + run - 1) / run), n_utts), dim3(RS_THREADS), mf->stream, (const float*)src.p,
-                    (const RsUtt*)utts.p, (const float*)bank, up, down, taps, lead, run, mf->wav.p, partials.p);
+                    (const RsUtt*)utts.p, (const float*)bank, up, down, taps, lead, run, dst, partials.p);
         if (!std::isnan(target_dbfs))
             MTTS_LAUNCH(resample_gain_kernel, dim3((unsigned)std::min((max_out + 1023) / 1024, 64), n_utts), dim3(256), mf->stream, (const RsUtt*)utts.p,
-                        (const double*)partials.p, run, target_dbfs, increase_only ? 1 : 0, mf->wav.p, gains.p);
+                        (const double*)partials.p, run, target_dbfs, increase_only ? 1 : 0, dst, gains.p);
         return 0;
     }
 

@@ -9,7 +9,8 @@
 // projection, no log, no clamp — and `compute_partial_slices`: 160-frame windows every frame_step = round(16000 / rate / 160) frames
 // over ceil((n + 1) / 160) frames, the last one dropped when it covers less than min_coverage of its span and is not the only one,
 // the waveform zero-extended to the end of the last window kept.  Of `preprocess_wav`, resampling and -30 dBFS normalisation are
-// resample.h's (embed_wavs with a Resample: the chained entry); webrtcvad trimming is NOT built.  Without a resampler inputs are 16 kHz
+// resample.h's (embed_wavs with a Resample: the chained entry) and silence trimming is vad.h's (embed_wavs with a Vad: all of
+// `preprocess_wav` chained; the detector is this project's, parity with webrtcvad is UNPINNED).  Without either, inputs are 16 kHz
 // waveforms as they are.
 //
 // MI355X layout.  All utterances of a chunk share every launch (melfront.h's packing): the reflect-pad kernel, ONE forward-STFT GEMM
@@ -36,6 +37,7 @@
 #include "dvector.h"
 #include "melfront.h"
 #include "resample.h"
+#include "vad.h"
 
 namespace mtts {
 
@@ -141,6 +143,7 @@ public:
     std::vector<std::vector<StftUtt>> keep_utts;  // MelFront's packing tables of the chunks already enqueued, kept for the same reason
     std::vector<std::vector<int>> keep_maps;
     std::vector<std::vector<RsUtt>> keep_rs;      // and the resampler's tables (embed_wavs with a resampler)
+    std::vector<std::vector<VadUtt>> keep_vad;    // and the trimmer's (embed_wavs with a Vad)
     std::vector<long long> h_n;                   // samples per utterance at the front-end's rate
     struct Chunk { int u0, u1, N; };
     std::vector<Chunk> chunks;
@@ -185,9 +188,15 @@ public:
     // to target_dbfs unless that is NaN) by rs straight into mf->wav, zero-extended there, and the front-end rate's signal never
     // visits the host.  The chunking, the launches behind the waveform buffer and the results are those of the plain entry on the
     // resampled waveforms.
+    // vad != nullptr (mtts_dvector_embed_wavs_preprocessed): every chunk's waveforms go (through rs when given, else as they are) into
+    // vad's staging buffer, are trimmed there, and the kept windows are compacted into mf->wav over zeros.  Chunks and capacities are
+    // planned from the untrimmed lengths (trimming only shortens, and the partial count never grows as a waveform shrinks); the partial
+    // rule then applies to the trimmed lengths, which the host reads back once per chunk (Vad::detect).  n_trimmed_out (or nullptr):
+    // the trimmed lengths.  slices_out holds the partials of the trimmed utterances one after another.
     int embed_wavs(DVector* dv, int dv_device, int n_utts, const int* n_samples, const float* wavs, int frames, int step, double min_coverage, float* out,
-                   int* n_partials_out, float* slices_out, Resample* rs = nullptr, double target_dbfs = 0.0, int increase_only = 0) {
-        const char* who = rs ? "mtts_dvector_embed_wavs_resampled: " : "mtts_dvector_embed_wavs: ";
+                   int* n_partials_out, float* slices_out, Resample* rs = nullptr, double target_dbfs = 0.0, int increase_only = 0, Vad* vad = nullptr,
+                   int* n_trimmed_out = nullptr) {
+        const char* who = vad ? "mtts_dvector_embed_wavs_preprocessed: " : rs ? "mtts_dvector_embed_wavs_resampled: " : "mtts_dvector_embed_wavs: ";
         const int hop = mf->hop, n_mel = mf->n_mel;
         if (!mf->have_basis || !mf->have_mel) return err(std::string(who) + "STFT bases not loaded");
         if (n_utts < 1 || !n_samples || !wavs || !n_partials_out) return err(std::string(who) + "bad arguments (n_utts < 1 or NULL n_samples / wavs / n_partials_out)");
@@ -205,6 +214,15 @@ public:
         h_ext.resize((size_t)n_utts);
         h_cnt.resize((size_t)n_utts);
         h_n.resize((size_t)n_utts);
+        if (vad) {
+            if (!rs && !std::isnan(target_dbfs))
+                return err(std::string(who) + "volume normalisation needs a resampler (mtts_stft_load_resampler; the identity bank for waveforms at the front-end's rate)");
+            for (int u = 0; u < n_utts; ++u) h_n[(size_t)u] = rs ? rs->out_len(n_samples[u]) : n_samples[u];
+            if (vad->check_lengths(who, n_utts, h_n.data())) return -1;
+            if (vad->c.W <= mf->n_fft / 2)
+                return err(std::string(who) + "a VAD window of " + std::to_string(vad->c.W) + " samples is too short for the reflection padding (need more than filter_length / 2 = " +
+                           std::to_string(mf->n_fft / 2) + ")");
+        }
         long long total = 0, total_parts = 0;
         for (int u = 0; u < n_utts; ++u) {
             const std::string utt = std::string(who) + "utterance " + std::to_string(u) + ": ";
@@ -222,7 +240,7 @@ public:
         if (dv && dv->dirty && dv->refresh() != 0) return err(std::string(who) + dv->last_error);
         const bool two_streams = dv && dv->stream != mf->stream;
         if (two_streams) { DEV_CHECK(mf->mem.event(ev_front)); DEV_CHECK(mf->mem.event(ev_enc)); }
-        if (!rs) {
+        if (!rs && !vad) {
             h_wav.assign((size_t)total, 0.f);
             long long src = 0, dst = 0;
             for (int u = 0; u < n_utts; ++u) {
@@ -237,6 +255,7 @@ public:
         keep_utts.clear();
         keep_maps.clear();
         keep_rs.clear();
+        keep_vad.clear();
         chunks.clear();
         int max_N = 0;
         for (int u0 = 0; u0 < n_utts;) {   // a chunk: consecutive utterances within the encoder's capacity (front-end only: the whole call)
@@ -263,13 +282,54 @@ public:
             if (max_src > (1LL << 31) - 1) return err(std::string(who) + "too many samples in one chunk");
             if (rs->reserve(max_src, max_slots, max_utts)) return -1;
         }
+        if (vad) {   // and for the trimmer's: the largest chunk's untrimmed samples, windows and utterances
+            long long max_n = 0, max_win = 0;
+            size_t max_utts = 0;
+            for (const Chunk& c : chunks) {
+                long long n = 0, nw = 0;
+                for (int u = c.u0; u < c.u1; ++u) { n += h_n[(size_t)u]; nw += h_n[(size_t)u] / vad->c.W; }
+                max_n = std::max(max_n, n);
+                max_win = std::max(max_win, nw);
+                max_utts = std::max(max_utts, (size_t)(c.u1 - c.u0));
+            }
+            if (max_n > (1LL << 31) - 1) return err(std::string(who) + "too many samples in one chunk");
+            if (vad->reserve(max_n, max_win, max_utts, false)) return -1;
+        }
         long long wav0 = 0, src0 = 0, part0 = 0;
         for (size_t c = 0; c < chunks.size(); ++c) {
-            const int u0 = chunks[c].u0, u1 = chunks[c].u1, N = chunks[c].N;
+            const int u0 = chunks[c].u0, u1 = chunks[c].u1;
+            int N = chunks[c].N;
+            if (vad) {   // untrimmed waveforms into the staging buffer, the mask, and the trimmed lengths back: the partial rule is theirs
+                vad->table_begin();
+                for (int u = u0; u < u1; ++u) vad->table_add(h_n[(size_t)u]);
+                if (rs) {
+                    rs->table_begin();
+                    for (int u = u0; u < u1; ++u) rs->table_add(n_samples[u], vad->h_utts[(size_t)(u - u0)].src0);
+                    if (rs->launch(wavs + src0, target_dbfs, increase_only != 0, vad->stage.p)) return -1;
+                    src0 += rs->n_src;
+                } else {
+                    DEV_CHECK(hipMemcpyAsync(vad->stage.p, wavs + src0, (size_t)vad->n_src * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+                    src0 += vad->n_src;
+                }
+                if (vad->detect(nullptr)) return -1;   // (synchronises mf->stream: the resampler's table is free again)
+                N = 0;
+                for (int u = u0; u < u1; ++u) {
+                    const int n = vad->h_nout[2 * (size_t)(u - u0)];
+                    n_partials_out[u] = h_cnt[(size_t)u] = spk_partial_count(n, hop, frames, step, min_coverage, &h_ext[(size_t)u]);
+                    if (n_trimmed_out) n_trimmed_out[u] = n;
+                    N += h_cnt[(size_t)u];
+                }
+            }
             mf->pack_begin();
             for (int u = u0; u < u1; ++u) mf->pack_add(h_ext[(size_t)u], mf->frames_of((int)h_ext[(size_t)u]));
             if (mf->stage("mtts_dvector_embed_wavs", true)) return -1;
-            if (rs) {   // source-rate samples up, resampled into mf->wav over zeros (the zero-extension to the last window's end)
+            if (vad) {   // the kept windows into mf->wav over zeros (the zero-extension to the last partial window's end)
+                DEV_CHECK(hipMemsetAsync(mf->wav.p, 0, (size_t)mf->n_samples * sizeof(float), mf->stream));
+                for (int u = u0; u < u1; ++u) vad->h_utts[(size_t)(u - u0)].dst0 = mf->h_utts[(size_t)(u - u0)].wav0;
+                if (vad->compact(mf->wav.p) || mf->pad_staged(false, true)) return -1;
+                keep_vad.emplace_back(std::move(vad->h_utts));
+                vad->h_utts.clear();
+            } else if (rs) {   // source-rate samples up, resampled into mf->wav over zeros (the zero-extension to the last window's end)
                 DEV_CHECK(hipMemsetAsync(mf->wav.p, 0, (size_t)mf->n_samples * sizeof(float), mf->stream));
                 rs->table_begin();
                 for (int u = u0; u < u1; ++u) rs->table_add(n_samples[u], mf->h_utts[(size_t)(u - u0)].wav0);

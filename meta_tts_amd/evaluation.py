@@ -11,8 +11,10 @@ are a few hundred scores and run on the host in numpy (sklearn's det_curve / roc
 resemblyzer is not vendored by the reference and not part of this project: its `wav_to_mel_spectrogram` and
 `VoiceEncoder.compute_partial_slices` are restated here from the published recipe.  Of its `preprocess_wav`, resampling to 16 kHz and
 the -30 dBFS volume normalisation run on the device when asked for (`embed_utterances(source_rate=, normalize_dbfs=)`,
-`WavsToDvector(resample=True)`; audio/resample.py, csrc/resample.h); webrtcvad silence trimming is NOT built.  Without those arguments
-every waveform handed to this module is taken as 16 kHz float32 as it is.  Figures (the reference's matplotlib / seaborn plots) are
+`WavsToDvector(resample=True)`; audio/resample.py, csrc/resample.h), and so does its silence trimming (`embed_utterances(trim=True)`,
+`WavsToDvector(trim=True)`; audio/vad.py, csrc/vad.h): resemblyzer's post-processing exactly, around an energy detector of this project's
+in place of webrtcvad's decision — parity with webrtcvad is UNPINNED.  Without those arguments every waveform handed to this module is
+taken as 16 kHz float32 as it is.  Figures (the reference's matplotlib / seaborn plots) are
 out of scope."""
 from __future__ import annotations
 
@@ -68,7 +70,8 @@ class SpeakerEmbedder:
     """The speaker encoder end to end on the device.  `state_dict`: the resemblyzer `VoiceEncoder` weights in torch's names
     (lstm.weight_ih_l0 ... linear.bias; None: deterministic synthetic weights, for tests and benchmarks); `encoder=False` builds the
     front-end only (`reference_mel_slices` for preprocessing).  Waveforms are 16 kHz float32 and are NOT resampled, normalised or
-    trimmed unless `embed_utterances` is given `source_rate` (resemblyzer's silence trimming is not part of this project)."""
+    trimmed unless `embed_utterances` is given `source_rate` / `normalize_dbfs` / `trim` (the detector behind `trim` is this project's
+    own, audio/vad.py: parity with resemblyzer's webrtcvad is unpinned)."""
 
     def __init__(self, state_dict=None, max_partials: int = 2048, max_utts: int = 256, hidden: int = HIDDEN, emb: int = EMBED, layers: int = LAYERS,
                  rate: float = 1.3, min_coverage: float = 0.75, device: int = 0, lib_path=None, encoder: bool = True):
@@ -82,6 +85,8 @@ class SpeakerEmbedder:
         self.encoder = DVectorEncoder(state_dict, max_partials=max_partials, max_utts=max_utts, hidden=hidden, emb=emb, layers=layers, device=device,
                                       lib_path=lib_path) if encoder else None
         self._resamplers = {}   # source rate -> audio.resample.Resampler on this front-end's handle (embed_utterances(source_rate=))
+        self._trimmers = {}     # configuration -> audio.vad.SilenceTrimmer on the same handle (embed_utterances(trim=True))
+        self.last_trimmed_lengths = None   # int32 [n]: the trimmed 16 kHz lengths of the last embed_utterances(trim=...) call
 
     def set_streams(self, stft_stream: int, encoder_stream: Optional[int] = None):
         """HIP streams of the two handles (the stages are ordered by events when they differ)."""
@@ -118,9 +123,23 @@ class SpeakerEmbedder:
             self._resamplers[key] = Resampler(int(source_rate), SAMPLING_RATE, preset, _handle=self._dev)
         return self._resamplers[key]
 
-    def _run(self, wavs, want_vectors: bool, want_slices: bool, source_rate=None, normalize_dbfs=None, increase_only=True):
+    def trimmer(self, **config):
+        """The silence trimmer on this front-end's handle (built on first use; `config`: audio.vad.SilenceTrimmer's detector keywords —
+        window_ms, ma_width, max_silence, floor_db, noise_quantile, margin_db; the rate is the encoder's 16 kHz)."""
+        from .audio.vad import SilenceTrimmer
+        fixed = sorted(set(config) & {"sampling_rate", "device", "lib_path", "max_samples", "_handle"})
+        if fixed:
+            raise ValueError(f"SpeakerEmbedder.trimmer: {', '.join(fixed)} cannot be set here (the trimmer runs on this front-end's handle at sampling_rate {SAMPLING_RATE})")
+        key = tuple(sorted(config.items()))
+        if key not in self._trimmers:
+            self._trimmers[key] = SilenceTrimmer(sampling_rate=SAMPLING_RATE, _handle=self._dev, **config)
+        return self._trimmers[key]
+
+    def _run(self, wavs, want_vectors: bool, want_slices: bool, source_rate=None, normalize_dbfs=None, increase_only=True, trim=False):
         ws, n, packed = self._pack(wavs)
         rs = None
+        if trim and source_rate is None:
+            source_rate = SAMPLING_RATE      # the chained entry resamples with whatever bank the handle holds: make it the identity
         if source_rate is not None:
             rs = self.resampler(source_rate)
             if getattr(self._dev, "_resampler_key", None) != rs._key:
@@ -128,6 +147,8 @@ class SpeakerEmbedder:
         elif normalize_dbfs is not None:
             raise ValueError("normalize_dbfs needs source_rate (16000 for waveforms that are at the encoder's rate already)")
         counts = np.asarray([len(compute_partial_slices(rs.output_length(int(k)) if rs else int(k), self.rate, self.min_coverage)[1]) for k in n], np.int32)
+        if trim:
+            return self._run_trimmed(ws, n, packed, counts, want_vectors, want_slices, normalize_dbfs, increase_only, trim)
         got = np.empty(len(ws), np.int32)
         out = np.empty((len(ws), self.emb), np.float32) if want_vectors else None
         slices = np.empty((int(counts.sum()), PARTIAL_FRAMES, MEL_N_CHANNELS), np.float32) if want_slices else None
@@ -143,24 +164,49 @@ class SpeakerEmbedder:
         assert np.array_equal(got, counts), (got, counts)   # the device entry and compute_partial_slices state the same rule
         return out, (np.split(slices, np.cumsum(counts)[:-1]) if want_slices else None)
 
+    def _run_trimmed(self, ws, n, packed, counts, want_vectors, want_slices, normalize_dbfs, increase_only, trim):
+        """All of `preprocess_wav` chained on the device: `counts` (from the untrimmed lengths) bounds the partials, the entry reports the
+        trimmed lengths and their partial counts."""
+        vad = self.trimmer(**(trim if isinstance(trim, dict) else {}))
+        if getattr(self._dev, "_vad_key", None) != vad._key:
+            vad.load()
+        got, n_trimmed = np.empty(len(ws), np.int32), np.empty(len(ws), np.int32)
+        out = np.empty((len(ws), self.emb), np.float32) if want_vectors else None
+        slices = np.empty((int(counts.sum()), PARTIAL_FRAMES, MEL_N_CHANNELS), np.float32) if want_slices else None
+        self._dev.check(self.lib.mtts_dvector_embed_wavs_preprocessed(
+            self.encoder.h if want_vectors else None, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step, float(self.min_coverage),
+            float("nan") if normalize_dbfs is None else float(normalize_dbfs), int(bool(increase_only)), _ptr(out) if want_vectors else None, _ptr(got),
+            _ptr(slices) if want_slices else None, _ptr(n_trimmed)))
+        want = [len(compute_partial_slices(int(k), self.rate, self.min_coverage)[1]) for k in n_trimmed]
+        assert np.array_equal(got, want) and np.all(got <= counts), (got, want, counts)
+        self.last_trimmed_lengths = n_trimmed
+        return out, ([s.copy() for s in np.split(slices[: int(got.sum())], np.cumsum(got)[:-1])] if want_slices else None)
+
     def embed_utterances(self, wavs, return_slices: bool = False, source_rate: Optional[int] = None, normalize_dbfs: Optional[float] = None,
-                         increase_only: bool = True):
+                         increase_only: bool = True, trim=False):
         """`VoiceEncoder.embed_utterance` (rate 1.3, min_coverage 0.75) of a list of 16 kHz float32 waveforms -> (B, emb) float32, every
         row L2-normalised.  One chain of launches per chunk of utterances (as many as fit the encoder's max_partials).
         source_rate: the waveforms are at that rate and are resampled to 16 kHz on the device in front of the same chain (the 16 kHz
         signal never visits the host); normalize_dbfs: and normalised to that level (resemblyzer: -30, increase_only) — the result
-        equals `embed_utterances(Resampler.resample_batch(wavs, normalize_dbfs))` bit for bit."""
+        equals `embed_utterances(Resampler.resample_batch(wavs, normalize_dbfs))` bit for bit.
+        trim: True (or a dict of audio.vad.SilenceTrimmer keywords): silence trimming behind those two steps, on the device as well — with
+        source_rate and normalize_dbfs=-30 all of resemblyzer's `preprocess_wav` (source_rate may be 16000, and is taken as that when
+        omitted: the chained entry runs whatever bank the handle holds, so the 16000 -> 16000 identity bank is loaded, a one-tap pass
+        that copies every sample as it is — a side effect on the handle's resampler, which `resampler(rate)` users reload by
+        themselves before each use); the result equals `embed_utterances(trimmer().trim_batch(resample_batch(...)))` bit for bit, and
+        `last_trimmed_lengths` holds the trimmed lengths.  The detector is this project's (parity with webrtcvad unpinned)."""
         if self.encoder is None:
             raise MttsError("SpeakerEmbedder(encoder=False) has no encoder")
-        out, slices = self._run(wavs, True, return_slices, source_rate, normalize_dbfs, increase_only)
+        out, slices = self._run(wavs, True, return_slices, source_rate, normalize_dbfs, increase_only, trim)
         return (out, slices) if return_slices else out
 
     def embed_utterance(self, wav):
         return self.embed_utterances([wav])[0]
 
-    def reference_mel_slices(self, wav) -> np.ndarray:
-        """The `spk_ref_mel_slices` payload of preprocessor.py:263-299 for one waveform: (n_partials, 160, 40) float32."""
-        return self._run([wav], False, True)[1][0]
+    def reference_mel_slices(self, wav, source_rate: Optional[int] = None, normalize_dbfs: Optional[float] = None, trim=False) -> np.ndarray:
+        """The `spk_ref_mel_slices` payload of preprocessor.py:263-299 for one waveform: (n_partials, 160, 40) float32.  source_rate,
+        normalize_dbfs, trim: as in `embed_utterances`."""
+        return self._run([wav], False, True, source_rate, normalize_dbfs, True, trim)[1][0]
 
     # ---- scoring kernels ---------------------------------------------------------------------------------------------------------
     def _scorer(self):
@@ -228,12 +274,13 @@ class WavsToDvector:
     instead, as in the reference).  `wav_loader(path) -> 16 kHz float32 waveform` (default: `read_wav_16k`).  All wavs of a mode go to
     the device in one `embed_utterances` call.  resample=True: files of any rate (a result tree's 22 050 Hz wavs) are read with
     `preprocessor.read_wav`, grouped by rate, and each group is resampled to 16 kHz and normalised to `normalize_dbfs` (resemblyzer's
-    `preprocess_wav` without its silence trimming; None: not normalised) on the device in front of the encoder, one call per group."""
+    `preprocess_wav`; None: not normalised) on the device in front of the encoder, one call per group.  trim=True: and trimmed of long
+    silences there (`embed_utterances(trim=True)`; this project's detector, parity with webrtcvad unpinned); default off."""
 
     def __init__(self, config: EvalConfig, embedder: SpeakerEmbedder, wav_loader: Optional[Callable[[str], np.ndarray]] = None, pair_list=None,
-                 rng: Optional[random.Random] = None, run: bool = True, resample: bool = False, normalize_dbfs: Optional[float] = -30.0):
+                 rng: Optional[random.Random] = None, run: bool = True, resample: bool = False, normalize_dbfs: Optional[float] = -30.0, trim=False):
         self.config, self.embedder = config, embedder
-        self.resample, self.normalize_dbfs = bool(resample), normalize_dbfs
+        self.resample, self.normalize_dbfs, self.trim = bool(resample), normalize_dbfs, trim
         if resample and wav_loader is not None:
             raise ValueError("WavsToDvector(resample=True) reads the files itself: wav_loader must be None")
         self.corpus, self.data_dir_dict = config.corpus, config.data_dir_dict
@@ -258,7 +305,7 @@ class WavsToDvector:
 
     def files_to_dvectors(self, paths: Sequence[str]) -> np.ndarray:
         if not self.resample:
-            return self.embedder.embed_utterances([self.wav_loader(p) for p in paths])
+            return self.embedder.embed_utterances([self.wav_loader(p) for p in paths], trim=self.trim)
         from .preprocessor import read_wav
         by_rate: Dict[int, List[int]] = {}
         wavs = []
@@ -270,7 +317,7 @@ class WavsToDvector:
             raise MttsError("no waveforms")
         out = np.empty((len(wavs), self.embedder.emb), np.float32)
         for rate, idx in sorted(by_rate.items()):
-            out[idx] = self.embedder.embed_utterances([wavs[i] for i in idx], source_rate=rate, normalize_dbfs=self.normalize_dbfs)
+            out[idx] = self.embedder.embed_utterances([wavs[i] for i in idx], source_rate=rate, normalize_dbfs=self.normalize_dbfs, trim=self.trim)
         return out
 
     def get_speaker_id_map(self):

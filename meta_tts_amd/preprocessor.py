@@ -297,12 +297,14 @@ class Preprocessor(_OnHandle):
             results[k] = Utterance(info, pitches[j][pkeep[j]], energies[j][ekeep[j]], int(mels[j].shape[0]), pparts[j].copy(), eparts[j].copy())
         return results
 
-    def speaker_reference_fn(self, embedder, wav_loader=None, resample=None):
+    def speaker_reference_fn(self, embedder, wav_loader=None, resample=None, trim=False):
         """A ready-made `spk_ref_fn` for `build_from_path` / `process_utterances` (preprocessor.py:263-299): (speaker, basename) -> the
         (n_partials, 160, 40) float32 `spk_ref_mel_slices` of the WHOLE raw file <raw_path>/<subset>/<speaker>/<basename>.wav, computed on
         the device by `embedder` (a meta_tts_amd.evaluation.SpeakerEmbedder; `encoder=False` is enough).  The speaker encoder takes
-        16 kHz waveforms and resemblyzer's `preprocess_wav` (resampling, volume normalisation, silence trimming) is not part of this
-        project: a file at another rate needs `resample(wav, rate) -> 16 kHz float32 waveform`, else it is an error."""
+        16 kHz waveforms: a file at another rate needs `resample(wav, rate) -> 16 kHz float32 waveform` (an audio.resample.Resampler),
+        else it is an error.  trim=True (or a dict of audio.vad.SilenceTrimmer keywords): the rest of resemblyzer's `preprocess_wav` on
+        the device in front of the slices — normalisation to -30 dBFS (increase only) and silence trimming (this project's detector;
+        parity with webrtcvad is unpinned).  Default: neither, as before."""
         from .evaluation import SAMPLING_RATE
         wav_loader = wav_loader or read_wav
         subsets = [d for ds in (self.train_set, self.val_set, self.test_set) for d in (ds if isinstance(ds, list) else [ds]) if isinstance(d, str)]
@@ -319,6 +321,8 @@ class Preprocessor(_OnHandle):
                 if resample is None:
                     raise MttsError(f"{path}: sampling rate {rate}, the speaker encoder takes {SAMPLING_RATE} Hz (no resampling here: pass resample=)")
                 wav = resample(wav, rate)
+            if trim:
+                return embedder.reference_mel_slices(np.asarray(wav, np.float32), source_rate=SAMPLING_RATE, normalize_dbfs=-30.0, trim=trim)
             return embedder.reference_mel_slices(np.asarray(wav, np.float32))
         return spk_ref_fn
 
