@@ -84,6 +84,46 @@ class _OnHandle:
         return self._dev.check(rc)
 
 
+class _StageOnHandle(_OnHandle):
+    """A stage of which an `mtts_stft` handle holds ONE configuration at a time (a resampler bank, a pitch or a VAD configuration).
+    A stand-alone stage owns a small handle; `_handle=` attaches it to an existing one.  A subclass names the handle attribute that
+    records the configuration loaded (`_slot`), sets `_key` (its own configuration), and sends it to the device in `_load()`."""
+    _slot = None
+
+    def _attach(self, _handle, *create):
+        self._owner = _handle is None
+        self._dev = _handle if _handle is not None else _Handle(*create)
+
+    def _first_load(self):
+        try:
+            self.load()
+        except MttsError:
+            self.close()
+            raise
+
+    def load(self):
+        """Make this stage's configuration the handle's current one (done by the constructor)."""
+        self._load()
+        setattr(self._dev, self._slot, self._key)
+
+    def ensure_loaded(self):
+        """`load()` when the handle holds another configuration: before each use, since several stages may share a handle."""
+        if getattr(self._dev, self._slot, None) != self._key:
+            self.load()
+
+    def close(self):
+        if self._owner:
+            self._dev.close()
+
+
+def _pack_wavs(wavs):
+    """A list of waveforms -> (the float32 vectors, their lengths int32, all of them one after another)."""
+    ws = [np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1)) for w in wavs]
+    if not ws:
+        raise MttsError("no waveforms")
+    return ws, np.asarray([len(w) for w in ws], np.int32), np.ascontiguousarray(np.concatenate(ws))
+
+
 def _np32(x):
     return np.ascontiguousarray(np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, np.float32))
 

@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ..engine import MttsError
-from .stft import _Handle, _OnHandle
+from .stft import _Handle, _StageOnHandle, _pack_wavs
 
 SAMPLING_RATE = 16000            # resemblyzer hparams: sampling_rate
 VAD_WINDOW_LENGTH = 30           # ms
@@ -84,10 +84,11 @@ def trim_long_silences(wav, flags, window: int = VAD_WINDOW_LENGTH * SAMPLING_RA
     return wav[: n_w * window][np.repeat(mask, window)]
 
 
-class SilenceTrimmer(_OnHandle):
+class SilenceTrimmer(_StageOnHandle):
     """Batched silence trimming on the device.  A stand-alone SilenceTrimmer owns a small mtts_stft handle; `_handle=` attaches it to an
     existing one (a SpeakerEmbedder's), which then also serves the chained entry.  A handle holds ONE configuration: `load()` makes this
     trimmer's the current one (done by the constructor and, when several share a handle, again before each use)."""
+    _slot = "_vad_key"
 
     def __init__(self, sampling_rate: int = SAMPLING_RATE, window_ms: int = VAD_WINDOW_LENGTH, ma_width: int = VAD_MOVING_AVERAGE_WIDTH,
                  max_silence: int = VAD_MAX_SILENCE_LENGTH, floor_db: float = FLOOR_DB, noise_quantile: float = NOISE_QUANTILE, margin_db: float = MARGIN_DB,
@@ -96,34 +97,20 @@ class SilenceTrimmer(_OnHandle):
         self.floor_db, self.noise_quantile, self.margin_db = float(floor_db), float(noise_quantile), float(margin_db)
         self.window = self.window_ms * self.sampling_rate // 1000
         self._key = (self.sampling_rate, self.window_ms, self.ma_width, self.max_silence, self.floor_db, self.noise_quantile, self.margin_db)
-        self._owner = _handle is None
-        self._dev = _handle if _handle is not None else _Handle(16, 4, 1, max_samples, device, lib_path)
-        try:
-            self.load()
-        except MttsError:
-            self.close()
-            raise
+        self._attach(_handle, 16, 4, 1, max_samples, device, lib_path)
+        self._first_load()
 
-    def load(self):
+    def _load(self):
         self._check(self.lib.mtts_stft_load_vad(self.h, self.sampling_rate, self.window_ms, self.ma_width, self.max_silence, self.floor_db, self.noise_quantile,
                                                 self.margin_db))
-        self._dev._vad_key = self._key
-
-    def close(self):
-        if self._owner:
-            self._dev.close()
 
     def trim_batch(self, wavs: Sequence, flags: Optional[Sequence] = None, return_masks: bool = False):
         """A list of waveforms -> the list of trimmed float32 waveforms, one device call.  flags: per utterance, one decision per window
         (len(wav) // window of them) in place of the energy detector's.  return_masks: also (masks, n_voiced, energies): the bool mask of
         kept windows and the float64 window energies per utterance (energies None with flags), n_voiced int32 — 0 where the utterance
         was passed through as it is."""
-        ws = [np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1)) for w in wavs]
-        if not ws:
-            raise MttsError("no waveforms")
-        if getattr(self._dev, "_vad_key", None) != self._key:
-            self.load()
-        n = np.asarray([len(w) for w in ws], np.int32)
+        ws, n, packed = _pack_wavs(wavs)
+        self.ensure_loaded()
         n_w = n // max(self.window, 1)
         fl = None
         if flags is not None:
@@ -131,7 +118,6 @@ class SilenceTrimmer(_OnHandle):
             if len(fs) != len(ws) or any(len(f) != k for f, k in zip(fs, n_w)):
                 raise MttsError(f"trim_batch: flags must hold len(wav) // {self.window} decisions per utterance")
             fl = np.ascontiguousarray(np.concatenate(fs + [np.zeros(1, np.uint8)]))
-        packed = np.ascontiguousarray(np.concatenate(ws))
         out, n_out, n_voiced = np.empty(len(packed), np.float32), np.zeros(len(ws), np.int32), np.zeros(len(ws), np.int32)
         mask, energy = np.zeros(int(n_w.sum()) + 1, np.uint8), np.zeros(int(n_w.sum()) + 1, np.float64)
         total = self._check(self.lib.mtts_stft_trim_batch(self.h, len(ws), _ptr(n), _ptr(packed), _ptr(fl) if fl is not None else None, _ptr(out), _ptr(n_out),

@@ -140,6 +140,26 @@ public:
 
     int frames_of(int n_samples) const { return n_samples / hop + 1; }   // conv1d over the padded signal: (n + n_fft - n_fft) / hop + 1
 
+    // What the batched entries refuse about their utterances before any launch, each asking for the conditions that are its own.
+    // UTT_GRID: more than 65535 utterances (its kernels take the utterance from gridDim.y).  UTT_CAP: a length below 1 or beyond
+    // max_samples.  UTT_PAD: a length the reflection padding cannot read (n <= n_fft / 2).  len_of(u) = samples of utterance u;
+    // resampled: they are counted behind a resampler (of n_in source samples each), and the texts say so.
+    enum { UTT_GRID = 1, UTT_CAP = 2, UTT_PAD = 4 };
+    template <class LenOf>
+    int check_utterances(const std::string& who, int n_utts, LenOf len_of, int checks, bool resampled = false) {
+        if ((checks & UTT_GRID) && n_utts > 65535) return err(who + "more than 65535 utterances in one call");
+        for (int u = 0; u < n_utts; ++u) {
+            const std::string utt = who + "utterance " + std::to_string(u) + ": ";
+            const long long n = len_of(u);
+            if ((checks & UTT_CAP) && n < 1) return err(utt + (resampled ? "n_in < 1" : "n_samples < 1"));
+            if ((checks & UTT_CAP) && n > cap_samples)
+                return err(utt + std::to_string(n) + (resampled ? " resampled" : "") + " samples exceed max_samples = " + std::to_string(cap_samples));
+            if ((checks & UTT_PAD) && n <= n_fft / 2)
+                return err(utt + "waveform too short for the reflection padding (need n_samples > filter_length / 2 = " + std::to_string(n_fft / 2) + ")");
+        }
+        return 0;
+    }
+
     // ---- packing: host only, so a caller validates utterance by utterance before anything is launched ------------------------------
     void pack_begin() { h_utts.clear(); n_frames = xp_rows = n_samples = max_span = 0; }
     // one more utterance of n samples of which T frames are kept; its padded signal starts at the next free multiple of hop

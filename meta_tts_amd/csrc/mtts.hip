@@ -58,6 +58,17 @@ struct mtts_stft {
     Vad vad;
 };
 
+// The three mtts_dvector_embed_wavs* entries: resample = through the handle's resampler; trim = through its trimmer, and through the
+// resampler when one is loaded.  A refusal is copied to the d-vector handle as well.
+static int embed_wavs_entry(const char* name, mtts_dvector* h, mtts_stft* stft, bool resample, bool trim, double target_dbfs, int increase_only, int n_utts,
+                            const int* n_samples, const float* wavs, PartialRule rule, EmbedOut o) {
+    if (!stft) { g_create_error = std::string(name) + ": NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
+    const WavPrep prep{&stft->m, resample || (trim && stft->rs.loaded()) ? &stft->rs : nullptr, trim ? &stft->vad : nullptr, target_dbfs, increase_only != 0};
+    const int rc = stft->se.embed_wavs(name, prep, h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, rule, o);
+    if (rc != 0 && h) h->d.set_error(stft->m.last_error);
+    return rc;
+}
+
 extern "C" {
 
 int mtts_create(const mtts_model_cfg* c, int device, int max_tasks, int max_B, int max_S, int max_T, mtts_handle** out) {
@@ -781,28 +792,19 @@ int mtts_dvector_embed_device(mtts_dvector* h, const float* mels_dev, int n_part
 }
 int mtts_dvector_embed_wavs(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
                             double min_coverage, float* out, int* n_partials_out, float* slices_out) {
-    if (!stft) { g_create_error = "mtts_dvector_embed_wavs: NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
-    const int rc = stft->se.embed_wavs(h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, partial_frames, frame_step, min_coverage, out,
-                                       n_partials_out, slices_out);
-    if (rc != 0 && h) h->d.set_error(stft->m.last_error);
-    return rc;
+    return embed_wavs_entry("mtts_dvector_embed_wavs", h, stft, false, false, 0.0, 0, n_utts, n_samples, wavs, {partial_frames, frame_step, min_coverage},
+                            {out, n_partials_out, slices_out, nullptr});
 }
 int mtts_dvector_embed_wavs_resampled(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
                                       double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out) {
-    if (!stft) { g_create_error = "mtts_dvector_embed_wavs_resampled: NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
-    const int rc = stft->se.embed_wavs(h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, partial_frames, frame_step, min_coverage, out,
-                                       n_partials_out, slices_out, &stft->rs, target_dbfs, increase_only);
-    if (rc != 0 && h) h->d.set_error(stft->m.last_error);
-    return rc;
+    return embed_wavs_entry("mtts_dvector_embed_wavs_resampled", h, stft, true, false, target_dbfs, increase_only, n_utts, n_samples, wavs,
+                            {partial_frames, frame_step, min_coverage}, {out, n_partials_out, slices_out, nullptr});
 }
 int mtts_dvector_embed_wavs_preprocessed(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
                                          double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out,
                                          int* n_trimmed_out) {
-    if (!stft) { g_create_error = "mtts_dvector_embed_wavs_preprocessed: NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
-    const int rc = stft->se.embed_wavs(h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, partial_frames, frame_step, min_coverage, out,
-                                       n_partials_out, slices_out, stft->rs.loaded() ? &stft->rs : nullptr, target_dbfs, increase_only, &stft->vad, n_trimmed_out);
-    if (rc != 0 && h) h->d.set_error(stft->m.last_error);
-    return rc;
+    return embed_wavs_entry("mtts_dvector_embed_wavs_preprocessed", h, stft, false, true, target_dbfs, increase_only, n_utts, n_samples, wavs,
+                            {partial_frames, frame_step, min_coverage}, {out, n_partials_out, slices_out, n_trimmed_out});
 }
 int mtts_dvector_cosine_indexed(mtts_dvector* h, const float* a, int n_a, const float* b, int n_b, int dim, int n, const int* index_a, const int* index_b,
                                 double eps, float* sim) {

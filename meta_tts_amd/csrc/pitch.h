@@ -185,14 +185,10 @@ public:
         const char* who = "mtts_stft_f0_batch: ";
         if (!loaded) return err(std::string(who) + "no pitch configuration loaded (mtts_stft_load_pitch)");
         if (n_utts < 1 || !n_samples || !wavs || !f0_out) return err(std::string(who) + "bad arguments (n_utts < 1 or NULL pointer)");
-        if (n_utts > 65535) return err(std::string(who) + "more than 65535 utterances in one call");
+        if (mf->check_utterances(who, n_utts, [&](int u) { return n_samples[u]; }, MelFront::UTT_GRID | MelFront::UTT_CAP)) return -1;
         mf->pack_begin();
         int max_T = 0;
         for (int u = 0; u < n_utts; ++u) {
-            if (n_samples[u] < 1) return err(std::string(who) + "utterance " + std::to_string(u) + ": n_samples < 1");
-            if (n_samples[u] > mf->cap_samples)
-                return err(std::string(who) + "utterance " + std::to_string(u) + ": " + std::to_string(n_samples[u]) + " samples exceed max_samples = " +
-                           std::to_string(mf->cap_samples));
             const int T = mf->frames_of(n_samples[u]);
             mf->pack_add(n_samples[u], T);
             max_T = std::max(max_T, T);

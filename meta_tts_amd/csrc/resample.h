@@ -168,24 +168,18 @@ public:
         return 0;
     }
 
-    // what both entries refuse before any launch
-    int check_lengths(const char* who, int n_utts, const int* n_in) {
-        if (!loaded()) return err(std::string(who) + "no resampler loaded (mtts_stft_load_resampler)");
-        for (int u = 0; u < n_utts; ++u) {
-            if (n_in[u] < 1) return err(std::string(who) + "utterance " + std::to_string(u) + ": n_in < 1");
-            if (out_len(n_in[u]) > mf->cap_samples)
-                return err(std::string(who) + "utterance " + std::to_string(u) + ": " + std::to_string(out_len(n_in[u])) + " resampled samples exceed max_samples = " +
-                           std::to_string(mf->cap_samples));
-        }
-        return 0;
+    // what both entries refuse before any launch (out_len(n_in) < 1 exactly when n_in < 1); checks: MelFront::UTT_GRID where the
+    // whole call is one launch
+    int check_lengths(const std::string& who, int n_utts, const int* n_in, int checks = 0) {
+        if (!loaded()) return err(who + "no resampler loaded (mtts_stft_load_resampler)");
+        return mf->check_utterances(who, n_utts, [&](int u) { return out_len(n_in[u]); }, checks | MelFront::UTT_CAP, true);
     }
 
     // host in, host out: wavs = the utterances one after another (n_in[u] samples each), out = the resampled ones one after another
     int resample_batch(int n_utts, const int* n_in, const float* wavs, double target_dbfs, int increase_only, float* out, double* gains_out) {
         const char* who = "mtts_stft_resample_batch: ";
         if (n_utts < 1 || !n_in || !wavs || !out) return err(std::string(who) + "bad arguments (n_utts < 1 or NULL pointer)");
-        if (n_utts > 65535) return err(std::string(who) + "more than 65535 utterances in one call");
-        if (check_lengths(who, n_utts, n_in)) return -1;
+        if (check_lengths(who, n_utts, n_in, MelFront::UTT_GRID)) return -1;
         table_begin();
         long long total = 0;
         for (int u = 0; u < n_utts; ++u) { table_add(n_in[u], total); total += out_len(n_in[u]); }

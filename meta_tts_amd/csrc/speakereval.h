@@ -9,9 +9,13 @@
 // projection, no log, no clamp — and `compute_partial_slices`: 160-frame windows every frame_step = round(16000 / rate / 160) frames
 // over ceil((n + 1) / 160) frames, the last one dropped when it covers less than min_coverage of its span and is not the only one,
 // the waveform zero-extended to the end of the last window kept.  Of `preprocess_wav`, resampling and -30 dBFS normalisation are
-// resample.h's (embed_wavs with a Resample: the chained entry) and silence trimming is vad.h's (embed_wavs with a Vad: all of
-// `preprocess_wav` chained; the detector is this project's, parity with webrtcvad is UNPINNED).  Without either, inputs are 16 kHz
-// waveforms as they are.
+// resample.h's and silence trimming is vad.h's (the detector is this project's, parity with webrtcvad is UNPINNED).  Without either,
+// inputs are 16 kHz waveforms as they are.
+//
+// embed_wavs is one function behind three entries, in three parts.  The plan: validate, cut the call into chunks, reserve every
+// buffer for the largest chunk.  The source (WavPrep): how a chunk's waveforms reach MelFront::wav — uploaded, resampled there, or
+// resampled / uploaded into the trimmer's staging buffer, trimmed and compacted there; it is the only place that knows which entry was
+// called.  The tail, shared: power mel, the partial windows, the gather, the encoder.
 //
 // MI355X layout.  All utterances of a chunk share every launch (melfront.h's packing): the reflect-pad kernel, ONE forward-STFT GEMM
 // with the rows between utterances dropped, stft_power_kernel (one wavefront per frame, HBM-bound: 2F floats in, F out), the mel GEMM,
@@ -129,6 +133,122 @@ inline int spk_partial_count(long long n, int hop, int frames, int step, double 
     return (int)std::min<long long>(cnt, 0x7fffffff);
 }
 
+// The partial rule and the outputs of an embed_wavs call.  out (with an encoder): [n_utts][E] d-vectors.  n_partials [n_utts].  slices
+// (or nullptr; required without an encoder): the partial stacks [sum N][frames][n_mel], all utterances one after another.  n_trimmed
+// (or nullptr; written with a Vad): the trimmed lengths.
+struct PartialRule { int frames, step; double min_coverage; };
+struct EmbedOut { float* out; int* n_partials; float* slices; int* n_trimmed; };
+
+// A chunk of a call: utterances [u0, u1) with N partials; src0 = its first sample in the waveforms WavPrep reads.
+struct Chunk { int u0, u1, N; long long src0; };
+
+// The host tables of one chunk.  Every one of them is the source of an asynchronous upload, so it stays alive, one ChunkTables per
+// chunk, until the call's final synchronise.
+struct ChunkTables {
+    std::vector<StftUtt> utts;   // MelFront's packing tables
+    std::vector<int> rowmap;
+    std::vector<int> win, off;   // first packed mel row of every partial; partials before every utterance
+    std::vector<RsUtt> rs;       // the resampler's table (WavPrep with a resampler and no trimmer)
+    std::vector<VadUtt> vad;     // the trimmer's
+    // the table a stage has just enqueued for upload moves here (a moved vector keeps its storage); the stage packs its next chunk into a fresh one
+    template <class T>
+    static void keep(std::vector<T>& kept, std::vector<T>& staged) { kept = std::move(staged); staged.clear(); }
+};
+
+// How a chunk's waveforms reach mf->wav: all that the three embed_wavs entries differ in.
+//   neither (mtts_dvector_embed_wavs): the waveforms are at the front-end's rate and are uploaded, zero-extended on the host.
+//   rs (.._resampled): n_samples counts SOURCE-rate samples; every chunk is resampled (and normalised to target_dbfs unless that is NaN)
+//     by rs straight into mf->wav over zeros, and the front-end rate's signal never visits the host.
+//   vad (.._preprocessed): every chunk's waveforms go (through rs when given, else as they are) into vad's staging buffer, are trimmed
+//     there, and the kept windows are compacted into mf->wav over zeros.  Chunks and capacities are planned from the untrimmed lengths
+//     (trimming only shortens, and the partial count never grows as a waveform shrinks); the partial rule then applies to the trimmed
+//     lengths, which the host reads back once per chunk (Vad::detect).
+// The chunking, the launches behind the waveform buffer and the results are those of the plain entry on the prepared waveforms.
+struct WavPrep {
+    MelFront* mf;
+    Resample* rs;
+    Vad* vad;
+    double target_dbfs;
+    bool increase_only;
+
+    int err(const std::string& s) const { return mf->err(s); }
+    bool plain() const { return !rs && !vad; }
+
+    // The refusals that are the stages' own, and h_n [n_utts]: every utterance's samples at the front-end's rate (before trimming).
+    int check(const std::string& who, int n_utts, const int* n_samples, std::vector<long long>& h_n) const {
+        if (rs && rs->check_lengths(who, n_utts, n_samples)) return -1;
+        if (vad && !rs && !std::isnan(target_dbfs))
+            return err(who + "volume normalisation needs a resampler (mtts_stft_load_resampler; the identity bank for waveforms at the front-end's rate)");
+        h_n.resize((size_t)n_utts);
+        for (int u = 0; u < n_utts; ++u) h_n[(size_t)u] = rs ? rs->out_len(n_samples[u]) : n_samples[u];
+        if (vad) {
+            if (vad->check_lengths(who, n_utts, h_n.data())) return -1;
+            if (vad->c.W <= mf->n_fft / 2)
+                return err(who + "a VAD window of " + std::to_string(vad->c.W) + " samples is too short for the reflection padding (need more than filter_length / 2 = " +
+                           std::to_string(mf->n_fft / 2) + ")");
+        }
+        return mf->check_utterances(who, n_utts, [&](int u) { return h_n[(size_t)u]; }, MelFront::UTT_PAD);
+    }
+
+    // The stages' buffers for the largest chunk: its source samples, its samples at the front-end's rate, slots, windows and utterances.
+    int reserve(const std::string& who, const std::vector<Chunk>& chunks, const int* n_samples, const long long* h_n) const {
+        if (plain()) return 0;
+        long long max_src = 0, max_n = 0, max_slots = 0, max_win = 0;
+        size_t max_utts = 0;
+        for (const Chunk& c : chunks) {
+            long long n_src = 0, n = 0, slots = 0, nw = 0;
+            for (int u = c.u0; u < c.u1; ++u) {
+                n_src += n_samples[u];
+                n += h_n[u];
+                if (rs) slots += (h_n[u] + rs->run - 1) / rs->run;
+                if (vad) nw += h_n[u] / vad->c.W;
+            }
+            max_src = std::max(max_src, n_src);
+            max_n = std::max(max_n, n);
+            max_slots = std::max(max_slots, slots);
+            max_win = std::max(max_win, nw);
+            max_utts = std::max(max_utts, (size_t)(c.u1 - c.u0));
+        }
+        if (max_src > (1LL << 31) - 1 || (vad && max_n > (1LL << 31) - 1)) return err(who + "too many samples in one chunk");
+        return (rs && rs->reserve(max_src, max_slots, max_utts)) || (vad && vad->reserve(max_n, max_win, max_utts, false)) ? -1 : 0;
+    }
+
+    // Before packing.  With a trimmer: the untrimmed waveforms into its staging buffer, the mask, and the chunk's trimmed lengths back
+    // into h_n (synchronises mf->stream: the resampler's table is free again).  Without one the lengths stand.
+    int lengths(const Chunk& c, const int* n_samples, const float* src, long long* h_n) const {
+        if (!vad) return 0;
+        vad->table_begin();
+        for (int u = c.u0; u < c.u1; ++u) vad->table_add(h_n[u]);
+        if (rs) {
+            rs->table_begin();
+            for (int u = c.u0; u < c.u1; ++u) rs->table_add(n_samples[u], vad->h_utts[(size_t)(u - c.u0)].src0);
+            if (rs->launch(src + c.src0, target_dbfs, increase_only, vad->stage.p)) return -1;
+        } else
+            DEV_CHECK(hipMemcpyAsync(vad->stage.p, src + c.src0, (size_t)vad->n_src * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+        if (vad->detect(nullptr)) return -1;
+        for (int u = c.u0; u < c.u1; ++u) h_n[u] = vad->h_nout[2 * (size_t)(u - c.u0)];
+        return 0;
+    }
+
+    // After packing: the chunk's waveforms into mf->wav at the places MelFront has packed, and the reflect-padded signals.  The stages
+    // write over zeros: the zero-extension to the last partial window's end.
+    int fill(const Chunk& c, const int* n_samples, const float* src, ChunkTables& t) const {
+        if (plain()) return mf->pad_waveforms(src + c.src0, false, true);
+        DEV_CHECK(hipMemsetAsync(mf->wav.p, 0, (size_t)mf->n_samples * sizeof(float), mf->stream));
+        if (vad) {   // the kept windows
+            for (int u = c.u0; u < c.u1; ++u) vad->h_utts[(size_t)(u - c.u0)].dst0 = mf->h_utts[(size_t)(u - c.u0)].wav0;
+            if (vad->compact(mf->wav.p)) return -1;
+            ChunkTables::keep(t.vad, vad->h_utts);
+        } else {     // source-rate samples up, resampled
+            rs->table_begin();
+            for (int u = c.u0; u < c.u1; ++u) rs->table_add(n_samples[u], mf->h_utts[(size_t)(u - c.u0)].wav0);
+            if (rs->launch(src + c.src0, target_dbfs, increase_only)) return -1;
+            ChunkTables::keep(t.rs, rs->h_utts);
+        }
+        return mf->pad_staged(false, true);
+    }
+};
+
 class SpeakerEval {
 public:
     MelFront* mf = nullptr;
@@ -136,17 +256,12 @@ public:
     DevBuf<float> stack;    // [N][frames][n_mel]: the partial utterances of a chunk
     DevBuf<int> win;        // first packed mel row of every partial
     hipEvent_t ev_front = nullptr, ev_enc = nullptr;
-    std::vector<float> h_wav;                  // the call's waveforms, zero-extended
-    std::vector<long long> h_ext;
-    std::vector<int> h_cnt;
-    std::vector<std::vector<int>> h_win, h_off;   // per chunk (alive until the call's last copy has been enqueued and waited for)
-    std::vector<std::vector<StftUtt>> keep_utts;  // MelFront's packing tables of the chunks already enqueued, kept for the same reason
-    std::vector<std::vector<int>> keep_maps;
-    std::vector<std::vector<RsUtt>> keep_rs;      // and the resampler's tables (embed_wavs with a resampler)
-    std::vector<std::vector<VadUtt>> keep_vad;    // and the trimmer's (embed_wavs with a Vad)
-    std::vector<long long> h_n;                   // samples per utterance at the front-end's rate
-    struct Chunk { int u0, u1, N; };
+    std::vector<float> h_wav;       // the plain entry's waveforms, zero-extended
+    std::vector<long long> h_n;     // per utterance: samples at the front-end's rate,
+    std::vector<long long> h_ext;   // the length it is zero-extended to,
+    std::vector<int> h_cnt;         // and its partials
     std::vector<Chunk> chunks;
+    std::vector<ChunkTables> tables;
 
     int err(const std::string& s) { return mf->err(s); }
 
@@ -167,11 +282,7 @@ public:
         const char* who = "mtts_stft_power_mel_batch: ";
         if (!mf->have_basis || !mf->have_mel) return err(std::string(who) + "STFT bases not loaded");
         if (n_utts < 1 || !n_samples || !wavs || !mel_host) return err(std::string(who) + "bad arguments (n_utts < 1 or NULL pointer)");
-        if (n_utts > 65535) return err(std::string(who) + "more than 65535 utterances in one call");
-        for (int u = 0; u < n_utts; ++u)
-            if (n_samples[u] <= mf->n_fft / 2)
-                return err(std::string(who) + "utterance " + std::to_string(u) + ": waveform too short for the reflection padding (need n_samples > filter_length / 2 = " +
-                           std::to_string(mf->n_fft / 2) + ")");
+        if (mf->check_utterances(who, n_utts, [&](int u) { return n_samples[u]; }, MelFront::UTT_GRID | MelFront::UTT_PAD)) return -1;
         mf->pack_begin();
         for (int u = 0; u < n_utts; ++u) mf->pack_add(n_samples[u], mf->frames_of(n_samples[u]));
         if (mf->stage("mtts_stft_power_mel_batch", true) || mf->pad_waveforms(wavs, false, true)) return -1;
@@ -182,197 +293,144 @@ public:
         return 0;
     }
 
-    // dv != nullptr: out [n_utts][E] d-vectors.  slices_out != nullptr: the partial stacks [sum N][frames][n_mel] (all utterances one
-    // after another).  n_partials_out [n_utts].  Everything that can be refused is refused before the first launch.
-    // rs != nullptr (mtts_dvector_embed_wavs_resampled): n_samples counts SOURCE-rate samples; every chunk is resampled (and normalised
-    // to target_dbfs unless that is NaN) by rs straight into mf->wav, zero-extended there, and the front-end rate's signal never
-    // visits the host.  The chunking, the launches behind the waveform buffer and the results are those of the plain entry on the
-    // resampled waveforms.
-    // vad != nullptr (mtts_dvector_embed_wavs_preprocessed): every chunk's waveforms go (through rs when given, else as they are) into
-    // vad's staging buffer, are trimmed there, and the kept windows are compacted into mf->wav over zeros.  Chunks and capacities are
-    // planned from the untrimmed lengths (trimming only shortens, and the partial count never grows as a waveform shrinks); the partial
-    // rule then applies to the trimmed lengths, which the host reads back once per chunk (Vad::detect).  n_trimmed_out (or nullptr):
-    // the trimmed lengths.  slices_out holds the partials of the trimmed utterances one after another.
-    int embed_wavs(DVector* dv, int dv_device, int n_utts, const int* n_samples, const float* wavs, int frames, int step, double min_coverage, float* out,
-                   int* n_partials_out, float* slices_out, Resample* rs = nullptr, double target_dbfs = 0.0, int increase_only = 0, Vad* vad = nullptr,
-                   int* n_trimmed_out = nullptr) {
-        const char* who = vad ? "mtts_dvector_embed_wavs_preprocessed: " : rs ? "mtts_dvector_embed_wavs_resampled: " : "mtts_dvector_embed_wavs: ";
-        const int hop = mf->hop, n_mel = mf->n_mel;
-        if (!mf->have_basis || !mf->have_mel) return err(std::string(who) + "STFT bases not loaded");
-        if (n_utts < 1 || !n_samples || !wavs || !n_partials_out) return err(std::string(who) + "bad arguments (n_utts < 1 or NULL n_samples / wavs / n_partials_out)");
-        if (dv ? !out : !slices_out) return err(std::string(who) + "NULL output (out with an encoder, slices_out without one)");
-        if (frames < 1 || step < 1 || step > frames || !(min_coverage > 0.0 && min_coverage <= 1.0))
-            return err(std::string(who) + "bad partial rule (need 1 <= frame_step <= partial_frames, 0 < min_coverage <= 1)");
-        if (n_mel & 3) return err(std::string(who) + "n_mel % 4 != 0");
-        if (dv) {
-            if (dv_device != device) return err(std::string(who) + "the encoder and the STFT handle are on different devices");
-            if (dv->n_mels != n_mel || dv->T != frames)
-                return err(std::string(who) + "the encoder expects partials of " + std::to_string(dv->T) + " x " + std::to_string(dv->n_mels) + ", the front-end makes " +
-                           std::to_string(frames) + " x " + std::to_string(n_mel));
-        }
-        if (rs && rs->check_lengths(who, n_utts, n_samples)) return -1;
-        h_ext.resize((size_t)n_utts);
-        h_cnt.resize((size_t)n_utts);
-        h_n.resize((size_t)n_utts);
-        if (vad) {
-            if (!rs && !std::isnan(target_dbfs))
-                return err(std::string(who) + "volume normalisation needs a resampler (mtts_stft_load_resampler; the identity bank for waveforms at the front-end's rate)");
-            for (int u = 0; u < n_utts; ++u) h_n[(size_t)u] = rs ? rs->out_len(n_samples[u]) : n_samples[u];
-            if (vad->check_lengths(who, n_utts, h_n.data())) return -1;
-            if (vad->c.W <= mf->n_fft / 2)
-                return err(std::string(who) + "a VAD window of " + std::to_string(vad->c.W) + " samples is too short for the reflection padding (need more than filter_length / 2 = " +
-                           std::to_string(mf->n_fft / 2) + ")");
-        }
-        long long total = 0, total_parts = 0;
-        for (int u = 0; u < n_utts; ++u) {
-            const std::string utt = std::string(who) + "utterance " + std::to_string(u) + ": ";
-            const long long n = h_n[(size_t)u] = rs ? rs->out_len(n_samples[u]) : n_samples[u];
-            if (n <= mf->n_fft / 2)
-                return err(utt + "waveform too short for the reflection padding (need n_samples > filter_length / 2 = " + std::to_string(mf->n_fft / 2) + ")");
-            h_cnt[(size_t)u] = spk_partial_count(n, hop, frames, step, min_coverage, &h_ext[(size_t)u]);
-            if (dv && h_cnt[(size_t)u] > dv->cap_N)
-                return err(utt + std::to_string(h_cnt[(size_t)u]) + " partial utterances exceed the encoder's max_partials = " + std::to_string(dv->cap_N));
-            if (h_ext[(size_t)u] > 0x7fffffffLL - hop) return err(utt + "too long");
-            total += h_ext[(size_t)u];
-            total_parts += h_cnt[(size_t)u];
-        }
-        if (total_parts > (1LL << 30) / ((long long)frames * n_mel)) return err(std::string(who) + "too many partial utterances in one call");
-        if (dv && dv->dirty && dv->refresh() != 0) return err(std::string(who) + dv->last_error);
+    // The three mtts_dvector_embed_wavs* entries (name: the one called; prep: what tells them apart).  dv == nullptr: the front-end only.
+    // Everything that can be refused is refused before the first launch.
+    int embed_wavs(const char* name, const WavPrep& prep, DVector* dv, int dv_device, int n_utts, const int* n_samples, const float* wavs, const PartialRule& r,
+                   const EmbedOut& o) {
+        const std::string who = std::string(name) + ": ";
+        if (validate(who, prep, dv, dv_device, n_utts, n_samples, wavs, r, o)) return -1;
         const bool two_streams = dv && dv->stream != mf->stream;
         if (two_streams) { DEV_CHECK(mf->mem.event(ev_front)); DEV_CHECK(mf->mem.event(ev_enc)); }
-        if (!rs && !vad) {
-            h_wav.assign((size_t)total, 0.f);
-            long long src = 0, dst = 0;
-            for (int u = 0; u < n_utts; ++u) {
-                std::copy(wavs + src, wavs + src + n_samples[u], h_wav.begin() + dst);
-                src += n_samples[u];
-                dst += h_ext[(size_t)u];
-            }
-        }
-        for (int u = 0; u < n_utts; ++u) n_partials_out[u] = h_cnt[(size_t)u];
-        h_win.clear();
-        h_off.clear();
-        keep_utts.clear();
-        keep_maps.clear();
-        keep_rs.clear();
-        keep_vad.clear();
-        chunks.clear();
-        int max_N = 0;
-        for (int u0 = 0; u0 < n_utts;) {   // a chunk: consecutive utterances within the encoder's capacity (front-end only: the whole call)
-            int u1 = u0, N = 0;
-            while (u1 < n_utts && u1 - u0 < 65535 && (!dv || (N + h_cnt[(size_t)u1] <= dv->cap_N && u1 - u0 < dv->cap_B))) N += h_cnt[(size_t)u1++];   // (65535: the pad kernel's gridDim.y)
-            chunks.push_back(Chunk{u0, u1, N});
-            max_N = std::max(max_N, N);
-            u0 = u1;
-        }
-        const int span4 = frames * n_mel / 4, per = std::min((span4 + 255) / 256, 8);
+        const float* src = prep.plain() ? zero_extended(n_utts, n_samples, wavs) : wavs;
+        for (int u = 0; u < n_utts; ++u) o.n_partials[u] = h_cnt[(size_t)u];
+        const int max_N = plan(dv, n_utts, n_samples, prep.plain());
         // sized once for the largest chunk, before the first launch: a later, larger chunk must not free the stack the previous chunk's
-        // encoder still reads on the other stream
-        if (mf->grow(stack, (size_t)max_N * span4 * 4 + 64, "partial utterances") || mf->grow(win, (size_t)max_N, "windows")) return -1;
-        if (rs) {   // the same for the resampler's buffers: the largest chunk's source samples, slots and utterances
-            long long max_src = 0, max_slots = 0;
-            size_t max_utts = 0;
-            for (const Chunk& c : chunks) {
-                long long n_src = 0, slots = 0;
-                for (int u = c.u0; u < c.u1; ++u) { n_src += n_samples[u]; slots += (h_n[(size_t)u] + rs->run - 1) / rs->run; }
-                max_src = std::max(max_src, n_src);
-                max_slots = std::max(max_slots, slots);
-                max_utts = std::max(max_utts, (size_t)(c.u1 - c.u0));
-            }
-            if (max_src > (1LL << 31) - 1) return err(std::string(who) + "too many samples in one chunk");
-            if (rs->reserve(max_src, max_slots, max_utts)) return -1;
-        }
-        if (vad) {   // and for the trimmer's: the largest chunk's untrimmed samples, windows and utterances
-            long long max_n = 0, max_win = 0;
-            size_t max_utts = 0;
-            for (const Chunk& c : chunks) {
-                long long n = 0, nw = 0;
-                for (int u = c.u0; u < c.u1; ++u) { n += h_n[(size_t)u]; nw += h_n[(size_t)u] / vad->c.W; }
-                max_n = std::max(max_n, n);
-                max_win = std::max(max_win, nw);
-                max_utts = std::max(max_utts, (size_t)(c.u1 - c.u0));
-            }
-            if (max_n > (1LL << 31) - 1) return err(std::string(who) + "too many samples in one chunk");
-            if (vad->reserve(max_n, max_win, max_utts, false)) return -1;
-        }
-        long long wav0 = 0, src0 = 0, part0 = 0;
+        // encoder still reads on the other stream (and the same for the stages' buffers)
+        if (mf->grow(stack, (size_t)max_N * span4(r) * 4 + 64, "partial utterances") || mf->grow(win, (size_t)max_N, "windows") ||
+            prep.reserve(who, chunks, n_samples, h_n.data()))
+            return -1;
+        tables.clear();
+        tables.resize(chunks.size());
+        long long part0 = 0;
         for (size_t c = 0; c < chunks.size(); ++c) {
-            const int u0 = chunks[c].u0, u1 = chunks[c].u1;
-            int N = chunks[c].N;
-            if (vad) {   // untrimmed waveforms into the staging buffer, the mask, and the trimmed lengths back: the partial rule is theirs
-                vad->table_begin();
-                for (int u = u0; u < u1; ++u) vad->table_add(h_n[(size_t)u]);
-                if (rs) {
-                    rs->table_begin();
-                    for (int u = u0; u < u1; ++u) rs->table_add(n_samples[u], vad->h_utts[(size_t)(u - u0)].src0);
-                    if (rs->launch(wavs + src0, target_dbfs, increase_only != 0, vad->stage.p)) return -1;
-                    src0 += rs->n_src;
-                } else {
-                    DEV_CHECK(hipMemcpyAsync(vad->stage.p, wavs + src0, (size_t)vad->n_src * sizeof(float), hipMemcpyHostToDevice, mf->stream));
-                    src0 += vad->n_src;
-                }
-                if (vad->detect(nullptr)) return -1;   // (synchronises mf->stream: the resampler's table is free again)
-                N = 0;
-                for (int u = u0; u < u1; ++u) {
-                    const int n = vad->h_nout[2 * (size_t)(u - u0)];
-                    n_partials_out[u] = h_cnt[(size_t)u] = spk_partial_count(n, hop, frames, step, min_coverage, &h_ext[(size_t)u]);
-                    if (n_trimmed_out) n_trimmed_out[u] = n;
-                    N += h_cnt[(size_t)u];
-                }
-            }
-            mf->pack_begin();
-            for (int u = u0; u < u1; ++u) mf->pack_add(h_ext[(size_t)u], mf->frames_of((int)h_ext[(size_t)u]));
-            if (mf->stage("mtts_dvector_embed_wavs", true)) return -1;
-            if (vad) {   // the kept windows into mf->wav over zeros (the zero-extension to the last partial window's end)
-                DEV_CHECK(hipMemsetAsync(mf->wav.p, 0, (size_t)mf->n_samples * sizeof(float), mf->stream));
-                for (int u = u0; u < u1; ++u) vad->h_utts[(size_t)(u - u0)].dst0 = mf->h_utts[(size_t)(u - u0)].wav0;
-                if (vad->compact(mf->wav.p) || mf->pad_staged(false, true)) return -1;
-                keep_vad.emplace_back(std::move(vad->h_utts));
-                vad->h_utts.clear();
-            } else if (rs) {   // source-rate samples up, resampled into mf->wav over zeros (the zero-extension to the last window's end)
-                DEV_CHECK(hipMemsetAsync(mf->wav.p, 0, (size_t)mf->n_samples * sizeof(float), mf->stream));
-                rs->table_begin();
-                for (int u = u0; u < u1; ++u) rs->table_add(n_samples[u], mf->h_utts[(size_t)(u - u0)].wav0);
-                if (rs->launch(wavs + src0, target_dbfs, increase_only != 0) || mf->pad_staged(false, true)) return -1;
-                keep_rs.emplace_back(std::move(rs->h_utts));
-                rs->h_utts.clear();
-                src0 += rs->n_src;
-            } else if (mf->pad_waveforms(h_wav.data() + wav0, false, true)) return -1;
-            power_mel();
-            h_win.emplace_back();
-            h_off.emplace_back(1, 0);
-            std::vector<int>& wv = h_win.back();
-            std::vector<int>& off = h_off.back();
-            for (int u = u0; u < u1; ++u) {
-                const StftUtt& q = mf->h_utts[(size_t)(u - u0)];
-                for (int p = 0; p < h_cnt[(size_t)u]; ++p) {
-                    if (p * step + frames > q.T) return err(std::string(who) + "internal: a window ends past its utterance's frames");
-                    wv.push_back(q.frame0 + p * step);
-                }
-                off.push_back((int)wv.size());
-            }
-            // the tables stage() has just enqueued for upload stay alive (a moved vector keeps its storage); MelFront packs the next chunk into fresh ones
-            keep_utts.emplace_back(std::move(mf->h_utts));
-            keep_maps.emplace_back(std::move(mf->h_rowmap));
-            mf->h_utts.clear();
-            mf->h_rowmap.clear();
-            DEV_CHECK(hipMemcpyAsync(win.p, wv.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, mf->stream));
-            if (two_streams && c > 0) DEV_CHECK(hipStreamWaitEvent(mf->stream, ev_enc, 0));   // the previous chunk's encoder still reads the stack
-            MTTS_LAUNCH(spk_gather_kernel, dim3((unsigned)N * (unsigned)per), dim3(256), mf->stream, (const float*)mf->mel, (const int*)win.p, n_mel, span4, per,
-                        stack.p);
-            if (mf->check_launch()) return -1;
-            if (slices_out)
-                DEV_CHECK(hipMemcpyAsync(slices_out + part0 * span4 * 4, stack.p, (size_t)N * span4 * 4 * sizeof(float), hipMemcpyDeviceToHost, mf->stream));
-            if (dv) {
-                if (two_streams) { DEV_CHECK(hipEventRecord(ev_front, mf->stream)); DEV_CHECK(hipStreamWaitEvent(dv->stream, ev_front, 0)); }
-                if (dv->forward_device(stack.p, N, off.data(), u1 - u0, out + (long long)u0 * dv->E, nullptr, false) != 0) return err(std::string(who) + dv->last_error);
-                if (two_streams) DEV_CHECK(hipEventRecord(ev_enc, dv->stream));
-            }
-            for (int u = u0; u < u1; ++u) wav0 += h_ext[(size_t)u];
-            part0 += N;
+            if (front(name, prep, chunks[c], n_samples, src, r, o, tables[c]) || tail(who, chunks[c], tables[c], dv, c > 0, part0, r, o)) return -1;
+            part0 += chunks[c].N;
         }
         if (dv) DEV_CHECK(hipStreamSynchronize(dv->stream));
         DEV_CHECK(hipStreamSynchronize(mf->stream));
+        return 0;
+    }
+
+    int span4(const PartialRule& r) const { return r.frames * mf->n_mel / 4; }
+
+    // the arguments, the stages' refusals, and per utterance the partial count and the zero-extended length (h_n, h_cnt, h_ext)
+    int validate(const std::string& who, const WavPrep& prep, DVector* dv, int dv_device, int n_utts, const int* n_samples, const float* wavs, const PartialRule& r,
+                 const EmbedOut& o) {
+        const int n_mel = mf->n_mel;
+        if (!mf->have_basis || !mf->have_mel) return err(who + "STFT bases not loaded");
+        if (n_utts < 1 || !n_samples || !wavs || !o.n_partials) return err(who + "bad arguments (n_utts < 1 or NULL n_samples / wavs / n_partials_out)");
+        if (dv ? !o.out : !o.slices) return err(who + "NULL output (out with an encoder, slices_out without one)");
+        if (r.frames < 1 || r.step < 1 || r.step > r.frames || !(r.min_coverage > 0.0 && r.min_coverage <= 1.0))
+            return err(who + "bad partial rule (need 1 <= frame_step <= partial_frames, 0 < min_coverage <= 1)");
+        if (n_mel & 3) return err(who + "n_mel % 4 != 0");
+        if (dv) {
+            if (dv_device != device) return err(who + "the encoder and the STFT handle are on different devices");
+            if (dv->n_mels != n_mel || dv->T != r.frames)
+                return err(who + "the encoder expects partials of " + std::to_string(dv->T) + " x " + std::to_string(dv->n_mels) + ", the front-end makes " +
+                           std::to_string(r.frames) + " x " + std::to_string(n_mel));
+        }
+        if (prep.check(who, n_utts, n_samples, h_n)) return -1;
+        h_ext.resize((size_t)n_utts);
+        h_cnt.resize((size_t)n_utts);
+        long long total_parts = 0;
+        for (int u = 0; u < n_utts; ++u) {
+            const std::string utt = who + "utterance " + std::to_string(u) + ": ";
+            h_cnt[(size_t)u] = spk_partial_count(h_n[(size_t)u], mf->hop, r.frames, r.step, r.min_coverage, &h_ext[(size_t)u]);
+            if (dv && h_cnt[(size_t)u] > dv->cap_N)
+                return err(utt + std::to_string(h_cnt[(size_t)u]) + " partial utterances exceed the encoder's max_partials = " + std::to_string(dv->cap_N));
+            if (h_ext[(size_t)u] > 0x7fffffffLL - mf->hop) return err(utt + "too long");
+            total_parts += h_cnt[(size_t)u];
+        }
+        if (total_parts > (1LL << 30) / ((long long)r.frames * n_mel)) return err(who + "too many partial utterances in one call");
+        if (dv && dv->dirty && dv->refresh() != 0) return err(who + dv->last_error);
+        return 0;
+    }
+
+    // the plain entry's waveforms, every one zero-extended to the end of its last partial window
+    const float* zero_extended(int n_utts, const int* n_samples, const float* wavs) {
+        long long total = 0, src = 0, dst = 0;
+        for (int u = 0; u < n_utts; ++u) total += h_ext[(size_t)u];
+        h_wav.assign((size_t)total, 0.f);
+        for (int u = 0; u < n_utts; ++u) {
+            std::copy(wavs + src, wavs + src + n_samples[u], h_wav.begin() + dst);
+            src += n_samples[u];
+            dst += h_ext[(size_t)u];
+        }
+        return h_wav.data();
+    }
+
+    // A chunk: consecutive utterances within the encoder's capacity (front-end only: the whole call; 65535: the pad kernel's gridDim.y).
+    // Returns the partials of the largest.
+    int plan(const DVector* dv, int n_utts, const int* n_samples, bool plain) {
+        chunks.clear();
+        int max_N = 0;
+        long long src0 = 0;
+        for (int u0 = 0; u0 < n_utts;) {
+            Chunk c{u0, u0, 0, src0};
+            while (c.u1 < n_utts && c.u1 - u0 < 65535 && (!dv || (c.N + h_cnt[(size_t)c.u1] <= dv->cap_N && c.u1 - u0 < dv->cap_B))) {
+                src0 += plain ? h_ext[(size_t)c.u1] : n_samples[c.u1];
+                c.N += h_cnt[(size_t)c.u1++];
+            }
+            chunks.push_back(c);
+            max_N = std::max(max_N, c.N);
+            u0 = c.u1;
+        }
+        return max_N;
+    }
+
+    // One chunk up to its mel: the lengths (with a trimmer: the trimmed ones, and the partial rule on them), packing, waveforms, front-end.
+    int front(const char* name, const WavPrep& prep, Chunk& c, const int* n_samples, const float* src, const PartialRule& r, const EmbedOut& o, ChunkTables& t) {
+        if (prep.lengths(c, n_samples, src, h_n.data())) return -1;
+        if (prep.vad) {
+            c.N = 0;
+            for (int u = c.u0; u < c.u1; ++u) {
+                o.n_partials[u] = h_cnt[(size_t)u] = spk_partial_count(h_n[(size_t)u], mf->hop, r.frames, r.step, r.min_coverage, &h_ext[(size_t)u]);
+                if (o.n_trimmed) o.n_trimmed[u] = (int)h_n[(size_t)u];
+                c.N += h_cnt[(size_t)u];
+            }
+        }
+        mf->pack_begin();
+        for (int u = c.u0; u < c.u1; ++u) mf->pack_add(h_ext[(size_t)u], mf->frames_of((int)h_ext[(size_t)u]));
+        if (mf->stage(name, true) || prep.fill(c, n_samples, src, t)) return -1;
+        power_mel();
+        return 0;
+    }
+
+    // The shared tail: the chunk's windows out of the packed mel into the partial stack, and the encoder on it.  With the two handles
+    // on different streams, every chunk but the first waits for the previous chunk's encoder, which still reads the stack.
+    int tail(const std::string& who, const Chunk& c, ChunkTables& t, DVector* dv, bool wait_enc, long long part0, const PartialRule& r, const EmbedOut& o) {
+        const bool two_streams = dv && dv->stream != mf->stream;
+        const int s4 = span4(r), per = std::min((s4 + 255) / 256, 8);
+        t.off.assign(1, 0);
+        for (int u = c.u0; u < c.u1; ++u) {
+            const StftUtt& q = mf->h_utts[(size_t)(u - c.u0)];
+            for (int p = 0; p < h_cnt[(size_t)u]; ++p) {
+                if (p * r.step + r.frames > q.T) return err(who + "internal: a window ends past its utterance's frames");
+                t.win.push_back(q.frame0 + p * r.step);
+            }
+            t.off.push_back((int)t.win.size());
+        }
+        ChunkTables::keep(t.utts, mf->h_utts);
+        ChunkTables::keep(t.rowmap, mf->h_rowmap);
+        DEV_CHECK(hipMemcpyAsync(win.p, t.win.data(), (size_t)c.N * sizeof(int), hipMemcpyHostToDevice, mf->stream));
+        if (two_streams && wait_enc) DEV_CHECK(hipStreamWaitEvent(mf->stream, ev_enc, 0));
+        MTTS_LAUNCH(spk_gather_kernel, dim3((unsigned)c.N * (unsigned)per), dim3(256), mf->stream, (const float*)mf->mel, (const int*)win.p, mf->n_mel, s4, per, stack.p);
+        if (mf->check_launch()) return -1;
+        if (o.slices) DEV_CHECK(hipMemcpyAsync(o.slices + part0 * s4 * 4, stack.p, (size_t)c.N * s4 * 4 * sizeof(float), hipMemcpyDeviceToHost, mf->stream));
+        if (!dv) return 0;
+        if (two_streams) { DEV_CHECK(hipEventRecord(ev_front, mf->stream)); DEV_CHECK(hipStreamWaitEvent(dv->stream, ev_front, 0)); }
+        if (dv->forward_device(stack.p, c.N, t.off.data(), c.u1 - c.u0, o.out + (long long)c.u0 * dv->E, nullptr, false) != 0) return err(who + dv->last_error);
+        if (two_streams) DEV_CHECK(hipEventRecord(ev_enc, dv->stream));
         return 0;
     }
 };

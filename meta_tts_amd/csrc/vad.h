@@ -222,16 +222,13 @@ public:
 
     // what both entries refuse before any launch; n[u] = samples at the rate the detector runs at
     template <class Len>
-    int check_lengths(const char* who, int n_utts, const Len* n) {
-        if (!loaded) return err(std::string(who) + "no VAD configuration loaded (mtts_stft_load_vad)");
-        if (n_utts > 65535) return err(std::string(who) + "more than 65535 utterances in one call");
-        for (int u = 0; u < n_utts; ++u) {
-            const std::string utt = std::string(who) + "utterance " + std::to_string(u) + ": ";
-            if (n[u] < 1) return err(utt + "n_samples < 1");
-            if (n[u] > mf->cap_samples) return err(utt + std::to_string(n[u]) + " samples exceed max_samples = " + std::to_string(mf->cap_samples));
+    int check_lengths(const std::string& who, int n_utts, const Len* n) {
+        if (!loaded) return err(who + "no VAD configuration loaded (mtts_stft_load_vad)");
+        if (mf->check_utterances(who, n_utts, [&](int u) { return n[u]; }, MelFront::UTT_GRID | MelFront::UTT_CAP)) return -1;
+        for (int u = 0; u < n_utts; ++u)
             if (n[u] / c.W > VAD_MAX_W)
-                return err(utt + std::to_string(n[u] / c.W) + " windows of " + std::to_string(c.W) + " samples exceed the " + std::to_string(VAD_MAX_W) + " a workgroup holds");
-        }
+                return err(who + "utterance " + std::to_string(u) + ": " + std::to_string(n[u] / c.W) + " windows of " + std::to_string(c.W) + " samples exceed the " +
+                           std::to_string(VAD_MAX_W) + " a workgroup holds");
         return 0;
     }
 

@@ -26,7 +26,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .audio.stft import _Handle, forward_basis, mel_filterbank
+from .audio.stft import _Handle, _pack_wavs, forward_basis, mel_filterbank
 from .engine import MttsError
 from .speaker_encoder import EMBED, HIDDEN, LAYERS, MEL_N_CHANNELS, PARTIAL_FRAMES, DVectorEncoder
 
@@ -100,16 +100,9 @@ class SpeakerEmbedder:
             self.encoder.close()
         self._dev.close()
 
-    @staticmethod
-    def _pack(wavs):
-        ws = [np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1)) for w in wavs]
-        if not ws:
-            raise MttsError("no waveforms")
-        return ws, np.asarray([len(w) for w in ws], np.int32), np.ascontiguousarray(np.concatenate(ws))
-
     def wav_to_mel_spectrogram(self, wavs) -> List[np.ndarray]:
         """resemblyzer's `wav_to_mel_spectrogram` for a list of waveforms: [(T_u, 40) float32], T_u = len // 160 + 1."""
-        ws, n, packed = self._pack(wavs)
+        ws, n, packed = _pack_wavs(wavs)
         T = n // HOP + 1
         mel = np.empty((int(T.sum()), MEL_N_CHANNELS), np.float32)
         self._dev.check(self.lib.mtts_stft_power_mel_batch(self._dev.h, len(ws), _ptr(n), _ptr(packed), _ptr(mel)))
@@ -136,51 +129,41 @@ class SpeakerEmbedder:
         return self._trimmers[key]
 
     def _run(self, wavs, want_vectors: bool, want_slices: bool, source_rate=None, normalize_dbfs=None, increase_only=True, trim=False):
-        ws, n, packed = self._pack(wavs)
-        rs = None
+        """One chained entry for all waveforms: the plain one, the resampled one (source_rate), or all of `preprocess_wav` (trim)."""
+        ws, n, packed = _pack_wavs(wavs)
+        rs = vad = None
         if trim and source_rate is None:
             source_rate = SAMPLING_RATE      # the chained entry resamples with whatever bank the handle holds: make it the identity
         if source_rate is not None:
             rs = self.resampler(source_rate)
-            if getattr(self._dev, "_resampler_key", None) != rs._key:
-                rs.load()
+            rs.ensure_loaded()
         elif normalize_dbfs is not None:
             raise ValueError("normalize_dbfs needs source_rate (16000 for waveforms that are at the encoder's rate already)")
+        # from the untrimmed 16 kHz lengths: with trim they bound the partials, and the entry reports the trimmed lengths and their counts
         counts = np.asarray([len(compute_partial_slices(rs.output_length(int(k)) if rs else int(k), self.rate, self.min_coverage)[1]) for k in n], np.int32)
         if trim:
-            return self._run_trimmed(ws, n, packed, counts, want_vectors, want_slices, normalize_dbfs, increase_only, trim)
-        got = np.empty(len(ws), np.int32)
-        out = np.empty((len(ws), self.emb), np.float32) if want_vectors else None
-        slices = np.empty((int(counts.sum()), PARTIAL_FRAMES, MEL_N_CHANNELS), np.float32) if want_slices else None
-        enc = self.encoder.h if want_vectors else None
-        outs = (_ptr(out) if want_vectors else None, _ptr(got), _ptr(slices) if want_slices else None)
-        if rs is None:
-            self._dev.check(self.lib.mtts_dvector_embed_wavs(enc, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step,
-                                                             float(self.min_coverage), *outs))
-        else:   # resampled (and normalised) on the device, chunk by chunk, into the packed waveform buffer
-            self._dev.check(self.lib.mtts_dvector_embed_wavs_resampled(enc, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step,
-                                                                       float(self.min_coverage), float("nan") if normalize_dbfs is None else float(normalize_dbfs),
-                                                                       int(bool(increase_only)), *outs))
-        assert np.array_equal(got, counts), (got, counts)   # the device entry and compute_partial_slices state the same rule
-        return out, (np.split(slices, np.cumsum(counts)[:-1]) if want_slices else None)
-
-    def _run_trimmed(self, ws, n, packed, counts, want_vectors, want_slices, normalize_dbfs, increase_only, trim):
-        """All of `preprocess_wav` chained on the device: `counts` (from the untrimmed lengths) bounds the partials, the entry reports the
-        trimmed lengths and their partial counts."""
-        vad = self.trimmer(**(trim if isinstance(trim, dict) else {}))
-        if getattr(self._dev, "_vad_key", None) != vad._key:
-            vad.load()
+            vad = self.trimmer(**(trim if isinstance(trim, dict) else {}))
+            vad.ensure_loaded()
         got, n_trimmed = np.empty(len(ws), np.int32), np.empty(len(ws), np.int32)
         out = np.empty((len(ws), self.emb), np.float32) if want_vectors else None
         slices = np.empty((int(counts.sum()), PARTIAL_FRAMES, MEL_N_CHANNELS), np.float32) if want_slices else None
-        self._dev.check(self.lib.mtts_dvector_embed_wavs_preprocessed(
-            self.encoder.h if want_vectors else None, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step, float(self.min_coverage),
-            float("nan") if normalize_dbfs is None else float(normalize_dbfs), int(bool(increase_only)), _ptr(out) if want_vectors else None, _ptr(got),
-            _ptr(slices) if want_slices else None, _ptr(n_trimmed)))
-        want = [len(compute_partial_slices(int(k), self.rate, self.min_coverage)[1]) for k in n_trimmed]
-        assert np.array_equal(got, want) and np.all(got <= counts), (got, want, counts)
-        self.last_trimmed_lengths = n_trimmed
-        return out, ([s.copy() for s in np.split(slices[: int(got.sum())], np.cumsum(got)[:-1])] if want_slices else None)
+        args = (self.encoder.h if want_vectors else None, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step, float(self.min_coverage))
+        outs = (_ptr(out) if want_vectors else None, _ptr(got), _ptr(slices) if want_slices else None)
+        level = (float("nan") if normalize_dbfs is None else float(normalize_dbfs), int(bool(increase_only)))
+        entry, level, trimmed = {(False, False): (self.lib.mtts_dvector_embed_wavs, (), ()),
+                                 (True, False): (self.lib.mtts_dvector_embed_wavs_resampled, level, ()),
+                                 (True, True): (self.lib.mtts_dvector_embed_wavs_preprocessed, level, (_ptr(n_trimmed),))}[rs is not None, vad is not None]
+        self._dev.check(entry(*args, *level, *outs, *trimmed))
+        if vad is None:
+            assert np.array_equal(got, counts), (got, counts)   # the device entry and compute_partial_slices state the same rule
+        else:
+            want = [len(compute_partial_slices(int(k), self.rate, self.min_coverage)[1]) for k in n_trimmed]
+            assert np.array_equal(got, want) and np.all(got <= counts), (got, want, counts)
+            self.last_trimmed_lengths = n_trimmed
+        if not want_slices:
+            return out, None
+        parts = np.split(slices[: int(got.sum())], np.cumsum(got)[:-1])
+        return out, ([s.copy() for s in parts] if vad is not None else parts)   # (copies: not views of a buffer sized for the untrimmed lengths)
 
     def embed_utterances(self, wavs, return_slices: bool = False, source_rate: Optional[int] = None, normalize_dbfs: Optional[float] = None,
                          increase_only: bool = True, trim=False):

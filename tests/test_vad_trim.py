@@ -360,6 +360,81 @@ def test_chain_gpu(dims):
     _check_chain(None, dims)
 
 
+def _chunk_wavs(sr):
+    """Five utterances of 0.3 .. 1.2 s at `sr`, in 30 ms windows of tone (1) and faint noise (0), three of them with a ragged tail.  One
+    partial each, so max_partials = 2 cuts them into the chunks (0, 1), (2, 3), (4), and the last chunk holds the most samples,
+    sum-of-squares slots and VAD windows.  Utterance 2 opens with 12 silent windows, more than smoothing and dilation bridge; utterance
+    0 is all tone (the noise quantile is the tone itself: nothing is kept and it passes through)."""
+    w, g = sr * 30 // 1000, np.random.RandomState(77)
+    out = []
+    for levels, tail in (([1] * 10, 0), ([1] * 5 + [0] * 2 + [1] * 4, 7), ([0] * 12 + [1] * 10, 0), ([1] * 10, 123), ([1] * 9 + [0] * 14 + [1] * 16, 5)):
+        x = [0.3 * np.sin(2 * np.pi * 200 * np.arange(w) / sr + g.rand()) if lv else 1e-4 * g.standard_normal(w) for lv in levels + [0]]
+        out.append(np.concatenate(x).astype(np.float32)[: len(levels) * w + tail])
+    n = [len(x) for x in out]
+    assert 0.3 * sr <= min(n) and max(n) <= 1.2 * sr and n[4] > n[2] + n[3] > n[0] + n[1]
+    return out
+
+
+def _embed_entry(emb, which, wavs, dbfs):
+    """One of the three C entries -> (d-vectors, slices, partial counts, trimmed lengths (-1 where the entry does not trim))."""
+    n, packed = np.asarray([len(w) for w in wavs], np.int32), np.ascontiguousarray(np.concatenate(wavs))
+    vec, cnt, ntr = np.empty((len(wavs), emb.emb), np.float32), np.full(len(wavs), -1, np.int32), np.full(len(wavs), -1, np.int32)
+    sl = np.empty((sum(len(E.compute_partial_slices(len(w))[1]) for w in wavs), 160, 40), np.float32)      # (a bound: no entry lengthens a waveform)
+    args = (emb.encoder.h, emb._dev.h, len(wavs), _ptr(n), _ptr(packed), 160, emb.frame_step, 0.75)
+    outs = (_ptr(vec), _ptr(cnt), _ptr(sl))
+    if which == "plain":
+        rc = emb.lib.mtts_dvector_embed_wavs(*args, *outs)
+    elif which == "resampled":
+        rc = emb.lib.mtts_dvector_embed_wavs_resampled(*args, dbfs, 1, *outs)
+    else:
+        rc = emb.lib.mtts_dvector_embed_wavs_preprocessed(*args, dbfs, 1, *outs, _ptr(ntr))
+    assert rc == 0, emb.lib.mtts_stft_last_error(emb._dev.h).decode()
+    return vec, sl[: cnt.sum()].copy(), cnt, ntr
+
+
+def _check_chunk_tables(lib_path, streams=None):
+    """All three entries over three chunks whose largest comes last (every buffer is sized before the first launch, every chunk keeps
+    host tables of its own): each utterance's d-vector, slices, partial count and trimmed length equal those of the same entry called
+    with that utterance alone."""
+    emb = E.SpeakerEmbedder(synthetic_state_dict(3, **TINY), lib_path=lib_path, max_partials=2, **TINY)
+    if streams:
+        emb.set_streams(*streams)
+    emb.trimmer()
+
+    def check(which, wavs, dbfs, rate_ratio):
+        vec, sl, cnt, ntr = _embed_entry(emb, which, wavs, dbfs)
+        assert np.all(cnt == 1), cnt                                                                 # hence the chunks (0, 1), (2, 3), (4)
+        if which == "preprocessed":
+            n16 = [-(-len(w) * rate_ratio[0] // rate_ratio[1]) for w in wavs]
+            assert ntr[0] == n16[0] and 480 <= ntr[2] <= n16[2] - 6 * 480 and ntr[4] < n16[4], (ntr, n16)   # passed through; the leading silence cut
+        for i, w in enumerate(wavs):
+            v1, s1, c1, t1 = _embed_entry(emb, which, [w], dbfs)
+            assert np.array_equal(v1[0], vec[i]) and np.array_equal(s1[0], sl[i]) and c1[0] == cnt[i] and t1[0] == ntr[i], (which, i)
+
+    w16, w24, nan = _chunk_wavs(16000), _chunk_wavs(24000), float("nan")
+    check("plain", w16, nan, (1, 1))
+    check("preprocessed", w16, nan, (1, 1))                                                          # no resampler loaded: uploaded into the staging buffer
+    assert getattr(emb._dev, "_resampler_key", None) is None
+    emb.resampler(24000)
+    check("resampled", w24, -30.0, (2, 3))
+    check("preprocessed", w24, -30.0, (2, 3))                                                        # through the resampler
+    if streams:
+        emb.set_streams(0, 0)
+    emb.close()
+
+
+def test_chunk_tables_emulator():
+    _check_chunk_tables(_emu())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("two_streams", [False, True], ids=["one_stream", "two_streams"])
+def test_chunk_tables_gpu(two_streams):
+    import torch
+    s = (torch.cuda.Stream(), torch.cuda.Stream()) if two_streams else None
+    _check_chunk_tables(None, (s[0].cuda_stream, s[1].cuda_stream) if s else None)
+
+
 def _check_result_tree(lib_path, tmp_path):
     """WavsToDvector(resample=True, trim=True) over a Saver-shaped result tree at 22 050 Hz, and the preprocessing hook."""
     import json
