@@ -637,6 +637,49 @@ int mtts_dvector_embed_wavs_preprocessed(mtts_dvector* h, mtts_stft* stft, int n
                                          int frame_step, double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out,
                                          float* slices_out, int* n_trimmed_out);
 
+/* ---- exact t-SNE of d-vectors: the numerical step of evaluation/visualize.py ------------------------------------
+ * The reference calls sklearn's TSNE(n_components=2, perplexity=40, n_iter=300), Barnes-Hut on the CPU.  This handle runs sklearn's
+ * method="exact" definition (sklearn 1.7: _binary_search_perplexity, _joint_probabilities, _kl_divergence, _gradient_descent) on the
+ * device: n^2 pair terms per iteration.  Two components only, squared Euclidean distances only.  All array arguments are host memory.
+ * create: room for max_points points of max_dim features.  The dense joint P is max_points^2 x 4 bytes of device memory (298 MB at
+ * 8 640 points); max_points is capped at 12 288 (604 MB; a row of distances must also fit a workgroup's LDS) and refused beyond,
+ * as is max_points < 2 or max_dim outside 1 .. 65 536.  Every other entry refuses, with a message in last_error and before any launch:
+ * a NULL handle or required pointer, n < 2, n > max_points, non-finite input.
+ * affinities: X [n][dim] float32 -> the joint P on the handle; optional P_out [n][n] float32, beta_out [n] float64.
+ *   D[i][j] = sum_k (x_ik - x_jk)^2 in float64 (ascending k), rounded once to float32 as sklearn rounds its distances: symmetric bit for
+ *   bit, exact zero diagonal.  Per row the binary search of _binary_search_perplexity (beta from 1, at most 100 steps, tolerance
+ *   float(1e-5) on H - log(perplexity), double then bisect, a row sum of 0 replaced by float(1e-8), j = i excluded), float64 in a fixed
+ *   order; the conditional row is stored as float32 and beta_out is the beta it was evaluated at.  P = max((C + C^T) / max(sum, eps),
+ *   eps), eps = 2^-52, diagonal 0, stored as float32, symmetric bit for bit.  Also refused: dim outside 1 .. max_dim, perplexity not
+ *   in (0, n).  Forgets the descent state.
+ * set_affinities: the caller's own P [n][n] float32 (finite, non-negative; taken as it is: not normalised, not symmetrised).
+ *   Forgets the descent state.
+ * set_state / get_state: Y, update, gains, each [n][2] float32.  set: update NULL = zeros, gains NULL = ones.  get: NULL = not wanted.
+ * gradient: at the current state, without stepping: grad_out [n][2] = 4 sum_j (exaggeration P_ij - Q_ij) num_ij (y_i - y_j), num_ij =
+ *   1 / (1 + |y_i - y_j|^2), Q_ij = max(num_ij / Z, eps), Z = sum_{i != j} num_ij; kl_out (or NULL) = sum_{i != j} P' log(max(P', eps)
+ *   / Q), P' = exaggeration P: sklearn's _kl_divergence on the P it is handed (it is handed exaggeration P during its first phase).
+ *   The pair sums are float32 in a fixed order (lane = j mod 64 ascending, 4 groups of 16 lanes, the 4 group sums), Z is folded in
+ *   float64 in row order, KL is float64 throughout.  Q's floor inside the gradient: the sweep records each row's smallest num, and a
+ *   row with min num < eps Z recomputes its repulsive sum with the floor applied pair by pair.
+ * run: n_iter iterations of _gradient_descent's rule with no host synchronisation between them (one at the end): inc = update grad
+ *   < 0; gains += 0.2 on inc, x 0.8 elsewhere, floored at min_gain; grad x= gains; update = momentum update - learning_rate grad;
+ *   Y += update, in float32.  kl_out (or NULL): the KL of the state the LAST iteration started from (sklearn's `error`);
+ *   grad_norm_out (or NULL): the 2-norm of the last iteration's grad x gains (what sklearn compares with min_grad_norm).  Also
+ *   refused: n_iter < 1, exaggeration or learning_rate not positive, momentum or min_gain negative.
+ * Every result is bit-identical from call to call (no atomics); run(a + b) equals run(a) then run(b). */
+typedef struct mtts_tsne mtts_tsne;
+int mtts_tsne_create(int max_points, int max_dim, int device, mtts_tsne** out);
+void mtts_tsne_destroy(mtts_tsne* h);
+const char* mtts_tsne_last_error(mtts_tsne* h);
+int mtts_tsne_set_stream(mtts_tsne* h, void* hip_stream);
+int mtts_tsne_affinities(mtts_tsne* h, const float* X, int n, int dim, double perplexity, float* P_out, double* beta_out);
+int mtts_tsne_set_affinities(mtts_tsne* h, const float* P, int n);
+int mtts_tsne_set_state(mtts_tsne* h, const float* Y, const float* update, const float* gains);
+int mtts_tsne_get_state(mtts_tsne* h, float* Y, float* update, float* gains);
+int mtts_tsne_gradient(mtts_tsne* h, double exaggeration, float* grad_out, double* kl_out);
+int mtts_tsne_run(mtts_tsne* h, int n_iter, double exaggeration, double momentum, double learning_rate, double min_gain, double* kl_out,
+                  double* grad_norm_out);
+
 #ifdef __cplusplus
 }
 #endif

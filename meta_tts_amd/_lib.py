@@ -190,6 +190,16 @@ EXPORTS = {
     "mtts_vocoder_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
     "mtts_vocoder_infer_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
     "mtts_get_mel_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "mtts_tsne_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mtts_tsne_destroy": (None, [C.c_void_p]),
+    "mtts_tsne_last_error": (C.c_char_p, [C.c_void_p]),
+    "mtts_tsne_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mtts_tsne_affinities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "mtts_tsne_set_affinities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "mtts_tsne_set_state": (C.c_int, [C.c_void_p] * 4),
+    "mtts_tsne_get_state": (C.c_int, [C.c_void_p] * 4),
+    "mtts_tsne_gradient": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "mtts_tsne_run": (C.c_int, [C.c_void_p, C.c_int] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p]),
 }
 
 _cache = {}

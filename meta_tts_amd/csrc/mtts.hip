@@ -14,6 +14,7 @@
 #include "pitch.h"
 #include "vad.h"
 #include "speakereval.h"
+#include "tsne.h"
 
 using namespace mtts;
 
@@ -47,6 +48,9 @@ struct mtts_dvector {
     DVector d;
     SpeakerScore sc;
     int device = 0;
+};
+struct mtts_tsne {
+    Tsne t;
 };
 struct mtts_stft {
     MelFront m;
@@ -659,6 +663,40 @@ int mtts_vocoder_infer(mtts_vocoder* h, const float* mel, int B, int T_max, cons
 int mtts_vocoder_infer_device(mtts_vocoder* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
                               float mel_scale, float* wav_dev) {
     return h->v.run(mel_dev, B, T_max, mel_lens, mel_scale, wav_dev, (long long)T_max * h->v.hop, (long long)mel_utt_stride);
+}
+
+// ---- exact t-SNE of d-vectors (tsne.h; reference evaluation/visualize.py:56-71) ---------------------------------------------
+int mtts_tsne_create(int max_points, int max_dim, int device, mtts_tsne** out) {
+    if (!out) { g_create_error = "mtts_tsne_create: NULL out"; return -1; }
+    if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
+    mtts_tsne* h = new mtts_tsne();
+    if (h->t.init(max_points, max_dim) != 0) { g_create_error = h->t.last_error; delete h; return -1; }
+    *out = h;
+    return 0;
+}
+void mtts_tsne_destroy(mtts_tsne* h) {
+    if (!h) return;
+    hipDeviceSynchronize();
+    delete h;
+}
+const char* mtts_tsne_last_error(mtts_tsne* h) { return h ? h->t.last_error.c_str() : g_create_error.c_str(); }
+// a NULL handle: the message goes where mtts_tsne_last_error(NULL) reads it
+static int tsne_null(const char* entry) { g_create_error = std::string(entry) + ": NULL handle"; return -1; }
+int mtts_tsne_set_stream(mtts_tsne* h, void* s) { if (!h) return tsne_null("mtts_tsne_set_stream"); h->t.stream = (hipStream_t)s; return 0; }
+int mtts_tsne_affinities(mtts_tsne* h, const float* X, int n, int dim, double perplexity, float* P_out, double* beta_out) {
+    return h ? h->t.affinities(X, n, dim, perplexity, P_out, beta_out) : tsne_null("mtts_tsne_affinities");
+}
+int mtts_tsne_set_affinities(mtts_tsne* h, const float* P, int n) { return h ? h->t.set_affinities(P, n) : tsne_null("mtts_tsne_set_affinities"); }
+int mtts_tsne_set_state(mtts_tsne* h, const float* Y, const float* update, const float* gains) {
+    return h ? h->t.set_state(Y, update, gains) : tsne_null("mtts_tsne_set_state");
+}
+int mtts_tsne_get_state(mtts_tsne* h, float* Y, float* update, float* gains) { return h ? h->t.get_state(Y, update, gains) : tsne_null("mtts_tsne_get_state"); }
+int mtts_tsne_gradient(mtts_tsne* h, double exaggeration, float* grad_out, double* kl_out) {
+    return h ? h->t.gradient(exaggeration, grad_out, kl_out) : tsne_null("mtts_tsne_gradient");
+}
+int mtts_tsne_run(mtts_tsne* h, int n_iter, double exaggeration, double momentum, double learning_rate, double min_gain, double* kl_out,
+                  double* grad_norm_out) {
+    return h ? h->t.run(n_iter, exaggeration, momentum, learning_rate, min_gain, kl_out, grad_norm_out) : tsne_null("mtts_tsne_run");
 }
 
 // ---- d-vector speaker encoder (dvector.h; reference lightning/model/speaker_encoder.py:11-31,54-60,71-76) ----------------

@@ -14,8 +14,13 @@ the -30 dBFS volume normalisation run on the device when asked for (`embed_utter
 `WavsToDvector(resample=True)`; audio/resample.py, csrc/resample.h), and so does its silence trimming (`embed_utterances(trim=True)`,
 `WavsToDvector(trim=True)`; audio/vad.py, csrc/vad.h): resemblyzer's post-processing exactly, around an energy detector of this project's
 in place of webrtcvad's decision — parity with webrtcvad is UNPINNED.  Without those arguments every waveform handed to this module is
-taken as 16 kHz float32 as it is.  Figures (the reference's matplotlib / seaborn plots) are
-out of scope."""
+taken as 16 kHz float32 as it is.
+
+The t-SNE behind the reference's scatter figure (evaluation/visualize.py) runs on the device too: `TSNE` keeps sklearn's surface for
+what the reference uses and drives csrc/tsne.h — sklearn's method="exact" definition, not the Barnes-Hut approximation the reference's
+call gets on the CPU; sklearn is not imported.  `VisualizeDvector` loads the modes' d-vectors, embeds them jointly, cuts out the
+speakers of the figure and returns (or writes as CSV) the table the plot is drawn from.  The figures themselves (the reference's
+matplotlib / seaborn plots) and MOS prediction (third-party networks) are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -234,12 +239,17 @@ def read_wav_16k(path: str) -> np.ndarray:
 class EvalConfig:
     """What evaluation/config.py holds: `corpus`, `data_dir_dict` ('recon', 'real', 'enrollment' and one entry per mode),
     `n_speaker`, `n_sample`, `mode_step_list` = [(mode, [steps])], and `work_dir` under which npy/<corpus>/, json/<corpus>/ and
-    txt/<corpus>/ are written (the reference writes them under its working directory)."""
+    txt/<corpus>/ are written (the reference writes them under its working directory).  Optional, for `VisualizeDvector`:
+    `tsne_mode_list`, `tsne_pseudo_speaker_list`, `tsne_legend_list`, `tsne_plot_color_list`."""
 
-    def __init__(self, corpus: str, data_dir_dict: Dict[str, str], n_speaker: int, n_sample: int, mode_step_list, work_dir: str = "."):
+    def __init__(self, corpus: str, data_dir_dict: Dict[str, str], n_speaker: int, n_sample: int, mode_step_list, work_dir: str = ".",
+                 tsne_mode_list=(), tsne_pseudo_speaker_list=(), tsne_legend_list=(), tsne_plot_color_list=()):
         self.corpus, self.data_dir_dict, self.n_speaker, self.n_sample = corpus, dict(data_dir_dict), int(n_speaker), int(n_sample)
         self.mode_step_list = [(m, list(s)) for m, s in mode_step_list]
         self.work_dir = work_dir
+        # visualize.py's four (config.py:142-150 and the per-corpus tsne_pseudo_speaker_list); only VisualizeDvector reads them
+        self.tsne_mode_list, self.tsne_pseudo_speaker_list = list(tsne_mode_list), list(tsne_pseudo_speaker_list)
+        self.tsne_legend_list, self.tsne_plot_color_list = list(tsne_legend_list), list(tsne_plot_color_list)
 
     def path(self, kind: str, name: str) -> str:
         d = os.path.join(self.work_dir, kind, self.corpus)
@@ -621,3 +631,214 @@ class SpeakerVerification:
             fpr, tpr, _ = roc_curve(y_true, y_score)
             self.auc_dict[mode] = auc(fpr, tpr)
         return self.auc_dict
+
+
+# ---- t-SNE of d-vectors (evaluation/visualize.py) ------------------------------------------------------------------------------------------
+class TSNE:
+    """sklearn.manifold.TSNE's surface for what the reference uses, on csrc/tsne.h: two components, squared Euclidean distances, and
+    the EXACT gradient (sklearn's method="exact") where the reference's call gets Barnes-Hut.  `n_iter=` is accepted as the alias of
+    `max_iter=` that it was before sklearn 1.7.  The schedule is sklearn 1.7's `_tsne` / `_gradient_descent`, driven from the host in
+    chunks of 50 iterations: 250 exploration iterations at momentum 0.5 on early_exaggeration x P, the rest at momentum 0.8, update and
+    gains starting afresh in each phase; every 50 iterations the KL divergence and the gradient norm come back and the run stops after
+    `n_iter_without_progress` iterations without a new best KL or at a gradient norm <= `min_grad_norm`.  `n_iter_` is sklearn's (the
+    index of the last iteration).  One deliberate difference: sklearn's `kl_divergence_` is the KL of the state its last iteration
+    STARTED from; here it is the KL of `embedding_` itself (one more pass over the pairs)."""
+
+    _EXPLORATION_MAX_ITER = 250
+    _N_ITER_CHECK = 50
+    MAX_POINTS = 12288     # csrc/tsne.h TSNE_MAX_POINTS: the dense P is n^2 x 4 bytes (298 MB at 8 640 points, 604 MB at the cap)
+
+    def __init__(self, n_components: int = 2, *, perplexity: float = 30.0, early_exaggeration: float = 12.0, learning_rate="auto", max_iter: Optional[int] = None,
+                 n_iter: Optional[int] = None, n_iter_without_progress: int = 300, min_grad_norm: float = 1e-7, init="pca", random_state=None,
+                 device: int = 0, lib_path=None):
+        if n_components != 2:
+            raise ValueError(f"TSNE: n_components={n_components}: only 2 components are built (the pair kernel is written for two)")
+        if max_iter is not None and n_iter is not None:
+            raise ValueError("TSNE: give max_iter or its alias n_iter, not both")
+        max_iter = 1000 if max_iter is None and n_iter is None else int(n_iter if max_iter is None else max_iter)
+        if max_iter < 250:
+            raise ValueError(f"TSNE: max_iter={max_iter} must be at least 250")
+        if not (isinstance(init, np.ndarray) or init in ("pca", "random")):
+            raise ValueError(f"TSNE: init={init!r}: 'pca', 'random' or an ndarray of shape (n, 2)")
+        if not (learning_rate == "auto" or float(learning_rate) > 0):
+            raise ValueError(f"TSNE: learning_rate={learning_rate!r}: 'auto' or a positive number")
+        self.n_components, self.perplexity, self.early_exaggeration = 2, float(perplexity), float(early_exaggeration)
+        self.learning_rate, self.max_iter, self.n_iter_without_progress = learning_rate, max_iter, int(n_iter_without_progress)
+        self.min_grad_norm, self.init, self.random_state = float(min_grad_norm), init, random_state
+        self.device, self.lib_path = device, lib_path
+        self.min_gain = 0.01
+
+    # ---- host pieces ---------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def auto_learning_rate(n: int, early_exaggeration: float) -> float:
+        return float(max(n / early_exaggeration / 4, 50))
+
+    @staticmethod
+    def pca_init(X) -> np.ndarray:
+        """sklearn's init="pca": the first two principal components (float64 SVD of the centred data), as float32, rescaled so that PC1
+        has standard deviation 1e-4.  Signs as sklearn 1.7's PCA fixes them, `svd_flip(U, Vt, u_based_decision=False)`: the entry of
+        largest magnitude in each RIGHT singular vector (a row of Vt) is positive."""
+        X = np.asarray(X, np.float64)
+        U, S, Vt = np.linalg.svd(X - X.mean(0), full_matrices=False)
+        U, Vt = U[:, :2], Vt[:2]
+        signs = np.sign(Vt[np.arange(2), np.abs(Vt).argmax(1)])
+        signs[signs == 0] = 1
+        emb = (U * signs * S[:2]).astype(np.float32)
+        return emb / np.std(emb[:, 0]) * 1e-4
+
+    def _initial(self, X) -> np.ndarray:
+        n = len(X)
+        if isinstance(self.init, np.ndarray):
+            if self.init.shape != (n, 2):
+                raise ValueError(f"TSNE: init has shape {self.init.shape}, expected {(n, 2)}")
+            return np.ascontiguousarray(self.init, np.float32)
+        if self.init == "pca":
+            return np.ascontiguousarray(self.pca_init(X), np.float32)
+        rs = self.random_state if isinstance(self.random_state, np.random.RandomState) else np.random.RandomState(self.random_state)
+        return np.ascontiguousarray(1e-4 * rs.standard_normal(size=(n, 2)).astype(np.float32))
+
+    def _schedule(self, run: Callable, restart: Callable):
+        """TSNE._tsne over `run(n_iter, exaggeration, momentum) -> (kl, grad_norm)` (both of the chunk's last iteration) and
+        `restart()` (update = 0, gains = 1 on the current embedding) -> (sklearn's `error` of the last phase, n_iter_)."""
+        def descend(it, max_iter, momentum, exaggeration, n_iter_without_progress):
+            error = best_error = np.finfo(float).max
+            best_iter = i = it
+            while i < max_iter:
+                last = min((i // self._N_ITER_CHECK + 1) * self._N_ITER_CHECK, max_iter) - 1     # the next check, or the last iteration
+                error, grad_norm = run(last - i + 1, exaggeration, momentum)
+                i = last
+                if (i + 1) % self._N_ITER_CHECK == 0:
+                    if error < best_error:
+                        best_error, best_iter = error, i
+                    elif i - best_iter > n_iter_without_progress:
+                        break
+                    if grad_norm <= self.min_grad_norm:
+                        break
+                i += 1
+            return error, min(i, max_iter - 1) if max_iter > it else it
+
+        restart()
+        error, it = descend(0, self._EXPLORATION_MAX_ITER, 0.5, self.early_exaggeration, self._EXPLORATION_MAX_ITER)
+        if it < self._EXPLORATION_MAX_ITER or self.max_iter - self._EXPLORATION_MAX_ITER > 0:
+            restart()
+            error, it = descend(it + 1, self.max_iter, 0.8, 1.0, self.n_iter_without_progress)
+        return error, it
+
+    # ---- the device ------------------------------------------------------------------------------------------------------------------------
+    def fit_transform(self, X, y=None) -> np.ndarray:
+        from . import _lib
+        X = np.ascontiguousarray(np.asarray(X), dtype=np.float32)
+        if X.ndim != 2:
+            raise ValueError(f"TSNE: X has shape {X.shape}, expected (n, dim)")
+        n, dim = X.shape
+        if n < 2:
+            raise ValueError(f"TSNE: {n} point(s): at least 2 are needed")
+        if self.perplexity >= n:
+            raise ValueError(f"perplexity ({self.perplexity}) must be less than n_samples ({n})")
+        if n > self.MAX_POINTS:
+            raise ValueError(f"TSNE: n_samples={n} exceeds the cap of {self.MAX_POINTS} points (the dense P would be {n * n * 4 >> 20} MB; Barnes-Hut is not built)")
+        if not np.isfinite(X).all():
+            raise ValueError("TSNE: X holds a non-finite value")
+        self.learning_rate_ = self.auto_learning_rate(n, self.early_exaggeration) if self.learning_rate == "auto" else float(self.learning_rate)
+        Y0 = self._initial(X)
+        lib = _lib.load(self.lib_path)
+        h = C.c_void_p()
+        if lib.mtts_tsne_create(n, dim, self.device, C.byref(h)) != 0:
+            raise MttsError(lib.mtts_tsne_last_error(None).decode())
+
+        def check(rc):
+            if rc != 0:
+                raise MttsError(lib.mtts_tsne_last_error(h).decode())
+
+        try:
+            check(lib.mtts_tsne_affinities(h, _ptr(X), n, dim, self.perplexity, None, None))
+            check(lib.mtts_tsne_set_state(h, _ptr(Y0), None, None))
+            Y = np.empty((n, 2), np.float32)
+
+            def run(k, exaggeration, momentum):
+                kl, gn = C.c_double(), C.c_double()
+                check(lib.mtts_tsne_run(h, k, exaggeration, momentum, self.learning_rate_, self.min_gain, C.byref(kl), C.byref(gn)))
+                return kl.value, gn.value
+
+            def restart():
+                check(lib.mtts_tsne_get_state(h, _ptr(Y), None, None))
+                check(lib.mtts_tsne_set_state(h, _ptr(Y), None, None))
+
+            _, self.n_iter_ = self._schedule(run, restart)
+            grad, kl = np.empty((n, 2), np.float32), C.c_double()
+            check(lib.mtts_tsne_gradient(h, 1.0, _ptr(grad), C.byref(kl)))
+            check(lib.mtts_tsne_get_state(h, _ptr(Y), None, None))
+        finally:
+            lib.mtts_tsne_destroy(h)
+        self.embedding_, self.kl_divergence_ = Y, kl.value
+        return Y
+
+    def fit(self, X, y=None):
+        self.fit_transform(X)
+        return self
+
+
+class VisualizeDvector:
+    """visualize.py without the figure: `load_dvector`, `tsne`, `get_speaker_dvectors`, `get_speaker_id_list_dict`, and in place of
+    `visualize_dvector` the table it hands to seaborn (`scatter_table`, `save_table`).  `tsne`: a `TSNE` (default: the reference's
+    perplexity 40 and 300 iterations)."""
+
+    def __init__(self, config: EvalConfig, tsne: Optional[TSNE] = None, seed: int = 531, lib_path=None):
+        self.config, self.corpus = config, config.corpus
+        self.tsne_mode_list, self.tsne_pseudo_speaker_list = config.tsne_mode_list, config.tsne_pseudo_speaker_list
+        self.tsne_plot_color_list, self.tsne_legend_list = config.tsne_plot_color_list, config.tsne_legend_list
+        if not self.tsne_mode_list or len(self.tsne_legend_list) != len(self.tsne_mode_list):
+            raise ValueError("VisualizeDvector: EvalConfig needs tsne_mode_list and a tsne_legend_list of the same length")
+        self.n_speaker, self.n_sample, self.seed = config.n_speaker, config.n_sample, seed
+        self._tsne = tsne or TSNE(n_components=2, perplexity=40, n_iter=300, lib_path=lib_path)
+        with open(os.path.join(config.data_dir_dict["recon"], "test_SQids.json")) as f:
+            self.sq_list = json.load(f)
+        self.speaker_id_map, self.inv_speaker_id_map = self.get_speaker_id_map()
+        self.tsne_speaker_list = [self.speaker_id_map[i] for i in self.tsne_pseudo_speaker_list]
+
+    get_speaker_id_map = WavsToDvector.get_speaker_id_map
+
+    def load_dvector(self):
+        self.dvector_list_dict = {mode: np.load(self.config.path("npy", f"{mode}_dvector.npy"), allow_pickle=True) for mode in self.tsne_mode_list}
+
+    def tsne(self):
+        cat = np.concatenate([self.dvector_list_dict[mode] for mode in self.tsne_mode_list], axis=0)
+        transformed = self._tsne.fit_transform(cat)
+        self.trans_dvector_list_dict_all, pointer = {}, 0
+        for mode in self.tsne_mode_list:
+            n_vector = self.dvector_list_dict[mode].shape[0]
+            self.trans_dvector_list_dict_all[mode] = transformed[pointer:pointer + n_vector, :]
+            pointer += n_vector
+
+    def get_speaker_dvectors(self):
+        self.trans_dvector_list_dict = {
+            mode: np.concatenate([self.trans_dvector_list_dict_all[mode][spk * self.n_sample:(spk + 1) * self.n_sample, :] for spk in self.tsne_pseudo_speaker_list], axis=0)
+            for mode in self.tsne_mode_list}
+
+    def get_speaker_id_list_dict(self):
+        ids = np.array([f"{speaker_id}" for speaker_id in self.tsne_speaker_list for _ in range(self.n_sample)])
+        self.speaker_id_list_dict = {mode: ids.copy() for mode in self.tsne_mode_list}
+
+    def scatter_table(self, rng: Optional[np.random.RandomState] = None) -> Dict[str, np.ndarray]:
+        """visualize.py:99-138: the `data` dict of the scatter plot.  The three columns are shuffled jointly (`rng`: default
+        RandomState(seed), the reference's np.random.seed(seed)) through the reference's string array, and points outside
+        x in (-12, 12), y > -12 are masked out."""
+        rng = rng or np.random.RandomState(self.seed)
+        transformed = np.concatenate([self.trans_dvector_list_dict[mode] for mode in self.tsne_mode_list], axis=0)
+        cat_id_list = np.concatenate([self.speaker_id_list_dict[mode] for mode in self.tsne_mode_list], axis=0)
+        mode_list = np.concatenate([np.array([legend] * len(self.tsne_speaker_list) * self.n_sample) for legend in self.tsne_legend_list], axis=0)
+        joint_list = np.concatenate((transformed, np.expand_dims(cat_id_list, axis=1), np.expand_dims(mode_list, axis=1)), axis=1)
+        rng.shuffle(joint_list)
+        transformed = joint_list[:, :2].astype(float)
+        cat_id_list, mode_list = joint_list[:, 2], joint_list[:, 3]
+        mask = np.logical_and.reduce([transformed[:, 0] < 12, transformed[:, 0] > -12, transformed[:, 1] > -12])
+        return {"dim-1": transformed[mask, 0], "dim-2": transformed[mask, 1], "Speaker": cat_id_list[mask], "Approach": mode_list[mask]}
+
+    def save_table(self, path: str, rng: Optional[np.random.RandomState] = None) -> Dict[str, np.ndarray]:
+        import csv
+        data = self.scatter_table(rng)
+        with open(path, "w", newline="", encoding="utf8") as f:
+            w = csv.writer(f)
+            w.writerow(list(data))
+            w.writerows(zip(*(data[k].tolist() for k in data)))
+        return data
