@@ -637,6 +637,37 @@ int mtts_dvector_embed_wavs_preprocessed(mtts_dvector* h, mtts_stft* stft, int n
                                          int frame_step, double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out,
                                          float* slices_out, int* n_trimmed_out);
 
+/* ---- waveform sources of the d-vector chain (csrc/wavsource.h) -----------------------------------------------------
+ * embed_wavs_source: the three entries above behind one signature, with the place the n_utts waveforms live as an argument.
+ *   MTTS_WAV_HOST_F32    data = host float32, packed one after another: exactly the three entries above (same code path, same launches).
+ *   MTTS_WAV_HOST_PCM16  data = host int16, packed one after another.  Every chunk's raw samples are uploaded at 2 bytes per sample and
+ *                        widened on the device, x = v / 32768 — exact in float32, so the results equal those of the float32 source
+ *                        holding int16 / 32768 bit for bit.
+ *   MTTS_WAV_DEVICE_F32  data = device float32, utterance u at data + u * row_stride (floats), n_samples[u] <= row_stride; what lies
+ *                        beyond n_samples[u] in a row is never read.  producer_stream: the HIP stream whose work fills `data`; the
+ *                        front-end's stream waits for an event recorded on it when the call starts (no host synchronisation), and the
+ *                        rows may be reused once the call has returned.  quantize_scale s > 0: every sample goes through a 16-bit
+ *                        file's round trip first, q = trunc(x * s) clamped to [-32768, 32767], x' = q / 32768 (s = max_wav_value, 32768
+ *                        in the reference configs; |x * s| >= 32768 is outside the contract, the clamp only keeps the result defined);
+ *                        0: the floats as they are.  row_stride, producer_stream and quantize_scale are ignored (and quantize_scale
+ *                        must be 0) for the host kinds.
+ * stages: bit 0 = resample (+ normalise to target_dbfs unless NaN) as embed_wavs_resampled does, bit 1 = trim as embed_wavs_preprocessed
+ * does (through the resampler when one is loaded); 0 = the plain chain, where target_dbfs and increase_only are ignored.  n_samples,
+ * the partial rule and the outputs are those of the entry with the same stages; n_trimmed_out is written with bit 1 only.
+ * Errors, before any launch and in both handles' last_error, besides those of the entry with the same stages: NULL source or data,
+ * unknown kind or stages, row_stride smaller than a length, negative quantize_scale, quantize_scale on a host source. */
+enum { MTTS_WAV_HOST_F32 = 0, MTTS_WAV_HOST_PCM16 = 1, MTTS_WAV_DEVICE_F32 = 2 };
+typedef struct mtts_wav_source {
+    int kind;
+    const void* data;
+    int64_t row_stride;
+    void* producer_stream;
+    float quantize_scale;
+} mtts_wav_source;
+int mtts_dvector_embed_wavs_source(mtts_dvector* h, mtts_stft* stft, const mtts_wav_source* src, int stages, int n_utts, const int* n_samples,
+                                   int partial_frames, int frame_step, double min_coverage, double target_dbfs, int increase_only, float* out,
+                                   int* n_partials_out, float* slices_out, int* n_trimmed_out);
+
 /* ---- exact t-SNE of d-vectors: the numerical step of evaluation/visualize.py ------------------------------------
  * The reference calls sklearn's TSNE(n_components=2, perplexity=40, n_iter=300), Barnes-Hut on the CPU.  This handle runs sklearn's
  * method="exact" definition (sklearn 1.7: _binary_search_perplexity, _joint_probabilities, _kl_divergence, _gradient_descent) on the

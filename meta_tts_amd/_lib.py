@@ -31,6 +31,12 @@ class Batch(C.Structure):
                 ("energies", C.c_void_p), ("durations", C.c_void_p), ("spk_emb", C.c_void_p)]
 
 
+class WavSource(C.Structure):
+    """mtts_wav_source: where the waveforms of mtts_dvector_embed_wavs_source live."""
+    HOST_F32, HOST_PCM16, DEVICE_F32 = 0, 1, 2
+    _fields_ = [("kind", C.c_int), ("data", C.c_void_p), ("row_stride", C.c_int64), ("producer_stream", C.c_void_p), ("quantize_scale", C.c_float)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "mtts_create": (C.c_int, [C.POINTER(ModelCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
@@ -176,6 +182,8 @@ EXPORTS = {
     "mtts_stft_trim_batch": (C.c_int64, [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
     "mtts_dvector_embed_wavs_preprocessed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_dvector_embed_wavs_source": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_stft_load_pitch": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
     "mtts_stft_f0_batch": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_vocoder_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,

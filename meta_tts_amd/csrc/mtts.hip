@@ -60,17 +60,25 @@ struct mtts_stft {
     Resample rs;
     Pitch pt;
     Vad vad;
+    WavIngest ing;
 };
 
-// The three mtts_dvector_embed_wavs* entries: resample = through the handle's resampler; trim = through its trimmer, and through the
-// resampler when one is loaded.  A refusal is copied to the d-vector handle as well.
+// The mtts_dvector_embed_wavs* entries: resample = through the handle's resampler; trim = through its trimmer, and through the
+// resampler when one is loaded; src = where the waveforms are (the three older entries: host float32 at src.data).  A refusal is copied
+// to the d-vector handle as well.
 static int embed_wavs_entry(const char* name, mtts_dvector* h, mtts_stft* stft, bool resample, bool trim, double target_dbfs, int increase_only, int n_utts,
-                            const int* n_samples, const float* wavs, PartialRule rule, EmbedOut o) {
+                            const int* n_samples, const WavSource& src, PartialRule rule, EmbedOut o) {
     if (!stft) { g_create_error = std::string(name) + ": NULL STFT handle"; if (h) h->d.set_error(g_create_error); return -1; }
-    const WavPrep prep{&stft->m, resample || (trim && stft->rs.loaded()) ? &stft->rs : nullptr, trim ? &stft->vad : nullptr, target_dbfs, increase_only != 0};
-    const int rc = stft->se.embed_wavs(name, prep, h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, wavs, rule, o);
+    const WavPrep prep{&stft->m, resample || (trim && stft->rs.loaded()) ? &stft->rs : nullptr, trim ? &stft->vad : nullptr, target_dbfs, increase_only != 0,
+                       src, &stft->ing};
+    const int rc = stft->se.embed_wavs(name, prep, h ? &h->d : nullptr, h ? h->device : 0, n_utts, n_samples, (const float*)src.data, rule, o);
     if (rc != 0 && h) h->d.set_error(stft->m.last_error);
     return rc;
+}
+static WavSource host_f32(const float* wavs) {
+    WavSource s;
+    s.data = wavs;
+    return s;
 }
 
 extern "C" {
@@ -746,6 +754,7 @@ int mtts_stft_create(int filter_length, int hop_length, int n_mel, int max_sampl
     h->rs.mf = &h->m;
     h->pt.mf = &h->m;
     h->vad.mf = &h->m;
+    h->ing.mf = &h->m;
     h->se.device = device;
     if (h->m.init(filter_length, hop_length, n_mel, max_samples) != 0) { g_create_error = h->m.last_error; delete h; return -1; }
     *out = h;
@@ -830,19 +839,33 @@ int mtts_dvector_embed_device(mtts_dvector* h, const float* mels_dev, int n_part
 }
 int mtts_dvector_embed_wavs(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
                             double min_coverage, float* out, int* n_partials_out, float* slices_out) {
-    return embed_wavs_entry("mtts_dvector_embed_wavs", h, stft, false, false, 0.0, 0, n_utts, n_samples, wavs, {partial_frames, frame_step, min_coverage},
+    return embed_wavs_entry("mtts_dvector_embed_wavs", h, stft, false, false, 0.0, 0, n_utts, n_samples, host_f32(wavs), {partial_frames, frame_step, min_coverage},
                             {out, n_partials_out, slices_out, nullptr});
 }
 int mtts_dvector_embed_wavs_resampled(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
                                       double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out) {
-    return embed_wavs_entry("mtts_dvector_embed_wavs_resampled", h, stft, true, false, target_dbfs, increase_only, n_utts, n_samples, wavs,
+    return embed_wavs_entry("mtts_dvector_embed_wavs_resampled", h, stft, true, false, target_dbfs, increase_only, n_utts, n_samples, host_f32(wavs),
                             {partial_frames, frame_step, min_coverage}, {out, n_partials_out, slices_out, nullptr});
 }
 int mtts_dvector_embed_wavs_preprocessed(mtts_dvector* h, mtts_stft* stft, int n_utts, const int* n_samples, const float* wavs, int partial_frames, int frame_step,
                                          double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out,
                                          int* n_trimmed_out) {
-    return embed_wavs_entry("mtts_dvector_embed_wavs_preprocessed", h, stft, false, true, target_dbfs, increase_only, n_utts, n_samples, wavs,
+    return embed_wavs_entry("mtts_dvector_embed_wavs_preprocessed", h, stft, false, true, target_dbfs, increase_only, n_utts, n_samples, host_f32(wavs),
                             {partial_frames, frame_step, min_coverage}, {out, n_partials_out, slices_out, n_trimmed_out});
+}
+int mtts_dvector_embed_wavs_source(mtts_dvector* h, mtts_stft* stft, const mtts_wav_source* src, int stages, int n_utts, const int* n_samples, int partial_frames,
+                                   int frame_step, double min_coverage, double target_dbfs, int increase_only, float* out, int* n_partials_out, float* slices_out,
+                                   int* n_trimmed_out) {
+    const char* name = "mtts_dvector_embed_wavs_source";
+    if (stft && (!src || !src->data || (stages & ~3))) {
+        stft->m.err(std::string(name) + (!src ? ": NULL source" : !src->data ? ": NULL source data" : ": unknown stages (bit 0: resample, bit 1: trim)"));
+        if (h) h->d.set_error(stft->m.last_error);
+        return -1;
+    }
+    WavSource s;
+    if (src) { s.kind = src->kind; s.data = src->data; s.row_stride = src->row_stride; s.producer = (hipStream_t)src->producer_stream; s.quantize_scale = src->quantize_scale; }
+    return embed_wavs_entry(name, h, stft, (stages & 1) != 0, (stages & 2) != 0, target_dbfs, increase_only, n_utts, n_samples, s,
+                            {partial_frames, frame_step, min_coverage}, {out, n_partials_out, slices_out, (stages & 2) ? n_trimmed_out : nullptr});
 }
 int mtts_dvector_cosine_indexed(mtts_dvector* h, const float* a, int n_a, const float* b, int n_b, int dim, int n, const int* index_a, const int* index_b,
                                 double eps, float* sim) {

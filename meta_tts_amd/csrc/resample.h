@@ -156,8 +156,12 @@ public:
     // mf->stream; h_utts and src_host must stay as they are until the stream has been synchronised.  dst: another buffer than mf->wav
     // (vad.h's staging buffer, when silence trimming follows and fills mf->wav itself).
     int launch(const float* src_host, double target_dbfs, bool increase_only, float* dst = nullptr) {
-        if (!dst) dst = mf->wav.p;
         DEV_CHECK(hipMemcpyAsync(src.p, src_host, (size_t)n_src * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+        return convert(target_dbfs, increase_only, dst);
+    }
+    // the same for source-rate samples an earlier launch on mf->stream has left in `src` at the table's src0 (wavsource.h): no upload
+    int convert(double target_dbfs, bool increase_only, float* dst = nullptr) {
+        if (!dst) dst = mf->wav.p;
         DEV_CHECK(hipMemcpyAsync(utts.p, h_utts.data(), h_utts.size() * sizeof(RsUtt), hipMemcpyHostToDevice, mf->stream));
         const unsigned n_utts = (unsigned)h_utts.size();
         MTTS_LAUNCH(resample_polyphase_kernel, dim3((unsigned)((max_out + run - 1) / run), n_utts), dim3(RS_THREADS), mf->stream, (const float*)src.p,

@@ -15,7 +15,8 @@
 // embed_wavs is one function behind three entries, in three parts.  The plan: validate, cut the call into chunks, reserve every
 // buffer for the largest chunk.  The source (WavPrep): how a chunk's waveforms reach MelFront::wav — uploaded, resampled there, or
 // resampled / uploaded into the trimmer's staging buffer, trimmed and compacted there; it is the only place that knows which entry was
-// called.  The tail, shared: power mel, the partial windows, the gather, the encoder.
+// called, and (mtts_dvector_embed_wavs_source, wavsource.h) where the waveforms live: packed host float32 as in the three entries, host
+// int16, or device float32 rows.  The tail, shared: power mel, the partial windows, the gather, the encoder.
 //
 // MI355X layout.  All utterances of a chunk share every launch (melfront.h's packing): the reflect-pad kernel, ONE forward-STFT GEMM
 // with the rows between utterances dropped, stft_power_kernel (one wavefront per frame, HBM-bound: 2F floats in, F out), the mel GEMM,
@@ -42,6 +43,7 @@
 #include "melfront.h"
 #include "resample.h"
 #include "vad.h"
+#include "wavsource.h"
 
 namespace mtts {
 
@@ -150,6 +152,7 @@ struct ChunkTables {
     std::vector<int> win, off;   // first packed mel row of every partial; partials before every utterance
     std::vector<RsUtt> rs;       // the resampler's table (WavPrep with a resampler and no trimmer)
     std::vector<VadUtt> vad;     // the trimmer's
+    std::vector<WavUtt> ingest;  // the source's (WavPrep with a source that is not host float32, outside the trimmer's lengths())
     // the table a stage has just enqueued for upload moves here (a moved vector keeps its storage); the stage packs its next chunk into a fresh one
     template <class T>
     static void keep(std::vector<T>& kept, std::vector<T>& staged) { kept = std::move(staged); staged.clear(); }
@@ -164,18 +167,37 @@ struct ChunkTables {
 //     (trimming only shortens, and the partial count never grows as a waveform shrinks); the partial rule then applies to the trimmed
 //     lengths, which the host reads back once per chunk (Vad::detect).
 // The chunking, the launches behind the waveform buffer and the results are those of the plain entry on the prepared waveforms.
+//
+// src (mtts_dvector_embed_wavs_source; wavsource.h) says where the waveforms are.  Host float32, the three entries' form, is uploaded
+// as above.  Host int16 and device float32 reach the first stage's input — the resampler's source buffer, the trimmer's staging
+// buffer, or mf->wav over zeros at the packed wav0 offsets — through ing's kernel instead of that upload; every launch behind that
+// buffer is the same, so the results are those of the host float32 route on the same sample values.
 struct WavPrep {
     MelFront* mf;
     Resample* rs;
     Vad* vad;
     double target_dbfs;
     bool increase_only;
+    WavSource src;
+    WavIngest* ing;
 
     int err(const std::string& s) const { return mf->err(s); }
     bool plain() const { return !rs && !vad; }
+    bool host_f32() const { return src.kind == WAV_HOST_F32; }
+    bool extended() const { return plain() && host_f32(); }   // the host zero-extends and one upload fills mf->wav
+    const float* f32(const Chunk& c) const { return (const float*)src.data + c.src0; }
+
+    // a chunk's utterances through the source's kernel into dst, utterance k of the chunk at dst0_of(k)
+    template <class Dst0>
+    int ingest(const Chunk& c, const int* n_samples, float* dst, Dst0 dst0_of) const {
+        ing->table_begin();
+        for (int u = c.u0; u < c.u1; ++u) ing->table_add(src, u, n_samples[u], dst0_of((size_t)(u - c.u0)));
+        return ing->launch(src, c.src0, dst);
+    }
 
     // The refusals that are the stages' own, and h_n [n_utts]: every utterance's samples at the front-end's rate (before trimming).
     int check(const std::string& who, int n_utts, const int* n_samples, std::vector<long long>& h_n) const {
+        if (ing->check(who, src, n_utts, n_samples)) return -1;
         if (rs && rs->check_lengths(who, n_utts, n_samples)) return -1;
         if (vad && !rs && !std::isnan(target_dbfs))
             return err(who + "volume normalisation needs a resampler (mtts_stft_load_resampler; the identity bank for waveforms at the front-end's rate)");
@@ -192,7 +214,7 @@ struct WavPrep {
 
     // The stages' buffers for the largest chunk: its source samples, its samples at the front-end's rate, slots, windows and utterances.
     int reserve(const std::string& who, const std::vector<Chunk>& chunks, const int* n_samples, const long long* h_n) const {
-        if (plain()) return 0;
+        if (extended()) return 0;
         long long max_src = 0, max_n = 0, max_slots = 0, max_win = 0;
         size_t max_utts = 0;
         for (const Chunk& c : chunks) {
@@ -210,21 +232,28 @@ struct WavPrep {
             max_utts = std::max(max_utts, (size_t)(c.u1 - c.u0));
         }
         if (max_src > (1LL << 31) - 1 || (vad && max_n > (1LL << 31) - 1)) return err(who + "too many samples in one chunk");
-        return (rs && rs->reserve(max_src, max_slots, max_utts)) || (vad && vad->reserve(max_n, max_win, max_utts, false)) ? -1 : 0;
+        return (!host_f32() && ing->reserve(src, max_src, max_utts)) || (rs && rs->reserve(max_src, max_slots, max_utts)) ||
+               (vad && vad->reserve(max_n, max_win, max_utts, false)) ? -1 : 0;
     }
+    // before the first launch: a device source's producer
+    int begin() const { return ing->after_producer(src); }
 
     // Before packing.  With a trimmer: the untrimmed waveforms into its staging buffer, the mask, and the chunk's trimmed lengths back
     // into h_n (synchronises mf->stream: the resampler's table is free again).  Without one the lengths stand.
-    int lengths(const Chunk& c, const int* n_samples, const float* src, long long* h_n) const {
+    int lengths(const Chunk& c, const int* n_samples, long long* h_n) const {
         if (!vad) return 0;
         vad->table_begin();
         for (int u = c.u0; u < c.u1; ++u) vad->table_add(h_n[u]);
         if (rs) {
             rs->table_begin();
             for (int u = c.u0; u < c.u1; ++u) rs->table_add(n_samples[u], vad->h_utts[(size_t)(u - c.u0)].src0);
-            if (rs->launch(src + c.src0, target_dbfs, increase_only, vad->stage.p)) return -1;
-        } else
-            DEV_CHECK(hipMemcpyAsync(vad->stage.p, src + c.src0, (size_t)vad->n_src * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+            if (host_f32() ? rs->launch(f32(c), target_dbfs, increase_only, vad->stage.p)
+                           : ingest(c, n_samples, rs->src.p, [&](size_t k) { return rs->h_utts[k].src0; }) || rs->convert(target_dbfs, increase_only, vad->stage.p))
+                return -1;
+        } else if (host_f32())
+            DEV_CHECK(hipMemcpyAsync(vad->stage.p, f32(c), (size_t)vad->n_src * sizeof(float), hipMemcpyHostToDevice, mf->stream));
+        else if (ingest(c, n_samples, vad->stage.p, [&](size_t k) { return vad->h_utts[k].src0; }))
+            return -1;
         if (vad->detect(nullptr)) return -1;
         for (int u = c.u0; u < c.u1; ++u) h_n[u] = vad->h_nout[2 * (size_t)(u - c.u0)];
         return 0;
@@ -232,19 +261,23 @@ struct WavPrep {
 
     // After packing: the chunk's waveforms into mf->wav at the places MelFront has packed, and the reflect-padded signals.  The stages
     // write over zeros: the zero-extension to the last partial window's end.
-    int fill(const Chunk& c, const int* n_samples, const float* src, ChunkTables& t) const {
-        if (plain()) return mf->pad_waveforms(src + c.src0, false, true);
+    int fill(const Chunk& c, const int* n_samples, ChunkTables& t) const {
+        if (extended()) return mf->pad_waveforms(f32(c), false, true);
         DEV_CHECK(hipMemsetAsync(mf->wav.p, 0, (size_t)mf->n_samples * sizeof(float), mf->stream));
         if (vad) {   // the kept windows
             for (int u = c.u0; u < c.u1; ++u) vad->h_utts[(size_t)(u - c.u0)].dst0 = mf->h_utts[(size_t)(u - c.u0)].wav0;
             if (vad->compact(mf->wav.p)) return -1;
             ChunkTables::keep(t.vad, vad->h_utts);
-        } else {     // source-rate samples up, resampled
+        } else if (rs) {   // source-rate samples up, resampled
             rs->table_begin();
             for (int u = c.u0; u < c.u1; ++u) rs->table_add(n_samples[u], mf->h_utts[(size_t)(u - c.u0)].wav0);
-            if (rs->launch(src + c.src0, target_dbfs, increase_only)) return -1;
+            if (host_f32() ? rs->launch(f32(c), target_dbfs, increase_only)
+                           : ingest(c, n_samples, rs->src.p, [&](size_t k) { return rs->h_utts[k].src0; }) || rs->convert(target_dbfs, increase_only))
+                return -1;
             ChunkTables::keep(t.rs, rs->h_utts);
-        }
+        } else if (ingest(c, n_samples, mf->wav.p, [&](size_t k) { return mf->h_utts[k].wav0; }))   // the source's samples as they are
+            return -1;
+        if (!host_f32() && !vad) ChunkTables::keep(t.ingest, ing->h_utts);
         return mf->pad_staged(false, true);
     }
 };
@@ -301,19 +334,20 @@ public:
         if (validate(who, prep, dv, dv_device, n_utts, n_samples, wavs, r, o)) return -1;
         const bool two_streams = dv && dv->stream != mf->stream;
         if (two_streams) { DEV_CHECK(mf->mem.event(ev_front)); DEV_CHECK(mf->mem.event(ev_enc)); }
-        const float* src = prep.plain() ? zero_extended(n_utts, n_samples, wavs) : wavs;
+        WavPrep fed = prep;   // what front() reads from: the plain chain's host float32 is zero-extended here, everything else is as the caller holds it
+        fed.src.data = prep.extended() ? zero_extended(n_utts, n_samples, wavs) : (const void*)wavs;
         for (int u = 0; u < n_utts; ++u) o.n_partials[u] = h_cnt[(size_t)u];
-        const int max_N = plan(dv, n_utts, n_samples, prep.plain());
+        const int max_N = plan(dv, n_utts, n_samples, prep.extended());
         // sized once for the largest chunk, before the first launch: a later, larger chunk must not free the stack the previous chunk's
         // encoder still reads on the other stream (and the same for the stages' buffers)
         if (mf->grow(stack, (size_t)max_N * span4(r) * 4 + 64, "partial utterances") || mf->grow(win, (size_t)max_N, "windows") ||
-            prep.reserve(who, chunks, n_samples, h_n.data()))
+            prep.reserve(who, chunks, n_samples, h_n.data()) || prep.begin())
             return -1;
         tables.clear();
         tables.resize(chunks.size());
         long long part0 = 0;
         for (size_t c = 0; c < chunks.size(); ++c) {
-            if (front(name, prep, chunks[c], n_samples, src, r, o, tables[c]) || tail(who, chunks[c], tables[c], dv, c > 0, part0, r, o)) return -1;
+            if (front(name, fed, chunks[c], n_samples, r, o, tables[c]) || tail(who, chunks[c], tables[c], dv, c > 0, part0, r, o)) return -1;
             part0 += chunks[c].N;
         }
         if (dv) DEV_CHECK(hipStreamSynchronize(dv->stream));
@@ -389,8 +423,8 @@ public:
     }
 
     // One chunk up to its mel: the lengths (with a trimmer: the trimmed ones, and the partial rule on them), packing, waveforms, front-end.
-    int front(const char* name, const WavPrep& prep, Chunk& c, const int* n_samples, const float* src, const PartialRule& r, const EmbedOut& o, ChunkTables& t) {
-        if (prep.lengths(c, n_samples, src, h_n.data())) return -1;
+    int front(const char* name, const WavPrep& prep, Chunk& c, const int* n_samples, const PartialRule& r, const EmbedOut& o, ChunkTables& t) {
+        if (prep.lengths(c, n_samples, h_n.data())) return -1;
         if (prep.vad) {
             c.N = 0;
             for (int u = c.u0; u < c.u1; ++u) {
@@ -401,7 +435,7 @@ public:
         }
         mf->pack_begin();
         for (int u = c.u0; u < c.u1; ++u) mf->pack_add(h_ext[(size_t)u], mf->frames_of((int)h_ext[(size_t)u]));
-        if (mf->stage(name, true) || prep.fill(c, n_samples, src, t)) return -1;
+        if (mf->stage(name, true) || prep.fill(c, n_samples, t)) return -1;
         power_mel();
         return 0;
     }

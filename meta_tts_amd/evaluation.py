@@ -31,6 +31,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from ._lib import WavSource as _WavSource
 from .audio.stft import _Handle, _pack_wavs, forward_basis, mel_filterbank
 from .engine import MttsError
 from .speaker_encoder import EMBED, HIDDEN, LAYERS, MEL_N_CHANNELS, PARTIAL_FRAMES, DVectorEncoder
@@ -135,7 +136,12 @@ class SpeakerEmbedder:
 
     def _run(self, wavs, want_vectors: bool, want_slices: bool, source_rate=None, normalize_dbfs=None, increase_only=True, trim=False):
         """One chained entry for all waveforms: the plain one, the resampled one (source_rate), or all of `preprocess_wav` (trim)."""
-        ws, n, packed = _pack_wavs(wavs)
+        _, n, packed = _pack_wavs(wavs)
+        return self._chain(n, packed, None, want_vectors, want_slices, source_rate, normalize_dbfs, increase_only, trim)
+
+    def _chain(self, n, packed, source, want_vectors: bool, want_slices: bool, source_rate=None, normalize_dbfs=None, increase_only=True, trim=False):
+        """`n` [B] int32 lengths of waveforms that are either `packed` host float32 (source None: the three older entries) or described by
+        `source`, a `_lib.WavSource` (mtts_dvector_embed_wavs_source; `packed` then only keeps its host memory alive)."""
         rs = vad = None
         if trim and source_rate is None:
             source_rate = SAMPLING_RATE      # the chained entry resamples with whatever bank the handle holds: make it the identity
@@ -149,16 +155,22 @@ class SpeakerEmbedder:
         if trim:
             vad = self.trimmer(**(trim if isinstance(trim, dict) else {}))
             vad.ensure_loaded()
-        got, n_trimmed = np.empty(len(ws), np.int32), np.empty(len(ws), np.int32)
-        out = np.empty((len(ws), self.emb), np.float32) if want_vectors else None
+        got, n_trimmed = np.empty(len(n), np.int32), np.empty(len(n), np.int32)
+        out = np.empty((len(n), self.emb), np.float32) if want_vectors else None
         slices = np.empty((int(counts.sum()), PARTIAL_FRAMES, MEL_N_CHANNELS), np.float32) if want_slices else None
-        args = (self.encoder.h if want_vectors else None, self._dev.h, len(ws), _ptr(n), _ptr(packed), PARTIAL_FRAMES, self.frame_step, float(self.min_coverage))
+        handles = (self.encoder.h if want_vectors else None, self._dev.h)
+        rule = (PARTIAL_FRAMES, self.frame_step, float(self.min_coverage))
         outs = (_ptr(out) if want_vectors else None, _ptr(got), _ptr(slices) if want_slices else None)
         level = (float("nan") if normalize_dbfs is None else float(normalize_dbfs), int(bool(increase_only)))
-        entry, level, trimmed = {(False, False): (self.lib.mtts_dvector_embed_wavs, (), ()),
-                                 (True, False): (self.lib.mtts_dvector_embed_wavs_resampled, level, ()),
-                                 (True, True): (self.lib.mtts_dvector_embed_wavs_preprocessed, level, (_ptr(n_trimmed),))}[rs is not None, vad is not None]
-        self._dev.check(entry(*args, *level, *outs, *trimmed))
+        if source is None:
+            args = (*handles, len(n), _ptr(n), _ptr(packed), *rule)
+            entry, level, trimmed = {(False, False): (self.lib.mtts_dvector_embed_wavs, (), ()),
+                                     (True, False): (self.lib.mtts_dvector_embed_wavs_resampled, level, ()),
+                                     (True, True): (self.lib.mtts_dvector_embed_wavs_preprocessed, level, (_ptr(n_trimmed),))}[rs is not None, vad is not None]
+            self._dev.check(entry(*args, *level, *outs, *trimmed))
+        else:
+            stages = (1 if rs is not None else 0) | (2 if vad is not None else 0)
+            self._dev.check(self.lib.mtts_dvector_embed_wavs_source(*handles, C.byref(source), stages, len(n), _ptr(n), *rule, *level, *outs, _ptr(n_trimmed)))
         if vad is None:
             assert np.array_equal(got, counts), (got, counts)   # the device entry and compute_partial_slices state the same rule
         else:
@@ -190,6 +202,41 @@ class SpeakerEmbedder:
 
     def embed_utterance(self, wav):
         return self.embed_utterances([wav])[0]
+
+    def embed_pcm16(self, wavs, return_slices: bool = False, source_rate: Optional[int] = None, normalize_dbfs: Optional[float] = None,
+                    increase_only: bool = True, trim=False):
+        """`embed_utterances` for a list of int16 arrays, 16-bit PCM as a .wav file holds it: the samples are uploaded at 2 bytes each and
+        widened on the device (x = v / 32768, exact in float32), so the result — vectors, slices, `last_trimmed_lengths` — equals
+        `embed_utterances([w.astype(np.float32) / 32768 for w in wavs], ...)` bit for bit.  Same keywords, same return values."""
+        if self.encoder is None:
+            raise MttsError("SpeakerEmbedder(encoder=False) has no encoder")
+        ws = [np.asarray(w) for w in wavs]
+        if not ws:
+            raise MttsError("no waveforms")
+        bad = [str(w.dtype) for w in ws if w.dtype != np.int16]
+        if bad:
+            raise TypeError(f"embed_pcm16 takes int16 arrays, got {bad[0]} (embed_utterances takes float samples)")
+        n = np.asarray([w.size for w in ws], np.int32)
+        packed = np.ascontiguousarray(np.concatenate([w.reshape(-1) for w in ws]))
+        source = _WavSource(_WavSource.HOST_PCM16, packed.ctypes.data, 0, None, 0.0)
+        out, slices = self._chain(n, packed, source, True, return_slices, source_rate, normalize_dbfs, increase_only, trim)
+        return (out, slices) if return_slices else out
+
+    def embed_device(self, ptr: int, row_stride: int, lengths, *, stream: int = 0, quantize: Optional[float] = None, source_rate: Optional[int] = None,
+                     normalize_dbfs: Optional[float] = None, increase_only: bool = True, trim=False):
+        """`embed_utterances` for float32 waveforms that are in device memory already: utterance u is the first lengths[u] floats of the
+        row at `ptr + 4 * u * row_stride` (what lies behind them in a row is never read) -> (B, emb) float32.  `stream`: the HIP stream
+        whose work fills the rows (`MelGAN.infer_device` returns its own); the front-end waits for it on the device, the host does not.
+        quantize: `max_wav_value` — every sample first goes through what writing it to a 16-bit file and reading it back does,
+        trunc(x * quantize) / 32768, so the result equals `embed_pcm16` of `(wav * max_wav_value).astype("int16")`; None: the floats as
+        they are.  The other keywords are `embed_utterances`'."""
+        if self.encoder is None:
+            raise MttsError("SpeakerEmbedder(encoder=False) has no encoder")
+        n = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if not len(n):
+            raise MttsError("no waveforms")
+        source = _WavSource(_WavSource.DEVICE_F32, int(ptr), int(row_stride), int(stream) or None, 0.0 if quantize is None else float(quantize))
+        return self._chain(n, None, source, True, False, source_rate, normalize_dbfs, increase_only, trim)[0]
 
     def reference_mel_slices(self, wav, source_rate: Optional[int] = None, normalize_dbfs: Optional[float] = None, trim=False) -> np.ndarray:
         """The `spk_ref_mel_slices` payload of preprocessor.py:263-299 for one waveform: (n_partials, 160, 40) float32.  source_rate,
@@ -235,6 +282,21 @@ def read_wav_16k(path: str) -> np.ndarray:
     return wav
 
 
+def embed_synthesized(engine, vocoder, embedder: SpeakerEmbedder, slot: int, task: int, mel_lens, max_wav_value: float, **chain) -> np.ndarray:
+    """The d-vectors of a test step's synthesis without a waveform leaving the device: `engine.mel_device(slot, task)` (the post-net mel
+    of the last forward / synthesize) -> `vocoder.infer_device` -> `embedder.embed_device(quantize=max_wav_value, ...)`, which puts every
+    sample through the 16-bit cut of `MelGAN.infer` before it is scored — the vectors are those of writing the `Saver`'s .synth.wav
+    files and reading them back.  mel_lens [B]: the synthesised frames per utterance (`engine.durations(slot, task)[1]`).  `chain`:
+    `embed_device`'s keywords; source_rate is the preprocess config's sampling rate (the vocoder's output rate) and is required.
+    The `Saver` still writes its files; this only spares the evaluation the trip through them."""
+    if "source_rate" not in chain:
+        raise ValueError("embed_synthesized needs source_rate=<the preprocess config's sampling rate>: the vocoder does not synthesise at the encoder's 16 kHz")
+    mel_lens = np.asarray(mel_lens).reshape(-1)
+    ptr, t_cap, stride = engine.mel_device(slot, task, postnet=True)
+    wav_ptr, row_stride, lengths, stream = vocoder.infer_device(ptr, stride, len(mel_lens), t_cap, mel_lens)
+    return embedder.embed_device(wav_ptr, row_stride, lengths, stream=stream, quantize=max_wav_value, **chain)
+
+
 # ---- the reference's class surface -----------------------------------------------------------------------------------------------------
 class EvalConfig:
     """What evaluation/config.py holds: `corpus`, `data_dir_dict` ('recon', 'real', 'enrollment' and one entry per mode),
@@ -268,14 +330,17 @@ class WavsToDvector:
     the device in one `embed_utterances` call.  resample=True: files of any rate (a result tree's 22 050 Hz wavs) are read with
     `preprocessor.read_wav`, grouped by rate, and each group is resampled to 16 kHz and normalised to `normalize_dbfs` (resemblyzer's
     `preprocess_wav`; None: not normalised) on the device in front of the encoder, one call per group.  trim=True: and trimmed of long
-    silences there (`embed_utterances(trim=True)`; this project's detector, parity with webrtcvad unpinned); default off."""
+    silences there (`embed_utterances(trim=True)`; this project's detector, parity with webrtcvad unpinned); default off.
+    pcm16=True (default off): the files are read here as well, and mono 16-bit PCM files stay int16 and go through `embed_pcm16` — half
+    the bytes on the host and in the upload, the same d-vectors bit for bit; files of any other sample format take the float path."""
 
     def __init__(self, config: EvalConfig, embedder: SpeakerEmbedder, wav_loader: Optional[Callable[[str], np.ndarray]] = None, pair_list=None,
-                 rng: Optional[random.Random] = None, run: bool = True, resample: bool = False, normalize_dbfs: Optional[float] = -30.0, trim=False):
+                 rng: Optional[random.Random] = None, run: bool = True, resample: bool = False, normalize_dbfs: Optional[float] = -30.0, trim=False,
+                 pcm16: bool = False):
         self.config, self.embedder = config, embedder
-        self.resample, self.normalize_dbfs, self.trim = bool(resample), normalize_dbfs, trim
-        if resample and wav_loader is not None:
-            raise ValueError("WavsToDvector(resample=True) reads the files itself: wav_loader must be None")
+        self.resample, self.normalize_dbfs, self.trim, self.pcm16 = bool(resample), normalize_dbfs, trim, bool(pcm16)
+        if (resample or pcm16) and wav_loader is not None:
+            raise ValueError("WavsToDvector(resample=True) and WavsToDvector(pcm16=True) read the files themselves: wav_loader must be None")
         self.corpus, self.data_dir_dict = config.corpus, config.data_dir_dict
         self.n_sample, self.n_speaker, self.mode_step_list = config.n_sample, config.n_speaker, config.mode_step_list
         self.wav_loader = wav_loader or read_wav_16k
@@ -297,20 +362,24 @@ class WavsToDvector:
             self.dvector_list_dict = self.get_dvector()
 
     def files_to_dvectors(self, paths: Sequence[str]) -> np.ndarray:
-        if not self.resample:
+        if not self.resample and not self.pcm16:
             return self.embedder.embed_utterances([self.wav_loader(p) for p in paths], trim=self.trim)
         from .preprocessor import read_wav
-        by_rate: Dict[int, List[int]] = {}
+        groups: Dict[tuple, List[int]] = {}   # (rate, held as int16) -> files
         wavs = []
         for i, p in enumerate(paths):
-            wav, rate = read_wav(p)
+            wav, rate = read_wav(p, keep_pcm16=self.pcm16)
+            if not self.resample and int(rate) != SAMPLING_RATE:
+                raise MttsError(f"{p}: sampling rate {rate}, the speaker encoder takes {SAMPLING_RATE} Hz (WavsToDvector(resample=True) resamples)")
             wavs.append(wav)
-            by_rate.setdefault(int(rate), []).append(i)
+            groups.setdefault((int(rate), wav.dtype == np.int16), []).append(i)
         if not wavs:
             raise MttsError("no waveforms")
         out = np.empty((len(wavs), self.embedder.emb), np.float32)
-        for rate, idx in sorted(by_rate.items()):
-            out[idx] = self.embedder.embed_utterances([wavs[i] for i in idx], source_rate=rate, normalize_dbfs=self.normalize_dbfs, trim=self.trim)
+        for (rate, pcm), idx in sorted(groups.items()):
+            embed = self.embedder.embed_pcm16 if pcm else self.embedder.embed_utterances
+            chain = dict(source_rate=rate, normalize_dbfs=self.normalize_dbfs) if self.resample else {}
+            out[idx] = embed([wavs[i] for i in idx], trim=self.trim, **chain)
         return out
 
     def get_speaker_id_map(self):

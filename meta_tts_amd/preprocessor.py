@@ -85,10 +85,14 @@ def read_textgrid(path, include_empty_intervals=False) -> TextGrid:
     return TextGrid(out)
 
 
-def read_wav(path):
-    """(float32 waveform in [-1, 1], sampling rate): integer PCM is scaled by its full range (int16: / 32768), multi-channel files are averaged."""
+def read_wav(path, keep_pcm16=False):
+    """(float32 waveform in [-1, 1], sampling rate): integer PCM is scaled by its full range (int16: / 32768), multi-channel files are averaged.
+    keep_pcm16: a mono 16-bit PCM file comes back as the int16 samples it holds (for `SpeakerEmbedder.embed_pcm16`, which widens them
+    on the device); every other file as above."""
     from scipy.io import wavfile
     sr, x = wavfile.read(path)
+    if keep_pcm16 and x.dtype == np.int16 and x.ndim == 1:
+        return x, int(sr)
     if x.dtype.kind == "i":
         x = x.astype(np.float32) / float(2 ** (8 * x.dtype.itemsize - 1))
     elif x.dtype.kind == "u":

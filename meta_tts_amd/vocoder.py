@@ -114,6 +114,7 @@ class MelGAN:
         self.lib = _lib.load(lib_path)
         self.n_mel, self.ratios = n_mel, tuple(ratios)
         self.max_B, self.max_T = max_B, max_T
+        self.device, self.stream, self._wav_dev = device, 0, None   # (the stream set_stream gave; the waveform buffer of infer_device)
         h = C.c_void_p()
         arr = (C.c_int * len(ratios))(*ratios)
         if self.lib.mtts_vocoder_create(n_mel, ngf, n_res, arr, len(ratios), device, max_B, max_T, C.byref(h)) != 0:
@@ -134,6 +135,7 @@ class MelGAN:
 
     def set_stream(self, stream_ptr):
         self.lib.mtts_vocoder_set_stream(self.h, C.c_void_p(stream_ptr))
+        self.stream = int(stream_ptr or 0)
 
     def mel2wav(self, mel, lengths=None, mel_scale=1.0):
         """mel (B, n_mel, T) float -> (B, T * hop) float32; rows beyond lengths[b] * hop are zero."""
@@ -155,6 +157,22 @@ class MelGAN:
         if self.lib.mtts_vocoder_infer_device(self.h, C.c_void_p(mel_ptr), C.c_int64(utt_stride), B, T, lens.ctypes.data_as(C.c_void_p),
                                               C.c_float(mel_scale), C.c_void_p(wav_ptr)) != 0:
             raise MttsError(self.lib.mtts_vocoder_last_error(self.h).decode())
+
+    def infer_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths):
+        """`infer` without the host: the mel at `mel_ptr` (layout as in `mel2wav_device`, natural-log mels as the engine makes them,
+        `lengths` [B] frames) -> (wav_ptr, row_stride, sample_lengths, stream): float32 waveforms in a device buffer this object owns,
+        utterance b in the first sample_lengths[b] = lengths[b] * hop floats of row b, rows `row_stride` floats apart; enqueued on the
+        vocoder's `stream` and NOT waited for.  The tuple is what `SpeakerEmbedder.embed_device` takes (with `quantize=max_wav_value`
+        for `infer`'s cut to int16).  The buffer is reused by the next call."""
+        import torch
+        lens = np.minimum(np.asarray(lengths, np.int64).reshape(-1), T).astype(np.int32)
+        if len(lens) != B:
+            raise ValueError(f"infer_device: {len(lens)} lengths for B = {B}")
+        row_stride = T * self.hop
+        if self._wav_dev is None or self._wav_dev.numel() < B * row_stride:
+            self._wav_dev = torch.empty(B * row_stride, dtype=torch.float32, device=f"cuda:{self.device}")
+        self.mel2wav_device(mel_ptr, utt_stride, B, T, lens, self._wav_dev.data_ptr(), mel_scale=1.0 / math.log(10.0))
+        return self._wav_dev.data_ptr(), row_stride, lens * self.hop, self.stream
 
     def inverse(self, mel):                      # lightning/utils.py:16-18
         return self.mel2wav(mel)

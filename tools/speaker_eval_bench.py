@@ -3,13 +3,18 @@
 16 kHz, LSTM(40, 256, 3) with synthetic weights; no file I/O): utterances/s and audio-seconds/s of
   new     the batched device chain (meta_tts_amd/evaluation.py: SpeakerEmbedder.embed_utterances — packed STFT, power, mel, device
           gather, encoder; all utterances of a chunk share every launch);
+  pcm16   the same set held as int16 through SpeakerEmbedder.embed_pcm16 (2 bytes per sample uploaded, widened on the device);
+  device  the same samples resident in device memory as [utts][longest] float32 rows through SpeakerEmbedder.embed_device;
   today   the route possible before it: a numpy float32 front-end on the host (framing, basis product, power, mel, slicing) and
           one mtts_dvector_embed call per utterance with host mels;
   cpu     the torch restatement on 16 threads, one utterance at a time as the reference's evaluation/wavs_to_dvector.py does
           (--cpu-utts utterances, 32 by default, one warm-up and at most three repeats: the rate is what is compared).
 Each leg runs in a child process of its own under a time limit, after warm-up, as the median wall time of repeated calls that end in
 a device synchronise (every entry point is synchronous); a leg that fails ends the run.  Writes profiles/speaker_eval_bench.json and
-prints it.  Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/speaker_eval_bench.py --leg new` run."""
+prints it; `--legs a,b` runs only those legs and merges them into the file that is there.  pcm16 and device hold the float leg's samples
+cut to 16 bits (trunc(x * 32768)), so their d-vectors differ from the float leg's in the last digits and agree with each other.
+Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/speaker_eval_bench.py --leg new` (or pcm16 /
+device: wav_ingest_kernel against 6 / 8 bytes per sample) run."""
 import argparse
 import json
 import os
@@ -90,6 +95,17 @@ def leg(name, a):
         else:
             emb = E.SpeakerEmbedder(sd, max_partials=a.max_partials, max_utts=a.max_partials)
             call = lambda: emb.embed_utterances(wavs)   # noqa: E731
+            if name != "new":
+                i16 = [np.trunc(w * np.float32(32768)).astype(np.int16) for w in wavs]
+                call = lambda: emb.embed_pcm16(i16)   # noqa: E731
+            if name == "device":
+                lengths = np.asarray([len(w) for w in i16], np.int32)
+                rows = np.zeros((len(i16), int(lengths.max())), np.float32)
+                for r, w in zip(rows, i16):
+                    r[: len(w)] = w.astype(np.float32) / np.float32(32768)
+                dev = torch.from_numpy(rows).cuda()
+                torch.cuda.synchronize()
+                call = lambda: emb.embed_device(dev.data_ptr(), rows.shape[1], lengths)   # noqa: E731
     warmup, reps = (1, min(a.reps, 3)) if name == "cpu" else (a.warmup, a.reps)
     for _ in range(warmup):
         vec = call()
@@ -113,7 +129,8 @@ def main():
     ap.add_argument("--max-partials", type=int, default=2048)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--leg", default="all", choices=["all", "new", "today", "cpu"])
+    ap.add_argument("--leg", default="all", choices=["all", "new", "pcm16", "device", "today", "cpu"])
+    ap.add_argument("--legs", default="new,pcm16,device,today,cpu", help="with --leg all: the legs to run, merged into the file at --out when it holds the same set-up")
     ap.add_argument("--timeout", type=int, default=300, help="seconds per leg")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "speaker_eval_bench.json"))
     a = ap.parse_args()
@@ -122,15 +139,22 @@ def main():
         return
     res = {"utts": a.utts, "cpu_utts": a.cpu_utts, "max_partials": a.max_partials, "warmup": a.warmup, "reps": a.reps,
            "config": "16 kHz, 3-10 s utterances, n_fft 400 / hop 160 / 40 mels, LSTM(40, 256, 3) + Linear(256, 256), synthetic weights"}
-    for name in ("new", "today", "cpu"):
+    legs = a.legs.split(",")
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            old = json.load(f)
+        if all(old.get(k) == v for k, v in res.items()):
+            res = old
+    for name in legs:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", name, "--utts", str(a.utts), "--cpu-utts", str(a.cpu_utts), "--max-partials",
                             str(a.max_partials), "--warmup", str(a.warmup), "--reps", str(a.reps)], capture_output=True, text=True, timeout=a.timeout)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             raise SystemExit(f"leg {name} failed with status {r.returncode}: nothing further is started")
         res[name] = json.loads(r.stdout.strip().splitlines()[-1])
-    res["speedup_vs_today"] = round(res["new"]["utterances_per_s"] / res["today"]["utterances_per_s"], 2)
-    res["speedup_vs_cpu"] = round(res["new"]["utterances_per_s"] / res["cpu"]["utterances_per_s"], 2)
+    for other in ("today", "cpu"):
+        if "new" in res and other in res:
+            res[f"speedup_vs_{other}"] = round(res["new"]["utterances_per_s"] / res[other]["utterances_per_s"], 2)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
