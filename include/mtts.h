@@ -711,6 +711,45 @@ int mtts_tsne_gradient(mtts_tsne* h, double exaggeration, float* grad_out, doubl
 int mtts_tsne_run(mtts_tsne* h, int n_iter, double exaggeration, double momentum, double learning_rate, double min_gain, double* kl_out,
                   double* grad_norm_out);
 
+/* ---- mel-cepstral distortion along a DTW path, with F0 figures on the same path (csrc/dtw.h) ---------------------
+ * Scores whether two utterances of different length SAY the same thing: a synthesis (on predicted durations) against its recording.  The
+ * reference has no such step; this is the project's own definition, and parity with SPTK / WORLD mel-cepstra is UNPINNED.
+ *   cepstra   for a natural-log mel frame m[0 .. n_mel) (what TacotronSTFT produces): c_k = sum_n B[k][n] m[n], k = 1 .. K.  B = rows 1 .. K
+ *             of the orthonormal DCT-II (scipy.fft.dct(type=2, norm="ortho"); c_0 dropped), designed on the host in float64 and loaded
+ *             as float64 [K][n_mel].  The sum is float64 in ascending n.  1 <= K <= 34, K < n_mel <= 128.
+ *   distance  d(i, j) = sqrt(sum_k (a_ik - b_jk)^2), float64 in ascending k.
+ *   DTW       D(0, 0) = d(0, 0); D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), unit weights, ties to the first in that order,
+ *             no band and no slope constraint.  The path runs back from (Ta-1, Tb-1) to (0, 0); L = its number of cells.
+ *   MCD       (10 sqrt(2) / ln 10) D(Ta-1, Tb-1) / L, in dB.
+ *   F0        both tracks or neither; float64, one value per mel frame, 0 = unvoiced (as mtts_stft_f0_batch returns them).  Along the
+ *             path, summed in the order of the walk back (from (Ta-1, Tb-1) to (0, 0)): the number of cells with both frames voiced, the
+ *             RMSE of 1200 log2(fa / fb) over those cells in cents (NaN when there is none), the number of cells with exactly one side voiced.
+ * create: n_coef = K; max_frames <= 2048 bounds either side of a pair (three float64 diagonals of the sweep live in a workgroup's LDS);
+ *   max_cells <= 2^33 bounds sum Ta Tb of one chunk — the direction map, one byte per cell in a workspace the handle owns and grows on
+ *   demand, is the only Ta x Tb object; max_pairs <= 2^20 bounds the pairs of one chunk.
+ * cepstra: n_utts <= 2 max_pairs utterances of 1 <= n_frames[u] <= max_frames frames (refused by name otherwise, before any launch), log_mel
+ *   packed [sum T][n_mel] host float32 -> cep_out [sum T][K] host float64.
+ * mcd_batch: pair p aligns frames_a[p] rows of mel_a with frames_b[p] rows of mel_b (both packed [sum T][n_mel] host float32, pairs one
+ *   after another).  f0_a / f0_b (packed [sum T] host float64) may both be NULL; when given, f0_frames_a / f0_frames_b hold each track's
+ *   own length and must equal frames_a / frames_b.  out [n_pairs][6] float64: D(Ta-1, Tb-1), L, MCD, n_voiced_both, cents RMSE,
+ *   n_vuv_mismatch; columns 3 .. 5 are NaN without F0.  path_len [n_pairs] (or NULL) = L.  path (or NULL): pair p owns the (Ta + Tb - 1)
+ *   (i, j) int pairs that follow those of the pairs before it; its first L hold the path from (0, 0) forward, the rest -1.
+ *   The call is a plan: validate; cut the pairs, in order, into chunks of sum Ta Tb <= max_cells and at most max_pairs pairs; reserve
+ *   every buffer for the largest chunk; run chunk by chunk.  A pair's out row and path are bit-identical alone, in any batch, at any
+ *   position and under any chunking.  Synchronous.
+ * Refused with < 0, the reason (naming the pair and the limit) in last_error, before any launch, the handle staying usable: no basis
+ *   loaded; a frame count < 1 or > max_frames; Ta Tb > max_cells; an F0 track on one side only; an F0 length that differs from the frame
+ *   count; non-finite mel values; negative or non-finite F0; NULL required pointers. */
+typedef struct mtts_dtw mtts_dtw;
+int mtts_dtw_create(int n_mel, int n_coef, int max_frames, int64_t max_cells, int max_pairs, int device, mtts_dtw** out);
+void mtts_dtw_destroy(mtts_dtw* h);
+const char* mtts_dtw_last_error(mtts_dtw* h);
+int mtts_dtw_set_stream(mtts_dtw* h, void* hip_stream);
+int mtts_dtw_load_basis(mtts_dtw* h, const double* basis);
+int mtts_dtw_cepstra(mtts_dtw* h, int n_utts, const int* n_frames, const float* log_mel, double* cep_out);
+int mtts_dtw_mcd_batch(mtts_dtw* h, int n_pairs, const int* frames_a, const float* mel_a, const int* frames_b, const float* mel_b, const int* f0_frames_a,
+                       const double* f0_a, const int* f0_frames_b, const double* f0_b, double* out, int* path_len, int* path);
+
 #ifdef __cplusplus
 }
 #endif

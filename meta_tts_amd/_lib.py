@@ -208,6 +208,13 @@ EXPORTS = {
     "mtts_tsne_get_state": (C.c_int, [C.c_void_p] * 4),
     "mtts_tsne_gradient": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "mtts_tsne_run": (C.c_int, [C.c_void_p, C.c_int] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p]),
+    "mtts_dtw_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mtts_dtw_destroy": (None, [C.c_void_p]),
+    "mtts_dtw_last_error": (C.c_char_p, [C.c_void_p]),
+    "mtts_dtw_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mtts_dtw_load_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mtts_dtw_cepstra": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_dtw_mcd_batch": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 11),
 }
 
 _cache = {}

@@ -15,6 +15,7 @@
 #include "vad.h"
 #include "speakereval.h"
 #include "tsne.h"
+#include "dtw.h"
 
 using namespace mtts;
 
@@ -51,6 +52,9 @@ struct mtts_dvector {
 };
 struct mtts_tsne {
     Tsne t;
+};
+struct mtts_dtw {
+    Dtw d;
 };
 struct mtts_stft {
     MelFront m;
@@ -705,6 +709,34 @@ int mtts_tsne_gradient(mtts_tsne* h, double exaggeration, float* grad_out, doubl
 int mtts_tsne_run(mtts_tsne* h, int n_iter, double exaggeration, double momentum, double learning_rate, double min_gain, double* kl_out,
                   double* grad_norm_out) {
     return h ? h->t.run(n_iter, exaggeration, momentum, learning_rate, min_gain, kl_out, grad_norm_out) : tsne_null("mtts_tsne_run");
+}
+
+// ---- mel-cepstral distortion along a DTW path (dtw.h; this project's own evaluation step) ------------------------------------------------------
+int mtts_dtw_create(int n_mel, int n_coef, int max_frames, int64_t max_cells, int max_pairs, int device, mtts_dtw** out) {
+    if (!out) { g_create_error = "mtts_dtw_create: NULL out"; return -1; }
+    if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
+    mtts_dtw* h = new mtts_dtw();
+    DtwLimits l;
+    l.n_mel = n_mel; l.n_coef = n_coef; l.max_frames = max_frames; l.max_cells = (long long)max_cells; l.max_pairs = max_pairs;
+    if (h->d.init(l) != 0) { g_create_error = h->d.last_error; delete h; return -1; }
+    *out = h;
+    return 0;
+}
+void mtts_dtw_destroy(mtts_dtw* h) {
+    if (!h) return;
+    hipDeviceSynchronize();
+    delete h;
+}
+const char* mtts_dtw_last_error(mtts_dtw* h) { return h ? h->d.last_error.c_str() : g_create_error.c_str(); }
+static int dtw_null(const char* entry) { g_create_error = std::string(entry) + ": NULL handle"; return -1; }
+int mtts_dtw_set_stream(mtts_dtw* h, void* s) { if (!h) return dtw_null("mtts_dtw_set_stream"); h->d.stream = (hipStream_t)s; return 0; }
+int mtts_dtw_load_basis(mtts_dtw* h, const double* basis) { return h ? h->d.load_basis(basis) : dtw_null("mtts_dtw_load_basis"); }
+int mtts_dtw_cepstra(mtts_dtw* h, int n_utts, const int* n_frames, const float* log_mel, double* cep_out) {
+    return h ? h->d.cepstra(n_utts, n_frames, log_mel, cep_out) : dtw_null("mtts_dtw_cepstra");
+}
+int mtts_dtw_mcd_batch(mtts_dtw* h, int n_pairs, const int* frames_a, const float* mel_a, const int* frames_b, const float* mel_b, const int* f0_frames_a,
+                       const double* f0_a, const int* f0_frames_b, const double* f0_b, double* out, int* path_len, int* path) {
+    return h ? h->d.mcd_batch(n_pairs, frames_a, mel_a, frames_b, mel_b, f0_frames_a, f0_a, f0_frames_b, f0_b, out, path_len, path) : dtw_null("mtts_dtw_mcd_batch");
 }
 
 // ---- d-vector speaker encoder (dvector.h; reference lightning/model/speaker_encoder.py:11-31,54-60,71-76) ----------------

@@ -20,7 +20,11 @@ The t-SNE behind the reference's scatter figure (evaluation/visualize.py) runs o
 what the reference uses and drives csrc/tsne.h — sklearn's method="exact" definition, not the Barnes-Hut approximation the reference's
 call gets on the CPU; sklearn is not imported.  `VisualizeDvector` loads the modes' d-vectors, embeds them jointly, cuts out the
 speakers of the figure and returns (or writes as CSV) the table the plot is drawn from.  The figures themselves (the reference's
-matplotlib / seaborn plots) and MOS prediction (third-party networks) are out of scope."""
+matplotlib / seaborn plots) and MOS prediction (third-party networks) are out of scope.
+
+Beyond the reference: `MelCepstralDistortion` and `ObjectiveEvaluation` score whether a synthesis SAYS what its recording says — mel-cepstral
+distortion along a DTW path, with F0 error and voiced/unvoiced disagreement on the same path (csrc/dtw.h; the definition is this
+project's own, include/mtts.h states it, and parity with SPTK / WORLD mel-cepstra is UNPINNED)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -911,3 +915,260 @@ class VisualizeDvector:
             w.writerow(list(data))
             w.writerows(zip(*(data[k].tolist() for k in data)))
         return data
+
+
+# ---- mel-cepstral distortion along a DTW path (csrc/dtw.h; this project's own step: the reference scores the voice only) ------------------
+class MelCepstralDistortion:
+    """Does a synthesis say what its recording says?  Mel-cepstral distortion along a dynamic-time-warping path, with log-F0 error and
+    voiced/unvoiced disagreement on the same path, on an `mtts_dtw` handle (include/mtts.h states the definition; parity with SPTK /
+    WORLD mel-cepstra is unpinned).  Mels are natural-log mels as `TacotronSTFT` produces them, one (T, n_mel) array per utterance.
+    max_frames bounds either side of a pair, max_cells the sum of Ta x Tb of one chunk of a call (the direction map, one byte per
+    cell, is the only device buffer of that size; longer calls are cut into chunks, with the same results bit for bit)."""
+
+    COLUMNS = ("D", "L", "MCD", "n_voiced_both", "cents_rmse", "n_vuv_mismatch")
+
+    def __init__(self, n_mel: int = 80, n_coef: int = 13, max_frames: int = 2048, max_cells: int = 1 << 28, lib_path=None, *, max_pairs: int = 4096,
+                 device: int = 0):
+        from . import _lib
+        self.n_mel, self.n_coef, self.max_frames, self.max_cells, self.max_pairs = int(n_mel), int(n_coef), int(max_frames), int(max_cells), int(max_pairs)
+        self.lib = _lib.load(lib_path)
+        self.h = None
+        h = C.c_void_p()
+        if self.lib.mtts_dtw_create(self.n_mel, self.n_coef, self.max_frames, self.max_cells, self.max_pairs, device, C.byref(h)) != 0:
+            raise MttsError(self.lib.mtts_dtw_last_error(None).decode())
+        self.h = h
+        self.basis = self.dct_basis()
+        self._check(self.lib.mtts_dtw_load_basis(self.h, _ptr(self.basis)))
+
+    def _check(self, rc):
+        if rc < 0:
+            raise MttsError(self.lib.mtts_dtw_last_error(self.h).decode())
+        return rc
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mtts_dtw_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def dct_basis(self) -> np.ndarray:
+        """Rows 1 .. n_coef of the orthonormal DCT-II over n_mel points (scipy.fft.dct(type=2, norm="ortho") without c0): float64 [n_coef][n_mel]."""
+        N = self.n_mel
+        # B[k-1][n] = sqrt(2 / N) cos(pi (2 n + 1) k / (2 N)); the angle as an integer count q of pi / (2 N), folded into the first octant
+        q = np.outer(np.arange(1, self.n_coef + 1), 2 * np.arange(N) + 1) % (4 * N)
+        q = np.where(q > 2 * N, 4 * N - q, q)
+        sign = np.where(q > N, -1.0, 1.0)
+        q = np.where(q > N, 2 * N - q, q)
+        val = np.where(2 * q > N, np.sin(np.pi * (N - q) / (2.0 * N)), np.cos(np.pi * q / (2.0 * N)))
+        return np.ascontiguousarray(np.sqrt(2.0 / N) * sign * val)
+
+    def _pack(self, mels, what):
+        ms = [np.ascontiguousarray(np.asarray(m, np.float32)) for m in mels]
+        for u, m in enumerate(ms):
+            if m.ndim != 2 or m.shape[1] != self.n_mel:
+                raise ValueError(f"{what}[{u}] has shape {m.shape}, expected (T, {self.n_mel})")
+        if not ms:
+            raise MttsError("no utterances")
+        return np.asarray([len(m) for m in ms], np.int32), np.ascontiguousarray(np.concatenate(ms, axis=0))
+
+    def cepstra(self, mels) -> List[np.ndarray]:
+        """[(T_u, n_mel) log-mel] -> [(T_u, n_coef) float64], one device call."""
+        T, packed = self._pack(mels, "mels")
+        out = np.empty((int(T.sum()), self.n_coef), np.float64)
+        self._check(self.lib.mtts_dtw_cepstra(self.h, len(T), _ptr(T), _ptr(packed), _ptr(out)))
+        return np.split(out, np.cumsum(T)[:-1])
+
+    def mcd_batch(self, mels_a, mels_b, f0_a=None, f0_b=None, return_paths: bool = False):
+        """Pair p aligns mels_a[p] with mels_b[p] -> float64 [n_pairs][6]: D, L, MCD [dB], n_voiced_both, cents RMSE, n_vuv_mismatch (see
+        `COLUMNS`; the last three NaN without F0, the RMSE NaN when no step has both frames voiced).  f0_a / f0_b: per utterance a
+        float64 track with one value per mel frame, 0 = unvoiced (`PitchExtractor.f0_batch`); both or neither.  return_paths: also
+        the list of (L_p, 2) int32 paths, (0, 0) first."""
+        if len(mels_a) != len(mels_b):
+            raise ValueError(f"mcd_batch: {len(mels_a)} mels_a but {len(mels_b)} mels_b")
+        Ta, pa = self._pack(mels_a, "mels_a")
+        Tb, pb = self._pack(mels_b, "mels_b")
+        f0 = [None, None, None, None]
+        for side, tracks in enumerate((f0_a, f0_b)):
+            if tracks is not None:
+                if len(tracks) != len(Ta):
+                    raise ValueError(f"mcd_batch: {len(tracks)} F0 tracks for {len(Ta)} pairs")
+                ts = [np.ascontiguousarray(np.asarray(t, np.float64).reshape(-1)) for t in tracks]
+                f0[2 * side] = np.asarray([len(t) for t in ts], np.int32)
+                f0[2 * side + 1] = np.ascontiguousarray(np.concatenate(ts))
+        out = np.empty((len(Ta), 6), np.float64)
+        L = np.empty(len(Ta), np.int32)
+        cap = Ta.astype(np.int64) + Tb - 1
+        path = np.empty((int(cap.sum()), 2), np.int32) if return_paths else None
+        self._check(self.lib.mtts_dtw_mcd_batch(self.h, len(Ta), _ptr(Ta), _ptr(pa), _ptr(Tb), _ptr(pb), *[None if v is None else _ptr(v) for v in f0], _ptr(out), _ptr(L),
+                                                None if path is None else _ptr(path)))
+        if not return_paths:
+            return out
+        starts = np.concatenate([[0], np.cumsum(cap)[:-1]])
+        return out, [path[s:s + n].copy() for s, n in zip(starts, L)]
+
+
+class ObjectiveEvaluation:
+    """MCD / F0 figures of a test run's result tree, next to the speaker-similarity classes above and over the same files: for every
+    mode and step of `config.mode_step_list` each synthesised wav against its real wav, and each recon wav (the vocoder on the
+    ground-truth mel) against its real wav as the floor the vocoder sets.  `mcd`: a `MelCepstralDistortion`; `stft`: the `TacotronSTFT`
+    whose log-mels are compared (its handle's batched front-end computes them); `pitch`: a `PitchExtractor` at the same sampling rate
+    and hop, or None for MCD only; `wav_loader(path) -> float32 waveform at the STFT's sampling rate` (default:
+    `preprocessor.read_wav`, refusing another rate).
+
+    An evaluation set is thousands of utterances, more than one call of the front-end holds (csrc/melfront.h refuses about a million
+    frames, and its spectrum workspace is 4 KB per frame), so the work is cut twice, with the same tables bit for bit whatever the cut:
+    a mode is scored `pairs_per_call` pairs at a time (only that many synthesised mels are alive at once), and the files of such a block
+    go to the front-end in calls of at most `frames_per_call` mel frames (default 65 536: a 270 MB spectrum at filter length 1 024)
+    and `MAX_UTTS_PER_CALL` utterances; an utterance longer than the budget goes alone.  Only the features of the REAL files are kept
+    (every mode and step is scored against them); a table row is one test file, in `mode_filelist` order."""
+
+    MAX_UTTS_PER_CALL = 4096
+
+    def __init__(self, config: EvalConfig, mcd: MelCepstralDistortion, stft, pitch=None, wav_loader: Optional[Callable[[str], np.ndarray]] = None, *,
+                 frames_per_call: int = 1 << 16, pairs_per_call: int = 512):
+        self.config, self.mcd, self.stft, self.pitch = config, mcd, stft, pitch
+        if mcd.n_mel != stft.n_mel_channels:
+            raise ValueError(f"ObjectiveEvaluation: the MCD handle takes {mcd.n_mel} mel channels, the STFT produces {stft.n_mel_channels}")
+        if pitch is not None and (pitch.hop_length != stft.hop_length or pitch.sampling_rate != stft.sampling_rate):
+            raise ValueError("ObjectiveEvaluation: the pitch extractor's sampling rate and hop length must be the STFT's (one F0 value per mel frame)")
+        self.frames_per_call, self.pairs_per_call = int(frames_per_call), int(pairs_per_call)
+        if self.frames_per_call < 1 or self.frames_per_call * int(stft.hop_length) >= 1 << 31 or self.frames_per_call > (1 << 30) // (int(stft.filter_length) + 2):
+            raise ValueError(f"ObjectiveEvaluation: frames_per_call = {frames_per_call} outside what one front-end call holds at hop {stft.hop_length}, filter length {stft.filter_length}")
+        if self.pairs_per_call < 1:
+            raise ValueError(f"ObjectiveEvaluation: pairs_per_call = {pairs_per_call} must be at least 1")
+        self.n_speaker, self.n_sample, self.mode_step_list, self.data_dir_dict = config.n_speaker, config.n_sample, config.mode_step_list, config.data_dir_dict
+        self.wav_loader = wav_loader or self._read_wav
+        with open(os.path.join(self.data_dir_dict["recon"], "test_SQids.json")) as f:
+            self.sq_list = json.load(f)
+        self.speaker_id_map, self.inv_speaker_id_map = self.get_speaker_id_map()
+        self.real_filelist = self.get_real_filelist()
+        self.mcd_dict: Dict[str, np.ndarray] = {}
+        self._real_features = {}      # real file -> (mel, f0): the only features kept
+        self.front_end_calls = 0      # mtts_stft_mel_batch calls so far
+
+    get_speaker_id_map = WavsToDvector.get_speaker_id_map
+    get_real_filelist = WavsToDvector.get_real_filelist
+    _find = WavsToDvector._find
+
+    def _read_wav(self, path: str) -> np.ndarray:
+        from .preprocessor import read_wav
+        wav, rate = read_wav(path)
+        if int(rate) != int(self.stft.sampling_rate):
+            raise MttsError(f"{path}: sampling rate {rate}, the STFT takes {self.stft.sampling_rate} Hz (pass a wav_loader that resamples)")
+        return wav
+
+    def _modes(self):
+        return ["recon"] + [f"{m}_step{s}" for m, steps in self.mode_step_list for s in steps]
+
+    def _front_end(self, wavs):
+        """One front-end call (and one F0 call) for waveforms the caller has kept within the budget -> ([mel], [f0] or [None])."""
+        n = np.asarray([len(w) for w in wavs], np.int32)
+        T = n.astype(np.int64) // self.stft.hop_length + 1
+        mel, energy = np.empty((int(T.sum()), self.stft.n_mel_channels), np.float32), np.empty(int(T.sum()), np.float32)
+        packed = np.ascontiguousarray(np.concatenate(wavs))
+        self.stft._check(self.stft.lib.mtts_stft_mel_batch(self.stft.h, len(wavs), _ptr(n), None, _ptr(packed), _ptr(mel), _ptr(energy)))
+        self.front_end_calls += 1
+        mels = [m.copy() for m in np.split(mel, np.cumsum(T)[:-1])]      # (copies: a kept mel must not pin its whole call's buffer)
+        return mels, (self.pitch.f0_batch(wavs)[0] if self.pitch is not None else [None] * len(wavs))
+
+    def features(self, paths: Sequence[str]):
+        """([log-mel (T_u, n_mel) float32], [f0 (T_u,) float64] or None) of the files, in order.  The files are read and sent to the
+        front-end in calls of at most `frames_per_call` frames and `MAX_UTTS_PER_CALL` utterances; an utterance's rows are the same
+        bits whatever else shares its call.  Nothing is kept."""
+        mels, f0s, wavs, frames = [], [], [], 0
+
+        def flush():
+            if wavs:
+                m, f = self._front_end(wavs)
+                mels.extend(m)
+                f0s.extend(f)
+                wavs.clear()
+
+        for p in paths:
+            w = np.ascontiguousarray(np.asarray(self.wav_loader(p), np.float32).reshape(-1))
+            T = len(w) // self.stft.hop_length + 1
+            if wavs and (frames + T > self.frames_per_call or len(wavs) >= self.MAX_UTTS_PER_CALL):
+                flush()
+                frames = 0
+            wavs.append(w)
+            frames += T
+        flush()
+        return mels, (f0s if self.pitch is not None else None)
+
+    def real_features(self, paths: Sequence[str]):
+        """`features` of real files, each computed once and kept: every mode and step is scored against the same recordings."""
+        todo = [p for p in dict.fromkeys(paths) if p not in self._real_features]
+        if todo:
+            mels, f0s = self.features(todo)
+            for k, p in enumerate(todo):
+                self._real_features[p] = (mels[k], None if f0s is None else f0s[k])
+        got = [self._real_features[p] for p in paths]
+        return [m for m, _ in got], ([f for _, f in got] if self.pitch is not None else None)
+
+    def mode_filelist(self, mode: str):
+        """(test files of the mode, the real file each is scored against): one per test sample in data_id order, five in the 1-shot
+        layout test_###_0 .. 4.  A test sample without its directory or its wav is an error, as in `get_syn_dvector_list`: a table has
+        a row for every file of every sample, so that the rows of all modes line up."""
+        if mode == "recon":
+            root, suffix = _testing_dir(self.data_dir_dict["recon"]), "recon.wav"
+        else:
+            name, step = mode.rsplit("_step", 1)
+            root, suffix = _testing_dir(self.data_dir_dict[name]), f"FTstep_{step}.synth.wav"
+        test, real = [], []
+        for data_id in range(self.n_speaker * self.n_sample):
+            d = os.path.join(root, f"test_{data_id:03d}")
+            if os.path.exists(d):
+                dirs = [d]
+            elif mode != "recon" and os.path.exists(d + "_0"):
+                dirs = [f"{d}_{i}" for i in range(5)]
+            else:
+                raise MttsError(f"ObjectiveEvaluation: mode {mode}: test sample {data_id} has no directory {d}")
+            for wav_dir in dirs:
+                p = self._find(wav_dir, suffix) if os.path.exists(wav_dir) else None
+                if p is None:
+                    raise MttsError(f"ObjectiveEvaluation: mode {mode}: test sample {data_id} has no *{suffix} in {wav_dir}")
+                test.append(p)
+                real.append(self.real_filelist[data_id])
+        return test, real
+
+    def compute_mcd(self, mode: str) -> np.ndarray:
+        test, real = self.mode_filelist(mode)
+        rows = []
+        for lo in range(0, len(test), self.pairs_per_call):
+            mels_t, f0_t = self.features(test[lo:lo + self.pairs_per_call])
+            mels_r, f0_r = self.real_features(real[lo:lo + self.pairs_per_call])
+            rows.append(self.mcd.mcd_batch(mels_t, mels_r, f0_t, f0_r))
+        return np.concatenate(rows, axis=0)
+
+    def get_mcd(self):
+        """One [n][6] table per mode (`MelCepstralDistortion.COLUMNS`), saved as npy/<corpus>/<mode>_mcd.npy; an existing file is loaded instead."""
+        for mode in self._modes():
+            path = self.config.path("npy", f"{mode}_mcd.npy")
+            if os.path.exists(path):
+                self.mcd_dict[mode] = np.load(path)
+            else:
+                self.mcd_dict[mode] = self.compute_mcd(mode)
+                np.save(path, self.mcd_dict[mode])
+        return self.mcd_dict
+
+    @staticmethod
+    def summarize(table: np.ndarray):
+        """(mean MCD [dB], mean cents RMSE over the pairs that have one, V/UV disagreement in % of all path steps); NaN without F0."""
+        t = np.asarray(table, np.float64)
+        rmse = t[:, 4][np.isfinite(t[:, 4])]
+        with_f0 = np.isfinite(t[:, 5]).all() and len(t) > 0
+        return float(t[:, 2].mean()), (float(rmse.mean()) if len(rmse) else float("nan")), (float(100.0 * t[:, 5].sum() / t[:, 1].sum()) if with_f0 else float("nan"))
+
+    def save_mcd(self, output_path: str = "mcd.txt"):
+        """npy/<corpus>/mcd_dict.npy and the text summary txt/<corpus>/<output_path>, next to eer.txt."""
+        np.save(self.config.path("npy", "mcd_dict.npy"), self.mcd_dict, allow_pickle=True)
+        with open(self.config.path("txt", output_path), "w+") as f:
+            for mode, table in self.mcd_dict.items():
+                m, c, v = self.summarize(table)
+                f.write(mode + ":\n")
+                f.write(f"MCD:{m:.4f}\tF0_RMSE_cents:{c:.2f}\tVUV_percent:{v:.2f}\n")
+
+    def load_mcd(self):
+        self.mcd_dict = np.load(self.config.path("npy", "mcd_dict.npy"), allow_pickle=True)[()]
+        return self.mcd_dict
