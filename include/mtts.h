@@ -388,6 +388,42 @@ int mtts_vocoder_infer(mtts_vocoder* h, const float* mel, int B, int T_max, cons
 int mtts_vocoder_infer_device(mtts_vocoder* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
                               float mel_scale, float* wav_dev);
 
+/* ---- HiFi-GAN generator: mel -> waveform, the second neural vocoder ------------------------
+ * Stands behind the `name == "HiFi-GAN"` branch of utils/model.py:32-50 (vocoder(mels).squeeze(1)).  The generator is NOT part of the
+ * reference tree (neither its code nor generator_universal.pth.tar): parity with published weights is UNPINNED; what is pinned is this
+ * definition (the published Generator with ResBlock type "1"), restated in torch by tests/hifigan_oracle.py:
+ *     x = conv_pre(mel)                                  Conv1d(n_mel -> C0, k 7, zero pad 3)
+ *     for i in 0..n_up-1:
+ *         x = leaky_relu(x, 0.1);  x = ups[i](x)         ConvTranspose1d(C_i -> C_i/2, k = 2 r_i, stride r_i, pad r_i/2)
+ *         x = (1/n_k) * sum_j resblocks[i*n_k + j](x)    (the "MRF" mean over the n_k kernel sizes)
+ *     x = leaky_relu(x, 0.01);  x = conv_post(x)         Conv1d(C_last -> 1, k 7, zero pad 3);  tanh
+ *     ResBlock1(k, (d_0..d_{m-1})): for each d:  t = leaky_relu(x, 0.1);  t = conv(k, dilation d, zero pad d(k-1)/2)(t)
+ *                                                t = leaky_relu(t, 0.1);  t = conv(k, dilation 1, zero pad (k-1)/2)(t);  x = t + x
+ * Zero padding is applied at each utterance's own ends: an utterance of a ragged batch is computed as if it were alone.
+ * create: rates [n_rates] (each even and >= 2; the transposed kernel is 2 * rate, the published V1 / V2 / V3 relation), res_kernels
+ * [n_res_kernels <= 4] odd and <= 11, res_dilations [n_res_kernels][n_dil <= 4] in 1..5, resblock_type 1 (2 is refused), n_mel a
+ * multiple of 16, initial_channels a multiple of 16 << n_rates; anything else is refused with a message that names the argument.
+ * direct_max_channels: 0, 32 or 64 — stages whose channel count is 32 or 64 and <= this value take the direct convolution kernel
+ * (csrc/hifigan.h) instead of the grouped GEMM; 0: GEMM route everywhere.  Both routes compute the same definition.
+ * Tensors (weight-norm already folded, see meta_tts_amd/hifigan.py):
+ *   conv_pre.w [C0][7][n_mel], conv_pre.b [C0];  ups.{i}.w [r][C_out][2*C_in] (phase-major polyphase image: x[q-1] | x[q]), ups.{i}.b;
+ *   resblocks.{i*n_k+j}.convs1.{m}.w and .convs2.{m}.w [C][k][C], .b [C];  conv_post.w [7][C_last], conv_post.b [1].
+ * infer / infer_device: the pointer, stride, stream and asynchrony contract of the MelGAN entries above; mel_lens[b] in 4..T_max. */
+typedef struct mtts_hifigan mtts_hifigan;
+int mtts_hifigan_create(int n_mel, int initial_channels, const int* rates, int n_rates, const int* res_kernels, int n_res_kernels,
+                        const int* res_dilations, int n_dil, int resblock_type, int direct_max_channels, int device, int max_B, int max_T,
+                        mtts_hifigan** out);
+void mtts_hifigan_destroy(mtts_hifigan* h);
+const char* mtts_hifigan_last_error(mtts_hifigan* h);
+int mtts_hifigan_set_stream(mtts_hifigan* h, void* hip_stream);
+int mtts_hifigan_hop(mtts_hifigan* h);
+int mtts_hifigan_param_count(mtts_hifigan* h);
+int mtts_hifigan_param_info(mtts_hifigan* h, int index, char* name, int name_cap, int64_t* numel);
+int mtts_hifigan_load(mtts_hifigan* h, const char* name, const float* data, int64_t numel);
+int mtts_hifigan_infer(mtts_hifigan* h, const float* mel, int B, int T_max, const int* mel_lens, float mel_scale, float* wav);
+int mtts_hifigan_infer_device(mtts_hifigan* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
+                              float mel_scale, float* wav_dev);
+
 /* ---- d-vector speaker encoder, forward only (`speaker_emb: dvec`) -------------------------
  * Replaces `SpeakerEncoder.forward` for emb_type "dvec" (lightning/model/speaker_encoder.py:54-60,71-76): the frozen
  * resemblyzer `VoiceEncoder` (un-vendored; architecture restated by the reference's own GE2E class, :11-31: LSTM(n_mels -> hidden,

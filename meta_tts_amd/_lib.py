@@ -197,6 +197,17 @@ EXPORTS = {
     "mtts_vocoder_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     "mtts_vocoder_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
     "mtts_vocoder_infer_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
+    "mtts_hifigan_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mtts_hifigan_destroy": (None, [C.c_void_p]),
+    "mtts_hifigan_last_error": (C.c_char_p, [C.c_void_p]),
+    "mtts_hifigan_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mtts_hifigan_hop": (C.c_int, [C.c_void_p]),
+    "mtts_hifigan_param_count": (C.c_int, [C.c_void_p]),
+    "mtts_hifigan_param_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
+    "mtts_hifigan_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "mtts_hifigan_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
+    "mtts_hifigan_infer_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
     "mtts_get_mel_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mtts_tsne_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mtts_tsne_destroy": (None, [C.c_void_p]),

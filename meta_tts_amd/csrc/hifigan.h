@@ -1,0 +1,429 @@
+// HiFi-GAN generator (mel -> waveform), ResBlock type "1" — DESIGN.md section 1 row a24, the second neural vocoder beside vocoder.h.
+//
+// Reference call site: utils/model.py:32-50 (vocoder_infer, branch name == "HiFi-GAN": vocoder(mels).squeeze(1), x max_wav_value ->
+// int16, cut to lengths).  The generator itself is NOT in the reference tree (its hifigan/ package and generator_universal.pth.tar are
+// absent): the architecture below is the published one (Kong et al. 2020, Generator with resblock "1"):
+//     x = conv_pre(mel)                                  Conv1d(n_mel -> C0, k 7, zero pad 3)
+//     for i in 0..n_up-1:
+//         x = leaky_relu(x, 0.1);  x = ups[i](x)         ConvTranspose1d(C_i -> C_i/2, k = 2 r_i, stride r_i, pad r_i/2)
+//         x = (1/n_k) * sum_j resblocks[i*n_k + j](x)    ("MRF": mean over the n_k kernel sizes)
+//     x = leaky_relu(x, 0.01);  x = conv_post(x)         Conv1d(C_last -> 1, k 7, zero pad 3);  tanh
+//     ResBlock1(k, (d_0..d_{m-1})): for each d:  t = leaky_relu(x, 0.1);  t = conv(k, dilation d, zero pad d(k-1)/2)(t)
+//                                                t = leaky_relu(t, 0.1);  t = conv(k, dilation 1, zero pad (k-1)/2)(t);  x = t + x
+// with weight normalisation folded on the host (meta_tts_amd/hifigan.py).  Parity with published weights is UNPINNED: checked against
+// tests/hifigan_oracle.py, a torch restatement of the same definition.  Padding is zero padding at each utterance's own ends.
+//
+// MI355X mapping: activations are channels-last row matrices [time][C] per utterance, row counts through GemmArgs::dimptr, as in vocoder.h.
+//   GEMM route (every channel count): conv_pre, the r polyphase GEMMs of a transposed convolution (one multi-problem launch) and the
+//   residual convolutions go through gemm_launch.  A pair costs three launches: hg_pad_kernel writes the zero-padded LeakyReLU image of
+//   x and clears the guard rows of the buffer conv1 writes into; conv1 (dilated taps inside the K-loop when C % 32 == 0, else one
+//   accumulate pass per tap) puts LeakyReLU(. + b) between those guard rows; conv2 (K = k C over contiguous rows) accumulates onto x
+//   in place (GEMM_ACCUM) — the residual add.  The MRF mean rides in the pad pass: the first pad of block j > 0 folds block j-1's result
+//   into the sum and restarts x from the stage input; the pad that feeds the next stage reads sum + x / n_k.
+//   Direct route (C in {32, 64}, C <= direct_max_channels): hg_conv_direct_kernel does a whole dilated convolution without a padded
+//   copy — a workgroup stages 128 + (k-1) d rows in LDS (LeakyReLU on the way in, zeros outside the utterance), runs the k C deep product
+//   on the fp32 MFMA pipe with the weights streamed from L2, and ends with bias + LeakyReLU, bias + residual, or bias + residual + MRF
+//   accumulation.  A pair costs two launches and no pad pass.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "vocoder.h"
+
+namespace mtts {
+
+constexpr int kHgMaxUps = 8, kHgMaxKernels = 4, kHgMaxDil = 4, kHgMaxResKernel = 11, kHgMaxDilation = 5;
+constexpr int kHgTileRows = 128;                                             // output rows of a direct-route workgroup
+constexpr int kHgMaxHalo = (kHgMaxResKernel - 1) * kHgMaxDilation;           // 50 rows (both sides together)
+
+struct HifiGanCfg {
+    int n_mel = 80, c0 = 512, n_up = 4, n_k = 3, n_dil = 3, resblock = 1, direct_max = 0;
+    int rates[kHgMaxUps] = {8, 8, 2, 2, 0, 0, 0, 0};
+    int kernels[kHgMaxKernels] = {3, 7, 11, 0};
+    int dil[kHgMaxKernels][kHgMaxDil] = {{1, 3, 5, 0}, {1, 3, 5, 0}, {1, 3, 5, 0}, {0, 0, 0, 0}};
+};
+
+// empty: supported; else the refusal, naming the argument
+inline std::string hifigan_check_cfg(const HifiGanCfg& c, int max_B, int max_T) {
+    if (c.resblock != 1) return "resblock_type " + std::to_string(c.resblock) + " is not supported (only ResBlock \"1\")";
+    if (c.n_mel < 16 || c.n_mel % 16) return "n_mel must be a positive multiple of 16";
+    if (c.n_up < 1 || c.n_up > kHgMaxUps) return "n_rates must be 1.." + std::to_string(kHgMaxUps);
+    if (c.n_k < 1 || c.n_k > kHgMaxKernels) return "n_res_kernels must be 1.." + std::to_string(kHgMaxKernels);
+    if (c.n_dil < 1 || c.n_dil > kHgMaxDil) return "n_dil must be 1.." + std::to_string(kHgMaxDil);
+    if (c.c0 < 16 || c.c0 % (16 << c.n_up)) return "initial_channels must halve per stage and stay a multiple of 16 (need a multiple of " + std::to_string(16 << c.n_up) + ")";
+    for (int i = 0; i < c.n_up; ++i)
+        if (c.rates[i] < 2 || (c.rates[i] & 1)) return "rates[" + std::to_string(i) + "] = " + std::to_string(c.rates[i]) + ": every rate must be even and >= 2";
+    for (int j = 0; j < c.n_k; ++j) {
+        if (c.kernels[j] < 1 || !(c.kernels[j] & 1) || c.kernels[j] > kHgMaxResKernel)
+            return "res_kernels[" + std::to_string(j) + "] = " + std::to_string(c.kernels[j]) + ": residual kernel sizes must be odd and <= " + std::to_string(kHgMaxResKernel);
+        for (int m = 0; m < c.n_dil; ++m)
+            if (c.dil[j][m] < 1 || c.dil[j][m] > kHgMaxDilation)
+                return "res_dilations[" + std::to_string(j) + "][" + std::to_string(m) + "] = " + std::to_string(c.dil[j][m]) + ": dilations must be 1.." + std::to_string(kHgMaxDilation);
+    }
+    if (c.direct_max != 0 && c.direct_max != 32 && c.direct_max != 64) return "direct_max_channels must be 0, 32 or 64";
+    if (max_B < 1) return "max_B must be >= 1";
+    if (max_T < 4) return "max_T must be >= 4";
+    return "";
+}
+
+// One pass over the rows of x (T = lens[z] * len_mult rows of C floats per utterance z):  v = xs * x[row] (+ add[row])
+//   y rows [0, T + 2d):  y[d + row] = leaky_relu(v, slope), zero rows outside       (the padded operand of the next convolution)
+//   mrf[row] = (fold_init ? 0 : mrf[row]) + fs * fold[row]                           (MRF sum; read BEFORE copy is written: fold may be copy)
+//   copy[row] = v                                                                     (restart of x from the stage input)
+//   guard rows [0, gp) and [gp + T, 2 gp + T) = 0                                     (zero padding of the buffer conv1 writes between them)
+struct HgPadArgs {
+    const int* lens = nullptr; int len_mult = 1, C = 0;
+    const float* x = nullptr; long long x_gs = 0; float xs = 1.f;
+    const float* add = nullptr; long long add_gs = 0;
+    float* y = nullptr; long long y_gs = 0; int d = 0; float slope = 1.f;
+    const float* fold = nullptr; long long fold_gs = 0; float fs = 0.f; int fold_init = 0;
+    float* mrf = nullptr; long long mrf_gs = 0;
+    float* copy = nullptr; long long copy_gs = 0;
+    float* guard = nullptr; long long guard_gs = 0; int gp = 0;
+};
+__device__ __forceinline__ float hg_lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
+__global__ void hg_pad_kernel(HgPadArgs a) {
+    const int z = blockIdx.z;
+    const int T = a.lens[z] * a.len_mult, C4 = a.C >> 2;
+    const long long idx = (long long)blockIdx.x * 256 + (int)threadIdx.x;
+    if (a.guard && idx < 2LL * a.gp * C4) {
+        const int g = (int)(idx / C4), c = (int)(idx - (long long)g * C4) * 4;
+        st4(a.guard + (long long)z * a.guard_gs + (long long)(g < a.gp ? g : T + g) * a.C + c, zero4());
+    }
+    const long long prow = idx / C4;
+    if (prow >= (long long)T + 2 * a.d) return;
+    const int c = (int)(idx - prow * C4) * 4;
+    const long long row = prow - a.d;
+    float4 v = zero4();
+    if (row >= 0 && row < T) {
+        const long long o = row * a.C + c;
+        v = ld4(a.x + (long long)z * a.x_gs + o);
+        v.x *= a.xs; v.y *= a.xs; v.z *= a.xs; v.w *= a.xs;
+        if (a.add) { const float4 s = ld4(a.add + (long long)z * a.add_gs + o); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
+        if (a.fold) {
+            const float4 f = ld4(a.fold + (long long)z * a.fold_gs + o);
+            float* pm = a.mrf + (long long)z * a.mrf_gs + o;
+            const float4 m = a.fold_init ? zero4() : ld4(pm);
+            st4(pm, make_float4(m.x + a.fs * f.x, m.y + a.fs * f.y, m.z + a.fs * f.z, m.w + a.fs * f.w));
+        }
+        if (a.copy) st4(a.copy + (long long)z * a.copy_gs + o, v);
+        v.x = hg_lrelu(v.x, a.slope); v.y = hg_lrelu(v.y, a.slope); v.z = hg_lrelu(v.z, a.slope); v.w = hg_lrelu(v.w, a.slope);
+    }
+    st4(a.y + (long long)z * a.y_gs + prow * a.C + c, v);
+}
+
+// Direct route: out = epilogue(bias + conv(k, dilation d, zero pad d (k-1)/2)(leaky_relu(x, in_slope))) for one utterance's 128-row tile.
+//   mode 0: out = leaky_relu(., 0.1)                          (first convolution of a pair; the second then reads with in_slope 1)
+//   mode 1: out = . + res                                     (second convolution: the residual add; out may be res)
+//   mode 2: mrf = (mrf_init ? 0 : mrf) + inv_nk * (. + res)   (last pair of a block: the block's result goes to the MRF sum only)
+// w: [C][k][C] (the GEMM route's image).  LDS: (128 + (k-1) d) rows of C + 4 floats (<= 48.4 KB at C = 64: three workgroups per CU).
+// Wave w owns rows [32 w, 32 w + 32) x all C columns: C / 32 MFMA tiles; fragments as in gemm.h (lane half h feeds k = 8 q + 4 h + e).
+struct HgConvArgs {
+    const int* lens = nullptr; int len_mult = 1;
+    const float* x = nullptr; long long x_gs = 0; float in_slope = 1.f;
+    const float* w = nullptr; const float* bias = nullptr; int k = 3, d = 1;
+    const float* res = nullptr; long long res_gs = 0;
+    float* out = nullptr; long long out_gs = 0;
+    float* mrf = nullptr; long long mrf_gs = 0; float inv_nk = 1.f; int mrf_init = 0;
+    int mode = 0;
+};
+template <int C>
+__global__ __launch_bounds__(256) void hg_conv_direct_kernel(HgConvArgs a) {
+    constexpr int LDA = C + 4, TN = C / 32;
+    __shared__ float As[(kHgTileRows + kHgMaxHalo) * LDA];
+    const int z = blockIdx.z, tid = (int)threadIdx.x;
+    const int T = a.lens[z] * a.len_mult, m0 = (int)blockIdx.x * kHgTileRows;
+    if (m0 >= T) return;   // (uniform over the workgroup, before the barrier)
+    const int halo = (a.k - 1) * a.d, pad = halo >> 1, nrows = kHgTileRows + halo;
+    const float* px = a.x + (long long)z * a.x_gs;
+    for (int i = tid; i < nrows * (C / 4); i += 256) {
+        const int lr = i / (C / 4), c = (i - lr * (C / 4)) * 4;
+        const int row = m0 - pad + lr;
+        float4 v = zero4();
+        if (row >= 0 && row < T) {
+            v = ld4(px + (long long)row * C + c);
+            v.x = hg_lrelu(v.x, a.in_slope); v.y = hg_lrelu(v.y, a.in_slope); v.z = hg_lrelu(v.z, a.in_slope); v.w = hg_lrelu(v.w, a.in_slope);
+        }
+        st4(As + lr * LDA + c, v);
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
+    const int KW = a.k * C;   // floats per output channel of w
+    f32x16 acc[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+#if defined(MTTS_EMU)
+    for (int j = 0; j < TN; ++j)
+        for (int r = 0; r < 16; ++r) {
+            const int lr = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const float* pw = a.w + (long long)(j * 32 + l31) * KW;
+            float s = 0.f;
+            for (int t = 0; t < a.k; ++t)
+                for (int c = 0; c < C; ++c) s = fmaf(As[(lr + t * a.d) * LDA + c], pw[t * C + c], s);
+            acc[j][r] = s;
+        }
+#else
+    for (int t = 0; t < a.k; ++t) {
+        const float* pa = As + (wave * 32 + l31 + t * a.d) * LDA + 4 * h;
+        const float* pw = a.w + (long long)l31 * KW + t * C + 4 * h;
+#pragma unroll
+        for (int q = 0; q < C / 8; ++q) {
+            const float4 av = ld4(pa + 8 * q);
+            float4 bv[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bv[j] = ld4(pw + (long long)j * 32 * KW + 8 * q);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv[j].x, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv[j].y, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv[j].z, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv[j].w, acc[j], 0, 0, 0);
+            }
+        }
+    }
+#endif
+    const float* pres = a.res ? a.res + (long long)z * a.res_gs : nullptr;
+    float* pout = a.out ? a.out + (long long)z * a.out_gs : nullptr;
+    float* pmrf = a.mrf ? a.mrf + (long long)z * a.mrf_gs : nullptr;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = j * 32 + l31;
+        const float bv = a.bias[n];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (m >= T) continue;
+            const long long o = (long long)m * C + n;
+            float v = acc[j][r] + bv;
+            if (a.mode == 0) pout[o] = hg_lrelu(v, 0.1f);
+            else {
+                v += pres[o];
+                if (a.mode == 1) pout[o] = v;
+                else pmrf[o] = (a.mrf_init ? 0.f : pmrf[o]) + a.inv_nk * v;
+            }
+        }
+    }
+}
+
+class HifiGan {
+public:
+    HifiGanCfg cfg;
+    int cap_B = 0, cap_T = 0;
+    hipStream_t stream = nullptr;
+    std::string last_error;
+
+    struct Tensor { std::string name; long long off, numel; };
+    std::vector<Tensor> tensors;
+    float* params = nullptr;
+    long long n_params = 0;
+    float* arena = nullptr;
+    int* lens_dev = nullptr;
+    float* mel_dev = nullptr;
+    float* wav_dev = nullptr;
+    int hop = 1;
+    struct Buf { long long off, gs; };
+    GemmCtx gx;
+    Buf b_up, b_xj, b_pad, b_h, b_mrf;   // stage input, running x of a block, padded operand, t of a pair, MRF sum
+
+    DevHeap mem;
+    int err(const std::string& s) { last_error = s; return -1; }
+    void set_error(const std::string& s) { err(s); }
+
+    int ch(int stage) const { return cfg.c0 >> stage; }   // channels after `stage` upsamples
+    long long find(const std::string& n) const { for (auto& t : tensors) if (t.name == n) return t.off; return -1; }
+    bool direct(int C) const { return (C == 32 || C == 64) && C <= cfg.direct_max; }
+
+    int init(const HifiGanCfg& c, int max_B, int max_T) {
+        cfg = c; cap_B = max_B; cap_T = max_T;
+        const std::string why = hifigan_check_cfg(c, max_B, max_T);
+        if (!why.empty()) return err("mtts_hifigan_create: " + why);
+        hop = 1;
+        for (int s = 0; s < cfg.n_up; ++s) hop *= cfg.rates[s];
+        auto add = [&](const std::string& n, long long numel) { tensors.push_back(Tensor{n, n_params, numel}); n_params += (numel + 3) & ~3LL; };
+        add("conv_pre.w", (long long)cfg.c0 * 7 * cfg.n_mel); add("conv_pre.b", cfg.c0);
+        for (int s = 0; s < cfg.n_up; ++s) {
+            const int cin = ch(s), cout = ch(s + 1), r = cfg.rates[s];
+            add("ups." + std::to_string(s) + ".w", (long long)r * cout * 2 * cin);   // [phase][C_out][x[q-1] | x[q]]
+            add("ups." + std::to_string(s) + ".b", cout);
+            for (int j = 0; j < cfg.n_k; ++j)
+                for (int m = 0; m < cfg.n_dil; ++m)
+                    for (int half = 1; half <= 2; ++half) {
+                        const std::string p = "resblocks." + std::to_string(s * cfg.n_k + j) + ".convs" + std::to_string(half) + "." + std::to_string(m);
+                        add(p + ".w", (long long)cout * cfg.kernels[j] * cout); add(p + ".b", cout);   // [C][k][C]
+                    }
+        }
+        add("conv_post.w", 7LL * ch(cfg.n_up)); add("conv_post.b", 1);
+        if (gx.alloc_workspace(mem)) return err("out of device memory (split-K workspace)");
+        DEV_CHECK(mem.alloc(params, (size_t)n_params * sizeof(float)));
+        DEV_CHECK(hipMemset(params, 0, (size_t)n_params * sizeof(float)));
+        long long worst = (long long)(cap_T + 32) * std::max(cfg.n_mel, cfg.c0);
+        long long mult = 1;
+        for (int s = 0; s < cfg.n_up; ++s) { mult *= cfg.rates[s]; worst = std::max(worst, ((long long)cap_T * mult + kHgMaxHalo + 32) * ch(s + 1)); }
+        const long long per = (worst + 63) & ~63LL;
+        DEV_CHECK(mem.alloc(arena, (size_t)per * cap_B * 5 * sizeof(float)));
+        DEV_CHECK(hipMemset(arena, 0, (size_t)per * cap_B * 5 * sizeof(float)));
+        b_up = Buf{0, per}; b_xj = Buf{per * cap_B, per}; b_pad = Buf{2 * per * cap_B, per}; b_h = Buf{3 * per * cap_B, per}; b_mrf = Buf{4 * per * cap_B, per};
+        DEV_CHECK(mem.alloc(lens_dev, cap_B * sizeof(int)));
+        DEV_CHECK(mem.alloc(mel_dev, (size_t)cap_B * cap_T * cfg.n_mel * sizeof(float)));
+        DEV_CHECK(mem.alloc(wav_dev, (size_t)cap_B * cap_T * hop * sizeof(float)));
+        return 0;
+    }
+    int load(const char* name, const float* host, long long numel) {
+        for (auto& t : tensors)
+            if (t.name == name) {
+                if (t.numel != numel) return err(std::string("size mismatch for ") + name + ": " + std::to_string(numel) + " floats given, " + std::to_string(t.numel) + " expected");
+                DEV_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+                return 0;
+            }
+        return err(std::string("unknown HiFi-GAN tensor ") + name);
+    }
+
+    float* at(const Buf& b) const { return arena + b.off; }
+    // one grouped GEMM: C[z][M_z, N] (+)= A[z][M_z, K] * W[N, K]^T + bias; M_z = lens[z] * len_mult
+    void gemm(const float* A, long long a_gs, int lda, const float* W, int ldb, int K, const float* bias, float* C, long long c_gs,
+              int ldc, int N, int B, int max_rows, int len_mult, int flags, int a_tap_k = 0, int a_tap_rows = 0) {
+        GemmArgs g;
+        if (a_tap_k > 0) { g.a_tap_k = a_tap_k; g.a_tap_rows = a_tap_rows; }
+        g.A = A; g.a_gs = a_gs; g.lda = lda;
+        g.B = W; g.b_gs = 0; g.ldb = ldb;
+        g.C = C; g.c_gs = c_gs; g.ldc = ldc;
+        g.M = max_rows; g.N = N; g.K = K;
+        g.dimptr = lens_dev; g.dim_stride = 1; g.dim_sel = 0; g.dim_mult = len_mult;
+        g.bias = bias; g.flags = flags; g.act_slope = 0.1f;
+        gemm_launch(gx, GEMM_NT, g, max_rows, N, B, stream, 0, 2.0 * max_rows * B * (double)N * K, 0);
+    }
+    void pad(HgPadArgs a, int B, int max_rows, int len_mult, int C) {
+        a.lens = lens_dev; a.len_mult = len_mult; a.C = C;
+        const long long n = std::max<long long>((long long)(max_rows + 2 * a.d) * (C / 4), 2LL * a.gp * (C / 4));
+        MTTS_LAUNCH(hg_pad_kernel, dim3((unsigned)((n + 255) / 256), 1, (unsigned)B), dim3(256), stream, a);
+    }
+    void conv_direct(HgConvArgs a, int B, int max_rows, int len_mult, int C) {
+        a.lens = lens_dev; a.len_mult = len_mult;
+        const dim3 grid((unsigned)((max_rows + kHgTileRows - 1) / kHgTileRows), 1, (unsigned)B);
+        if (C == 64) MTTS_LAUNCH(hg_conv_direct_kernel<64>, grid, dim3(256), stream, a);
+        else MTTS_LAUNCH(hg_conv_direct_kernel<32>, grid, dim3(256), stream, a);
+    }
+    // a convolution of k taps, dilation d, over the zero-padded rows at A (row 0 = the first pad row): out (+)= conv + bias
+    void conv_gemm(const float* A, long long a_gs, const float* w, const float* bias, float* out, long long out_gs, int C, int k, int d, int B, int rows,
+                   int mult, int flags) {
+        if (d == 1) gemm(A, a_gs, C, w, k * C, k * C, bias, out, out_gs, C, C, B, rows, mult, flags);
+        else if (C % 32 == 0) gemm(A, a_gs, C, w, k * C, k * C, bias, out, out_gs, C, C, B, rows, mult, flags, C, d);   // k = t * C + c reads row m + t * d
+        else
+            for (int t = 0; t < k; ++t)
+                gemm(A + (long long)t * d * C, a_gs, C, w + (long long)t * C, k * C, C, t == 0 ? bias : nullptr, out, out_gs, C, C, B, rows, mult,
+                     (t ? GEMM_ACCUM : (flags & GEMM_ACCUM)) | (t == k - 1 ? (flags & GEMM_LRELU) : 0));
+    }
+
+    int check_batch(int B, int T_max, const int* lens_host) {
+        if (B < 1 || B > cap_B) return err("HiFi-GAN: B = " + std::to_string(B) + " exceeds max_B = " + std::to_string(cap_B));
+        if (T_max < 4 || T_max > cap_T) return err("HiFi-GAN: T_max = " + std::to_string(T_max) + " out of range (need 4 <= T_max <= max_T = " + std::to_string(cap_T) + ")");
+        for (int b = 0; b < B; ++b)
+            if (lens_host[b] < 4 || lens_host[b] > T_max)
+                return err("HiFi-GAN: mel_lens[" + std::to_string(b) + "] = " + std::to_string(lens_host[b]) + " out of range (need 4 <= len <= T_max = " + std::to_string(T_max) + ")");
+        return 0;
+    }
+
+    // mel: device pointer [B][T_max][n_mel]; wav: device [B][wav_gs]; mel_gs: floats between utterances of `mel` (0: T_max * n_mel)
+    int run(const float* mel, int B, int T_max, const int* lens_host, float mel_scale, float* wav, long long wav_gs, long long mel_gs = 0) {
+        if (check_batch(B, T_max, lens_host) != 0) return -1;
+        DEV_CHECK(hipMemcpyAsync(lens_dev, lens_host, B * sizeof(int), hipMemcpyHostToDevice, stream));
+        const int nm = cfg.n_mel;
+        {   // conv_pre: zero pad 3 of the scaled mel, k = 7
+            HgPadArgs p;
+            p.x = mel; p.x_gs = mel_gs > 0 ? mel_gs : (long long)T_max * nm; p.xs = mel_scale; p.y = at(b_pad); p.y_gs = b_pad.gs; p.d = 3; p.slope = 1.f;
+            pad(p, B, T_max, 1, nm);
+            gemm(at(b_pad), b_pad.gs, nm, params + find("conv_pre.w"), 7 * nm, 7 * nm, params + find("conv_pre.b"), at(b_up), b_up.gs, ch(0), ch(0), B, T_max, 1, 0);
+        }
+        // what the next stage reads: xs * src (+ add)
+        HgPadArgs next;
+        next.x = at(b_up); next.x_gs = b_up.gs;
+        int mult = 1;
+        const float inv_nk = 1.f / (float)cfg.n_k;
+        for (int s = 0; s < cfg.n_up; ++s) {
+            const int cin = ch(s), C = ch(s + 1), r = cfg.rates[s], p = r / 2;
+            const int rows_in = T_max * mult;
+            {   // LeakyReLU + one zero row each side, then r polyphase GEMMs into the stage input
+                HgPadArgs a = next;
+                a.y = at(b_pad); a.y_gs = b_pad.gs; a.d = 1; a.slope = 0.1f;
+                pad(a, B, rows_in, mult, cin);
+                const float* W = params + find("ups." + std::to_string(s) + ".w");
+                const float* bias = params + find("ups." + std::to_string(s) + ".b");
+                gemm_batch_begin(gx);
+                for (int ph = 0; ph < r; ++ph) {
+                    const int q0 = ph >= p ? 0 : 1;
+                    gemm(at(b_pad) + (long long)q0 * cin, b_pad.gs, cin, W + (long long)ph * C * 2 * cin, 2 * cin, 2 * cin, bias,
+                         at(b_up) + (long long)(q0 * r + ph - p) * C, b_up.gs, r * C, C, B, rows_in, mult, 0);
+                }
+                gemm_batch_end(gx, stream);
+            }
+            mult *= r;
+            const int rows = T_max * mult;
+            const bool dir = direct(C);
+            for (int j = 0; j < cfg.n_k; ++j) {
+                const int k = cfg.kernels[j], p2 = (k - 1) / 2;
+                for (int m = 0; m < cfg.n_dil; ++m) {
+                    const int d = cfg.dil[j][m];
+                    const std::string pre = "resblocks." + std::to_string(s * cfg.n_k + j);
+                    const float* w1 = params + find(pre + ".convs1." + std::to_string(m) + ".w");
+                    const float* b1 = params + find(pre + ".convs1." + std::to_string(m) + ".b");
+                    const float* w2 = params + find(pre + ".convs2." + std::to_string(m) + ".w");
+                    const float* b2 = params + find(pre + ".convs2." + std::to_string(m) + ".b");
+                    const Buf& src = m == 0 ? b_up : b_xj;
+                    if (dir) {
+                        HgConvArgs c1;
+                        c1.x = at(src); c1.x_gs = src.gs; c1.in_slope = 0.1f; c1.w = w1; c1.bias = b1; c1.k = k; c1.d = d;
+                        c1.out = at(b_h); c1.out_gs = b_h.gs; c1.mode = 0;
+                        conv_direct(c1, B, rows, mult, C);
+                        HgConvArgs c2;
+                        c2.x = at(b_h); c2.x_gs = b_h.gs; c2.in_slope = 1.f; c2.w = w2; c2.bias = b2; c2.k = k; c2.d = 1;
+                        c2.res = at(src); c2.res_gs = src.gs;
+                        if (m == cfg.n_dil - 1) { c2.mode = 2; c2.mrf = at(b_mrf); c2.mrf_gs = b_mrf.gs; c2.inv_nk = inv_nk; c2.mrf_init = j == 0; }
+                        else { c2.mode = 1; c2.out = at(b_xj); c2.out_gs = b_xj.gs; }
+                        conv_direct(c2, B, rows, mult, C);
+                    } else {
+                        HgPadArgs a;
+                        a.x = at(src); a.x_gs = src.gs; a.y = at(b_pad); a.y_gs = b_pad.gs; a.d = d * p2; a.slope = 0.1f;
+                        a.guard = at(b_h); a.guard_gs = b_h.gs; a.gp = p2;
+                        if (m == 0) {
+                            if (j > 0) { a.fold = at(b_xj); a.fold_gs = b_xj.gs; a.fs = inv_nk; a.fold_init = j == 1; a.mrf = at(b_mrf); a.mrf_gs = b_mrf.gs; }
+                            a.copy = at(b_xj); a.copy_gs = b_xj.gs;
+                        }
+                        pad(a, B, rows, mult, C);
+                        conv_gemm(at(b_pad), b_pad.gs, w1, b1, at(b_h) + (long long)p2 * C, b_h.gs, C, k, d, B, rows, mult, GEMM_LRELU);
+                        conv_gemm(at(b_h), b_h.gs, w2, b2, at(b_xj), b_xj.gs, C, k, 1, B, rows, mult, GEMM_ACCUM);
+                    }
+                }
+            }
+            next = HgPadArgs();
+            if (dir) { next.x = at(b_mrf); next.x_gs = b_mrf.gs; }
+            else {
+                next.x = at(b_xj); next.x_gs = b_xj.gs; next.xs = inv_nk;
+                if (cfg.n_k > 1) { next.add = at(b_mrf); next.add_gs = b_mrf.gs; }
+            }
+        }
+        // LeakyReLU(0.01), zero pad 3, k = 7 conv to one channel, tanh
+        const int cl = ch(cfg.n_up), rows = T_max * mult;
+        next.y = at(b_pad); next.y_gs = b_pad.gs; next.d = 3; next.slope = 0.01f;
+        pad(next, B, rows, mult, cl);
+        MTTS_LAUNCH(dot_tanh_kernel, dim3((unsigned)((rows + 3) / 4), 1, (unsigned)B), dim3(256), stream, (const int*)lens_dev, mult,
+                    (const float*)at(b_pad), b_pad.gs, (const float*)(params + find("conv_post.w")), (const float*)(params + find("conv_post.b")),
+                    wav, wav_gs, cl, 7 * cl);
+        return 0;
+    }
+
+    // host entry: mel_host [B][T_max][n_mel] -> wav_host [B][T_max * hop] (samples beyond len * hop are left untouched)
+    int infer_host(const float* mel_host, int B, int T_max, const int* lens_host, float mel_scale, float* wav_host) {
+        if (check_batch(B, T_max, lens_host) != 0) return -1;
+        DEV_CHECK(hipMemcpyAsync(mel_dev, mel_host, (size_t)B * T_max * cfg.n_mel * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (run(mel_dev, B, T_max, lens_host, mel_scale, wav_dev, (long long)T_max * hop) != 0) return -1;
+        DEV_CHECK(hipStreamSynchronize(stream));
+        for (int b = 0; b < B; ++b)
+            DEV_CHECK(hipMemcpy(wav_host + (long long)b * T_max * hop, wav_dev + (long long)b * T_max * hop, (size_t)lens_host[b] * hop * sizeof(float),
+                                hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+
+}  // namespace mtts

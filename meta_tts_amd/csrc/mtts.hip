@@ -6,6 +6,7 @@
 #include "comm.h"
 #include "engine.h"
 #include "vocoder.h"
+#include "hifigan.h"
 #include "dvector.h"
 #include "melfront.h"
 #include "griffin.h"
@@ -44,6 +45,9 @@ static int launched(Engine& e, int rc) {
 
 struct mtts_vocoder {
     Vocoder v;
+};
+struct mtts_hifigan {
+    HifiGan v;
 };
 struct mtts_dvector {
     DVector d;
@@ -675,6 +679,58 @@ int mtts_vocoder_infer(mtts_vocoder* h, const float* mel, int B, int T_max, cons
 int mtts_vocoder_infer_device(mtts_vocoder* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
                               float mel_scale, float* wav_dev) {
     return h->v.run(mel_dev, B, T_max, mel_lens, mel_scale, wav_dev, (long long)T_max * h->v.hop, (long long)mel_utt_stride);
+}
+
+// ---- HiFi-GAN generator (hifigan.h; reference call site utils/model.py:32-50) -------------------------------------------------
+int mtts_hifigan_create(int n_mel, int initial_channels, const int* rates, int n_rates, const int* res_kernels, int n_res_kernels,
+                        const int* res_dilations, int n_dil, int resblock_type, int direct_max_channels, int device, int max_B, int max_T,
+                        mtts_hifigan** out) {
+    if (!out || !rates || !res_kernels || !res_dilations) { g_create_error = "mtts_hifigan_create: NULL argument"; return -1; }
+    HifiGanCfg c;
+    c.n_mel = n_mel; c.c0 = initial_channels; c.n_up = n_rates; c.n_k = n_res_kernels; c.n_dil = n_dil; c.resblock = resblock_type;
+    c.direct_max = direct_max_channels;
+    for (int i = 0; i < n_rates && i < kHgMaxUps; ++i) c.rates[i] = rates[i];
+    for (int j = 0; j < n_res_kernels && j < kHgMaxKernels; ++j) {
+        c.kernels[j] = res_kernels[j];
+        for (int m = 0; m < n_dil && m < kHgMaxDil; ++m) c.dil[j][m] = res_dilations[j * n_dil + m];
+    }
+    const std::string why = hifigan_check_cfg(c, max_B, max_T);   // (refused before the device is touched)
+    if (!why.empty()) { g_create_error = "mtts_hifigan_create: " + why; return -1; }
+    if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
+    mtts_hifigan* h = new mtts_hifigan();
+    if (h->v.init(c, max_B, max_T) != 0) { g_create_error = h->v.last_error; delete h; return -1; }
+    *out = h;
+    return 0;
+}
+void mtts_hifigan_destroy(mtts_hifigan* h) {
+    if (!h) return;
+    hipDeviceSynchronize();
+    delete h;
+}
+const char* mtts_hifigan_last_error(mtts_hifigan* h) { return h ? h->v.last_error.c_str() : g_create_error.c_str(); }
+int mtts_hifigan_set_stream(mtts_hifigan* h, void* s) { h->v.stream = (hipStream_t)s; return 0; }
+int mtts_hifigan_hop(mtts_hifigan* h) { return h->v.hop; }
+int mtts_hifigan_param_count(mtts_hifigan* h) { return (int)h->v.tensors.size(); }
+int mtts_hifigan_param_info(mtts_hifigan* h, int i, char* name, int cap, int64_t* numel) {
+    if (i < 0 || i >= (int)h->v.tensors.size()) return -1;
+    snprintf(name, cap, "%s", h->v.tensors[i].name.c_str());
+    *numel = h->v.tensors[i].numel;
+    return 0;
+}
+int mtts_hifigan_load(mtts_hifigan* h, const char* name, const float* data, int64_t numel) { return h->v.load(name, data, numel); }
+static int hifigan_launched(HifiGan& v, int rc) {
+    if (rc) return rc;
+    if (v.gx.error) { v.set_error(std::string("GEMM launcher: ") + v.gx.error); v.gx.error = nullptr; return -1; }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { v.set_error(std::string("kernel launch failed: ") + hipGetErrorString(e)); return -1; }
+    return 0;
+}
+int mtts_hifigan_infer(mtts_hifigan* h, const float* mel, int B, int T_max, const int* mel_lens, float mel_scale, float* wav) {
+    return hifigan_launched(h->v, h->v.infer_host(mel, B, T_max, mel_lens, mel_scale, wav));
+}
+int mtts_hifigan_infer_device(mtts_hifigan* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
+                              float mel_scale, float* wav_dev) {
+    return hifigan_launched(h->v, h->v.run(mel_dev, B, T_max, mel_lens, mel_scale, wav_dev, (long long)T_max * h->v.hop, (long long)mel_utt_stride));
 }
 
 // ---- exact t-SNE of d-vectors (tsne.h; reference evaluation/visualize.py:56-71) ---------------------------------------------

@@ -1,0 +1,211 @@
+"""HiFi-GAN generator host layer: what stands behind the `name == "HiFi-GAN"` branch of the reference's `vocoder_infer`
+(utils/model.py:32-50: `vocoder(mels).squeeze(1)`, x max_wav_value -> int16, cut to `lengths`).
+
+Neither the generator's code nor a checkpoint (`generator_universal.pth.tar`) is part of the reference tree, so parity with published
+weights is UNPINNED: this class takes a state dict in the published module's naming (`conv_pre`, `ups.{i}`,
+`resblocks.{i*n_k+j}.convs1.{m}` / `convs2.{m}`, `conv_post`, each with `weight_g` / `weight_v` / `bias` or an already folded `weight`;
+a `{"generator": sd}` wrapper is unwrapped) or synthetic weights, folds the weight normalisation and re-packs the ConvTranspose1d
+kernels into the polyphase images `libmtts.so` consumes (include/mtts.h, mtts_hifigan_*).  `config` carries the keys of the published
+json (`upsample_rates`, `upsample_kernel_sizes`, `upsample_initial_channel`, `resblock_kernel_sizes`, `resblock_dilation_sizes`,
+`resblock`); only ResBlock type "1" is built (V1, V2), V3 is refused.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import zlib
+
+import numpy as np
+
+from . import _lib
+from .engine import MttsError
+from .vocoder import fold_weight_norm
+
+V1 = {"resblock": "1", "upsample_rates": [8, 8, 2, 2], "upsample_kernel_sizes": [16, 16, 4, 4], "upsample_initial_channel": 512,
+      "resblock_kernel_sizes": [3, 7, 11], "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5], [1, 3, 5]]}
+V2 = dict(V1, upsample_initial_channel=128)
+V3 = {"resblock": "2", "upsample_rates": [8, 8, 4], "upsample_kernel_sizes": [16, 16, 8], "upsample_initial_channel": 256,
+      "resblock_kernel_sizes": [3, 5, 7], "resblock_dilation_sizes": [[1, 2], [2, 6], [3, 12]]}
+
+# `direct_max_channels` of a HiFiGAN built without one: 0 (GEMM route everywhere) until both routes have been timed in one session
+# (tools/hifigan_bench.py; README "HiFi-GAN generator").
+DEFAULT_DIRECT_MAX_CHANNELS = 0
+
+
+def _check(config):
+    """The refusals that can be decided on the host before anything is created; the rest is mtts_hifigan_create's."""
+    if str(config["resblock"]) != "1":
+        raise MttsError(f"HiFiGAN: resblock {config['resblock']!r} is not supported (only ResBlock \"1\": V1 / V2)")
+    rates, ks = list(config["upsample_rates"]), list(config["upsample_kernel_sizes"])
+    if len(rates) != len(ks):
+        raise MttsError("HiFiGAN: upsample_kernel_sizes and upsample_rates differ in length")
+    for i, (r, k) in enumerate(zip(rates, ks)):
+        if r < 2 or r % 2:
+            raise MttsError(f"HiFiGAN: upsample_rates[{i}] = {r}: every rate must be even and >= 2")
+        if k != 2 * r:
+            raise MttsError(f"HiFiGAN: upsample_kernel_sizes[{i}] = {k} is not 2 * upsample_rates[{i}] = {2 * r}")
+    dil = [list(d) for d in config["resblock_dilation_sizes"]]
+    if len(dil) != len(config["resblock_kernel_sizes"]) or len({len(d) for d in dil}) != 1:
+        raise MttsError("HiFiGAN: resblock_dilation_sizes must give one equally long list per resblock_kernel_sizes entry")
+
+
+def generator_spec(config=V1, n_mel=80):
+    """[(published name prefix, kind, shape of weight_v)] in module order; kinds: conv / convT."""
+    _check(config)
+    c = int(config["upsample_initial_channel"])
+    n_k = len(config["resblock_kernel_sizes"])
+    spec = [("conv_pre", "conv", (c, n_mel, 7))]
+    for i, r in enumerate(config["upsample_rates"]):
+        spec.append((f"ups.{i}", "convT", (c, c // 2, 2 * r)))
+        c //= 2
+        for j, k in enumerate(config["resblock_kernel_sizes"]):
+            for half in (1, 2):
+                for m in range(len(config["resblock_dilation_sizes"][j])):
+                    spec.append((f"resblocks.{i * n_k + j}.convs{half}.{m}", "conv", (c, c, k)))
+    spec.append(("conv_post", "conv", (1, c, 7)))
+    return spec
+
+
+def synthetic_state_dict(seed=0, config=V1, n_mel=80):
+    """Deterministic weights in the published naming (weight_g / weight_v / bias).  The gains keep activations O(1) through all blocks,
+    by the reasoning of `vocoder.synthetic_state_dict`: a weight-normed conv output has variance g^2 per unit second moment of its input.
+    LeakyReLU(0.1) halves the second moment (0.505), so convs1 and the transposed convolutions carry sqrt(2) (the latter times MelGAN's
+    sqrt(r C_out / C_in)); convs2 — the residual branch — carries 1/2, so a pair adds 0.125 to a unit variance and three pairs leave
+    `t + x` under 1.4; conv_pre takes natural-log mels (second moment ~ 18 for the tests' mels): 1/4; conv_post 1/2 keeps tanh out of
+    saturation."""
+    sd = {}
+    for name, kind, shape in generator_spec(config, n_mel):
+        g = np.random.RandomState((zlib.crc32(name.encode()) ^ seed) & 0x7FFFFFFF)
+        v = g.standard_normal(shape).astype(np.float32)
+        if kind == "convT":
+            gain, nb = math.sqrt(2.0 * (shape[2] // 2) * shape[1] / shape[0]), shape[1]
+        else:
+            nb = shape[0]
+            gain = 0.25 if name == "conv_pre" else 0.5 if (name == "conv_post" or ".convs2." in name) else math.sqrt(2.0)
+        sd[name + ".weight_v"] = v
+        sd[name + ".weight_g"] = np.full((shape[0], 1, 1), gain, np.float32)
+        sd[name + ".bias"] = (0.05 * g.standard_normal(nb)).astype(np.float32)
+    return sd
+
+
+def pack_tensors(sd, config=V1, n_mel=80):
+    """published-style state dict -> {libmtts tensor name: float32 array} (layouts documented in include/mtts.h)."""
+    if "generator" in sd and "conv_pre.bias" not in sd:
+        sd = sd["generator"]
+    sd = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in sd.items()}
+    out = {}
+    for name, kind, shape in generator_spec(config, n_mel):
+        w = fold_weight_norm(sd, name)
+        if tuple(w.shape) != tuple(shape):
+            raise MttsError(f"HiFiGAN: {name} has shape {tuple(w.shape)}, the config asks for {tuple(shape)}")
+        if kind == "convT":
+            cin, cout, k2 = shape
+            r = k2 // 2
+            img = np.empty((r, cout, 2 * cin), np.float32)
+            for ph in range(r):
+                img[ph, :, :cin] = w[:, :, ph + r].T   # multiplies x[q-1]
+                img[ph, :, cin:] = w[:, :, ph].T       # multiplies x[q]
+            out[name + ".w"] = img
+        elif name == "conv_post":
+            out[name + ".w"] = np.ascontiguousarray(w[0].T)                     # [7][C_last]
+        else:
+            out[name + ".w"] = np.ascontiguousarray(w.transpose(0, 2, 1))       # [C_out][k][C_in]
+        out[name + ".b"] = np.asarray(sd[name + ".bias"], np.float32).reshape(-1)
+    return out
+
+
+class HiFiGAN:
+    """The reference's HiFi-GAN vocoder object with `vocoder.MelGAN`'s duck type: `__call__(mels)` is the reference branch's call,
+    `infer(mels, max_wav_value, lengths)` is `vocoder_infer`; mel (B, n_mel, T), natural-log mels as the model makes them."""
+
+    def __init__(self, state_dict=None, config=V1, n_mel=80, max_B=8, max_T=1024, device=0, lib_path=None, direct_max_channels=None):
+        _check(config)
+        self.lib = _lib.load(lib_path)
+        self.config, self.n_mel = config, n_mel
+        self.max_B, self.max_T = max_B, max_T
+        self.device, self.stream, self._wav_dev = device, 0, None
+        self.direct_max_channels = DEFAULT_DIRECT_MAX_CHANNELS if direct_max_channels is None else int(direct_max_channels)
+        rates = [int(r) for r in config["upsample_rates"]]
+        kernels = [int(k) for k in config["resblock_kernel_sizes"]]
+        dil = [[int(d) for d in row] for row in config["resblock_dilation_sizes"]]
+        flat = [d for row in dil for d in row]
+        h = C.c_void_p()
+        self.h = None
+        if self.lib.mtts_hifigan_create(n_mel, int(config["upsample_initial_channel"]), (C.c_int * len(rates))(*rates), len(rates),
+                                        (C.c_int * len(kernels))(*kernels), len(kernels), (C.c_int * len(flat))(*flat), len(dil[0]),
+                                        int(config["resblock"]), self.direct_max_channels, device, max_B, max_T, C.byref(h)) != 0:
+            raise MttsError(self.lib.mtts_hifigan_last_error(None).decode())
+        self.h = h
+        self.hop = self.lib.mtts_hifigan_hop(h)
+        sd = state_dict if state_dict is not None else synthetic_state_dict(0, config, n_mel)
+        self.state_dict_ = sd
+        try:
+            for k, v in pack_tensors(sd, config, n_mel).items():
+                self.load(k, v)
+        except Exception:
+            self.close()
+            raise
+
+    def load(self, name, array):
+        a = np.ascontiguousarray(array, np.float32)
+        if self.lib.mtts_hifigan_load(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size) != 0:
+            raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mtts_hifigan_destroy(self.h)
+            self.h = None
+
+    def set_stream(self, stream_ptr):
+        self.lib.mtts_hifigan_set_stream(self.h, C.c_void_p(stream_ptr))
+        self.stream = int(stream_ptr or 0)
+
+    def mel2wav(self, mel, lengths=None, mel_scale=1.0):
+        """mel (B, n_mel, T) float -> (B, T * hop) float32; samples beyond lengths[b] * hop are zero."""
+        mel = np.asarray(mel, np.float32)
+        B, nm, T = mel.shape
+        assert nm == self.n_mel
+        lens = np.full(B, T, np.int32) if lengths is None else np.ascontiguousarray(lengths, np.int32)
+        x = np.ascontiguousarray(mel.transpose(0, 2, 1))  # channels-last rows
+        wav = np.zeros((B, T * self.hop), np.float32)
+        if self.lib.mtts_hifigan_infer(self.h, x.ctypes.data_as(C.c_void_p), B, T, lens.ctypes.data_as(C.c_void_p),
+                                       C.c_float(mel_scale), wav.ctypes.data_as(C.c_void_p)) != 0:
+            raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
+        return wav
+
+    def mel2wav_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths, wav_ptr: int, mel_scale: float = 1.0):
+        """Device-to-device, as `MelGAN.mel2wav_device`: mel at `mel_ptr` laid out [B][..][n_mel] with `utt_stride` floats between
+        utterances, waveform written to `wav_ptr` as [B][T * hop] floats; asynchronous on the vocoder's stream."""
+        lens = np.ascontiguousarray(lengths, np.int32)
+        if self.lib.mtts_hifigan_infer_device(self.h, C.c_void_p(mel_ptr), C.c_int64(utt_stride), B, T, lens.ctypes.data_as(C.c_void_p),
+                                              C.c_float(mel_scale), C.c_void_p(wav_ptr)) != 0:
+            raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
+
+    def infer_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths):
+        """`infer` without the host, with `MelGAN.infer_device`'s contract: -> (wav_ptr, row_stride, sample_lengths, stream), float32
+        waveforms in a device buffer this object owns, enqueued on the vocoder's `stream` and NOT waited for; the tuple is what
+        `SpeakerEmbedder.embed_device` takes.  The mel is used as it is (natural log: HiFi-GAN's own scale).  The buffer is reused by
+        the next call."""
+        import torch
+        lens = np.minimum(np.asarray(lengths, np.int64).reshape(-1), T).astype(np.int32)
+        if len(lens) != B:
+            raise ValueError(f"infer_device: {len(lens)} lengths for B = {B}")
+        row_stride = T * self.hop
+        if self._wav_dev is None or self._wav_dev.numel() < B * row_stride:
+            self._wav_dev = torch.empty(B * row_stride, dtype=torch.float32, device=f"cuda:{self.device}")
+        self.mel2wav_device(mel_ptr, utt_stride, B, T, lens, self._wav_dev.data_ptr(), mel_scale=1.0)
+        return self._wav_dev.data_ptr(), row_stride, lens * self.hop, self.stream
+
+    def __call__(self, mels):                      # utils/model.py:38: vocoder(mels) -> (B, 1, T * hop)
+        return self.mel2wav(mels)[:, None, :]
+
+    def infer(self, mels, max_wav_value, lengths=None):   # utils/model.py:32-50
+        mels = np.asarray(mels, np.float32)
+        frame_lens = None if lengths is None else [int(math.ceil(l / self.hop)) for l in lengths]
+        wavs = self.mel2wav(mels, None if frame_lens is None else np.minimum(frame_lens, mels.shape[2]))
+        wavs = (wavs * max_wav_value).astype("int16")
+        wavs = [w for w in wavs]
+        for i in range(len(mels)):
+            if lengths is not None:
+                wavs[i] = wavs[i][: lengths[i]]
+        return wavs

@@ -1,0 +1,140 @@
+"""Time the device HiFi-GAN generator (meta_tts_amd.hifigan.HiFiGAN on csrc/hifigan.h) at the shape of the adaptation / synthesis path:
+the published V1 configuration with synthetic weights, 5 utterances x 400 frames (512 000 samples per call).
+
+Method: per leg the median wall time of 7 calls after 2 warm-up calls; a device call is one `mel2wav` (upload of the mel, the generator,
+download of the waveform); "spread" is max - min of the 7 calls.  Legs:
+  a   GEMM route (direct_max_channels = 0)
+  b   direct route for the stages with C <= 64 (direct_max_channels = 64)
+  c   tests/hifigan_oracle.py in float32 on 16 host threads
+  d   vocoder.MelGAN (synthetic weights) on the same mels, for context
+  k   hg_conv_direct_kernel's own time per call and its TFLOP/s against the fp32 matrix peak, from the statistics of a kernel trace of
+      leg b (rocprofv3 --kernel-trace --stats -- python tools/hifigan_bench.py --leg b; then --kernel-stats <the kernel_stats csv>)
+`HiFiGAN`'s default direct_max_channels becomes 64 only if b beats a in one session by more than the larger of the two spreads
+("direct_route_wins").  Writes profiles/hifigan_bench.json; legs that were not run keep the value the file already holds, or
+"not measured"."""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+OUT = os.path.join(ROOT, "profiles", "hifigan_bench.json")
+B, T, N_MEL = 5, 400, 80
+LEGS = ("c", "a", "b", "d")
+FP32_MATRIX_PEAK_TFLOPS = 157.3   # v_mfma_f32_32x32x2_f32 dense peak of the MI355X
+
+
+def mels():
+    g = np.random.RandomState(0)
+    return (g.standard_normal((B, N_MEL, T)) * 1.5 - 4.0).astype(np.float32)
+
+
+def median_of(fn, calls=7, warmup=2):
+    for _ in range(warmup):
+        fn()
+    t = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()
+        t.append(time.perf_counter() - t0)
+    return {"ms_median": round(1e3 * float(np.median(t)), 3), "ms_spread": round(1e3 * (max(t) - min(t)), 3), "ms_all": [round(1e3 * v, 3) for v in t]}
+
+
+def direct_flops(config):
+    """multiply-add flops per call of the convolutions the direct route takes (C in {32, 64})"""
+    c, rows, total = config["upsample_initial_channel"], T, 0.0
+    for i, r in enumerate(config["upsample_rates"]):
+        c //= 2
+        rows *= r
+        if c in (32, 64):
+            for j, k in enumerate(config["resblock_kernel_sizes"]):
+                total += 2.0 * len(config["resblock_dilation_sizes"][j]) * 2.0 * B * rows * k * c * c
+    return total
+
+
+def hifigan_leg(direct_max, calls, warmup):
+    from meta_tts_amd import hifigan as H
+    voc = H.HiFiGAN(H.synthetic_state_dict(0), max_B=B, max_T=T, direct_max_channels=direct_max)
+    try:
+        m = mels()
+        res = median_of(lambda: voc.mel2wav(m), calls, warmup)
+    finally:
+        voc.close()
+    res["direct_max_channels"] = direct_max
+    return res
+
+
+def oracle_leg(calls, warmup):
+    import torch
+    import hifigan_oracle as HO
+    from meta_tts_amd import hifigan as H
+    torch.set_num_threads(16)
+    sd, m = H.synthetic_state_dict(0), mels()
+    res = median_of(lambda: HO.generator(sd, m, H.V1, torch.float32), calls, warmup)
+    res["threads"] = 16
+    return res
+
+
+def melgan_leg(calls, warmup):
+    from meta_tts_amd import vocoder as V
+    voc = V.MelGAN(V.synthetic_state_dict(0), max_B=B, max_T=T)
+    try:
+        m = mels()
+        return median_of(lambda: voc.mel2wav(m, mel_scale=1.0 / np.log(10.0)), calls, warmup)
+    finally:
+        voc.close()
+
+
+def kernel_from_stats(path, calls_per_run):
+    from meta_tts_amd import hifigan as H
+    total_ns = 0.0
+    for row in csv.DictReader(open(path, newline="")):
+        if "hg_conv_direct_kernel" in row.get("Name", ""):
+            total_ns += float(row["TotalDurationNs"])
+    if total_ns == 0.0:
+        return "not measured"
+    per_call = total_ns / calls_per_run * 1e-9
+    tf = direct_flops(H.V1) / per_call * 1e-12
+    return {"ms_per_call": round(1e3 * per_call, 3), "tflops": round(tf, 2), "fraction_of_fp32_matrix_peak": round(tf / FP32_MATRIX_PEAK_TFLOPS, 3),
+            "generator_calls_in_trace": calls_per_run}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", action="append", choices=LEGS, help="legs to run (default: all)")
+    ap.add_argument("--calls", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--kernel-stats", help="a rocprofv3 kernel_stats csv of a run of leg b: fills leg k")
+    ap.add_argument("--out", default=OUT)
+    a = ap.parse_args()
+    res = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    res.setdefault("method", "median of 7 calls after 2 warm-up calls; HiFi-GAN V1, synthetic weights, 5 utterances x 400 frames; a device call is one "
+                             "mel2wav (mel upload, generator, waveform download); spread = max - min of the 7 calls")
+    ran = a.leg or ([] if a.kernel_stats else list(LEGS))
+    for leg in ran:
+        res[leg] = (oracle_leg(a.calls, a.warmup) if leg == "c" else melgan_leg(a.calls, a.warmup) if leg == "d"
+                    else hifigan_leg(0 if leg == "a" else 64, a.calls, a.warmup))
+        print(leg, json.dumps(res[leg]), flush=True)
+    if a.kernel_stats:
+        res["k"] = kernel_from_stats(a.kernel_stats, a.calls + a.warmup)
+        print("k", json.dumps(res["k"]), flush=True)
+    for leg in LEGS + ("k",):
+        res.setdefault(leg, "not measured")
+    if "a" in ran and "b" in ran:   # one session: the comparison that decides the default
+        margin = max(res["a"]["ms_spread"], res["b"]["ms_spread"])
+        res["direct_route_wins"] = bool(res["a"]["ms_median"] - res["b"]["ms_median"] > margin)
+    res.setdefault("direct_route_wins", "not measured")
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
