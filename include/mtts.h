@@ -318,6 +318,19 @@ int mtts_layernorm_bwd(int rows, int C, const float* dy, const float* z, const f
 int mtts_softmax_fwd(int n_mat, int L, float* S, void* ws, void* hip_stream);
 int mtts_softmax_bwd(int n_mat, int L, const float* P, float* dP, float alpha, void* ws, void* hip_stream);
 int mtts_sdpa_fwd(int n_mat, int L, int dk, const float* q, const float* k, const float* v, float* P, float* o, void* ws, void* hip_stream);
+/* attention in the packed layout the engine runs: n_seq sequences of lens[i] rows starting at row row0[i] (host arrays) of
+ *   qkv / gqkv [rows][3 * heads * dk] (column blocks Q | K | V, one head = dk columns) and O / dO [rows][heads * dk]; group
+ *   n = seq * heads + head keeps its P / dS matrix [L][ldS], ldS = (L + 3) & ~3, at the running sum of L * ldS.  fwd: P = softmax(Q K^T /
+ *   sqrt(dk)), O = P V; path 0 = the engine's route (the fused kernel where it serves the launch, else GEMM + softmax + GEMM), 1 = the
+ *   three launches.  bwd: dS = P o (dP - rowsum(dP o P)) / sqrt(dk) with dP = dO V^T, gqkv = dS K | dS^T Q | P^T dO.  Rows outside the
+ *   sequences are neither read into a result nor written; P and dS may hold anything on entry (their pad columns are written, zero).
+ *   ws = mtts_attn_packed_ws_bytes(n_seq, heads) bytes of device scratch.  -1: null pointer, dk % 4, n_seq / heads / a length < 1, a
+ *   negative row0, ws_bytes too small, path not 0 / 1. */
+int64_t mtts_attn_packed_ws_bytes(int n_seq, int heads);
+int mtts_attn_packed_fwd(int n_seq, int heads, int dk, const int* lens, const int* row0, int path, const float* qkv, float* P, float* O,
+                         void* ws, int64_t ws_bytes, void* hip_stream);
+int mtts_attn_packed_bwd(int n_seq, int heads, int dk, const int* lens, const int* row0, const float* qkv, const float* P, const float* dO,
+                         float* dS, float* gqkv, void* ws, int64_t ws_bytes, void* hip_stream);
 int mtts_batchnorm_fwd(int rows, int C, const float* x, const unsigned char* inrect, const float* gamma, const float* beta, int do_tanh,
                        float* stats, float* y, void* ws, void* hip_stream);
 int mtts_batchnorm_bwd(int rows, int n_in, int C, const float* dy, const float* y, const float* x, const float* stats, const unsigned char* inrect,

@@ -75,6 +75,23 @@ struct ParamEntry {
     int module = 0;
 };
 
+// The per-group descriptors of one (sequence, head) of the attention launches: its score matrix and the six table-mode products of
+// fft_fwd / fft_bwd.  qo: element offset of the head's Q columns in the [rows][3 d] qkv buffer (K at + d, V at + 2 d; the same offsets
+// address dQ / dK / dV in the gradient buffer), oo: of its columns in the [rows][d] buffer of O / dO, so: of its [L][ldS] matrix in
+// P / dS.  The leading dimensions left 0 come from the launch (GemmArgs).  One place for build_plan and the kernel-level entry points
+// (kernel_api.inc: mtts_attn_packed_*).
+enum { TAB_QK = 0, TAB_PV, TAB_DP, TAB_DV, TAB_DQ, TAB_DK };
+inline void attn_group_descs(long long qo, long long oo, long long so, int L, int dk, int d, AttnSeq& seq, GemmGroupDesc (&tab)[6]) {
+    const int ldS = (L + 3) & ~3;
+    seq = AttnSeq{so, L, ldS};
+    tab[TAB_QK] = GemmGroupDesc{qo, qo + d, so, L, L, dk, 0, 0, ldS};          // S  = Q K^T
+    tab[TAB_PV] = GemmGroupDesc{so, qo + 2 * d, oo, L, dk, L, ldS, 0, 0};     // O  = P V
+    tab[TAB_DP] = GemmGroupDesc{oo, qo + 2 * d, so, L, L, dk, 0, 0, ldS};     // dP = dO V^T
+    tab[TAB_DV] = GemmGroupDesc{so, oo, qo + 2 * d, L, dk, L, ldS, 0, 0};     // dV = P^T dO
+    tab[TAB_DQ] = GemmGroupDesc{so, qo + d, qo, L, dk, L, ldS, 0, 0};         // dQ = dS K
+    tab[TAB_DK] = GemmGroupDesc{so, qo, qo + d, L, dk, L, ldS, 0, 0};         // dK = dS^T Q
+}
+
 class Engine {
 public:
     ModelCfg cfg;
@@ -161,7 +178,6 @@ public:
     // byte offsets inside a compact image (fixed by the capacities; computed in init)
     size_t pe_cap_p = 0, pe_cap_e = 0;  // per-task floats of the pitch / energy areas of an image
     struct ImgLayout { size_t meta, hdr, src_len, flen, foff, spk, spk_emb, texts, dur, pitch, energy, seq_e, seq_d, tab_e[6], tab_d[6], mels, total; } img;
-    enum { TAB_QK = 0, TAB_PV, TAB_DP, TAB_DV, TAB_DQ, TAB_DK };
     Plan plans[2];
     long long row_ts_p, row_ts_f, row_ts_r;  // strides of per-row index arrays
 
@@ -1128,15 +1144,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                         const long long so = (long long)t * task_s + soff[which];
                         soff[which] += (long long)L * ldS;
                         const int n = nseq[which]++;
-                        seqs[which][n] = AttnSeq{so, L, ldS};
                         const long long qo = (long long)t * ((long long)(capM + 2 * G) * 3 * d) + (long long)ro * 3 * d + hh * dk;
                         const long long oo = (long long)t * ((long long)(capM + 2 * G) * d) + (long long)ro * d + hh * dk;
-                        tabs[which][TAB_QK][n] = GemmGroupDesc{qo, qo + d, so, L, L, dk, 0, 0, ldS};          // S  = Q K^T
-                        tabs[which][TAB_PV][n] = GemmGroupDesc{so, qo + 2 * d, oo, L, dk, L, ldS, 0, 0};     // O  = P V
-                        tabs[which][TAB_DP][n] = GemmGroupDesc{oo, qo + 2 * d, so, L, L, dk, 0, 0, ldS};     // dP = dO V^T
-                        tabs[which][TAB_DV][n] = GemmGroupDesc{so, oo, qo + 2 * d, L, dk, L, ldS, 0, 0};     // dV = P^T dO
-                        tabs[which][TAB_DQ][n] = GemmGroupDesc{so, qo + d, qo, L, dk, L, ldS, 0, 0};         // dQ = dS K
-                        tabs[which][TAB_DK][n] = GemmGroupDesc{so, qo, qo + d, L, dk, L, ldS, 0, 0};         // dK = dS^T Q
+                        GemmGroupDesc gd[6];
+                        attn_group_descs(qo, oo, so, L, dk, d, seqs[which][n], gd);
+                        for (int k = 0; k < 6; ++k) tabs[which][k][n] = gd[k];
                     }
                 }
             p.hB[t] = B; p.hSmax[t] = S; p.hTcap[t] = Tcap; p.hMp[t] = Mp; p.hMf[t] = Mf; p.hMr[t] = Mr;

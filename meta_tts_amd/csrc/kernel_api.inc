@@ -125,6 +125,108 @@ int mtts_sdpa_fwd(int n_mat, int L, int dk, const float* q, const float* kk, con
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// Attention in the layout the engine runs (engine.h: fft_fwd / fft_bwd): n_seq sequences of ragged lengths lens[i] at rows row0[i] of one
+// packed [rows][3 d] buffer (d = heads * dk; Q | K | V column blocks, a head = dk columns), O / dO in [rows][d]; group n = seq * heads + head,
+// its P / dS matrix [L][ldS] at the running sum of L * ldS.  The descriptors are attn_group_descs' — the plan's own.  Contract on buffer
+// contents: nothing outside a sequence's rows is read into a result, and the pad columns [L, ldS) of P and dS are WRITTEN (zero) by the
+// softmax of either path before any product reads them, so P and dS may hold anything on entry of _fwd / _bwd.
+namespace {
+struct AttnPackedWs { AttnSeq* seqs; GemmGroupDesc* tab[6]; };
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline long long attn_packed_ws_bytes(long long n) { return (long long)(up256(n * sizeof(AttnSeq)) + 6 * up256(n * sizeof(GemmGroupDesc))); }
+struct AttnPacked {
+    int n = 0, max_L = 0, d = 0;
+    long long sumL = 0;
+    double sumL2 = 0.0;
+    AttnPackedWs w;
+};
+// validates, builds the descriptors of every (sequence, head) and uploads them: one synchronous copy
+inline int attn_packed_setup(int n_seq, int heads, int dk, const int* lens, const int* row0, void* ws, int64_t ws_bytes, AttnPacked& a) {
+    if (n_seq < 1 || heads < 1 || dk < 4 || (dk & 3) || !lens || !row0 || !ws) return -1;
+    for (int i = 0; i < n_seq; ++i) if (lens[i] < 1 || row0[i] < 0) return -1;
+    a.n = n_seq * heads; a.d = heads * dk;
+    const long long need = attn_packed_ws_bytes(a.n);
+    if (ws_bytes < need) return -1;
+    std::vector<char> img((size_t)need, 0);
+    const size_t sb = up256((size_t)a.n * sizeof(AttnSeq)), tb = up256((size_t)a.n * sizeof(GemmGroupDesc));
+    AttnSeq* hs = (AttnSeq*)img.data();
+    a.w.seqs = (AttnSeq*)ws;
+    for (int k = 0; k < 6; ++k) a.w.tab[k] = (GemmGroupDesc*)((char*)ws + sb + k * tb);
+    long long so = 0;
+    for (int i = 0; i < n_seq; ++i) {
+        const int L = lens[i];
+        a.max_L = std::max(a.max_L, L);
+        a.sumL += (long long)heads * L; a.sumL2 += (double)heads * L * L;
+        for (int hh = 0; hh < heads; ++hh) {
+            const int n = i * heads + hh;
+            GemmGroupDesc gd[6];
+            attn_group_descs((long long)row0[i] * 3 * a.d + hh * dk, (long long)row0[i] * a.d + hh * dk, so, L, dk, a.d, hs[n], gd);
+            for (int k = 0; k < 6; ++k) ((GemmGroupDesc*)(img.data() + sb + k * tb))[n] = gd[k];
+            so += (long long)L * hs[n].ldS;
+        }
+    }
+    return hipMemcpy(ws, img.data(), (size_t)need, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+// one table-mode product with the launch bounds and cost hints of Engine::attn_gemm
+inline void attn_packed_gemm(const AttnPacked& a, int which, int form, int dk, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                             float alpha, hipStream_t stream) {
+    GemmArgs g;
+    g.table = a.w.tab[which];
+    g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.alpha = alpha;
+    const bool sq = which == TAB_QK || which == TAB_DP;
+    g.K = sq ? dk : a.max_L;
+    gemm_launch(kernel_ctx(), form, g, a.max_L, sq ? a.max_L : dk, a.n, stream, 0, 2.0 * a.sumL2 * dk, a.sumL, 4.0 * (a.sumL2 + 2.0 * (double)a.sumL * dk));
+}
+}  // namespace
+
+int64_t mtts_attn_packed_ws_bytes(int n_seq, int heads) { return attn_packed_ws_bytes((long long)(n_seq < 1 ? 1 : n_seq) * (heads < 1 ? 1 : heads)); }
+
+// path 0: what fft_fwd launches (the fused kernel when it serves max_L and dk, else the three launches); path 1: the three launches
+int mtts_attn_packed_fwd(int n_seq, int heads, int dk, const int* lens, const int* row0, int path, const float* qkv, float* P, float* O, void* ws,
+                         int64_t ws_bytes, void* stream) {
+    if (!qkv || !P || !O || (path != 0 && path != 1)) return -1;
+    AttnPacked a;
+    if (attn_packed_setup(n_seq, heads, dk, lens, row0, ws, ws_bytes, a)) return -1;
+    const int d = a.d;
+    const float scale = 1.f / sqrtf((float)dk);
+    if (path == 0 && knobs().fused_attn && attn_fused_ok(a.max_L, dk)) {
+        AttnFwdArgs fa;
+        fa.seqs = a.w.seqs; fa.tab_qk = a.w.tab[TAB_QK]; fa.tab_pv = a.w.tab[TAB_PV];
+        fa.Q = fa.K = fa.V = qkv; fa.ld_q = fa.ld_k = fa.ld_v = 3 * d;
+        fa.P = P; fa.O = O; fa.ld_o = d; fa.scale = scale; fa.dk = dk; fa.rot = 0; fa.prio = 0;
+#if defined(MTTS_ATTN_DIAG)
+        fa.diag = 0;
+#endif
+        attn_fwd_launch(fa, a.max_L, a.n, (hipStream_t)stream);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
+    attn_packed_gemm(a, TAB_QK, GEMM_NT, dk, qkv, 3 * d, qkv, 3 * d, P, 0, scale, (hipStream_t)stream);
+    launch_softmax_fwd(a.w.seqs, a.max_L, a.n, P, (hipStream_t)stream);
+    attn_packed_gemm(a, TAB_PV, GEMM_NN, dk, P, 0, qkv, 3 * d, O, d, 1.f, (hipStream_t)stream);
+    return kernel_launch_rc();
+}
+// fft_bwd's attention part: dP = dO V^T and dV = P^T dO as one batch, dP -> dS in place, dQ = dS K and dK = dS^T Q as one batch;
+// gqkv receives dQ | dK | dV in the column blocks of qkv
+int mtts_attn_packed_bwd(int n_seq, int heads, int dk, const int* lens, const int* row0, const float* qkv, const float* P, const float* dO, float* dS,
+                         float* gqkv, void* ws, int64_t ws_bytes, void* stream) {
+    if (!qkv || !P || !dO || !dS || !gqkv) return -1;
+    AttnPacked a;
+    if (attn_packed_setup(n_seq, heads, dk, lens, row0, ws, ws_bytes, a)) return -1;
+    const int d = a.d;
+    hipStream_t st = (hipStream_t)stream;
+    GemmCtx& cx = kernel_ctx();
+    gemm_batch_begin(cx);
+    attn_packed_gemm(a, TAB_DP, GEMM_NT, dk, dO, d, qkv, 3 * d, dS, 0, 1.f, st);
+    attn_packed_gemm(a, TAB_DV, GEMM_TN, dk, P, 0, dO, d, gqkv, 3 * d, 1.f, st);
+    gemm_batch_end(cx, st);
+    launch_softmax_bwd(a.w.seqs, a.max_L, a.n, P, dS, 1.f / sqrtf((float)dk), st);
+    gemm_batch_begin(cx);
+    attn_packed_gemm(a, TAB_DQ, GEMM_NN, dk, dS, 0, qkv, 3 * d, gqkv, 3 * d, 1.f, st);
+    attn_packed_gemm(a, TAB_DK, GEMM_TN, dk, dS, 0, qkv, 3 * d, gqkv, 3 * d, 1.f, st);
+    gemm_batch_end(cx, st);
+    return kernel_launch_rc();
+}
+
 // PostNet BatchNorm1d in training mode (transformer/Layers.py:129-137): statistics over the rows with inrect != 0 (the padded
 // frames of the rectangle count, as in the reference), y = [tanh](gamma * xhat + beta) on those rows, 0 elsewhere.
 // stats [3C] = mean | rstd | unbiased variance (what the running-var update uses).

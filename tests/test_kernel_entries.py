@@ -89,7 +89,8 @@ def test_layernorm_fwd_bwd(dev, rows, Cc, with_res, with_mask):
 
 
 @pytest.mark.parametrize("n_mat,L,dk", [(3, 17, 16), (2, 80, 128), (4, 5, 32), (2, 130, 64), (1, 333, 128), (1, 700, 128),
-                                        (2, 128, 64)])   # (4 chunks of 32 keys: every wavefront of phase A carries the same count; the others are no multiple of 4)
+                                        (2, 128, 64),    # (4 chunks of 32 keys: every wavefront of phase A carries the same count; the others are no multiple of 4)
+                                        (1, 1, 16), (1, 352, 32), (1, 1024, 64)])   # one key; the upper edges of the 352 and 1024 tile classes
 def test_sdpa_and_softmax(dev, n_mat, L, dk):
     # (the fused attention forward, csrc/attention.h: L <= 128 / <= 640 / <= 1024 take the three LDS tile classes)
     g = np.random.RandomState(L * 7 + dk)
