@@ -799,6 +799,52 @@ int mtts_dtw_cepstra(mtts_dtw* h, int n_utts, const int* n_frames, const float* 
 int mtts_dtw_mcd_batch(mtts_dtw* h, int n_pairs, const int* frames_a, const float* mel_a, const int* frames_b, const float* mel_b, const int* f0_frames_a,
                        const double* f0_a, const int* f0_frames_b, const double* f0_b, double* out, int* path_len, int* path);
 
+/* ---- MOSNet: magnitude spectrograms / waveforms -> naturalness scores -------------------------------
+ * Stands behind evaluation/compute_mos.py (NeuralMOS.compute_mosnet, speechmetrics' MOSNet on one wav at a time).  Neither speechmetrics,
+ * its TensorFlow model nor cnn_blstm.h5 is part of the reference tree: parity with the published weights is UNPINNED, and so are the
+ * analysis window (a symmetric Hamming window, which lives in the forward basis the caller loads) and the recurrent activation (sigmoid,
+ * tf.keras 2's default); what is pinned is this definition — the published CNN-BLSTM MOSNet (Lo et al. 2019) in inference mode —
+ * restated in torch by tests/mosnet_oracle.py:
+ *   input     per utterance a magnitude spectrogram [T][n_freq]: |STFT| at 16 kHz, n_fft = 2 (n_freq - 1) = 512, hop 256, window length
+ *             n_fft, centred with reflection padding; T = n / 256 + 1.
+ *   conv      four blocks of C = 16, 32, 64, 128: Conv2d(C_prev -> C), Conv2d(C -> C), Conv2d(C -> C), 3x3 kernels (time x frequency),
+ *             bias + ReLU each, C_prev of the first = 1; the third of a block has stride (1, 3).  Padding is TensorFlow's "same": in time one
+ *             zero row before and after the utterance's OWN first and last frame (a ragged batch equals its utterances scored alone); in
+ *             frequency one zero column each side at stride 1, and at stride 3, F_in -> F_out = ceil(F_in / 3), total = max((F_out - 1) 3 +
+ *             3 - F_in, 0), left = total / 2 (floor), right = total - left.  n_freq = 257: widths 257 -> 86 -> 29 -> 10 -> 4, left 0, 0, 0, 1.
+ *   features  [F4 * 128] per frame, frequency-major then channel (Keras' Reshape((-1, 4 * 128)) of a channels-last tensor).
+ *   BLSTM     128 units per direction, gate order i, f, g, o, sigmoid recurrent activation, tanh elsewhere, zero initial state; the
+ *             backward direction starts at the utterance's own last frame; outputs concatenated [forward | backward] = 256.
+ *   head      Dense(256 -> 128) + ReLU, Dense(128 -> 1) = the frame score; the utterance score is the mean of its own T frame scores.
+ * create: n_freq is a parameter (tests use narrow spectra; the channel counts stay the published four and the BLSTM input is 128 F4);
+ *   max_frames_per_call bounds sum T of one call (the activations are [sum T][n_freq][16] floats, twice), max_utts <= 65535 its utterances.
+ * Tensors (device images, packed by meta_tts_amd/mosnet.py from torch-layout weights):
+ *   conv.0.w [9][16] (tap = 3 dt + df), conv.{l}.w [9][cin / 8][cout][8] (input channel 8 q + e at [tap][q][n][e]), conv.{l}.b [cout];
+ *   blstm.w_ih [2][512][128 F4] and blstm.b [2][512] (forward, then backward), blstm.w_hh [2][32][512][4] (hidden unit 4 k + e of gate
+ *   column g at [dir][k][g][e]);  dense.w [128][256], dense.b [128];  frame_score.w [128], frame_score.b [1].
+ * score: mag [sum T][n_freq] host float32, utterances one after another -> utt_scores [n_utts], frame_scores [sum T] (or NULL).
+ * score_wavs: waveforms (host float32, one after another, n_samples[u] each) through `front` — pack, upload, reflect pad, forward STFT,
+ *   magnitude — and, with resampled != 0, behind the resampler loaded on `front` (n_samples then counts source-rate samples; no volume
+ *   normalisation); the network reads the front-end's magnitudes where they lie, neither the 16 kHz signal nor the magnitudes visit the
+ *   host.  n_frames_out [n_utts] = each utterance's T.  `front` must have filter_length 2 (n_freq - 1) and a forward basis loaded; the
+ *   whole chain runs on front's stream.
+ * An utterance's scores are bit-identical alone, in any batch and at any position.  Both entries are synchronous.  Refused with < 0,
+ *   the reason in last_error, before any launch, the handle staying usable: NULL required pointers; a tensor that has not been loaded;
+ *   n_utts < 1, > max_utts or > 65535; T < 1; sum T > max_frames_per_call (cutting a list into calls is the caller's job); non-finite
+ *   magnitudes (score only); a front of another filter length or without a basis; no resampler loaded although resampled; a waveform
+ *   too short for the reflection padding or longer than front's max_samples.  load refuses an unknown name and a wrong numel. */
+typedef struct mtts_mosnet mtts_mosnet;
+int mtts_mosnet_create(int n_freq, int max_frames_per_call, int max_utts, int device, mtts_mosnet** out);
+void mtts_mosnet_destroy(mtts_mosnet* h);
+const char* mtts_mosnet_last_error(mtts_mosnet* h);
+int mtts_mosnet_set_stream(mtts_mosnet* h, void* hip_stream);
+int mtts_mosnet_param_count(mtts_mosnet* h);
+int mtts_mosnet_param_info(mtts_mosnet* h, int index, char* name, int name_cap, int64_t* numel);
+int mtts_mosnet_load(mtts_mosnet* h, const char* name, const float* data, int64_t numel);
+int mtts_mosnet_score(mtts_mosnet* h, int n_utts, const int* n_frames, const float* mag, float* utt_scores, float* frame_scores);
+int mtts_mosnet_score_wavs(mtts_mosnet* h, mtts_stft* front, int n_utts, const int* n_samples, const float* wavs, int resampled, float* utt_scores,
+                           int* n_frames_out, float* frame_scores);
+
 #ifdef __cplusplus
 }
 #endif

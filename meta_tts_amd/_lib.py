@@ -231,6 +231,15 @@ EXPORTS = {
     "mtts_dtw_load_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mtts_dtw_cepstra": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_dtw_mcd_batch": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 11),
+    "mtts_mosnet_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mtts_mosnet_destroy": (None, [C.c_void_p]),
+    "mtts_mosnet_last_error": (C.c_char_p, [C.c_void_p]),
+    "mtts_mosnet_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mtts_mosnet_param_count": (C.c_int, [C.c_void_p]),
+    "mtts_mosnet_param_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
+    "mtts_mosnet_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "mtts_mosnet_score": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_mosnet_score_wavs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _cache = {}

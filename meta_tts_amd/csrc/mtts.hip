@@ -17,6 +17,7 @@
 #include "speakereval.h"
 #include "tsne.h"
 #include "dtw.h"
+#include "mosnet.h"
 
 using namespace mtts;
 
@@ -59,6 +60,9 @@ struct mtts_tsne {
 };
 struct mtts_dtw {
     Dtw d;
+};
+struct mtts_mosnet {
+    MosNet n;
 };
 struct mtts_stft {
     MelFront m;
@@ -731,6 +735,42 @@ int mtts_hifigan_infer(mtts_hifigan* h, const float* mel, int B, int T_max, cons
 int mtts_hifigan_infer_device(mtts_hifigan* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
                               float mel_scale, float* wav_dev) {
     return hifigan_launched(h->v, h->v.run(mel_dev, B, T_max, mel_lens, mel_scale, wav_dev, (long long)T_max * h->v.hop, (long long)mel_utt_stride));
+}
+
+// ---- MOSNet naturalness scores (mosnet.h; reference evaluation/compute_mos.py) ------------------------------------------------
+int mtts_mosnet_create(int n_freq, int max_frames_per_call, int max_utts, int device, mtts_mosnet** out) {
+    if (!out) { g_create_error = "mtts_mosnet_create: NULL out"; return -1; }
+    const std::string why = MosNet::check_cfg(n_freq, max_frames_per_call, max_utts);   // (refused before the device is touched)
+    if (!why.empty()) { g_create_error = "mtts_mosnet_create: " + why; return -1; }
+    if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
+    mtts_mosnet* h = new mtts_mosnet();
+    if (h->n.init(n_freq, max_frames_per_call, max_utts) != 0) { g_create_error = h->n.last_error; delete h; return -1; }
+    *out = h;
+    return 0;
+}
+void mtts_mosnet_destroy(mtts_mosnet* h) {
+    if (!h) return;
+    hipDeviceSynchronize();
+    delete h;
+}
+const char* mtts_mosnet_last_error(mtts_mosnet* h) { return h ? h->n.last_error.c_str() : g_create_error.c_str(); }
+int mtts_mosnet_set_stream(mtts_mosnet* h, void* s) { if (!h) return -1; h->n.stream = (hipStream_t)s; return 0; }
+int mtts_mosnet_param_count(mtts_mosnet* h) { return h ? (int)h->n.tensors.size() : -1; }
+int mtts_mosnet_param_info(mtts_mosnet* h, int i, char* name, int cap, int64_t* numel) {
+    if (!h || !name || !numel || i < 0 || i >= (int)h->n.tensors.size()) return -1;
+    snprintf(name, cap, "%s", h->n.tensors[i].name.c_str());
+    *numel = h->n.tensors[i].numel;
+    return 0;
+}
+int mtts_mosnet_load(mtts_mosnet* h, const char* name, const float* data, int64_t numel) { return h ? h->n.load(name, data, numel) : -1; }
+int mtts_mosnet_score(mtts_mosnet* h, int n_utts, const int* n_frames, const float* mag, float* utt_scores, float* frame_scores) {
+    return h ? h->n.score(n_utts, n_frames, mag, utt_scores, frame_scores) : -1;
+}
+int mtts_mosnet_score_wavs(mtts_mosnet* h, mtts_stft* front, int n_utts, const int* n_samples, const float* wavs, int resampled, float* utt_scores,
+                           int* n_frames_out, float* frame_scores) {
+    if (!h) return -1;
+    if (!front) return h->n.err("mtts_mosnet_score_wavs: NULL STFT handle");
+    return h->n.score_wavs(front->m, front->rs, n_utts, n_samples, wavs, resampled != 0, utt_scores, n_frames_out, frame_scores);
 }
 
 // ---- exact t-SNE of d-vectors (tsne.h; reference evaluation/visualize.py:56-71) ---------------------------------------------

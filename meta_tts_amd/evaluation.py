@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 import os
 import random
 from typing import Callable, Dict, List, Optional, Sequence
@@ -1172,3 +1173,154 @@ class ObjectiveEvaluation:
     def load_mcd(self):
         self.mcd_dict = np.load(self.config.path("npy", "mcd_dict.npy"), allow_pickle=True)[()]
         return self.mcd_dict
+
+
+def _student_t_ppf(p: float, df: float) -> float:
+    """The p-quantile of Student's t with df degrees of freedom, for where scipy is not importable: bisection on the distribution
+    function, itself the regularised incomplete beta function I_x(df / 2, 1 / 2) by Lentz's continued fraction."""
+    def betainc(a, b, x):
+        if x <= 0.0 or x >= 1.0:
+            return 0.0 if x <= 0.0 else 1.0
+        if x > (a + 1.0) / (a + b + 2.0):
+            return 1.0 - betainc(b, a, 1.0 - x)
+        front = math.exp(math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b) + a * math.log(x) + b * math.log1p(-x)) / a
+        tiny, f, c, d = 1e-300, 1.0, 1.0, 0.0
+        for i in range(400):
+            m = i // 2
+            num = 1.0 if i == 0 else (m * (b - m) * x / ((a + 2 * m - 1) * (a + 2 * m)) if i % 2 == 0 else -(a + m) * (a + b + m) * x / ((a + 2 * m) * (a + 2 * m + 1)))
+            d = 1.0 + num * d
+            d = 1.0 / (d if abs(d) > tiny else tiny)
+            c = 1.0 + num / (c if abs(c) > tiny else tiny)
+            f *= c * d
+            if abs(1.0 - c * d) < 1e-15:
+                break
+        return front * (f - 1.0)
+
+    def cdf(t):
+        tail = 0.5 * betainc(0.5 * df, 0.5, df / (df + t * t))
+        return 1.0 - tail if t > 0 else tail
+
+    if not 0.0 < p < 1.0 or df <= 0:
+        return float("nan")
+    lo, hi = -1.0, 1.0
+    while cdf(lo) > p:
+        lo *= 2.0
+    while cdf(hi) < p:
+        hi *= 2.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if cdf(mid) < p else (lo, mid)
+    return 0.5 * (lo + hi)
+
+
+class NeuralMOS:
+    """compute_mos.py's `NeuralMOS` for MOSNet: the naturalness score of every wav of a test run's result tree, over the file lists of the
+    reference (:65-96) — `real`, `recon`, and `<mode>_step<k>` for every mode of `config.mode_step_list` except scratch_encoder / encoder /
+    dvec — found through the helpers the other evaluation classes use.  `mosnet`: a `meta_tts_amd.mosnet.MOSNet`; `wav_loader(path) ->
+    (float32 waveform, sampling rate)` (default `preprocessor.read_wav`): a file is read at its own rate and resampled to 16 kHz on the
+    device in front of the STFT, where the reference's `librosa.load(sr=16000)` resamples on the host.  A test sample without its
+    directory or wav is refused (the reference asserts one candidate), not skipped: every table has a row per test sample.  `compute_mbnet`
+    (its model code is not in the reference tree) and the plots are not built."""
+
+    SKIPPED_MODES = ("scratch_encoder", "encoder", "dvec")   # compute_mos.py:78
+
+    def __init__(self, config: EvalConfig, mosnet, wav_loader: Optional[Callable[[str], tuple]] = None, *, frames_per_call: Optional[int] = None):
+        self.config, self.mosnet, self.frames_per_call = config, mosnet, frames_per_call
+        self.corpus, self.data_dir_dict = config.corpus, config.data_dir_dict
+        self.n_sample, self.n_speaker, self.mode_step_list = config.n_sample, config.n_speaker, config.mode_step_list
+        self.wav_loader = wav_loader or self._read_wav
+        with open(os.path.join(self.data_dir_dict["recon"], "test_SQids.json")) as f:
+            self.sq_list = json.load(f)
+        self.speaker_id_map, self.inv_speaker_id_map = self.get_speaker_id_map()
+        self.file_list = self.setup_filelist()
+
+    get_speaker_id_map = WavsToDvector.get_speaker_id_map
+    get_real_filelist = WavsToDvector.get_real_filelist
+    _find = WavsToDvector._find
+
+    @staticmethod
+    def _read_wav(path: str):
+        from .preprocessor import read_wav
+        return read_wav(path)
+
+    def _test_files(self, mode: str, data_dir: str, suffix: str):
+        root, out = _testing_dir(data_dir), []
+        for data_id in range(self.n_speaker * self.n_sample):
+            d = os.path.join(root, f"test_{data_id:03d}")
+            if not os.path.isdir(d):
+                raise MttsError(f"NeuralMOS: mode {mode}: test sample {data_id} has no directory {d}")
+            p = self._find(d, suffix)
+            if p is None:
+                raise MttsError(f"NeuralMOS: mode {mode}: test sample {data_id} has no *{suffix} in {d}")
+            out.append(p)
+        return out
+
+    def setup_filelist(self):
+        file_list = {"real": self.get_real_filelist()}
+        for p in file_list["real"]:
+            if not os.path.exists(p):
+                raise MttsError(f"NeuralMOS: real wav {p} does not exist")
+        file_list["recon"] = self._test_files("recon", self.data_dir_dict["recon"], ".recon.wav")
+        for mode, steps in self.mode_step_list:
+            if mode in self.SKIPPED_MODES:
+                continue
+            for step in steps:
+                file_list[f"{mode}_step{step}"] = self._test_files(f"{mode}_step{step}", self.data_dir_dict[mode], f"FTstep_{step}.synth.wav")
+        return file_list
+
+    def score_files(self, paths: Sequence[str]) -> np.ndarray:
+        """MOSNet scores of the files, in order: read, grouped by sampling rate, one `score_wavs` per rate."""
+        wavs, groups = [], {}
+        for i, p in enumerate(paths):
+            wav, rate = self.wav_loader(p)
+            wavs.append(np.asarray(wav, np.float32).reshape(-1))
+            groups.setdefault(int(rate), []).append(i)
+        out = np.empty(len(wavs), np.float32)
+        for rate, idx in sorted(groups.items()):
+            out[idx] = self.mosnet.score_wavs([wavs[i] for i in idx], source_rate=rate, frames_per_call=self.frames_per_call)[0]
+        return out
+
+    def compute_mosnet(self):
+        """csv/<corpus>/mosnet_<mode>.csv per mode (`test_id, mos` and one `test_XXX, score` row per test sample); a mode whose csv
+        exists is skipped, as in the reference.  Returns {mode: scores} of the modes computed now."""
+        done = {}
+        for mode, files in self.file_list.items():
+            path = self.config.path("csv", f"mosnet_{mode}.csv")
+            if os.path.exists(path):
+                continue
+            for _id, filepath in enumerate(files):      # compute_mos.py:132-134
+                basename, realbase = os.path.basename(filepath).split(".")[0], os.path.basename(self.file_list["real"][_id]).split(".")[0]
+                if basename != realbase:
+                    raise MttsError(f"NeuralMOS: mode {mode}: test sample {_id} is {basename}, the real file is {realbase}")
+            scores = self.score_files(files)
+            with open(path, "w") as f:
+                f.write("test_id, mos\n")
+                for _id, score in enumerate(scores):
+                    f.write(f"test_{_id:03}, {float(score)}\n")
+            done[mode] = scores
+        return done
+
+    @staticmethod
+    def get_mean_confidence_interval(data, confidence: float = 0.95):
+        """compute_mos.py:175-180: (mean, half width of the Student-t interval), scipy.stats.sem's ddof = 1."""
+        a = 1.0 * np.array(data)
+        n = len(a)
+        m, se = np.mean(a), (np.std(a, ddof=1) / np.sqrt(n) if n > 1 else float("nan"))
+        try:
+            from scipy import stats
+            q = stats.t.ppf((1 + confidence) / 2.0, n - 1)
+        except ImportError:
+            q = _student_t_ppf((1 + confidence) / 2.0, n - 1)
+        return m, se * q
+
+    def add_up(self, net: str = "mosnet"):
+        """txt/<corpus>/<net>.txt: one `mode, mean, ci` line per mode, from the csv files."""
+        rows = []
+        with open(self.config.path("txt", f"{net}.txt"), "w") as fo:
+            for mode in self.file_list:
+                with open(self.config.path("csv", f"{net}_{mode}.csv")) as f:
+                    scores = [float(line.strip().split(",")[1].strip()) for line in f.readlines()[1:]]
+                mean, ci = self.get_mean_confidence_interval(scores)
+                fo.write(f"{mode}, {mean}, {ci}\n")
+                rows.append((mode, mean, ci))
+        return rows
