@@ -436,6 +436,27 @@ int mtts_hifigan_load(mtts_hifigan* h, const char* name, const float* data, int6
 int mtts_hifigan_infer(mtts_hifigan* h, const float* mel, int B, int T_max, const int* mel_lens, float mel_scale, float* wav);
 int mtts_hifigan_infer_device(mtts_hifigan* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
                               float mel_scale, float* wav_dev);
+/* Numerics of the generator.  Mode 0 (fp32) is the default and is what create built, bit for bit.  Mode 1, "bf16 operands", is the
+ * definition above with these changes, restated in torch by tests/hifigan_bf16_oracle.py:
+ *   - rounded convolutions: conv_pre, the polyphase images of every ups[i] and every residual convolution multiply operands rounded to
+ *     bf16 (round to nearest even); products are exact, accumulation is fp32;
+ *   - what gets rounded: the activation operand is the value the fp32 route feeds the convolution — mel * mel_scale for conv_pre, the
+ *     LeakyReLU image of x elsewhere — each element rounded once; the weight operand is the folded fp32 weight, rounded once (when the
+ *     operand is staged, or when the direct kernel's image is packed at load / set_numerics);
+ *   - what stays fp32: bias, LeakyReLU, residual add, the MRF mean, every tensor in HBM, and conv_post + tanh;
+ *   - zero padding stays at each utterance's own ends, and no split-K is used: an utterance is the same bits alone or in any ragged batch.
+ * set_numerics(mode, direct_max_channels): mode 0 takes direct_max_channels 0 / 32 / 64, mode 1 takes 0 / 32 / 64 / 128 (stages of 32,
+ * 64 or 128 channels and <= the value run hg_conv_direct_bf16_kernel, the rest the bf16 GEMM family); anything else is refused before
+ * any launch with a message naming the argument.  Tensors loaded after the call are re-packed.  get_numerics: the mode in force.
+ * conv_bf16 (kernel-level, for tests): ONE convolution of mode 1 on HOST arrays, without the network around it:
+ *   v = bias + conv(k odd <= 11, dilation d in 1..5, zero pad d (k-1)/2)(bf16(leaky_relu(x, in_slope))) with bf16(w)
+ *   epilogue 0: out = leaky_relu(v, 0.1);  1: out = v + res;  2: mrf = (mrf_init ? 0 : mrf) + inv_nk * (v + res)
+ * x, res, out, mrf [B][T_max][C] with C in {32, 64, 128}, B <= max_B, w [C][k][C], lens[b] in 1..T_max; rows >= lens[b] of out / mrf
+ * are left untouched.  route 0: the direct kernel; route 1: the GEMM route (pad pass, bf16 GEMM family, accumulate epilogue). */
+int mtts_hifigan_set_numerics(mtts_hifigan* h, int mode, int direct_max_channels);
+int mtts_hifigan_get_numerics(mtts_hifigan* h);
+int mtts_hifigan_conv_bf16(mtts_hifigan* h, int route, int C, int k, int d, int B, int T_max, const int* lens, const float* x, const float* w,
+                           const float* bias, float in_slope, int epilogue, const float* res, float* mrf, float inv_nk, int mrf_init, float* out);
 
 /* ---- d-vector speaker encoder, forward only (`speaker_emb: dvec`) -------------------------
  * Replaces `SpeakerEncoder.forward` for emb_type "dvec" (lightning/model/speaker_encoder.py:54-60,71-76): the frozen

@@ -213,6 +213,10 @@ EXPORTS = {
     "mtts_hifigan_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     "mtts_hifigan_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
     "mtts_hifigan_infer_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
+    "mtts_hifigan_set_numerics": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "mtts_hifigan_get_numerics": (C.c_int, [C.c_void_p]),
+    "mtts_hifigan_conv_bf16": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
+                                         C.c_void_p]),
     "mtts_get_mel_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mtts_tsne_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mtts_tsne_destroy": (None, [C.c_void_p]),

@@ -1147,6 +1147,7 @@ struct GemmCtx {
     bool prefer_bk16 = false;   // multi-problem launches of this context take the BK = 16 kernels (20 KB of LDS per workgroup instead of 37) whatever their K
     int wave_prio = 0;      // GemmArgs::wave_prio of every launch of this context (the engine sets it on the critical stream's context while side streams carry work)
     bool no_glds = false;   // never pick the LDS-DMA kernels (48 KB of LDS per workgroup: a side-stream launch would leave no LDS for the main stream's)
+    bool no_splitk = false;   // never split K (the split factor follows the batch's size: an owner whose results must not depend on what else is in the batch sets it)
     DevHeap* heap = nullptr;   // the owner's: the workspace and the profiler's events come from it and go back with it
     int alloc_workspace(DevHeap& h) {
         heap = &h;
@@ -1452,7 +1453,7 @@ inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream) {
         int S = 1;
         const int nch = (gemm_keff(p.g) + 15) / 16;
         constexpr double ratio = 1.5;
-        if (knobs().batch_splitk && small_batch && T == 64 && !p.g.table && !p.g.colsum && !p.g.ln.y && nch > per_cu / ratio) {
+        if (knobs().batch_splitk && !cx.no_splitk && small_batch && T == 64 && !p.g.table && !p.g.colsum && !p.g.ln.y && nch > per_cu / ratio) {
             S = (int)std::min<double>(std::min<double>(std::ceil(nch / std::max(per_cu / ratio, 1.0)), nch / 16), 8);
             const long long slots = (long long)tiles * p.groups;
             if (S >= 2 && ((ws_off + slots * S * 4096) > kSplitWsFloats || ctr_off + slots > kSplitCtrs - kLnCtrs)) S = 1;

@@ -429,10 +429,11 @@ constexpr int kBf16BK = 32;
 // queued behind them) and the extra registers cost the chip-filling launches 10-25 % (occupancy 7 -> 4 workgroups per CU): 1.
 constexpr int kBf16PF64 = 1, kBf16PF128 = 1;
 // a problem the bf16 K-loop can take: every conv tap must cover whole K-slices (the others — PostNet's 80-channel output layer in
-// dgrad form, the vocoder's dilated taps — keep the fp32 kernels: a few per cent of the step's flops)
+// dgrad form — keep the fp32 kernels: a few per cent of the step's flops).  Dilated taps of the A operand (HiFi-GAN's bf16 mode) likewise:
+// a_tap_k a multiple of the slice, so that load_a's tap walk moves whole slices.
 inline bool gemm_bf16_ok(const GemmArgs& g) {
     if (g.taps > 1 && g.tap_k % kBf16BK != 0) return false;
-    if (g.a_tap_rows != 0) return false;
+    if (g.a_tap_rows != 0 && g.a_tap_k % kBf16BK != 0) return false;
     return true;
 }
 // an NT problem whose operand planes the plane-staged K-loop can take: 16-byte loads (leading dimensions and K in whole groups of 8), plain

@@ -24,10 +24,15 @@
 //   copy — a workgroup stages 128 + (k-1) d rows in LDS (LeakyReLU on the way in, zeros outside the utterance), runs the k C deep product
 //   on the fp32 MFMA pipe with the weights streamed from L2, and ends with bias + LeakyReLU, bias + residual, or bias + residual + MRF
 //   accumulation.  A pair costs two launches and no pad pass.
+//   bf16-operand mode (set_numerics(1, .); include/mtts.h): the same graph with every convolution but conv_post multiplying operands
+//   rounded to bf16 — the GEMM route on the bf16 family of gemm_bf16.h through this handle's GemmCtx (rounding in its staging pass, no
+//   split-K), the direct route (C in {32, 64, 128}) on hg_conv_direct_bf16_kernel over weight images packed once per tensor.  Everything
+//   between the convolutions, every tensor in HBM and conv_post + tanh stay fp32.
 #pragma once
 #include <string>
 #include <vector>
 
+#include "gemm_bf16.h"
 #include "vocoder.h"
 
 namespace mtts {
@@ -207,9 +212,119 @@ __global__ __launch_bounds__(256) void hg_conv_direct_kernel(HgConvArgs a) {
     }
 }
 
+// ---- bf16-operand mode (numerics mode 1; definition in include/mtts.h) -----------------------------------------------------------------
+// Weight image of the direct bf16 kernel: [tap][cin / 16][cout / 32][half][cout % 32][8] bf16 — the B fragment of one wavefront for one
+// (tap, 16-deep k-step, 32-column tile) is 64 lanes x 16 bytes = ONE contiguous KB (lane l = half * 32 + column reads bytes [16 l, 16 l + 16)),
+// against the 32-byte pieces the fp32 kernel gathers from the [C][k][C] image.  Rounded here, once (round to nearest even).
+// One thread per 8 elements: 8 consecutive cin of one (cout, tap).
+__global__ void hg_pack_bf16_kernel(const float* __restrict__ w, bf16_t* __restrict__ out, int C, int k) {
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;   // one 16-byte piece of the image
+    if (i >= C * k * (C / 8)) return;
+    const int TN = C / 32, KS = C / 16;
+    const int n32 = i & 31, h = (i >> 5) & 1, j = (i >> 6) % TN, q = ((i >> 6) / TN) % KS, t = (i >> 6) / (TN * KS);
+    const float* src = w + ((long long)(j * 32 + n32) * k + t) * C + 16 * q + 8 * h;
+    const float4 lo = ld4(src), hi = ld4(src + 4);
+    u32x4 v;
+    v.x = pack2_bf16(lo.x, lo.y); v.y = pack2_bf16(lo.z, lo.w); v.z = pack2_bf16(hi.x, hi.y); v.w = pack2_bf16(hi.z, hi.w);
+    *reinterpret_cast<u32x4*>(out + (long long)i * 8) = v;
+}
+
+// Direct route of the bf16 mode: the convolution of hg_conv_direct_kernel with both operands rounded to bf16, exact products, fp32
+// accumulation (v_mfma_f32_32x32x16_bf16).  Same tile contract (128 output rows per workgroup, wave w owns rows [32 w, 32 w + 32) x all C
+// columns) and the same three epilogues in fp32 registers.  wpk: the image of hg_pack_bf16_kernel, streamed from L2 (not staged in LDS: at
+// C = 128 a tap's slab is 32 KB beside 48.4 KB of activations).  LDS: (128 + (k-1) d) rows of C + 8 bf16, LeakyReLU and the utterance-end
+// zeros applied on the way in, one packed convert per two elements: 48.4 KB at C = 128, 25.6 KB at C = 64, 14.2 KB at C = 32.  Fragments as in
+// bf16_compute_slice: lane l feeds row / column l & 31 and the 8 consecutive k of half l >> 5; a dilated tap is a row offset t d.
+struct HgConvBf16Args {
+    HgConvArgs a;
+    const bf16_t* wpk = nullptr;
+};
+template <int C>
+__global__ __launch_bounds__(256) void hg_conv_direct_bf16_kernel(HgConvBf16Args p) {
+    constexpr int LDA = C + 8, TN = C / 32, KS = C / 16;
+    __shared__ __attribute__((aligned(16))) bf16_t As[(kHgTileRows + kHgMaxHalo) * LDA];
+    const HgConvArgs& a = p.a;
+    const int z = blockIdx.z, tid = (int)threadIdx.x;
+    const int T = a.lens[z] * a.len_mult, m0 = (int)blockIdx.x * kHgTileRows;
+    if (m0 >= T) return;   // (uniform over the workgroup, before the barrier)
+    const int halo = (a.k - 1) * a.d, pad = halo >> 1, nrows = kHgTileRows + halo;
+    const float* px = a.x + (long long)z * a.x_gs;
+    for (int i = tid; i < nrows * (C / 8); i += 256) {
+        const int lr = i / (C / 8), c = (i - lr * (C / 8)) * 8;
+        const int row = m0 - pad + lr;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (row >= 0 && row < T) {
+            const float4 lo = ld4(px + (long long)row * C + c), hi = ld4(px + (long long)row * C + c + 4);
+            v.x = pack2_bf16(hg_lrelu(lo.x, a.in_slope), hg_lrelu(lo.y, a.in_slope));
+            v.y = pack2_bf16(hg_lrelu(lo.z, a.in_slope), hg_lrelu(lo.w, a.in_slope));
+            v.z = pack2_bf16(hg_lrelu(hi.x, a.in_slope), hg_lrelu(hi.y, a.in_slope));
+            v.w = pack2_bf16(hg_lrelu(hi.z, a.in_slope), hg_lrelu(hi.w, a.in_slope));
+        }
+        *reinterpret_cast<u32x4*>(As + lr * LDA + c) = v;
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
+    f32x16 acc[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+#if defined(MTTS_EMU)
+    for (int j = 0; j < TN; ++j)
+        for (int r = 0; r < 16; ++r) {
+            const int lr = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            float s = 0.f;
+            for (int t = 0; t < a.k; ++t)
+                for (int c = 0; c < C; ++c) {
+                    const long long wi = ((((long long)(t * KS + (c >> 4)) * TN + j) * 2 + ((c >> 3) & 1)) * 32 + l31) * 8 + (c & 7);
+                    s = fmaf(bf16_to_f32(As[(lr + t * a.d) * LDA + c]), bf16_to_f32(p.wpk[wi]), s);
+                }
+            acc[j][r] = s;
+        }
+#else
+    for (int t = 0; t < a.k; ++t) {
+        const bf16_t* pa = As + (wave * 32 + l31 + t * a.d) * LDA + 8 * h;
+        const bf16_t* pw = p.wpk + (long long)t * KS * TN * 512 + lane * 8;
+#pragma unroll
+        for (int q = 0; q < KS; ++q) {
+            const bf16x8 av = *reinterpret_cast<const bf16x8*>(pa + 16 * q);
+            bf16x8 bv[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bv[j] = *reinterpret_cast<const bf16x8*>(pw + (q * TN + j) * 512);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv[j], acc[j], 0, 0, 0);
+        }
+    }
+#endif
+    const float* pres = a.res ? a.res + (long long)z * a.res_gs : nullptr;
+    float* pout = a.out ? a.out + (long long)z * a.out_gs : nullptr;
+    float* pmrf = a.mrf ? a.mrf + (long long)z * a.mrf_gs : nullptr;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = j * 32 + l31;
+        const float bv = a.bias[n];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (m >= T) continue;
+            const long long o = (long long)m * C + n;
+            float v = acc[j][r] + bv;
+            if (a.mode == 0) pout[o] = hg_lrelu(v, 0.1f);
+            else {
+                v += pres[o];
+                if (a.mode == 1) pout[o] = v;
+                else pmrf[o] = (a.mrf_init ? 0.f : pmrf[o]) + a.inv_nk * v;
+            }
+        }
+    }
+}
+constexpr bool hg_direct_bf16_channels(int C) { return C == 32 || C == 64 || C == 128; }   // (C = 256 is not built: 94 KB of activations)
+
 class HifiGan {
 public:
     HifiGanCfg cfg;
+    int numerics = 0;           // 0: fp32 (the default); 1: bf16 operands (set_numerics)
+    bf16_t* wpk = nullptr;      // bf16 mode: the direct kernel's weight images, at the offsets of `params` (residual convolutions of 32 / 64 / 128 channels)
     int cap_B = 0, cap_T = 0;
     hipStream_t stream = nullptr;
     std::string last_error;
@@ -233,7 +348,41 @@ public:
 
     int ch(int stage) const { return cfg.c0 >> stage; }   // channels after `stage` upsamples
     long long find(const std::string& n) const { for (auto& t : tensors) if (t.name == n) return t.off; return -1; }
-    bool direct(int C) const { return (C == 32 || C == 64) && C <= cfg.direct_max; }
+    bool direct(int C) const { return (numerics ? hg_direct_bf16_channels(C) : (C == 32 || C == 64)) && C <= cfg.direct_max; }
+
+    // bf16 mode: (re)build the direct kernel's image of one tensor, if it is a residual convolution of a channel count the kernel is built for
+    void pack_tensor(const Tensor& t) {
+        if (t.name.compare(0, 10, "resblocks.") != 0 || t.name.size() < 2 || t.name.compare(t.name.size() - 2, 2, ".w") != 0) return;
+        for (int s = 0; s < cfg.n_up; ++s) {
+            const int C = ch(s + 1);
+            if (!hg_direct_bf16_channels(C)) continue;
+            for (int j = 0; j < cfg.n_k; ++j) {
+                const std::string pre = "resblocks." + std::to_string(s * cfg.n_k + j) + ".";
+                if (t.name.compare(0, pre.size(), pre) != 0) continue;
+                const int k = cfg.kernels[j], pieces = C * k * (C / 8);
+                MTTS_LAUNCH(hg_pack_bf16_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), stream, (const float*)(params + t.off), wpk + t.off, C, k);
+                return;
+            }
+        }
+    }
+    // mode 0: fp32, direct_max in {0, 32, 64} — what create built; mode 1: bf16 operands, direct_max in {0, 32, 64, 128}.  Refused before any launch.
+    int set_numerics(int mode, int direct_max) {
+        if (mode != 0 && mode != 1) return err("mtts_hifigan_set_numerics: mode = " + std::to_string(mode) + " (0: fp32, 1: bf16 operands)");
+        const bool ok = direct_max == 0 || direct_max == 32 || direct_max == 64 || (mode == 1 && direct_max == 128);
+        if (!ok) return err("mtts_hifigan_set_numerics: direct_max_channels = " + std::to_string(direct_max) + (mode ? " (bf16 operands: 0, 32, 64 or 128)" : " (fp32: 0, 32 or 64)"));
+        if (mode == 1) {
+            if (!wpk) {
+                for (const Tensor& t : tensors) if (t.off % 8) return err("mtts_hifigan_set_numerics: tensor " + t.name + " is not 16-byte aligned in the bf16 image");
+                DEV_CHECK(mem.alloc(wpk, (size_t)n_params * sizeof(bf16_t)));
+            }
+            numerics = 1;   // (pack_tensor needs no mode; set first so that a failure below leaves a consistent handle)
+            for (const Tensor& t : tensors) pack_tensor(t);
+            DEV_CHECK(hipStreamSynchronize(stream));
+        }
+        numerics = mode; cfg.direct_max = direct_max;
+        gx.bf16 = mode == 1; gx.no_splitk = mode == 1;   // (no split-K: the split factor follows the batch, and an utterance must not)
+        return 0;
+    }
 
     int init(const HifiGanCfg& c, int max_B, int max_T) {
         cfg = c; cap_B = max_B; cap_T = max_T;
@@ -275,6 +424,7 @@ public:
             if (t.name == name) {
                 if (t.numel != numel) return err(std::string("size mismatch for ") + name + ": " + std::to_string(numel) + " floats given, " + std::to_string(t.numel) + " expected");
                 DEV_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+                if (numerics == 1) { pack_tensor(t); DEV_CHECK(hipStreamSynchronize(stream)); }   // a tensor loaded after the mode was set
                 return 0;
             }
         return err(std::string("unknown HiFi-GAN tensor ") + name);
@@ -299,9 +449,17 @@ public:
         const long long n = std::max<long long>((long long)(max_rows + 2 * a.d) * (C / 4), 2LL * a.gp * (C / 4));
         MTTS_LAUNCH(hg_pad_kernel, dim3((unsigned)((n + 255) / 256), 1, (unsigned)B), dim3(256), stream, a);
     }
-    void conv_direct(HgConvArgs a, int B, int max_rows, int len_mult, int C) {
+    void conv_direct(HgConvArgs a, int B, int max_rows, int len_mult, int C, const bf16_t* image = nullptr) {
         a.lens = lens_dev; a.len_mult = len_mult;
         const dim3 grid((unsigned)((max_rows + kHgTileRows - 1) / kHgTileRows), 1, (unsigned)B);
+        if (numerics == 1) {
+            HgConvBf16Args p;
+            p.a = a; p.wpk = image ? image : wpk + (a.w - params);   // (a.w names the tensor: its image sits at the same offset)
+            if (C == 128) MTTS_LAUNCH(hg_conv_direct_bf16_kernel<128>, grid, dim3(256), stream, p);
+            else if (C == 64) MTTS_LAUNCH(hg_conv_direct_bf16_kernel<64>, grid, dim3(256), stream, p);
+            else MTTS_LAUNCH(hg_conv_direct_bf16_kernel<32>, grid, dim3(256), stream, p);
+            return;
+        }
         if (C == 64) MTTS_LAUNCH(hg_conv_direct_kernel<64>, grid, dim3(256), stream, a);
         else MTTS_LAUNCH(hg_conv_direct_kernel<32>, grid, dim3(256), stream, a);
     }
@@ -411,6 +569,78 @@ public:
                     (const float*)at(b_pad), b_pad.gs, (const float*)(params + find("conv_post.w")), (const float*)(params + find("conv_post.b")),
                     wav, wav_gs, cl, 7 * cl);
         return 0;
+    }
+
+    // Kernel-level entry (mtts_hifigan_conv_bf16): ONE convolution of the bf16 mode on host arrays, without the network around it.
+    //   out / mrf = epilogue(bias + conv(k, dilation d, zero pad d (k-1)/2)(bf16(leaky_relu(x, in_slope))) with bf16(w)), modes as HgConvArgs.
+    // x, res, out, mrf: [B][T_max][C]; w: [C][k][C]; rows >= lens[b] of out / mrf are left as the caller filled them.
+    // route 0: hg_conv_direct_bf16_kernel; route 1: the GEMM route of the same convolution (hg_pad_kernel, the bf16 GEMM family through
+    // this handle's GemmCtx, accumulate epilogue for the residual, the pad pass's fold for the MRF sum).
+    int conv_bf16_host(int route, int C, int k, int d, int B, int T_max, const int* lens_host, const float* x, const float* w, const float* bias,
+                       float in_slope, int mode, const float* res, float* mrf, float inv_nk, int mrf_init, float* out) {
+        const std::string e = "mtts_hifigan_conv_bf16: ";
+        if (route != 0 && route != 1) return err(e + "route = " + std::to_string(route) + " (0: direct kernel, 1: GEMM route)");
+        if (!hg_direct_bf16_channels(C)) return err(e + "C = " + std::to_string(C) + " (32, 64 or 128)");
+        if (k < 1 || !(k & 1) || k > kHgMaxResKernel) return err(e + "k = " + std::to_string(k) + " (odd, <= " + std::to_string(kHgMaxResKernel) + ")");
+        if (d < 1 || d > kHgMaxDilation) return err(e + "d = " + std::to_string(d) + " (1.." + std::to_string(kHgMaxDilation) + ")");
+        if (mode < 0 || mode > 2) return err(e + "mode = " + std::to_string(mode) + " (0, 1 or 2)");
+        if (B < 1 || B > cap_B) return err(e + "B = " + std::to_string(B) + " exceeds max_B = " + std::to_string(cap_B));
+        if (T_max < 1 || !lens_host || !x || !w || !bias) return err(e + "NULL argument or T_max < 1");
+        for (int b = 0; b < B; ++b)
+            if (lens_host[b] < 1 || lens_host[b] > T_max) return err(e + "lens[" + std::to_string(b) + "] = " + std::to_string(lens_host[b]) + " out of range (1..T_max)");
+        if ((mode == 0 || mode == 1) && !out) return err(e + "out is NULL");
+        if (mode >= 1 && !res) return err(e + "res is NULL");
+        if (mode == 2 && !mrf) return err(e + "mrf is NULL");
+        const int p2 = (k - 1) / 2, hp = d * p2;
+        const long long gs = (long long)T_max * C, pgs = (long long)(T_max + 2 * hp + 8) * C, nw = (long long)C * k * C;
+        const size_t bytes = (size_t)gs * B * sizeof(float);
+        float *dx = nullptr, *dres = nullptr, *dout = nullptr, *dmrf = nullptr, *dpad = nullptr, *dw = nullptr, *db = nullptr;
+        bf16_t* dimg = nullptr;
+        struct Saved { HifiGan& h; int num; bool b, s; ~Saved() { h.numerics = num; h.gx.bf16 = b; h.gx.no_splitk = s; } } saved{*this, numerics, gx.bf16, gx.no_splitk};
+        auto done = [&](int rc) { mem.give_back(dx); mem.give_back(dres); mem.give_back(dout); mem.give_back(dmrf); mem.give_back(dpad); mem.give_back(dw); mem.give_back(db); mem.give_back(dimg); return rc; };
+#define HG_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(err(std::string(#x) + ": " + hipGetErrorString(e_))); } while (0)
+        HG_TRY(hipStreamSynchronize(stream));   // (lens_dev may still be read by an earlier run)
+        HG_TRY(mem.alloc(dx, bytes)); HG_TRY(mem.alloc(dres, bytes)); HG_TRY(mem.alloc(dout, bytes)); HG_TRY(mem.alloc(dmrf, bytes));
+        HG_TRY(mem.alloc(dpad, (size_t)pgs * B * sizeof(float))); HG_TRY(mem.alloc(dw, (size_t)nw * sizeof(float))); HG_TRY(mem.alloc(db, C * sizeof(float)));
+        HG_TRY(mem.alloc(dimg, (size_t)nw * sizeof(bf16_t)));
+        HG_TRY(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
+        HG_TRY(hipMemcpy(dw, w, (size_t)nw * sizeof(float), hipMemcpyHostToDevice));
+        HG_TRY(hipMemcpy(db, bias, C * sizeof(float), hipMemcpyHostToDevice));
+        if (res) HG_TRY(hipMemcpy(dres, res, bytes, hipMemcpyHostToDevice));
+        if (mrf) HG_TRY(hipMemcpy(dmrf, mrf, bytes, hipMemcpyHostToDevice));
+        if (out) HG_TRY(hipMemcpy(dout, out, bytes, hipMemcpyHostToDevice));
+        HG_TRY(hipMemcpy(lens_dev, lens_host, B * sizeof(int), hipMemcpyHostToDevice));
+        numerics = 1; gx.bf16 = true; gx.no_splitk = true;
+        if (route == 0) {
+            MTTS_LAUNCH(hg_pack_bf16_kernel, dim3((unsigned)((nw / 8 + 255) / 256)), dim3(256), stream, (const float*)dw, dimg, C, k);
+            HgConvArgs c;
+            c.x = dx; c.x_gs = gs; c.in_slope = in_slope; c.w = dw; c.bias = db; c.k = k; c.d = d; c.mode = mode;
+            c.res = dres; c.res_gs = gs; c.out = dout; c.out_gs = gs; c.mrf = dmrf; c.mrf_gs = gs; c.inv_nk = inv_nk; c.mrf_init = mrf_init;
+            conv_direct(c, B, T_max, 1, C, dimg);
+        } else {
+            HgPadArgs a;
+            a.x = dx; a.x_gs = gs; a.y = dpad; a.y_gs = pgs; a.d = hp; a.slope = in_slope;
+            pad(a, B, T_max, 1, C);
+            // the residual add is the accumulate epilogue: the valid rows of the target start as res
+            float* acc_to = mode == 1 ? dout : dx;   // (mode 2: x has been consumed by the pad pass)
+            if (mode >= 1)
+                for (int b = 0; b < B; ++b)
+                    HG_TRY(hipMemcpyAsync(acc_to + b * gs, dres + b * gs, (size_t)lens_host[b] * C * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            conv_gemm(dpad, pgs, dw, db, mode == 0 ? dout : acc_to, gs, C, k, d, B, T_max, 1, mode == 0 ? GEMM_LRELU : GEMM_ACCUM);
+            if (mode == 2) {
+                HgPadArgs f;
+                f.x = acc_to; f.x_gs = gs; f.y = dpad; f.y_gs = pgs; f.d = 0; f.slope = 1.f;
+                f.fold = acc_to; f.fold_gs = gs; f.fs = inv_nk; f.fold_init = mrf_init; f.mrf = dmrf; f.mrf_gs = gs;
+                pad(f, B, T_max, 1, C);
+            }
+        }
+        if (gx.error) { const std::string m = std::string("GEMM launcher: ") + gx.error; gx.error = nullptr; return done(err(e + m)); }
+        HG_TRY(hipGetLastError());
+        HG_TRY(hipStreamSynchronize(stream));
+        if (mode <= 1) HG_TRY(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+        else HG_TRY(hipMemcpy(mrf, dmrf, bytes, hipMemcpyDeviceToHost));
+#undef HG_TRY
+        return done(0);
     }
 
     // host entry: mel_host [B][T_max][n_mel] -> wav_host [B][T_max * hop] (samples beyond len * hop are left untouched)

@@ -736,6 +736,14 @@ int mtts_hifigan_infer_device(mtts_hifigan* h, const float* mel_dev, int64_t mel
                               float mel_scale, float* wav_dev) {
     return hifigan_launched(h->v, h->v.run(mel_dev, B, T_max, mel_lens, mel_scale, wav_dev, (long long)T_max * h->v.hop, (long long)mel_utt_stride));
 }
+int mtts_hifigan_set_numerics(mtts_hifigan* h, int mode, int direct_max_channels) {
+    return hifigan_launched(h->v, h->v.set_numerics(mode, direct_max_channels));
+}
+int mtts_hifigan_get_numerics(mtts_hifigan* h) { return h->v.numerics; }
+int mtts_hifigan_conv_bf16(mtts_hifigan* h, int route, int C, int k, int d, int B, int T_max, const int* lens, const float* x, const float* w,
+                           const float* bias, float in_slope, int epilogue, const float* res, float* mrf, float inv_nk, int mrf_init, float* out) {
+    return hifigan_launched(h->v, h->v.conv_bf16_host(route, C, k, d, B, T_max, lens, x, w, bias, in_slope, epilogue, res, mrf, inv_nk, mrf_init, out));
+}
 
 // ---- MOSNet naturalness scores (mosnet.h; reference evaluation/compute_mos.py) ------------------------------------------------
 int mtts_mosnet_create(int n_freq, int max_frames_per_call, int max_utts, int device, mtts_mosnet** out) {

@@ -30,6 +30,10 @@ V3 = {"resblock": "2", "upsample_rates": [8, 8, 4], "upsample_kernel_sizes": [16
 # `direct_max_channels` of a HiFiGAN built without one: 0 (GEMM route everywhere) until both routes have been timed in one session
 # (tools/hifigan_bench.py; README "HiFi-GAN generator").
 DEFAULT_DIRECT_MAX_CHANNELS = 0
+# the same rule for the bf16-operand mode: legs (e) / (f) of tools/hifigan_bench.py were timed in one session, 8.78 against 6.18 ms with
+# spreads of 0.05 ms, so the direct route is the bf16 mode's default
+DEFAULT_DIRECT_MAX_CHANNELS_BF16 = 128
+NUMERICS = {"fp32": 0, "bf16": 1}
 
 
 def _check(config):
@@ -118,12 +122,18 @@ class HiFiGAN:
     """The reference's HiFi-GAN vocoder object with `vocoder.MelGAN`'s duck type: `__call__(mels)` is the reference branch's call,
     `infer(mels, max_wav_value, lengths)` is `vocoder_infer`; mel (B, n_mel, T), natural-log mels as the model makes them."""
 
-    def __init__(self, state_dict=None, config=V1, n_mel=80, max_B=8, max_T=1024, device=0, lib_path=None, direct_max_channels=None):
+    def __init__(self, state_dict=None, config=V1, n_mel=80, max_B=8, max_T=1024, device=0, lib_path=None, direct_max_channels=None,
+                 numerics="fp32"):
         _check(config)
+        if numerics not in NUMERICS:
+            raise MttsError(f"HiFiGAN: numerics {numerics!r} is not one of {sorted(NUMERICS)}")
         self.lib = _lib.load(lib_path)
         self.config, self.n_mel = config, n_mel
         self.max_B, self.max_T = max_B, max_T
         self.device, self.stream, self._wav_dev = device, 0, None
+        requested = direct_max_channels
+        if numerics == "bf16":   # the handle is created in fp32 (the C entry's only mode) and switched below
+            direct_max_channels = 0
         self.direct_max_channels = DEFAULT_DIRECT_MAX_CHANNELS if direct_max_channels is None else int(direct_max_channels)
         rates = [int(r) for r in config["upsample_rates"]]
         kernels = [int(k) for k in config["resblock_kernel_sizes"]]
@@ -142,9 +152,46 @@ class HiFiGAN:
         try:
             for k, v in pack_tensors(sd, config, n_mel).items():
                 self.load(k, v)
+            if numerics != "fp32":
+                self.set_numerics(numerics, requested)
         except Exception:
             self.close()
             raise
+
+    @property
+    def numerics(self):
+        """"fp32" or "bf16": the mode in force (include/mtts.h: mtts_hifigan_set_numerics)."""
+        mode = self.lib.mtts_hifigan_get_numerics(self.h)
+        return next(k for k, v in NUMERICS.items() if v == mode)
+
+    def set_numerics(self, mode, direct_max_channels=None):
+        """mode "fp32" / "bf16" (or 0 / 1); direct_max_channels None: the mode's default.  Takes effect at the next call; tensors loaded
+        later are re-packed by the library."""
+        m = NUMERICS.get(mode, mode)
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+            raise MttsError(f"HiFiGAN.set_numerics: mode {mode!r} is not one of {sorted(NUMERICS)}")
+        if direct_max_channels is None:
+            direct_max_channels = DEFAULT_DIRECT_MAX_CHANNELS_BF16 if m == 1 else DEFAULT_DIRECT_MAX_CHANNELS
+        if self.lib.mtts_hifigan_set_numerics(self.h, int(m), int(direct_max_channels)) != 0:
+            raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
+        self.direct_max_channels = int(direct_max_channels)
+
+    def conv_bf16(self, x, lens, w, bias, k, d, in_slope=1.0, epilogue=0, res=None, mrf=None, inv_nk=1.0, mrf_init=0, out=None, route=0):
+        """Kernel-level entry (mtts_hifigan_conv_bf16): one convolution of the bf16 mode on host arrays x [B][T][C], w [C][k][C].
+        Returns `out` (epilogues 0, 1) or `mrf` (epilogue 2), which must be C-contiguous float32 arrays and are written in place."""
+        x = np.ascontiguousarray(x, np.float32)
+        B, T, Cc = x.shape
+        lens = np.ascontiguousarray(lens, np.int32)
+        w, bias = np.ascontiguousarray(w, np.float32), np.ascontiguousarray(bias, np.float32)
+        assert w.shape == (Cc, k, Cc) and bias.shape == (Cc,) and lens.shape == (B,)
+        res = None if res is None else np.ascontiguousarray(res, np.float32)
+        for a in (out, mrf):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == x.shape)
+        P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        if self.lib.mtts_hifigan_conv_bf16(self.h, route, Cc, k, d, B, T, P(lens), P(x), P(w), P(bias), C.c_float(in_slope), epilogue, P(res),
+                                           P(mrf), C.c_float(inv_nk), mrf_init, P(out)) != 0:
+            raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
+        return mrf if epilogue == 2 else out
 
     def load(self, name, array):
         a = np.ascontiguousarray(array, np.float32)
