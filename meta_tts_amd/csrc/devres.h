@@ -1,7 +1,8 @@
 // What a handle owns on the device, once: the check macro of every host-side runtime call, the allocator that remembers what it
 // handed out (DevHeap), the grow-on-demand buffer on top of it (DevBuf / grow), and a side stream with its events (Lane).
 //
-// Every handle class (Engine, Vocoder, DVector, MelFront and what builds on it) holds ONE DevHeap and asks it for device memory,
+// Every handle class (Engine, WaveGen — the base of Vocoder and HifiGan, wavegen.h —, DVector, MosNet, MelFront and what builds on it;
+// the networks' weights sit in a ParamTable, params.h, allocated from it) holds ONE DevHeap and asks it for device memory,
 // pinned host memory and single-purpose events; nothing else in this directory calls the runtime's allocation, stream-creation or
 // event-creation entry points.  The heap frees whatever is left when it is told to (release_all) and when it dies, so a create that
 // fails half way, a later reservation that fails, and destroy all end in the same place and free each block exactly once.  All of it

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "gemm.h"
+#include "params.h"
 #include "rowops.h"
 #include "tangent.h"
 
@@ -219,10 +220,7 @@ public:
     hipStream_t stream = nullptr;
     std::string last_error;
     GemmCtx gx;
-    struct Tensor { std::string name; long long off, numel; };
-    std::vector<Tensor> tensors;
-    float* params = nullptr;
-    long long n_params = 0;
+    ParamTable tab;   // grads / adam_m / adam_v mirror its block: the same offsets
     // derived images, rebuilt by load(): transposed recurrent / head weights and the summed biases
     float *whhT = nullptr, *linT = nullptr, *bsum = nullptr;
     float *mels = nullptr, *xp = nullptr, *hseq[2] = {nullptr, nullptr}, *hlast = nullptr, *part = nullptr, *out = nullptr;
@@ -239,7 +237,8 @@ public:
     DevHeap mem;   // every device block of this handle, the scoring workspace included (devres.h)
     int err(const std::string& s) { last_error = s; return -1; }
     void set_error(const std::string& s) { err(s); }
-    long long find(const std::string& n) const { for (auto& t : tensors) if (t.name == n) return t.off; return -1; }
+    long long find(const std::string& n) const { return tab.find(n); }
+    const float* P(const std::string& n) const { return tab.ptr(n); }
     int in_dim(int l) const { return l == 0 ? n_mels : H; }
 
     int init(int n_mels_, int hidden, int layers_, int emb, int max_partials, int frames, int max_utts) {
@@ -249,15 +248,13 @@ public:
             set_error("unsupported d-vector configuration (n_mels % 4, hidden % 64 <= 1024, emb <= 256)");
             return -1;
         }
-        auto add = [&](const std::string& n, long long numel) { tensors.push_back(Tensor{n, n_params, numel}); n_params += (numel + 3) & ~3LL; };
         for (int l = 0; l < layers; ++l) {
             const std::string s = std::to_string(l);
-            add("lstm.weight_ih_l" + s, 4LL * H * in_dim(l)); add("lstm.weight_hh_l" + s, 4LL * H * H);
-            add("lstm.bias_ih_l" + s, 4LL * H); add("lstm.bias_hh_l" + s, 4LL * H);
+            tab.add("lstm.weight_ih_l" + s, 4LL * H * in_dim(l)); tab.add("lstm.weight_hh_l" + s, 4LL * H * H);
+            tab.add("lstm.bias_ih_l" + s, 4LL * H); tab.add("lstm.bias_hh_l" + s, 4LL * H);
         }
-        add("linear.weight", (long long)E * H); add("linear.bias", E);
-        DEV_CHECK(mem.alloc(params, (size_t)n_params * sizeof(float)));
-        DEV_CHECK(hipMemset(params, 0, (size_t)n_params * sizeof(float)));
+        tab.add("linear.weight", (long long)E * H); tab.add("linear.bias", E);
+        DEV_CHECK(tab.alloc(mem));
         DEV_CHECK(mem.alloc(whhT, (size_t)layers * 4 * H * H * sizeof(float)));
         DEV_CHECK(mem.alloc(linT, (size_t)E * H * sizeof(float)));
         DEV_CHECK(mem.alloc(bsum, (size_t)layers * 4 * H * sizeof(float)));
@@ -289,7 +286,7 @@ public:
         DEV_CHECK(mem.alloc(dz, ((size_t)cap_N * E + 64) * sizeof(float)));
         DEV_CHECK(mem.alloc(dh_last, (size_t)cap_N * H * sizeof(float)));
         DEV_CHECK(mem.alloc(dout, (size_t)cap_B * E * sizeof(float)));
-        for (float** p : {&grads, &adam_m, &adam_v}) { DEV_CHECK(mem.alloc(*p, (size_t)n_params * sizeof(float))); DEV_CHECK(hipMemset(*p, 0, (size_t)n_params * sizeof(float))); }
+        for (float** p : {&grads, &adam_m, &adam_v}) { DEV_CHECK(mem.alloc(*p, (size_t)tab.n_params * sizeof(float))); DEV_CHECK(hipMemset(*p, 0, (size_t)tab.n_params * sizeof(float))); }
         DEV_CHECK(mem.alloc(ones4, (rows * 4 + 64) * sizeof(float)));
         MTTS_LAUNCH(dv_fill_kernel, dim3(256), dim3(256), stream, ones4, 1.f, (long long)(rows * 4));
         DEV_CHECK(mem.alloc(sq_partial, 512 * sizeof(float)));
@@ -299,26 +296,20 @@ public:
         return 0;
     }
     int load(const char* name, const float* host, long long numel) {
-        for (auto& t : tensors)
-            if (t.name == name) {
-                if (t.numel != numel) { set_error(std::string("size mismatch for ") + name); return -1; }
-                DEV_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-                dirty = true;
-                return 0;
-            }
-        set_error(std::string("unknown d-vector tensor ") + name);
-        return -1;
+        if (!tab.load(name, host, numel, "d-vector", last_error)) return -1;
+        dirty = true;
+        return 0;
     }
     // transposed images + summed biases, rebuilt on the device whenever the weights changed (load / adam_step)
     int refresh() {
         for (int l = 0; l < layers; ++l) {
             const std::string s = std::to_string(l);
-            MTTS_LAUNCH(dv_transpose_kernel, dim3(512), dim3(256), stream, (const float*)(params + find("lstm.weight_hh_l" + s)),
+            MTTS_LAUNCH(dv_transpose_kernel, dim3(512), dim3(256), stream, P("lstm.weight_hh_l" + s),
                         whhT + (long long)l * 4 * H * H, 4 * H, H);
-            MTTS_LAUNCH(dv_add_kernel, dim3(8), dim3(256), stream, (const float*)(params + find("lstm.bias_ih_l" + s)),
-                        (const float*)(params + find("lstm.bias_hh_l" + s)), bsum + (long long)l * 4 * H, 4 * H);
+            MTTS_LAUNCH(dv_add_kernel, dim3(8), dim3(256), stream, P("lstm.bias_ih_l" + s),
+                        P("lstm.bias_hh_l" + s), bsum + (long long)l * 4 * H, 4 * H);
         }
-        MTTS_LAUNCH(dv_transpose_kernel, dim3(256), dim3(256), stream, (const float*)(params + find("linear.weight")), linT, E, H);
+        MTTS_LAUNCH(dv_transpose_kernel, dim3(256), dim3(256), stream, P("linear.weight"), linT, E, H);
         DEV_CHECK(hipGetLastError());
         dirty = false;
         return 0;
@@ -359,7 +350,7 @@ public:
             const std::string s = std::to_string(l);
             GemmArgs g;
             g.A = x; g.lda = in_dim(l);
-            g.B = params + find("lstm.weight_ih_l" + s); g.ldb = in_dim(l);
+            g.B = P("lstm.weight_ih_l" + s); g.ldb = in_dim(l);
             g.C = xp; g.ldc = 4 * H;
             g.M = (int)rows; g.N = 4 * H; g.K = in_dim(l);
             g.bias = bsum + (long long)l * 4 * H;
@@ -371,7 +362,7 @@ public:
             x = hs;
         }
         MTTS_LAUNCH(dvec_head_kernel, dim3((unsigned)N), dim3((unsigned)((E + 63) & ~63)), stream, (const float*)hlast, (const float*)linT,
-                    (const float*)(params + find("linear.bias")), part, H, E, train ? eraw : (float*)nullptr);
+                    P("linear.bias"), part, H, E, train ? eraw : (float*)nullptr);
         if (train) { last_N = N; last_B = B; have_forward = true; }
         MTTS_LAUNCH(dvec_utterance_kernel, dim3((unsigned)B), dim3((unsigned)((E + 63) & ~63)), stream, (const float*)part, (const int*)off_dev, out, E);
         if (gx.error) { set_error(std::string("GEMM launcher: ") + gx.error); gx.error = nullptr; return -1; }
@@ -396,17 +387,17 @@ public:
         const int N = last_N, B = last_B;
         const long long rows = (long long)N * T;
         const unsigned eb = (unsigned)((E + 63) & ~63);
-        DEV_CHECK(hipMemsetAsync(grads, 0, (size_t)n_params * sizeof(float), stream));
+        DEV_CHECK(hipMemsetAsync(grads, 0, (size_t)tab.n_params * sizeof(float), stream));
         DEV_CHECK(hipMemcpyAsync(dout, dout_host, (size_t)B * E * sizeof(float), hipMemcpyHostToDevice, stream));
         MTTS_LAUNCH(dvec_utterance_bwd_kernel, dim3((unsigned)B), dim3(eb), stream, (const float*)part, (const int*)off_dev, (const float*)dout, dpart, E);
         MTTS_LAUNCH(dvec_head_bwd_kernel, dim3((unsigned)N), dim3(eb), stream, (const float*)eraw, (const float*)dpart,
-                    (const float*)(params + find("linear.weight")), dz, dh_last, H, E);
+                    P("linear.weight"), dz, dh_last, H, E);
         wgrad(dz, E, hlast, H, N, grads + find("linear.weight"), grads + find("linear.bias"));
         const float* dh_ext = nullptr;
         for (int l = layers - 1; l >= 0; --l) {
             const std::string s = std::to_string(l);
             MTTS_LAUNCH(lstm_bptt_kernel, dim3((unsigned)N), dim3((unsigned)H), stream, (const float*)gates[l], (const float*)cseq[l], dh_ext,
-                        (const float*)(l == layers - 1 ? dh_last : nullptr), (const float*)(params + find("lstm.weight_hh_l" + s)), dgates, T, H);
+                        (const float*)(l == layers - 1 ? dh_last : nullptr), P("lstm.weight_hh_l" + s), dgates, T, H);
             const float* x = l == 0 ? mels : hkeep[l - 1];
             wgrad(dgates, 4 * H, x, in_dim(l), rows, grads + find("lstm.weight_ih_l" + s), grads + find("lstm.bias_ih_l" + s));
             wgrad(dgates, 4 * H, hprev[l], H, rows, grads + find("lstm.weight_hh_l" + s), nullptr);
@@ -414,7 +405,7 @@ public:
             if (l > 0) {   // gradient reaching the layer below: dx = dgates W_ih  ([rows][4H] x [4H][H])
                 float* dx = dxbuf[l & 1];
                 GemmArgs g;
-                g.A = dgates; g.lda = 4 * H; g.B = params + find("lstm.weight_ih_l" + s); g.ldb = H; g.C = dx; g.ldc = H;
+                g.A = dgates; g.lda = 4 * H; g.B = P("lstm.weight_ih_l" + s); g.ldb = H; g.C = dx; g.ldc = H;
                 g.M = (int)rows; g.N = H; g.K = 4 * H;
                 gemm_launch(gx, GEMM_NN, g, (int)rows, H, 1, stream, 0, 2.0 * rows * 4.0 * H * H, 0);
                 dh_ext = dx;
@@ -426,7 +417,7 @@ public:
     }
     // device scalar: sum of squares of the parameter gradients (a term of the joint clip_grad_norm_, main.py:61)
     const float* grad_sumsq() {
-        launch_sumsq_partial(grads, n_params / 4, sq_partial, 64, stream);
+        launch_sumsq_partial(grads, tab.n_params / 4, sq_partial, 64, stream);
         MTTS_LAUNCH(dv_sum_partials_kernel, dim3(1), dim3(64), stream, (const float*)sq_partial, 64, sq_out);
         return sq_out;
     }
@@ -435,38 +426,30 @@ public:
         if (!train_ready) { set_error("mtts_dvector_enable_training first"); return -1; }
         ++adam_steps;
         const float bc1 = 1.f - (float)std::pow((double)b1, (double)adam_steps), bc2 = 1.f - (float)std::pow((double)b2, (double)adam_steps);
-        launch_adam_clip(params, grads, adam_m, adam_v, n_params / 4, norm_dev, norm_dev ? max_norm : 0.f, lr, b1, b2, eps, bc1, bc2, weight_decay, stream, 256);
+        launch_adam_clip(tab.data, grads, adam_m, adam_v, tab.n_params / 4, norm_dev, norm_dev ? max_norm : 0.f, lr, b1, b2, eps, bc1, bc2, weight_decay, stream, 256);
         DEV_CHECK(hipGetLastError());
         dirty = true;
         return 0;
     }
     // which: 0 parameter, 1 gradient, 2 Adam m, 3 Adam v
-    float* state_ptr(int which) { return which == 0 ? params : which == 1 ? grads : which == 2 ? adam_m : which == 3 ? adam_v : nullptr; }
+    float* state_ptr(int which) { return which == 0 ? tab.data : which == 1 ? grads : which == 2 ? adam_m : which == 3 ? adam_v : nullptr; }
     int export_state(const char* name, int which, float* out_host, long long numel) {
         float* base = state_ptr(which);
-        if (!base) { set_error("state not available (enable training first)"); return -1; }
-        for (auto& t : tensors)
-            if (t.name == name) {
-                if (t.numel != numel) { set_error(std::string("size mismatch for ") + name); return -1; }
-                DEV_CHECK(hipStreamSynchronize(stream));
-                DEV_CHECK(hipMemcpy(out_host, base + t.off, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-                return 0;
-            }
-        set_error(std::string("unknown d-vector tensor ") + name);
-        return -1;
+        if (!base) return err("state not available (enable training first)");
+        const ParamTable::Tensor* t = tab.check(name, numel, "d-vector", last_error);
+        if (!t) return -1;
+        DEV_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpy(out_host, base + t->off, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
     }
     int import_state(const char* name, int which, const float* host, long long numel) {
         if (which == 0) return load(name, host, numel);
         float* base = state_ptr(which);
-        if (!base) { set_error("state not available (enable training first)"); return -1; }
-        for (auto& t : tensors)
-            if (t.name == name) {
-                if (t.numel != numel) { set_error(std::string("size mismatch for ") + name); return -1; }
-                DEV_CHECK(hipMemcpy(base + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-                return 0;
-            }
-        set_error(std::string("unknown d-vector tensor ") + name);
-        return -1;
+        if (!base) return err("state not available (enable training first)");
+        const ParamTable::Tensor* t = tab.check(name, numel, "d-vector", last_error);
+        if (!t) return -1;
+        DEV_CHECK(hipMemcpy(base + t->off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
     }
 };
 

@@ -320,34 +320,16 @@ __global__ __launch_bounds__(256) void hg_conv_direct_bf16_kernel(HgConvBf16Args
 }
 constexpr bool hg_direct_bf16_channels(int C) { return C == 32 || C == 64 || C == 128; }   // (C = 256 is not built: 94 KB of activations)
 
-class HifiGan {
+class HifiGan : public WaveGen {
 public:
     HifiGanCfg cfg;
     int numerics = 0;           // 0: fp32 (the default); 1: bf16 operands (set_numerics)
-    bf16_t* wpk = nullptr;      // bf16 mode: the direct kernel's weight images, at the offsets of `params` (residual convolutions of 32 / 64 / 128 channels)
-    int cap_B = 0, cap_T = 0;
-    hipStream_t stream = nullptr;
-    std::string last_error;
-
-    struct Tensor { std::string name; long long off, numel; };
-    std::vector<Tensor> tensors;
-    float* params = nullptr;
-    long long n_params = 0;
-    float* arena = nullptr;
-    int* lens_dev = nullptr;
-    float* mel_dev = nullptr;
-    float* wav_dev = nullptr;
-    int hop = 1;
-    struct Buf { long long off, gs; };
-    GemmCtx gx;
+    bf16_t* wpk = nullptr;      // bf16 mode: the direct kernel's weight images, at the offsets of the tensor table (residual convolutions of 32 / 64 / 128 channels)
     Buf b_up, b_xj, b_pad, b_h, b_mrf;   // stage input, running x of a block, padded operand, t of a pair, MRF sum
+    using Tensor = ParamTable::Tensor;
 
-    DevHeap mem;
-    int err(const std::string& s) { last_error = s; return -1; }
-    void set_error(const std::string& s) { err(s); }
-
+    HifiGan() { kind = "HiFi-GAN"; act_slope = 0.1f; }
     int ch(int stage) const { return cfg.c0 >> stage; }   // channels after `stage` upsamples
-    long long find(const std::string& n) const { for (auto& t : tensors) if (t.name == n) return t.off; return -1; }
     bool direct(int C) const { return (numerics ? hg_direct_bf16_channels(C) : (C == 32 || C == 64)) && C <= cfg.direct_max; }
 
     // bf16 mode: (re)build the direct kernel's image of one tensor, if it is a residual convolution of a channel count the kernel is built for
@@ -360,7 +342,7 @@ public:
                 const std::string pre = "resblocks." + std::to_string(s * cfg.n_k + j) + ".";
                 if (t.name.compare(0, pre.size(), pre) != 0) continue;
                 const int k = cfg.kernels[j], pieces = C * k * (C / 8);
-                MTTS_LAUNCH(hg_pack_bf16_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), stream, (const float*)(params + t.off), wpk + t.off, C, k);
+                MTTS_LAUNCH(hg_pack_bf16_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), stream, (const float*)(tab.data + t.off), wpk + t.off, C, k);
                 return;
             }
         }
@@ -372,11 +354,11 @@ public:
         if (!ok) return err("mtts_hifigan_set_numerics: direct_max_channels = " + std::to_string(direct_max) + (mode ? " (bf16 operands: 0, 32, 64 or 128)" : " (fp32: 0, 32 or 64)"));
         if (mode == 1) {
             if (!wpk) {
-                for (const Tensor& t : tensors) if (t.off % 8) return err("mtts_hifigan_set_numerics: tensor " + t.name + " is not 16-byte aligned in the bf16 image");
-                DEV_CHECK(mem.alloc(wpk, (size_t)n_params * sizeof(bf16_t)));
+                for (const Tensor& t : tab.tensors) if (t.off % 8) return err("mtts_hifigan_set_numerics: tensor " + t.name + " is not 16-byte aligned in the bf16 image");
+                DEV_CHECK(mem.alloc(wpk, (size_t)tab.n_params * sizeof(bf16_t)));
             }
             numerics = 1;   // (pack_tensor needs no mode; set first so that a failure below leaves a consistent handle)
-            for (const Tensor& t : tensors) pack_tensor(t);
+            for (const Tensor& t : tab.tensors) pack_tensor(t);
             DEV_CHECK(hipStreamSynchronize(stream));
         }
         numerics = mode; cfg.direct_max = direct_max;
@@ -390,60 +372,33 @@ public:
         if (!why.empty()) return err("mtts_hifigan_create: " + why);
         hop = 1;
         for (int s = 0; s < cfg.n_up; ++s) hop *= cfg.rates[s];
-        auto add = [&](const std::string& n, long long numel) { tensors.push_back(Tensor{n, n_params, numel}); n_params += (numel + 3) & ~3LL; };
-        add("conv_pre.w", (long long)cfg.c0 * 7 * cfg.n_mel); add("conv_pre.b", cfg.c0);
+        tab.add("conv_pre.w", (long long)cfg.c0 * 7 * cfg.n_mel); tab.add("conv_pre.b", cfg.c0);
         for (int s = 0; s < cfg.n_up; ++s) {
             const int cin = ch(s), cout = ch(s + 1), r = cfg.rates[s];
-            add("ups." + std::to_string(s) + ".w", (long long)r * cout * 2 * cin);   // [phase][C_out][x[q-1] | x[q]]
-            add("ups." + std::to_string(s) + ".b", cout);
+            tab.add("ups." + std::to_string(s) + ".w", (long long)r * cout * 2 * cin);   // [phase][C_out][x[q-1] | x[q]]
+            tab.add("ups." + std::to_string(s) + ".b", cout);
             for (int j = 0; j < cfg.n_k; ++j)
                 for (int m = 0; m < cfg.n_dil; ++m)
                     for (int half = 1; half <= 2; ++half) {
                         const std::string p = "resblocks." + std::to_string(s * cfg.n_k + j) + ".convs" + std::to_string(half) + "." + std::to_string(m);
-                        add(p + ".w", (long long)cout * cfg.kernels[j] * cout); add(p + ".b", cout);   // [C][k][C]
+                        tab.add(p + ".w", (long long)cout * cfg.kernels[j] * cout); tab.add(p + ".b", cout);   // [C][k][C]
                     }
         }
-        add("conv_post.w", 7LL * ch(cfg.n_up)); add("conv_post.b", 1);
-        if (gx.alloc_workspace(mem)) return err("out of device memory (split-K workspace)");
-        DEV_CHECK(mem.alloc(params, (size_t)n_params * sizeof(float)));
-        DEV_CHECK(hipMemset(params, 0, (size_t)n_params * sizeof(float)));
+        tab.add("conv_post.w", 7LL * ch(cfg.n_up)); tab.add("conv_post.b", 1);
         long long worst = (long long)(cap_T + 32) * std::max(cfg.n_mel, cfg.c0);
         long long mult = 1;
         for (int s = 0; s < cfg.n_up; ++s) { mult *= cfg.rates[s]; worst = std::max(worst, ((long long)cap_T * mult + kHgMaxHalo + 32) * ch(s + 1)); }
-        const long long per = (worst + 63) & ~63LL;
-        DEV_CHECK(mem.alloc(arena, (size_t)per * cap_B * 5 * sizeof(float)));
-        DEV_CHECK(hipMemset(arena, 0, (size_t)per * cap_B * 5 * sizeof(float)));
-        b_up = Buf{0, per}; b_xj = Buf{per * cap_B, per}; b_pad = Buf{2 * per * cap_B, per}; b_h = Buf{3 * per * cap_B, per}; b_mrf = Buf{4 * per * cap_B, per};
-        DEV_CHECK(mem.alloc(lens_dev, cap_B * sizeof(int)));
-        DEV_CHECK(mem.alloc(mel_dev, (size_t)cap_B * cap_T * cfg.n_mel * sizeof(float)));
-        DEV_CHECK(mem.alloc(wav_dev, (size_t)cap_B * cap_T * hop * sizeof(float)));
+        if (alloc_common(5, (worst + 63) & ~63LL, cfg.n_mel) != 0) return -1;
+        b_up = buf(0); b_xj = buf(1); b_pad = buf(2); b_h = buf(3); b_mrf = buf(4);
         return 0;
     }
     int load(const char* name, const float* host, long long numel) {
-        for (auto& t : tensors)
-            if (t.name == name) {
-                if (t.numel != numel) return err(std::string("size mismatch for ") + name + ": " + std::to_string(numel) + " floats given, " + std::to_string(t.numel) + " expected");
-                DEV_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-                if (numerics == 1) { pack_tensor(t); DEV_CHECK(hipStreamSynchronize(stream)); }   // a tensor loaded after the mode was set
-                return 0;
-            }
-        return err(std::string("unknown HiFi-GAN tensor ") + name);
+        const Tensor* t = tab.load(name, host, numel, kind, last_error);
+        if (!t) return -1;
+        if (numerics == 1) { pack_tensor(*t); DEV_CHECK(hipStreamSynchronize(stream)); }   // a tensor loaded after the mode was set
+        return 0;
     }
 
-    float* at(const Buf& b) const { return arena + b.off; }
-    // one grouped GEMM: C[z][M_z, N] (+)= A[z][M_z, K] * W[N, K]^T + bias; M_z = lens[z] * len_mult
-    void gemm(const float* A, long long a_gs, int lda, const float* W, int ldb, int K, const float* bias, float* C, long long c_gs,
-              int ldc, int N, int B, int max_rows, int len_mult, int flags, int a_tap_k = 0, int a_tap_rows = 0) {
-        GemmArgs g;
-        if (a_tap_k > 0) { g.a_tap_k = a_tap_k; g.a_tap_rows = a_tap_rows; }
-        g.A = A; g.a_gs = a_gs; g.lda = lda;
-        g.B = W; g.b_gs = 0; g.ldb = ldb;
-        g.C = C; g.c_gs = c_gs; g.ldc = ldc;
-        g.M = max_rows; g.N = N; g.K = K;
-        g.dimptr = lens_dev; g.dim_stride = 1; g.dim_sel = 0; g.dim_mult = len_mult;
-        g.bias = bias; g.flags = flags; g.act_slope = 0.1f;
-        gemm_launch(gx, GEMM_NT, g, max_rows, N, B, stream, 0, 2.0 * max_rows * B * (double)N * K, 0);
-    }
     void pad(HgPadArgs a, int B, int max_rows, int len_mult, int C) {
         a.lens = lens_dev; a.len_mult = len_mult; a.C = C;
         const long long n = std::max<long long>((long long)(max_rows + 2 * a.d) * (C / 4), 2LL * a.gp * (C / 4));
@@ -454,7 +409,7 @@ public:
         const dim3 grid((unsigned)((max_rows + kHgTileRows - 1) / kHgTileRows), 1, (unsigned)B);
         if (numerics == 1) {
             HgConvBf16Args p;
-            p.a = a; p.wpk = image ? image : wpk + (a.w - params);   // (a.w names the tensor: its image sits at the same offset)
+            p.a = a; p.wpk = image ? image : wpk + (a.w - tab.data);   // (a.w names the tensor: its image sits at the same offset)
             if (C == 128) MTTS_LAUNCH(hg_conv_direct_bf16_kernel<128>, grid, dim3(256), stream, p);
             else if (C == 64) MTTS_LAUNCH(hg_conv_direct_bf16_kernel<64>, grid, dim3(256), stream, p);
             else MTTS_LAUNCH(hg_conv_direct_bf16_kernel<32>, grid, dim3(256), stream, p);
@@ -462,25 +417,6 @@ public:
         }
         if (C == 64) MTTS_LAUNCH(hg_conv_direct_kernel<64>, grid, dim3(256), stream, a);
         else MTTS_LAUNCH(hg_conv_direct_kernel<32>, grid, dim3(256), stream, a);
-    }
-    // a convolution of k taps, dilation d, over the zero-padded rows at A (row 0 = the first pad row): out (+)= conv + bias
-    void conv_gemm(const float* A, long long a_gs, const float* w, const float* bias, float* out, long long out_gs, int C, int k, int d, int B, int rows,
-                   int mult, int flags) {
-        if (d == 1) gemm(A, a_gs, C, w, k * C, k * C, bias, out, out_gs, C, C, B, rows, mult, flags);
-        else if (C % 32 == 0) gemm(A, a_gs, C, w, k * C, k * C, bias, out, out_gs, C, C, B, rows, mult, flags, C, d);   // k = t * C + c reads row m + t * d
-        else
-            for (int t = 0; t < k; ++t)
-                gemm(A + (long long)t * d * C, a_gs, C, w + (long long)t * C, k * C, C, t == 0 ? bias : nullptr, out, out_gs, C, C, B, rows, mult,
-                     (t ? GEMM_ACCUM : (flags & GEMM_ACCUM)) | (t == k - 1 ? (flags & GEMM_LRELU) : 0));
-    }
-
-    int check_batch(int B, int T_max, const int* lens_host) {
-        if (B < 1 || B > cap_B) return err("HiFi-GAN: B = " + std::to_string(B) + " exceeds max_B = " + std::to_string(cap_B));
-        if (T_max < 4 || T_max > cap_T) return err("HiFi-GAN: T_max = " + std::to_string(T_max) + " out of range (need 4 <= T_max <= max_T = " + std::to_string(cap_T) + ")");
-        for (int b = 0; b < B; ++b)
-            if (lens_host[b] < 4 || lens_host[b] > T_max)
-                return err("HiFi-GAN: mel_lens[" + std::to_string(b) + "] = " + std::to_string(lens_host[b]) + " out of range (need 4 <= len <= T_max = " + std::to_string(T_max) + ")");
-        return 0;
     }
 
     // mel: device pointer [B][T_max][n_mel]; wav: device [B][wav_gs]; mel_gs: floats between utterances of `mel` (0: T_max * n_mel)
@@ -492,7 +428,7 @@ public:
             HgPadArgs p;
             p.x = mel; p.x_gs = mel_gs > 0 ? mel_gs : (long long)T_max * nm; p.xs = mel_scale; p.y = at(b_pad); p.y_gs = b_pad.gs; p.d = 3; p.slope = 1.f;
             pad(p, B, T_max, 1, nm);
-            gemm(at(b_pad), b_pad.gs, nm, params + find("conv_pre.w"), 7 * nm, 7 * nm, params + find("conv_pre.b"), at(b_up), b_up.gs, ch(0), ch(0), B, T_max, 1, 0);
+            gemm(at(b_pad), b_pad.gs, nm, P("conv_pre.w"), 7 * nm, 7 * nm, P("conv_pre.b"), at(b_up), b_up.gs, ch(0), ch(0), B, T_max, 1, 0);
         }
         // what the next stage reads: xs * src (+ add)
         HgPadArgs next;
@@ -500,21 +436,13 @@ public:
         int mult = 1;
         const float inv_nk = 1.f / (float)cfg.n_k;
         for (int s = 0; s < cfg.n_up; ++s) {
-            const int cin = ch(s), C = ch(s + 1), r = cfg.rates[s], p = r / 2;
+            const int cin = ch(s), C = ch(s + 1), r = cfg.rates[s];
             const int rows_in = T_max * mult;
             {   // LeakyReLU + one zero row each side, then r polyphase GEMMs into the stage input
                 HgPadArgs a = next;
                 a.y = at(b_pad); a.y_gs = b_pad.gs; a.d = 1; a.slope = 0.1f;
                 pad(a, B, rows_in, mult, cin);
-                const float* W = params + find("ups." + std::to_string(s) + ".w");
-                const float* bias = params + find("ups." + std::to_string(s) + ".b");
-                gemm_batch_begin(gx);
-                for (int ph = 0; ph < r; ++ph) {
-                    const int q0 = ph >= p ? 0 : 1;
-                    gemm(at(b_pad) + (long long)q0 * cin, b_pad.gs, cin, W + (long long)ph * C * 2 * cin, 2 * cin, 2 * cin, bias,
-                         at(b_up) + (long long)(q0 * r + ph - p) * C, b_up.gs, r * C, C, B, rows_in, mult, 0);
-                }
-                gemm_batch_end(gx, stream);
+                upsample_polyphase(b_pad, P("ups." + std::to_string(s) + ".w"), P("ups." + std::to_string(s) + ".b"), b_up, cin, C, r, B, rows_in, mult);
             }
             mult *= r;
             const int rows = T_max * mult;
@@ -524,10 +452,10 @@ public:
                 for (int m = 0; m < cfg.n_dil; ++m) {
                     const int d = cfg.dil[j][m];
                     const std::string pre = "resblocks." + std::to_string(s * cfg.n_k + j);
-                    const float* w1 = params + find(pre + ".convs1." + std::to_string(m) + ".w");
-                    const float* b1 = params + find(pre + ".convs1." + std::to_string(m) + ".b");
-                    const float* w2 = params + find(pre + ".convs2." + std::to_string(m) + ".w");
-                    const float* b2 = params + find(pre + ".convs2." + std::to_string(m) + ".b");
+                    const float* w1 = P(pre + ".convs1." + std::to_string(m) + ".w");
+                    const float* b1 = P(pre + ".convs1." + std::to_string(m) + ".b");
+                    const float* w2 = P(pre + ".convs2." + std::to_string(m) + ".w");
+                    const float* b2 = P(pre + ".convs2." + std::to_string(m) + ".b");
                     const Buf& src = m == 0 ? b_up : b_xj;
                     if (dir) {
                         HgConvArgs c1;
@@ -566,7 +494,7 @@ public:
         next.y = at(b_pad); next.y_gs = b_pad.gs; next.d = 3; next.slope = 0.01f;
         pad(next, B, rows, mult, cl);
         MTTS_LAUNCH(dot_tanh_kernel, dim3((unsigned)((rows + 3) / 4), 1, (unsigned)B), dim3(256), stream, (const int*)lens_dev, mult,
-                    (const float*)at(b_pad), b_pad.gs, (const float*)(params + find("conv_post.w")), (const float*)(params + find("conv_post.b")),
+                    (const float*)at(b_pad), b_pad.gs, P("conv_post.w"), P("conv_post.b"),
                     wav, wav_gs, cl, 7 * cl);
         return 0;
     }
@@ -641,18 +569,6 @@ public:
         else HG_TRY(hipMemcpy(mrf, dmrf, bytes, hipMemcpyDeviceToHost));
 #undef HG_TRY
         return done(0);
-    }
-
-    // host entry: mel_host [B][T_max][n_mel] -> wav_host [B][T_max * hop] (samples beyond len * hop are left untouched)
-    int infer_host(const float* mel_host, int B, int T_max, const int* lens_host, float mel_scale, float* wav_host) {
-        if (check_batch(B, T_max, lens_host) != 0) return -1;
-        DEV_CHECK(hipMemcpyAsync(mel_dev, mel_host, (size_t)B * T_max * cfg.n_mel * sizeof(float), hipMemcpyHostToDevice, stream));
-        if (run(mel_dev, B, T_max, lens_host, mel_scale, wav_dev, (long long)T_max * hop) != 0) return -1;
-        DEV_CHECK(hipStreamSynchronize(stream));
-        for (int b = 0; b < B; ++b)
-            DEV_CHECK(hipMemcpy(wav_host + (long long)b * T_max * hop, wav_dev + (long long)b * T_max * hop, (size_t)lens_host[b] * hop * sizeof(float),
-                                hipMemcpyDeviceToHost));
-        return 0;
     }
 };
 

@@ -37,6 +37,7 @@
 
 #include "gemm.h"
 #include "melfront.h"
+#include "params.h"
 #include "resample.h"
 
 namespace mtts {
@@ -272,10 +273,7 @@ public:
     hipStream_t stream = nullptr;
     std::string last_error;
 
-    struct Tensor { std::string name; long long off, numel; bool loaded; };
-    std::vector<Tensor> tensors;
-    float* params = nullptr;
-    long long n_params = 0;
+    ParamTable tab;   // (plan_call refuses a call while a tensor has not been loaded)
     float *act0 = nullptr, *act1 = nullptr, *mag_dev = nullptr, *xproj = nullptr, *hseq = nullptr, *dense = nullptr, *fs_dev = nullptr, *us_dev = nullptr;
     MosUtt* utts_dev = nullptr;
     std::vector<MosUtt> h_utts;
@@ -287,7 +285,7 @@ public:
     int err(const std::string& s) { last_error = s; return -1; }
     void set_error(const std::string& s) { err(s); }
     static int chan(int b) { return 16 << b; }
-    const float* P(const std::string& n) const { for (auto& t : tensors) if (t.name == n) return params + t.off; return nullptr; }
+    const float* P(const std::string& n) const { return tab.ptr(n); }
 
     static std::string check_cfg(int n_freq_, int max_frames, int max_utts) {
         if (n_freq_ < 2 || n_freq_ > 4097) return "n_freq must be 2..4097";
@@ -308,21 +306,20 @@ public:
             widest = std::max(widest, (long long)chan(b) * F[b]);
         }
         IN = chan(kMosBlocks - 1) * F[kMosBlocks];
-        auto add = [&](const std::string& n, long long numel) { tensors.push_back(Tensor{n, n_params, numel, false}); n_params += (numel + 3) & ~3LL; };
         for (int l = 0; l < 3 * kMosBlocks; ++l) {
             const int b = l / 3, cout = chan(b), cin = l % 3 ? cout : (b ? chan(b - 1) : 1);
-            add("conv." + std::to_string(l) + ".w", 9LL * cin * cout);   // conv.0: [9][16]; else [9][cin / 8][cout][8]
-            add("conv." + std::to_string(l) + ".b", cout);
+            tab.add("conv." + std::to_string(l) + ".w", 9LL * cin * cout);   // conv.0: [9][16]; else [9][cin / 8][cout][8]
+            tab.add("conv." + std::to_string(l) + ".b", cout);
         }
-        add("blstm.w_ih", 2LL * 4 * kMosH * IN);      // [2][4H][IN]: forward rows, then backward
-        add("blstm.b", 2LL * 4 * kMosH);
-        add("blstm.w_hh", 2LL * 4 * kMosH * kMosH);   // [2][H / 4][4H][4]
-        add("dense.w", 2LL * kMosH * kMosH);          // [128][256]
-        add("dense.b", kMosH);
-        add("frame_score.w", kMosH);
-        add("frame_score.b", 1);
+        tab.add("blstm.w_ih", 2LL * 4 * kMosH * IN);      // [2][4H][IN]: forward rows, then backward
+        tab.add("blstm.b", 2LL * 4 * kMosH);
+        tab.add("blstm.w_hh", 2LL * 4 * kMosH * kMosH);   // [2][H / 4][4H][4]
+        tab.add("dense.w", 2LL * kMosH * kMosH);          // [128][256]
+        tab.add("dense.b", kMosH);
+        tab.add("frame_score.w", kMosH);
+        tab.add("frame_score.b", 1);
         if (gx.alloc_workspace(mem)) return err("out of device memory (split-K workspace)");
-        DEV_CHECK(mem.alloc_zeroed(params, (size_t)n_params * sizeof(float)));
+        DEV_CHECK(tab.alloc(mem));
         const size_t fr = (size_t)cap_frames;
         DEV_CHECK(mem.alloc(act0, fr * (size_t)widest * sizeof(float)));
         DEV_CHECK(mem.alloc(act1, fr * (size_t)widest * sizeof(float)));
@@ -335,21 +332,11 @@ public:
         DEV_CHECK(mem.alloc(utts_dev, (size_t)cap_utts * sizeof(MosUtt)));
         return 0;
     }
-    int load(const char* name, const float* host, long long numel) {
-        if (!name || !host) return err("mtts_mosnet_load: NULL argument");
-        for (auto& t : tensors)
-            if (t.name == name) {
-                if (t.numel != numel) return err(std::string("size mismatch for ") + name + ": " + std::to_string(numel) + " floats given, " + std::to_string(t.numel) + " expected");
-                DEV_CHECK(hipMemcpy(params + t.off, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-                t.loaded = true;
-                return 0;
-            }
-        return err(std::string("unknown MOSNet tensor ") + name);
-    }
+    int load(const char* name, const float* host, long long numel) { return tab.load(name, host, numel, "MOSNet", last_error) ? 0 : -1; }
 
     // what both entries refuse about the frame counts before any launch; fills the utterance table
     int plan_call(const std::string& who, int n_utts, const int* n_frames) {
-        for (auto& t : tensors)
+        for (auto& t : tab.tensors)
             if (!t.loaded) return err(who + "tensor " + t.name + " has not been loaded (mtts_mosnet_load)");
         if (n_utts < 1) return err(who + "n_utts < 1");
         if (n_utts > 65535) return err(who + "more than 65535 utterances in one call");

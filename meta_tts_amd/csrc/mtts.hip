@@ -93,6 +93,26 @@ static WavSource host_f32(const float* wavs) {
     return s;
 }
 
+// What the *_param_info entries of the network handles answer from a tensor table (params.h).
+static int param_info(const ParamTable& t, int i, char* name, int cap, int64_t* numel) {
+    if (!name || !numel || i < 0 || i >= (int)t.tensors.size()) return -1;
+    snprintf(name, cap, "%s", t.tensors[(size_t)i].name.c_str());
+    *numel = t.tensors[(size_t)i].numel;
+    return 0;
+}
+// The entries of the two mel-to-waveform generators (wavegen.h), written once: every compute entry ends in launched().
+template <class H> static void gen_destroy(H* h) {
+    if (!h) return;
+    hipDeviceSynchronize();
+    delete h;
+}
+template <class Gen> static int gen_infer(Gen& v, const float* mel, int B, int T_max, const int* mel_lens, float mel_scale, float* wav) {
+    return v.launched(WaveGen::infer_host(v, mel, B, T_max, mel_lens, mel_scale, wav));
+}
+template <class Gen> static int gen_infer_device(Gen& v, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens, float mel_scale, float* wav_dev) {
+    return v.launched(v.run(mel_dev, B, T_max, mel_lens, mel_scale, wav_dev, (long long)T_max * v.hop, (long long)mel_utt_stride));
+}
+
 extern "C" {
 
 int mtts_create(const mtts_model_cfg* c, int device, int max_tasks, int max_B, int max_S, int max_T, mtts_handle** out) {
@@ -661,28 +681,19 @@ int mtts_vocoder_create(int n_mel, int ngf, int n_res, const int* ratios, int n_
     *out = h;
     return 0;
 }
-void mtts_vocoder_destroy(mtts_vocoder* h) {
-    if (!h) return;
-    hipDeviceSynchronize();
-    delete h;
-}
+void mtts_vocoder_destroy(mtts_vocoder* h) { gen_destroy(h); }
 const char* mtts_vocoder_last_error(mtts_vocoder* h) { return h ? h->v.last_error.c_str() : g_create_error.c_str(); }
 int mtts_vocoder_set_stream(mtts_vocoder* h, void* s) { h->v.stream = (hipStream_t)s; return 0; }
 int mtts_vocoder_hop(mtts_vocoder* h) { return h->v.hop; }
-int mtts_vocoder_param_count(mtts_vocoder* h) { return (int)h->v.tensors.size(); }
-int mtts_vocoder_param_info(mtts_vocoder* h, int i, char* name, int cap, int64_t* numel) {
-    if (i < 0 || i >= (int)h->v.tensors.size()) return -1;
-    snprintf(name, cap, "%s", h->v.tensors[i].name.c_str());
-    *numel = h->v.tensors[i].numel;
-    return 0;
-}
+int mtts_vocoder_param_count(mtts_vocoder* h) { return (int)h->v.tab.tensors.size(); }
+int mtts_vocoder_param_info(mtts_vocoder* h, int i, char* name, int cap, int64_t* numel) { return param_info(h->v.tab, i, name, cap, numel); }
 int mtts_vocoder_load(mtts_vocoder* h, const char* name, const float* data, int64_t numel) { return h->v.load(name, data, numel); }
 int mtts_vocoder_infer(mtts_vocoder* h, const float* mel, int B, int T_max, const int* mel_lens, float mel_scale, float* wav) {
-    return h->v.infer_host(mel, B, T_max, mel_lens, mel_scale, wav);
+    return gen_infer(h->v, mel, B, T_max, mel_lens, mel_scale, wav);
 }
 int mtts_vocoder_infer_device(mtts_vocoder* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
                               float mel_scale, float* wav_dev) {
-    return h->v.run(mel_dev, B, T_max, mel_lens, mel_scale, wav_dev, (long long)T_max * h->v.hop, (long long)mel_utt_stride);
+    return gen_infer_device(h->v, mel_dev, mel_utt_stride, B, T_max, mel_lens, mel_scale, wav_dev);
 }
 
 // ---- HiFi-GAN generator (hifigan.h; reference call site utils/model.py:32-50) -------------------------------------------------
@@ -706,43 +717,27 @@ int mtts_hifigan_create(int n_mel, int initial_channels, const int* rates, int n
     *out = h;
     return 0;
 }
-void mtts_hifigan_destroy(mtts_hifigan* h) {
-    if (!h) return;
-    hipDeviceSynchronize();
-    delete h;
-}
+void mtts_hifigan_destroy(mtts_hifigan* h) { gen_destroy(h); }
 const char* mtts_hifigan_last_error(mtts_hifigan* h) { return h ? h->v.last_error.c_str() : g_create_error.c_str(); }
 int mtts_hifigan_set_stream(mtts_hifigan* h, void* s) { h->v.stream = (hipStream_t)s; return 0; }
 int mtts_hifigan_hop(mtts_hifigan* h) { return h->v.hop; }
-int mtts_hifigan_param_count(mtts_hifigan* h) { return (int)h->v.tensors.size(); }
-int mtts_hifigan_param_info(mtts_hifigan* h, int i, char* name, int cap, int64_t* numel) {
-    if (i < 0 || i >= (int)h->v.tensors.size()) return -1;
-    snprintf(name, cap, "%s", h->v.tensors[i].name.c_str());
-    *numel = h->v.tensors[i].numel;
-    return 0;
-}
+int mtts_hifigan_param_count(mtts_hifigan* h) { return (int)h->v.tab.tensors.size(); }
+int mtts_hifigan_param_info(mtts_hifigan* h, int i, char* name, int cap, int64_t* numel) { return param_info(h->v.tab, i, name, cap, numel); }
 int mtts_hifigan_load(mtts_hifigan* h, const char* name, const float* data, int64_t numel) { return h->v.load(name, data, numel); }
-static int hifigan_launched(HifiGan& v, int rc) {
-    if (rc) return rc;
-    if (v.gx.error) { v.set_error(std::string("GEMM launcher: ") + v.gx.error); v.gx.error = nullptr; return -1; }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { v.set_error(std::string("kernel launch failed: ") + hipGetErrorString(e)); return -1; }
-    return 0;
-}
 int mtts_hifigan_infer(mtts_hifigan* h, const float* mel, int B, int T_max, const int* mel_lens, float mel_scale, float* wav) {
-    return hifigan_launched(h->v, h->v.infer_host(mel, B, T_max, mel_lens, mel_scale, wav));
+    return gen_infer(h->v, mel, B, T_max, mel_lens, mel_scale, wav);
 }
 int mtts_hifigan_infer_device(mtts_hifigan* h, const float* mel_dev, int64_t mel_utt_stride, int B, int T_max, const int* mel_lens,
                               float mel_scale, float* wav_dev) {
-    return hifigan_launched(h->v, h->v.run(mel_dev, B, T_max, mel_lens, mel_scale, wav_dev, (long long)T_max * h->v.hop, (long long)mel_utt_stride));
+    return gen_infer_device(h->v, mel_dev, mel_utt_stride, B, T_max, mel_lens, mel_scale, wav_dev);
 }
 int mtts_hifigan_set_numerics(mtts_hifigan* h, int mode, int direct_max_channels) {
-    return hifigan_launched(h->v, h->v.set_numerics(mode, direct_max_channels));
+    return h->v.launched(h->v.set_numerics(mode, direct_max_channels));
 }
 int mtts_hifigan_get_numerics(mtts_hifigan* h) { return h->v.numerics; }
 int mtts_hifigan_conv_bf16(mtts_hifigan* h, int route, int C, int k, int d, int B, int T_max, const int* lens, const float* x, const float* w,
                            const float* bias, float in_slope, int epilogue, const float* res, float* mrf, float inv_nk, int mrf_init, float* out) {
-    return hifigan_launched(h->v, h->v.conv_bf16_host(route, C, k, d, B, T_max, lens, x, w, bias, in_slope, epilogue, res, mrf, inv_nk, mrf_init, out));
+    return h->v.launched(h->v.conv_bf16_host(route, C, k, d, B, T_max, lens, x, w, bias, in_slope, epilogue, res, mrf, inv_nk, mrf_init, out));
 }
 
 // ---- MOSNet naturalness scores (mosnet.h; reference evaluation/compute_mos.py) ------------------------------------------------
@@ -763,13 +758,8 @@ void mtts_mosnet_destroy(mtts_mosnet* h) {
 }
 const char* mtts_mosnet_last_error(mtts_mosnet* h) { return h ? h->n.last_error.c_str() : g_create_error.c_str(); }
 int mtts_mosnet_set_stream(mtts_mosnet* h, void* s) { if (!h) return -1; h->n.stream = (hipStream_t)s; return 0; }
-int mtts_mosnet_param_count(mtts_mosnet* h) { return h ? (int)h->n.tensors.size() : -1; }
-int mtts_mosnet_param_info(mtts_mosnet* h, int i, char* name, int cap, int64_t* numel) {
-    if (!h || !name || !numel || i < 0 || i >= (int)h->n.tensors.size()) return -1;
-    snprintf(name, cap, "%s", h->n.tensors[i].name.c_str());
-    *numel = h->n.tensors[i].numel;
-    return 0;
-}
+int mtts_mosnet_param_count(mtts_mosnet* h) { return h ? (int)h->n.tab.tensors.size() : -1; }
+int mtts_mosnet_param_info(mtts_mosnet* h, int i, char* name, int cap, int64_t* numel) { return h ? param_info(h->n.tab, i, name, cap, numel) : -1; }
 int mtts_mosnet_load(mtts_mosnet* h, const char* name, const float* data, int64_t numel) { return h ? h->n.load(name, data, numel) : -1; }
 int mtts_mosnet_score(mtts_mosnet* h, int n_utts, const int* n_frames, const float* mag, float* utt_scores, float* frame_scores) {
     return h ? h->n.score(n_utts, n_frames, mag, utt_scores, frame_scores) : -1;

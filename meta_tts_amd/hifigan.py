@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from .engine import MttsError
-from .vocoder import fold_weight_norm
+from .vocoder import WaveGenerator, fold_weight_norm, polyphase_image
 
 V1 = {"resblock": "1", "upsample_rates": [8, 8, 2, 2], "upsample_kernel_sizes": [16, 16, 4, 4], "upsample_initial_channel": 512,
       "resblock_kernel_sizes": [3, 7, 11], "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5], [1, 3, 5]]}
@@ -54,7 +54,8 @@ def _check(config):
 
 
 def generator_spec(config=V1, n_mel=80):
-    """[(published name prefix, kind, shape of weight_v)] in module order; kinds: conv / convT."""
+    """[(published name prefix, kind, shape of weight_v)] in the order of the library's tensor table (a block's pairs convs1.m, convs2.m
+    one after another); kinds: conv / convT."""
     _check(config)
     c = int(config["upsample_initial_channel"])
     n_k = len(config["resblock_kernel_sizes"])
@@ -63,8 +64,8 @@ def generator_spec(config=V1, n_mel=80):
         spec.append((f"ups.{i}", "convT", (c, c // 2, 2 * r)))
         c //= 2
         for j, k in enumerate(config["resblock_kernel_sizes"]):
-            for half in (1, 2):
-                for m in range(len(config["resblock_dilation_sizes"][j])):
+            for m in range(len(config["resblock_dilation_sizes"][j])):
+                for half in (1, 2):
                     spec.append((f"resblocks.{i * n_k + j}.convs{half}.{m}", "conv", (c, c, k)))
     spec.append(("conv_post", "conv", (1, c, 7)))
     return spec
@@ -103,13 +104,7 @@ def pack_tensors(sd, config=V1, n_mel=80):
         if tuple(w.shape) != tuple(shape):
             raise MttsError(f"HiFiGAN: {name} has shape {tuple(w.shape)}, the config asks for {tuple(shape)}")
         if kind == "convT":
-            cin, cout, k2 = shape
-            r = k2 // 2
-            img = np.empty((r, cout, 2 * cin), np.float32)
-            for ph in range(r):
-                img[ph, :, :cin] = w[:, :, ph + r].T   # multiplies x[q-1]
-                img[ph, :, cin:] = w[:, :, ph].T       # multiplies x[q]
-            out[name + ".w"] = img
+            out[name + ".w"] = polyphase_image(w)
         elif name == "conv_post":
             out[name + ".w"] = np.ascontiguousarray(w[0].T)                     # [7][C_last]
         else:
@@ -118,9 +113,11 @@ def pack_tensors(sd, config=V1, n_mel=80):
     return out
 
 
-class HiFiGAN:
+class HiFiGAN(WaveGenerator):
     """The reference's HiFi-GAN vocoder object with `vocoder.MelGAN`'s duck type: `__call__(mels)` is the reference branch's call,
-    `infer(mels, max_wav_value, lengths)` is `vocoder_infer`; mel (B, n_mel, T), natural-log mels as the model makes them."""
+    `infer(mels, max_wav_value, lengths)` is `vocoder_infer`; mel (B, n_mel, T), natural-log mels as the model makes them and as the
+    generator takes them (mel scale 1)."""
+    _prefix = "mtts_hifigan_"
 
     def __init__(self, state_dict=None, config=V1, n_mel=80, max_B=8, max_T=1024, device=0, lib_path=None, direct_max_channels=None,
                  numerics="fp32"):
@@ -193,66 +190,5 @@ class HiFiGAN:
             raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
         return mrf if epilogue == 2 else out
 
-    def load(self, name, array):
-        a = np.ascontiguousarray(array, np.float32)
-        if self.lib.mtts_hifigan_load(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size) != 0:
-            raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.mtts_hifigan_destroy(self.h)
-            self.h = None
-
-    def set_stream(self, stream_ptr):
-        self.lib.mtts_hifigan_set_stream(self.h, C.c_void_p(stream_ptr))
-        self.stream = int(stream_ptr or 0)
-
-    def mel2wav(self, mel, lengths=None, mel_scale=1.0):
-        """mel (B, n_mel, T) float -> (B, T * hop) float32; samples beyond lengths[b] * hop are zero."""
-        mel = np.asarray(mel, np.float32)
-        B, nm, T = mel.shape
-        assert nm == self.n_mel
-        lens = np.full(B, T, np.int32) if lengths is None else np.ascontiguousarray(lengths, np.int32)
-        x = np.ascontiguousarray(mel.transpose(0, 2, 1))  # channels-last rows
-        wav = np.zeros((B, T * self.hop), np.float32)
-        if self.lib.mtts_hifigan_infer(self.h, x.ctypes.data_as(C.c_void_p), B, T, lens.ctypes.data_as(C.c_void_p),
-                                       C.c_float(mel_scale), wav.ctypes.data_as(C.c_void_p)) != 0:
-            raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
-        return wav
-
-    def mel2wav_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths, wav_ptr: int, mel_scale: float = 1.0):
-        """Device-to-device, as `MelGAN.mel2wav_device`: mel at `mel_ptr` laid out [B][..][n_mel] with `utt_stride` floats between
-        utterances, waveform written to `wav_ptr` as [B][T * hop] floats; asynchronous on the vocoder's stream."""
-        lens = np.ascontiguousarray(lengths, np.int32)
-        if self.lib.mtts_hifigan_infer_device(self.h, C.c_void_p(mel_ptr), C.c_int64(utt_stride), B, T, lens.ctypes.data_as(C.c_void_p),
-                                              C.c_float(mel_scale), C.c_void_p(wav_ptr)) != 0:
-            raise MttsError(self.lib.mtts_hifigan_last_error(self.h).decode())
-
-    def infer_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths):
-        """`infer` without the host, with `MelGAN.infer_device`'s contract: -> (wav_ptr, row_stride, sample_lengths, stream), float32
-        waveforms in a device buffer this object owns, enqueued on the vocoder's `stream` and NOT waited for; the tuple is what
-        `SpeakerEmbedder.embed_device` takes.  The mel is used as it is (natural log: HiFi-GAN's own scale).  The buffer is reused by
-        the next call."""
-        import torch
-        lens = np.minimum(np.asarray(lengths, np.int64).reshape(-1), T).astype(np.int32)
-        if len(lens) != B:
-            raise ValueError(f"infer_device: {len(lens)} lengths for B = {B}")
-        row_stride = T * self.hop
-        if self._wav_dev is None or self._wav_dev.numel() < B * row_stride:
-            self._wav_dev = torch.empty(B * row_stride, dtype=torch.float32, device=f"cuda:{self.device}")
-        self.mel2wav_device(mel_ptr, utt_stride, B, T, lens, self._wav_dev.data_ptr(), mel_scale=1.0)
-        return self._wav_dev.data_ptr(), row_stride, lens * self.hop, self.stream
-
     def __call__(self, mels):                      # utils/model.py:38: vocoder(mels) -> (B, 1, T * hop)
         return self.mel2wav(mels)[:, None, :]
-
-    def infer(self, mels, max_wav_value, lengths=None):   # utils/model.py:32-50
-        mels = np.asarray(mels, np.float32)
-        frame_lens = None if lengths is None else [int(math.ceil(l / self.hop)) for l in lengths]
-        wavs = self.mel2wav(mels, None if frame_lens is None else np.minimum(frame_lens, mels.shape[2]))
-        wavs = (wavs * max_wav_value).astype("int16")
-        wavs = [w for w in wavs]
-        for i in range(len(mels)):
-            if lengths is not None:
-                wavs[i] = wavs[i][: lengths[i]]
-        return wavs

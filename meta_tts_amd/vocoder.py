@@ -74,6 +74,17 @@ def fold_weight_norm(sd, name):
     return (g * v / n).astype(np.float32)
 
 
+def polyphase_image(w):
+    """ConvTranspose1d weight [C_in][C_out][2r] -> [r][C_out][2 C_in]: phase ph multiplies the row pair [x[q-1] | x[q]]."""
+    cin, cout, k2 = w.shape
+    r = k2 // 2
+    img = np.empty((r, cout, 2 * cin), np.float32)
+    for ph in range(r):
+        img[ph, :, :cin] = w[:, :, ph + r].T   # multiplies x[q-1]
+        img[ph, :, cin:] = w[:, :, ph].T       # multiplies x[q]
+    return img
+
+
 def pack_tensors(sd, n_mel=80, ngf=32, n_res=3, ratios=RATIOS):
     """hub-style state dict -> {libmtts tensor name: float32 array} (layouts documented in include/mtts.h)."""
     out = {}
@@ -83,14 +94,8 @@ def pack_tensors(sd, n_mel=80, ngf=32, n_res=3, ratios=RATIOS):
     out["conv_in.w"] = np.ascontiguousarray(fold_weight_norm(sd, name).transpose(0, 2, 1))  # [C0][7][n_mel]
     out["conv_in.b"] = np.asarray(sd[name + ".bias"], np.float32)
     for s, r in enumerate(ratios):
-        name, _, shape = next(it)
-        w = fold_weight_norm(sd, name)  # [C_in][C_out][2r]
-        cin, cout, _ = shape
-        img = np.empty((r, cout, 2 * cin), np.float32)
-        for ph in range(r):
-            img[ph, :, :cin] = w[:, :, ph + r].T   # multiplies x[q-1]
-            img[ph, :, cin:] = w[:, :, ph].T       # multiplies x[q]
-        out[f"up{s}.w"] = img
+        name, _, _ = next(it)
+        out[f"up{s}.w"] = polyphase_image(fold_weight_norm(sd, name))  # from [C_in][C_out][2r]
         out[f"up{s}.b"] = np.asarray(sd[name + ".bias"], np.float32)
         for j in range(n_res):
             n1, _, _ = next(it); n2, _, _ = next(it); ns, _, _ = next(it)
@@ -106,9 +111,81 @@ def pack_tensors(sd, n_mel=80, ngf=32, n_res=3, ratios=RATIOS):
     return out
 
 
-class MelGAN:
+class WaveGenerator:
+    """What the two mel-to-waveform vocoders (`MelGAN`, `hifigan.HiFiGAN`) share over their C entries: a subclass names the symbol
+    prefix and the factor `infer` / `infer_device` put on the model's natural-log mels, creates the handle (`self.h`, `self.hop`) and
+    sets `lib`, `n_mel`, `device`, `stream = 0` and `_wav_dev = None`."""
+    _prefix = None        # "mtts_vocoder_" / "mtts_hifigan_"
+    _infer_mel_scale = 1.0
+
+    def _call(self, entry, *args):
+        if getattr(self.lib, self._prefix + entry)(self.h, *args) != 0:
+            raise MttsError(getattr(self.lib, self._prefix + "last_error")(self.h).decode())
+
+    def load(self, name, array):
+        a = np.ascontiguousarray(array, np.float32)
+        self._call("load", name.encode(), a.ctypes.data_as(C.c_void_p), a.size)
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self._prefix + "destroy")(self.h)
+            self.h = None
+
+    def set_stream(self, stream_ptr):
+        self._call("set_stream", C.c_void_p(stream_ptr))
+        self.stream = int(stream_ptr or 0)
+
+    def mel2wav(self, mel, lengths=None, mel_scale=1.0):
+        """mel (B, n_mel, T) float -> (B, T * hop) float32; samples beyond lengths[b] * hop are zero."""
+        mel = np.asarray(mel, np.float32)
+        B, nm, T = mel.shape
+        assert nm == self.n_mel
+        lens = np.full(B, T, np.int32) if lengths is None else np.ascontiguousarray(lengths, np.int32)
+        x = np.ascontiguousarray(mel.transpose(0, 2, 1))  # channels-last rows
+        wav = np.zeros((B, T * self.hop), np.float32)
+        self._call("infer", x.ctypes.data_as(C.c_void_p), B, T, lens.ctypes.data_as(C.c_void_p), C.c_float(mel_scale), wav.ctypes.data_as(C.c_void_p))
+        return wav
+
+    def mel2wav_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths, wav_ptr: int, mel_scale: float = 1.0):
+        """Device-to-device: mel at `mel_ptr` laid out [B][..][n_mel] with `utt_stride` floats between utterances (e.g.
+        Engine.mel_device()), waveform written to `wav_ptr` as [B][T * hop] floats; asynchronous on the vocoder's stream."""
+        lens = np.ascontiguousarray(lengths, np.int32)
+        self._call("infer_device", C.c_void_p(mel_ptr), C.c_int64(utt_stride), B, T, lens.ctypes.data_as(C.c_void_p), C.c_float(mel_scale),
+                   C.c_void_p(wav_ptr))
+
+    def infer_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths):
+        """`infer` without the host: the mel at `mel_ptr` (layout as in `mel2wav_device`, natural-log mels as the engine makes them,
+        `lengths` [B] frames) -> (wav_ptr, row_stride, sample_lengths, stream): float32 waveforms in a device buffer this object owns,
+        utterance b in the first sample_lengths[b] = lengths[b] * hop floats of row b, rows `row_stride` floats apart; enqueued on the
+        vocoder's `stream` and NOT waited for.  The tuple is what `SpeakerEmbedder.embed_device` takes (with `quantize=max_wav_value`
+        for `infer`'s cut to int16).  The mel is scaled as `infer` scales it.  The buffer is reused by the next call."""
+        import torch
+        lens = np.minimum(np.asarray(lengths, np.int64).reshape(-1), T).astype(np.int32)
+        if len(lens) != B:
+            raise ValueError(f"infer_device: {len(lens)} lengths for B = {B}")
+        row_stride = T * self.hop
+        if self._wav_dev is None or self._wav_dev.numel() < B * row_stride:
+            self._wav_dev = torch.empty(B * row_stride, dtype=torch.float32, device=f"cuda:{self.device}")
+        self.mel2wav_device(mel_ptr, utt_stride, B, T, lens, self._wav_dev.data_ptr(), mel_scale=self._infer_mel_scale)
+        return self._wav_dev.data_ptr(), row_stride, lens * self.hop, self.stream
+
+    def infer(self, mels, max_wav_value, lengths=None):   # lightning/utils.py:20-30, utils/model.py:32-50
+        mels = np.asarray(mels, np.float32)
+        frame_lens = None if lengths is None else [int(math.ceil(l / self.hop)) for l in lengths]
+        wavs = self.mel2wav(mels, None if frame_lens is None else np.minimum(frame_lens, mels.shape[2]), mel_scale=self._infer_mel_scale)
+        wavs = (wavs * max_wav_value).astype("int16")
+        wavs = [w for w in wavs]
+        for i in range(len(mels)):
+            if lengths is not None:
+                wavs[i] = wavs[i][: lengths[i]]
+        return wavs
+
+
+class MelGAN(WaveGenerator):
     """`LightningMelGAN` drop-in: inverse(mel) and infer(mels, max_wav_value, lengths) with the reference's semantics
-    (mel (B, n_mel, T) like the reference's call sites; output waveform (B, T * hop))."""
+    (mel (B, n_mel, T) like the reference's call sites; output waveform (B, T * hop)); `infer` hands the generator mel / ln 10."""
+    _prefix = "mtts_vocoder_"
+    _infer_mel_scale = 1.0 / math.log(10.0)
 
     def __init__(self, state_dict=None, n_mel=80, ngf=32, n_res=3, ratios=RATIOS, max_B=8, max_T=1024, device=0, lib_path=None):
         self.lib = _lib.load(lib_path)
@@ -124,66 +201,7 @@ class MelGAN:
         sd = state_dict if state_dict is not None else synthetic_state_dict(0, n_mel, ngf, n_res, ratios)
         self.state_dict_ = sd
         for k, v in pack_tensors(sd, n_mel, ngf, n_res, ratios).items():
-            a = np.ascontiguousarray(v, np.float32)
-            if self.lib.mtts_vocoder_load(h, k.encode(), a.ctypes.data_as(C.c_void_p), a.size) != 0:
-                raise MttsError(self.lib.mtts_vocoder_last_error(h).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.mtts_vocoder_destroy(self.h)
-            self.h = None
-
-    def set_stream(self, stream_ptr):
-        self.lib.mtts_vocoder_set_stream(self.h, C.c_void_p(stream_ptr))
-        self.stream = int(stream_ptr or 0)
-
-    def mel2wav(self, mel, lengths=None, mel_scale=1.0):
-        """mel (B, n_mel, T) float -> (B, T * hop) float32; rows beyond lengths[b] * hop are zero."""
-        mel = np.asarray(mel, np.float32)
-        B, nm, T = mel.shape
-        assert nm == self.n_mel
-        lens = np.full(B, T, np.int32) if lengths is None else np.asarray(lengths, np.int32)
-        x = np.ascontiguousarray(mel.transpose(0, 2, 1))  # channels-last rows
-        wav = np.zeros((B, T * self.hop), np.float32)
-        if self.lib.mtts_vocoder_infer(self.h, x.ctypes.data_as(C.c_void_p), B, T, lens.ctypes.data_as(C.c_void_p),
-                                       C.c_float(mel_scale), wav.ctypes.data_as(C.c_void_p)) != 0:
-            raise MttsError(self.lib.mtts_vocoder_last_error(self.h).decode())
-        return wav
-
-    def mel2wav_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths, wav_ptr: int, mel_scale: float = 1.0):
-        """Device-to-device: mel at `mel_ptr` laid out [B][..][n_mel] with `utt_stride` floats between utterances (e.g.
-        Engine.mel_device()), waveform written to `wav_ptr` as [B][T * hop] floats; asynchronous on the vocoder's stream."""
-        lens = np.ascontiguousarray(lengths, np.int32)
-        if self.lib.mtts_vocoder_infer_device(self.h, C.c_void_p(mel_ptr), C.c_int64(utt_stride), B, T, lens.ctypes.data_as(C.c_void_p),
-                                              C.c_float(mel_scale), C.c_void_p(wav_ptr)) != 0:
-            raise MttsError(self.lib.mtts_vocoder_last_error(self.h).decode())
-
-    def infer_device(self, mel_ptr: int, utt_stride: int, B: int, T: int, lengths):
-        """`infer` without the host: the mel at `mel_ptr` (layout as in `mel2wav_device`, natural-log mels as the engine makes them,
-        `lengths` [B] frames) -> (wav_ptr, row_stride, sample_lengths, stream): float32 waveforms in a device buffer this object owns,
-        utterance b in the first sample_lengths[b] = lengths[b] * hop floats of row b, rows `row_stride` floats apart; enqueued on the
-        vocoder's `stream` and NOT waited for.  The tuple is what `SpeakerEmbedder.embed_device` takes (with `quantize=max_wav_value`
-        for `infer`'s cut to int16).  The buffer is reused by the next call."""
-        import torch
-        lens = np.minimum(np.asarray(lengths, np.int64).reshape(-1), T).astype(np.int32)
-        if len(lens) != B:
-            raise ValueError(f"infer_device: {len(lens)} lengths for B = {B}")
-        row_stride = T * self.hop
-        if self._wav_dev is None or self._wav_dev.numel() < B * row_stride:
-            self._wav_dev = torch.empty(B * row_stride, dtype=torch.float32, device=f"cuda:{self.device}")
-        self.mel2wav_device(mel_ptr, utt_stride, B, T, lens, self._wav_dev.data_ptr(), mel_scale=1.0 / math.log(10.0))
-        return self._wav_dev.data_ptr(), row_stride, lens * self.hop, self.stream
+            self.load(k, v)
 
     def inverse(self, mel):                      # lightning/utils.py:16-18
         return self.mel2wav(mel)
-
-    def infer(self, mels, max_wav_value, lengths=None):   # lightning/utils.py:20-30
-        mels = np.asarray(mels, np.float32)
-        frame_lens = None if lengths is None else [int(math.ceil(l / self.hop)) for l in lengths]
-        wavs = self.mel2wav(mels, None if frame_lens is None else np.minimum(frame_lens, mels.shape[2]), mel_scale=1.0 / math.log(10.0))
-        wavs = (wavs * max_wav_value).astype("int16")
-        wavs = [w for w in wavs]
-        for i in range(len(mels)):
-            if lengths is not None:
-                wavs[i] = wavs[i][: lengths[i]]
-        return wavs

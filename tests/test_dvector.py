@@ -60,6 +60,26 @@ def test_state_dict_names_and_errors():
     enc.close()
 
 
+def test_refused_loads_leave_the_handle_unchanged():
+    import ctypes as C
+    cfg = dict(n_mels=8, hidden=64, emb=64, layers=1)
+    enc = se.DVectorEncoder(se.synthetic_state_dict(0, **cfg), max_partials=4, max_utts=2, frames=5, lib_path=ge.build_emulator(), **cfg)
+    mels, slices = np.random.RandomState(1).standard_normal((3, 5, 8)).astype(np.float32), [slice(0, 1), slice(1, 3)]
+    before = enc.embed(mels, slices)
+    junk = np.ones(8, np.float32)
+
+    def load(name, n):
+        rc = enc.lib.mtts_dvector_load(enc.h, name.encode(), junk.ctypes.data_as(C.c_void_p), n)
+        return rc, enc.lib.mtts_dvector_last_error(enc.h).decode()
+
+    rc, msg = load("lstm.weight_ih_l1", 4)
+    assert rc != 0 and msg == "unknown d-vector tensor lstm.weight_ih_l1"
+    rc, msg = load("linear.bias", 8)
+    assert rc != 0 and msg == "size mismatch for linear.bias: 8 floats given, 64 expected"
+    np.testing.assert_array_equal(enc.embed(mels, slices), before)
+    enc.close()
+
+
 @pytest.mark.gpu
 def test_dvector_gpu_reference_shapes():
     ge.build_device()

@@ -218,6 +218,25 @@ def test_bad_batches_and_tensors_are_refused_without_a_launch(emu_lib):
     voc.close()
 
 
+def test_refused_loads_leave_the_handle_unchanged_and_the_table_lists_pack_tensors(emu_lib):
+    sd = H.synthetic_state_dict(5, CFG_A, 16)
+    voc = H.HiFiGAN(sd, CFG_A, n_mel=16, max_B=2, max_T=24, lib_path=emu_lib)
+    mel, lens = _mel(1, 2, 20, 16), np.array([20, 13], np.int32)
+    before = voc.mel2wav(mel, lens)
+    with pytest.raises(MttsError, match="unknown HiFi-GAN tensor resblocks.9.convs1.0.w"):
+        voc.load("resblocks.9.convs1.0.w", np.ones(4, np.float32))
+    with pytest.raises(MttsError, match="size mismatch for conv_post.w: 8 floats given, 112 expected"):
+        voc.load("conv_post.w", np.ones(8, np.float32))
+    assert np.array_equal(voc.mel2wav(mel, lens), before)
+    table, name, numel = [], C.create_string_buffer(128), C.c_int64()
+    for i in range(voc.lib.mtts_hifigan_param_count(voc.h)):
+        assert voc.lib.mtts_hifigan_param_info(voc.h, i, name, 128, C.byref(numel)) == 0
+        table.append((name.value.decode(), numel.value))
+    assert table == [(k, v.size) for k, v in H.pack_tensors(sd, CFG_A, 16).items()]
+    assert voc.lib.mtts_hifigan_param_info(voc.h, len(table), name, 128, C.byref(numel)) != 0
+    voc.close()
+
+
 # ---- 6. duck type ----------------------------------------------------------------------------------------------------------------------
 def test_hifigan_feeds_the_unmodified_saver(tmp_path, emu_lib):
     from scipy.io import wavfile

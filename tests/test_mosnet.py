@@ -242,6 +242,25 @@ def test_score_wavs_equals_score_magnitudes_of_the_front_end(emu_lib):
     net.close()
 
 
+def test_refused_loads_leave_the_handle_unchanged_and_the_table_lists_pack_tensors(emu_lib):
+    sd = M.synthetic_state_dict(1, 33)
+    mags = _mags(33, 33, (3, 2))
+    net = M.MOSNet(sd, 33, max_frames=8, max_utts=2, lib_path=emu_lib)
+    before = net.score_magnitudes(mags)
+    with pytest.raises(MttsError, match="unknown MOSNet tensor conv.12.w"):
+        net.load("conv.12.w", np.ones(4, np.float32))
+    with pytest.raises(MttsError, match="size mismatch for dense.b: 127 floats given, 128 expected"):
+        net.load("dense.b", np.ones(127, np.float32))
+    assert _same(net.score_magnitudes(mags), before)
+    table, name, numel = [], C.create_string_buffer(128), C.c_int64()
+    for i in range(net.lib.mtts_mosnet_param_count(net.h)):
+        assert net.lib.mtts_mosnet_param_info(net.h, i, name, 128, C.byref(numel)) == 0
+        table.append((name.value.decode(), numel.value))
+    assert table == [(k, v.size) for k, v in M.pack_tensors(sd, 33).items()]
+    assert net.lib.mtts_mosnet_param_info(net.h, len(table), name, 128, C.byref(numel)) != 0
+    net.close()
+
+
 # ---- 8. refusals --------------------------------------------------------------------------------------------------------------------------
 def test_refusals(emu_lib):
     sd = M.synthetic_state_dict(1, 33)

@@ -73,6 +73,50 @@ def test_tiny_generator_through_emulator(emu_lib):
     voc.close()
 
 
+TINY = dict(n_mel=16, ngf=16, n_res=2, ratios=(4, 2))
+
+
+def test_refused_loads_leave_the_handle_unchanged_and_the_table_lists_pack_tensors(emu_lib):
+    import ctypes as C
+    from meta_tts_amd.engine import MttsError
+    sd = V.synthetic_state_dict(5, **TINY)
+    voc = V.MelGAN(sd, max_B=2, max_T=24, lib_path=emu_lib, **TINY)
+    mel, lens = _mel(1, 2, 20, 16), np.array([20, 13], np.int32)
+    before = voc.mel2wav(mel, lens)
+    with pytest.raises(MttsError, match="unknown vocoder tensor res2.0.w1"):
+        voc.load("res2.0.w1", np.ones(4, np.float32))
+    with pytest.raises(MttsError, match="size mismatch for conv_out.w: 8 floats given, 112 expected"):
+        voc.load("conv_out.w", np.ones(8, np.float32))
+    assert np.array_equal(voc.mel2wav(mel, lens), before)
+    packed = V.pack_tensors(sd, **TINY)
+    table, name, numel = [], C.create_string_buffer(128), C.c_int64()
+    for i in range(voc.lib.mtts_vocoder_param_count(voc.h)):
+        assert voc.lib.mtts_vocoder_param_info(voc.h, i, name, 128, C.byref(numel)) == 0
+        table.append((name.value.decode(), numel.value))
+    assert table == [(k, v.size) for k, v in packed.items()]
+    assert voc.lib.mtts_vocoder_param_info(voc.h, len(table), name, 128, C.byref(numel)) != 0
+    voc.close()
+
+
+def test_melgan_and_hifigan_share_one_base_and_infer_is_mel2wav_scaled_and_cut(emu_lib):
+    from meta_tts_amd import hifigan as H
+    shared = ("load", "close", "set_stream", "mel2wav", "mel2wav_device", "infer_device", "infer")
+    for m in shared:
+        assert getattr(V.MelGAN, m) is getattr(V.WaveGenerator, m) is getattr(H.HiFiGAN, m), m
+    public = lambda cls: {n for n in vars(cls) if not n.startswith("_")}   # noqa: E731
+    assert public(V.WaveGenerator) == set(shared) and public(V.MelGAN) == {"inverse"}
+    assert public(H.HiFiGAN) == {"numerics", "set_numerics", "conv_bf16"} and "__call__" in vars(H.HiFiGAN)
+    voc = V.MelGAN(V.synthetic_state_dict(5, **TINY), max_B=2, max_T=24, lib_path=emu_lib, **TINY)
+    mel, lengths = _mel(1, 2, 20, 16), [20 * 8, 13 * 8 - 3]
+    wav = voc.mel2wav(mel, np.array([20, 13], np.int32), mel_scale=1.0 / math.log(10.0))   # 13 = ceil((13 * 8 - 3) / hop)
+    i16 = voc.infer(mel, 32768.0, lengths=lengths)
+    for b, n in enumerate(lengths):
+        assert i16[b].dtype == np.int16 and np.array_equal(i16[b], (wav[b] * 32768.0).astype("int16")[:n])
+    full = voc.infer(mel, 32768.0)
+    assert all(np.array_equal(w, (x * 32768.0).astype("int16")) for w, x in zip(full, voc.mel2wav(mel, mel_scale=1.0 / math.log(10.0))))
+    voc.close()
+
+
 @pytest.mark.gpu
 def test_full_generator_on_gpu_vs_oracle():
     sd = V.synthetic_state_dict(0)
