@@ -277,6 +277,52 @@ int mtts_gemm_f32(int form, int M, int N, int K, const float* A, int lda, const 
  * reference: the double backward that `higher` records for lightning/systems/base_adaptor.py:107). */
 int mtts_gemm_f32_dual(int form, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* A2, const float* B2,
                        float* C, int ldc, const float* bias, float alpha, int flags, int tile, void* hip_stream);
+/* The grouped launcher at kernel level (csrc/gemm.h: gemm_launch / gemm_batch_end as the engine drives them): n = 1 .. 6 problems of any
+ * mix of forms in ONE launch.  A descriptor carries the GemmArgs fields of the same names:
+ *   groups (blockIdx.z), max_M / max_N bound the tile grid over all groups; TASK mode: group z adds z * a_gs / b_gs / c_gs / bias_gs / ...
+ *   (elements) to the bases, and dimptr[z * dim_stride] * dim_mult (DEVICE ints) replaces M (dim_sel 0) or K (dim_sel 2); host_dims = the
+ *   same values on the HOST (enables the task-per-XCD schedule of 8-group launches); TABLE mode: `table` = DEVICE array of `groups`
+ *   group records, offsets in elements, ld* 0 = inherit; a group with M <= 0 or K <= 0 is skipped — nothing of it is written;
+ *   epilogue: v = alpha * acc + bias[n]; flags bit1: v += C; bit0: ReLU; bit2: v < 0 -> act_slope * v; relu_ref (leading dimension
+ *   ld_relu): v kept only where relu_ref[m][n] > 0; rowmask[m] == 0: v = 0; c_rowmap[m]: output row (< 0: row dropped; the accumulate
+ *   read is at the remapped row);  taps > 1 (form 1): the conv input-gradient tap walk of mtts_conv1d_f32 mode 1;  a_tap_rows != 0 (forms 0 / 1):
+ *   k = tap * a_tap_k + kin reads A row m + tap * a_tap_rows (a_tap_k % 32 == 0);  colsum (form 2): colsum[z * colsum_gs + m] = sum over the
+ *   group's K rows r of A[r][m] * colsum_w[z * colsum_w_gs + 4 r] (colsum_w is [rows][4], only column 0 counts); A2 / B2: dual source.
+ * family 0 (auto) / 4064 (force the LDS-DMA kernels: device build only; -1 where they cannot take a problem, and -1 after the launch if any
+ * other kernel ran — a forced family never falls back silently).
+ * splitk_ws / splitk_ctr: both NULL (K is never split) or the CALLER's device workspace of mtts_gemm_splitk_ws_bytes() /
+ * mtts_gemm_splitk_ctr_bytes() bytes, counters zeroed once (a launch leaves them zero); nothing is allocated inside.
+ * report (host, [n][2], may be NULL): per problem the split factor S and the placement (0 plain, 1 task-per-XCD schedule, 2 panel order).
+ * Returns -1 without launching for: n outside 1..6, a family other than 0 / 4064, one of splitk_ws / splitk_ctr without the other, NULL
+ * operands, one of A2 / B2 without the other, a form outside 0..2, groups / max_M / max_N < 1, flag bits beyond 0..2, colsum on a form
+ * other than 2, with a table or without colsum_w, a_tap_rows != 0 with a_tap_k % 32 != 0 or on form 2, table together with dimptr,
+ * host_dims without dimptr, dimptr with dim_stride < 1, dim_mult < 1 or dim_sel other than 0 / 2, relu_ref with ld_relu < 1, taps > 1 on
+ * a form other than 1 or with tap_k < 1 (family 4064: with tap_k % 32 != 0). */
+typedef struct mtts_gemm_group {
+    long long a_off, b_off, c_off;
+    int M, N, K;
+    int lda, ldb, ldc;
+} mtts_gemm_group;
+typedef struct mtts_gemm_desc {
+    const float* A; const float* B; float* C; const float* A2; const float* B2;
+    long long a_gs, b_gs, c_gs, a2_gs, b2_gs;
+    const int* dimptr; const int* host_dims; const mtts_gemm_group* table;
+    const float* bias; long long bias_gs;
+    const unsigned char* rowmask; long long rowmask_gs;
+    const float* relu_ref; long long relu_ref_gs;
+    const int* c_rowmap; long long c_rowmap_gs;
+    float* colsum; long long colsum_gs;
+    const float* colsum_w; long long colsum_w_gs;
+    int form, groups, max_M, max_N;
+    int M, N, K, lda, ldb, ldc;
+    int dim_stride, dim_sel, dim_mult;
+    int ld_relu, flags;
+    float alpha, act_slope;
+    int taps, tap_k, tap_bstride, a_tap_k, a_tap_rows;
+} mtts_gemm_desc;
+int64_t mtts_gemm_splitk_ws_bytes(void);
+int64_t mtts_gemm_splitk_ctr_bytes(void);
+int mtts_gemm_f32_grouped(const mtts_gemm_desc* probs, int n, int family, float* splitk_ws, int* splitk_ctr, int* report, void* hip_stream);
 /* The bf16 operand family on one problem (csrc/gemm_bf16.h): C = alpha * (op(A, B) [+ op(A2, B2)]) + bias with fp32 A / B in memory,
  * rounded to bf16 on the way into LDS, v_mfma_f32_32x32x16_bf16, fp32 accumulation.  A2 / B2 both NULL or both set.  tile 0 (auto) / 64 / 128
  * (+ 1000 * K-slices kept in flight per workgroup: micro-benchmarks). */

@@ -155,7 +155,9 @@ struct GemmArgs {
     long long a_gs = 0, b_gs = 0, c_gs = 0;  // per-group strides (elements), TASK mode
     int lda = 0, ldb = 0, ldc = 0;
     int M = 0, N = 0, K = 0;
-    const int* dimptr = nullptr;  // per-group override of M (dim_sel 0) or K (dim_sel 2)
+    const int* dimptr = nullptr;  // per-group override of M (dim_sel 0) or K (dim_sel 2).  A group whose M or K is <= 0 is SKIPPED: nothing of its
+                                  // C / colsum is written (not even bias or zeros) — the task-per-XCD schedule gives such a group no workgroup at all.
+                                  // The engine never launches one (every task has >= 1 utterance, so >= 1 row in every row space it uses).
     int dim_stride = 1, dim_sel = 0, dim_mult = 1;  // value used = dimptr[group * dim_stride] * dim_mult
     const GemmGroupDesc* table = nullptr;  // TABLE mode: per-group offsets and sizes
     const float* bias = nullptr;
@@ -1127,7 +1129,7 @@ constexpr int kLnCtrs = 4096;                     // the last kLnCtrs counters: 
 // instead of launched; gemm_batch_end() issues the queue as ONE launch (gemm_f32_multi_kernel / gemm_glds_multi_kernel).
 // The caller guarantees the queued problems are mutually independent and that nothing launched before gemm_batch_end()
 // reads their outputs (engine: the wgrad / dgrad pair of a layer, dQ / dK / dV of an attention block).
-struct GemmPending { int form; GemmArgs g; int max_M, max_N, groups; double flops, rows, bytes; };
+struct GemmPending { int form; GemmArgs g; int max_M, max_N, groups; double flops, rows, bytes; int tag = -1; };   // tag: GemmCtx::next_tag when it was queued
 struct GemmBatch { bool open = false; std::vector<GemmPending> q; int force_family = 0; int force_tile = 0; };   // force_family: 16 / 32 (BK of the register-staged multi-problem kernel) or 4064 (LDS-DMA) for the next flush (explicit tile codes of dual-source problems)
 
 // Every piece of MUTABLE launcher state — the launch-batching queue, the per-launch profiler, the split-K workspace —
@@ -1148,6 +1150,12 @@ struct GemmCtx {
     int wave_prio = 0;      // GemmArgs::wave_prio of every launch of this context (the engine sets it on the critical stream's context while side streams carry work)
     bool no_glds = false;   // never pick the LDS-DMA kernels (48 KB of LDS per workgroup: a side-stream launch would leave no LDS for the main stream's)
     bool no_splitk = false;   // never split K (the split factor follows the batch's size: an owner whose results must not depend on what else is in the batch sets it)
+    // What the launcher decided for the problems queued under a tag (next_tag >= 0 while they are queued: mtts_gemm_f32_grouped): the split
+    // factor and the placement (0 plain / XCD-grouped order, 1 task-per-XCD schedule, 2 panel order).  Host bookkeeping only.
+    int next_tag = -1;
+    int note_splitk[kGemmMultiMax] = {0}, note_place[kGemmMultiMax] = {0};
+    int last_place = 0;   // placement of the last stand-alone launch
+    void note(int tag, int S, int place) { if (tag >= 0 && tag < kGemmMultiMax) { note_splitk[tag] = S; note_place[tag] = place; } }
     DevHeap* heap = nullptr;   // the owner's: the workspace and the profiler's events come from it and go back with it
     int alloc_workspace(DevHeap& h) {
         heap = &h;
@@ -1270,7 +1278,7 @@ inline void gemm_launch(GemmCtx& cx, int form, const GemmArgs& g_in, int max_M, 
     if (user_tile == 0) {
         if (!cx.flushing) {
             // through the queue: with the batch's other problems, or alone
-            cx.batch.q.push_back(GemmPending{form, g, max_M, max_N, groups, alg_flops, rows, alg_bytes});
+            cx.batch.q.push_back(GemmPending{form, g, max_M, max_N, groups, alg_flops, rows, alg_bytes, cx.next_tag});
             if (!cx.batch.open) {
                 gemm_batch_end(cx, stream);
             } else if ((int)cx.batch.q.size() == kGemmMultiMax) { gemm_batch_end(cx, stream); cx.batch.open = true; }
@@ -1311,10 +1319,12 @@ inline void gemm_launch(GemmCtx& cx, int form, const GemmArgs& g_in, int max_M, 
     const int nth = 256;
     const long grid_tiles = ntiles(tile);
     dim3 block(nth), grid((unsigned)(grid_tiles * S), 1, (unsigned)groups);
-    if (gemm_xcd_sched_for(g, max_M, max_N, groups, S, tile)) grid = dim3((unsigned)gemm_xcd_sched_slots(g.xs), 1, 1);   // 1-D, task-per-XCD order
+    cx.last_place = 0;
+    if (gemm_xcd_sched_for(g, max_M, max_N, groups, S, tile)) { grid = dim3((unsigned)gemm_xcd_sched_slots(g.xs), 1, 1); cx.last_place = 1; }   // 1-D, task-per-XCD order
     else if (gemm_panel_order_for(g, form, rows, max_M, max_N, groups)) {
         g.swizzle = 2; g.po_tiles_m = (max_M + tile - 1) / tile;
         grid = dim3((unsigned)xcd_panel_slots(g.po_tiles_m, gemm_tiles_n(g, max_N, tile), S), 1, (unsigned)groups);
+        cx.last_place = 2;
     }
     GemmProfiler& prof = cx.prof;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1399,7 +1409,10 @@ inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream) {
     if (solo) {
         const std::vector<GemmPending> q = b.q;
         b.q.clear();
-        for (const GemmPending& p : q) gemm_launch(cx, p.form, p.g, p.max_M, p.max_N, p.groups, stream, 0, p.flops, (long long)p.rows, p.bytes);
+        for (const GemmPending& p : q) {
+            gemm_launch(cx, p.form, p.g, p.max_M, p.max_N, p.groups, stream, 0, p.flops, (long long)p.rows, p.bytes);
+            cx.note(p.tag, 1, cx.last_place);
+        }
         return;
     }
     GemmMulti mp;
@@ -1476,6 +1489,7 @@ inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream) {
             mp.po_tm[i] = (short)((p.max_M + T - 1) / T); mp.po_tn[i] = (short)gemm_tiles_n(p.g, p.max_N, T); mp.po_s[i] = (short)S;
             slots = (long)xcd_panel_slots(mp.po_tm[i], mp.po_tn[i], S) * p.groups;
         }
+        cx.note(p.tag, S, mp.xcd_group[i] == -2 ? 1 : (mp.xcd_group[i] == -3 ? 2 : 0));
         mp.start[i + 1] = mp.start[i] + (int)((slots + 7) & ~7L);   // (every problem starts on a multiple of 8: workgroup slot % 8 = XCD)
         max_groups = std::max(max_groups, p.groups);
         flops += p.flops; rows += p.rows; bytes += p.bytes;

@@ -540,7 +540,8 @@ int mtts_profile_report(mtts_handle* h, double* out, int kinds) {
 // launcher state of the handle-less kernel-level entry points: one context per host thread, WITHOUT a split-K workspace — nothing is
 // allocated behind the caller's back, nothing is tied to the device that happened to be current on a thread's first call, and two
 // streams driven from one thread share no counters or slabs (the launcher keeps S = 1 when a context has no workspace; split-K is a
-// handle's business: its workspace is allocated by mtts_create on the handle's device and used on the handle's streams only)
+// handle's business: its workspace is allocated by mtts_create on the handle's device and used on the handle's streams only;
+// mtts_gemm_f32_grouped binds the CALLER's workspace for the length of its own call)
 static GemmCtx& kernel_ctx() {
     static thread_local GemmCtx cx;
     return cx;
@@ -603,6 +604,70 @@ int mtts_gemm_f32_dual(int form, int M, int N, int K, const float* A, int lda, c
     g.A = A; g.B = B; g.A2 = A2; g.B2 = B2; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
     g.bias = bias; g.alpha = alpha; g.flags = flags & 0xff;
     gemm_launch(kernel_ctx(), form, g, M, N, 1, (hipStream_t)stream, tile);
+    return kernel_launch_rc();
+}
+
+// The grouped launcher at kernel level: 1 .. kGemmMultiMax problems with the GemmArgs fields the engine's launches use, queued on
+// kernel_ctx() and flushed as ONE gemm_batch_end.  Split-K only with the CALLER's workspace (sizes: mtts_gemm_splitk_*_bytes), bound to the
+// context for this call alone — the contract above kernel_ctx() stays true.  report[2 i], report[2 i + 1] = split factor, placement of problem i.
+int64_t mtts_gemm_splitk_ws_bytes(void) { return (int64_t)kSplitWsFloats * (int64_t)sizeof(float); }
+int64_t mtts_gemm_splitk_ctr_bytes(void) { return (int64_t)(kSplitCtrs + 16) * (int64_t)sizeof(int); }
+static_assert(sizeof(mtts_gemm_group) == sizeof(GemmGroupDesc), "mtts_gemm_group mirrors GemmGroupDesc");
+
+int mtts_gemm_f32_grouped(const mtts_gemm_desc* probs, int n, int family, float* splitk_ws, int* splitk_ctr, int* report, void* stream) {
+    if (!probs || n < 1 || n > kGemmMultiMax) return -1;
+    if (family != 0 && family != 4064) return -1;
+#if defined(MTTS_EMU)
+    if (family == 4064) return -1;   // the LDS-DMA kernels exist in the device build only
+#endif
+    if ((splitk_ws == nullptr) != (splitk_ctr == nullptr)) return -1;
+    for (int i = 0; i < n; ++i) {
+        const mtts_gemm_desc& d = probs[i];
+        if (!d.A || !d.B || !d.C || d.form < 0 || d.form > 2 || d.groups < 1 || d.max_M < 1 || d.max_N < 1) return -1;
+        if ((d.A2 == nullptr) != (d.B2 == nullptr) || (d.flags & ~7)) return -1;
+        if (d.colsum && (d.form != GEMM_TN || !d.colsum_w || d.table)) return -1;
+        if (d.a_tap_rows != 0 && (d.a_tap_k <= 0 || d.a_tap_k % 32 != 0 || d.form == GEMM_TN)) return -1;
+        if (d.table && d.dimptr) return -1;
+        if (d.host_dims && !d.dimptr) return -1;
+        if (d.dimptr && (d.dim_stride < 1 || d.dim_mult < 1 || (d.dim_sel != 0 && d.dim_sel != 2))) return -1;
+        if (d.relu_ref && d.ld_relu < 1) return -1;
+        if (d.taps > 1 && (d.tap_k < 1 || d.form != GEMM_NN)) return -1;
+        if (family == 4064 && d.taps > 1 && d.tap_k % 32 != 0) return -1;   // (gemm_glds_ok: the launcher would fall back to the register-staged kernel)
+    }
+    GemmCtx& cx = kernel_ctx();
+    cx.wsp.ws = splitk_ws; cx.wsp.ctr = splitk_ctr;
+    cx.batch.force_family = family;
+    cx.last_kind = GK_OTHER;
+    gemm_batch_begin(cx);
+    for (int i = 0; i < n; ++i) {
+        const mtts_gemm_desc& d = probs[i];
+        GemmArgs g;
+        g.A = d.A; g.B = d.B; g.C = d.C; g.A2 = d.A2; g.B2 = d.B2;
+        g.a_gs = d.a_gs; g.b_gs = d.b_gs; g.c_gs = d.c_gs; g.a2_gs = d.a2_gs; g.b2_gs = d.b2_gs;
+        g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc; g.M = d.M; g.N = d.N; g.K = d.K;
+        if (d.dimptr) { g.dimptr = d.dimptr; g.dim_stride = d.dim_stride; g.dim_sel = d.dim_sel; g.dim_mult = d.dim_mult; g.host_dims = d.host_dims; }
+        g.table = (const GemmGroupDesc*)d.table;
+        g.bias = d.bias; g.bias_gs = d.bias_gs;
+        g.rowmask = d.rowmask; g.rowmask_gs = d.rowmask_gs;
+        g.relu_ref = d.relu_ref; g.relu_ref_gs = d.relu_ref_gs; g.ld_relu = d.ld_relu;
+        g.c_rowmap = d.c_rowmap; g.c_rowmap_gs = d.c_rowmap_gs;
+        g.alpha = d.alpha; g.act_slope = d.act_slope; g.flags = d.flags;
+        if (d.taps > 1) { g.taps = d.taps; g.tap_k = d.tap_k; g.tap_bstride = d.tap_bstride; }
+        if (d.a_tap_rows != 0) { g.a_tap_k = d.a_tap_k; g.a_tap_rows = d.a_tap_rows; }
+        g.colsum = d.colsum; g.colsum_gs = d.colsum_gs; g.colsum_w = d.colsum_w; g.colsum_w_gs = d.colsum_w_gs;
+        cx.next_tag = i;
+        cx.note(i, 0, 0);
+        gemm_launch(cx, d.form, g, d.max_M, d.max_N, d.groups, (hipStream_t)stream, 0);   // (the sixth problem flushes the queue by itself)
+    }
+    cx.next_tag = -1;
+    gemm_batch_end(cx, (hipStream_t)stream);
+    cx.batch.force_family = 0;
+    cx.wsp.ws = nullptr; cx.wsp.ctr = nullptr;
+    if (report) for (int i = 0; i < n; ++i) { report[2 * i] = cx.note_splitk[i]; report[2 * i + 1] = cx.note_place[i]; }
+    // a forced family that did not run is an error, never a silent fall-back: the caller's test would prove nothing about it
+    const int k = cx.last_kind;
+    const bool lds_dma = k == GK_GLDS_MULTI || k == GK_GLDS_MULTI_DUAL || (k >= GK_GLDS && k < GK_GLDS + 3);
+    if (family == 4064 && !lds_dma && !cx.error) cx.error = "mtts_gemm_f32_grouped: the forced LDS-DMA family did not run";
     return kernel_launch_rc();
 }
 

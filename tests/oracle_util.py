@@ -1,4 +1,5 @@
 """Shared helpers for tests that drive the oracle (tests/ may import oracle/, the product may not)."""
+import ctypes as C
 import os
 import sys
 
@@ -75,3 +76,41 @@ def check_grads(pairs, rtol, arbitrate, atol=0.0, label=""):
     bad = {n: rep["tensors"][n] for n in failing if not rep["tensors"][n]["ok"]}
     assert not bad, (label, bad, rep["parties"])
     return rep
+
+
+class Dev:
+    """Device-or-host buffers behind one interface: torch CUDA tensors on the GPU, numpy arrays for the emulator (whose 'device'
+    memory is host memory)."""
+
+    def __init__(self, gpu):
+        import __graft_entry__ as ge
+        from meta_tts_amd import _lib
+        self.gpu = gpu
+        self.lib = _lib.load(None if gpu else ge.build_emulator())
+        self.keep = []
+
+    def put(self, a):
+        a = np.ascontiguousarray(a)
+        if self.gpu:
+            t = torch.from_numpy(a).cuda()
+            self.keep.append(t)
+            return t
+        self.keep.append(a)
+        return a
+
+    def empty(self, shape, dtype=np.float32, fill=0):
+        return self.put(np.full(shape, fill, dtype))
+
+    def ptr(self, x):
+        if x is None:
+            return None
+        return C.c_void_p(x.data_ptr()) if self.gpu else x.ctypes.data_as(C.c_void_p)
+
+    def get(self, x):
+        if self.gpu:
+            torch.cuda.synchronize()
+            return x.cpu().numpy()
+        return x
+
+    def ws(self, rows, n_mat=0):
+        return self.empty((int(self.lib.mtts_kernel_ws_bytes(rows, n_mat)) + 3) // 4, np.float32)

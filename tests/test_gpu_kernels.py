@@ -64,8 +64,8 @@ def test_gemm_forms(lib, form, tile, M, N, K):
 @pytest.mark.parametrize("form", [0, 1, 2])
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (257, 80, 256), (33, 130, 100), (200, 256, 1100), (190, 70, 517), (2100, 256, 2304)])
 def test_gemm_dual_source(lib, form, tile, M, N, K):
-    """C = alpha (A B + A2 B2) + bias in one K-loop chain (the tangent pairs of second-order MAML): every kernel family, the
-    split-K path of under-filled launches included, against float64."""
+    """C = alpha (A B + A2 B2) + bias in one K-loop chain (the tangent pairs of second-order MAML): every kernel family against float64.
+    (Never split-K: the handle-less entries have no workspace, so the launcher keeps S = 1 — tests/test_gemm_grouped.py covers split-K.)"""
     g = np.random.RandomState(M * 5 + N * 11 + K + form)
     pad4 = lambda x: (x + 3) & ~3
 
