@@ -420,6 +420,22 @@ int mtts_rowdot_jvp(int rows, int C, const float* x, const float* tx, const floa
                     float* tout, void* ws, void* hip_stream);
 int mtts_rowdot_jvp_bwd(int rows, int C, const float* dout, const float* tgout, const float* w, const float* tw, float* dx, float* tdx, void* ws,
                         void* hip_stream);
+/* The d-vector speaker encoder's kernels (mtts_dvector_* below), one at a time: raw device pointers, no scratch, asynchronous on the
+ * stream, -1 (nothing launched) on a null required pointer or a shape mtts_dvector_create refuses: H a multiple of 64 in 64 .. 1024, E a
+ * multiple of 4 in 4 .. 256, N, T, B >= 1.  Gate order i, f, g, o.
+ * lstm_recurrent: xp [N][T][4H] (input projection, biases included), whhT [H][4H] (weight_hh TRANSPOSED) -> hlast [N][H], hseq [N][T][H]
+ * or NULL, and gates [N][T][4H] (after their non-linearities) / cseq [N][T][H] / hprev [N][T][H]: all three (training) or all NULL.
+ * lstm_bptt: dh_ext [N][T][H] or NULL, dh_last [N][H] or NULL, whh [4H][H] -> dgates [N][T][4H] (gradient of the gate pre-activations).
+ * dvec_head: part = raw / ||raw||, raw = relu(hlast wT + bias) (wT [H][E]; eraw [N][E] = raw or NULL); dvec_head_bwd: w [E][H].
+ * dvec_utterance: out[b] = normalize(mean(part[off[b] .. off[b+1]))) with off [B + 1] device ints; dvec_utterance_bwd: dout -> dpart. */
+int mtts_lstm_recurrent(int N, int T, int H, const float* xp, const float* whhT, float* hseq, float* hlast, float* gates, float* cseq, float* hprev,
+                        void* hip_stream);
+int mtts_lstm_bptt(int N, int T, int H, const float* gates, const float* cseq, const float* dh_ext, const float* dh_last, const float* whh,
+                   float* dgates, void* hip_stream);
+int mtts_dvec_head(int N, int H, int E, const float* hlast, const float* wT, const float* bias, float* part, float* eraw, void* hip_stream);
+int mtts_dvec_head_bwd(int N, int H, int E, const float* eraw, const float* dpart, const float* w, float* dz, float* dh_last, void* hip_stream);
+int mtts_dvec_utterance(int B, int E, const float* part, const int* off, float* out, void* hip_stream);
+int mtts_dvec_utterance_bwd(int B, int E, const float* part, const int* off, const float* dout, float* dpart, void* hip_stream);
 
 /* ---- MelGAN generator: mel -> waveform --------------------------------------------
  * Replaces `LightningMelGAN.inverse / infer`, lightning/utils.py:8-30 (vocoder.mel2wav of torch.hub

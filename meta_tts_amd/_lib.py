@@ -142,6 +142,12 @@ EXPORTS = {
     "mtts_batchnorm_jvp_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13 + [C.c_int] + [C.c_void_p] * 6),
     "mtts_rowdot_jvp": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 9),
     "mtts_rowdot_jvp_bwd": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "mtts_lstm_recurrent": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 8),
+    "mtts_lstm_bptt": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 7),
+    "mtts_dvec_head": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 6),
+    "mtts_dvec_head_bwd": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 6),
+    "mtts_dvec_utterance": (C.c_int, [C.c_int] * 2 + [C.c_void_p] * 4),
+    "mtts_dvec_utterance_bwd": (C.c_int, [C.c_int] * 2 + [C.c_void_p] * 5),
     "mtts_dvector_create": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_void_p)]),
     "mtts_dvector_destroy": (None, [C.c_void_p]),
     "mtts_dvector_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -23,6 +23,13 @@ namespace mtts {
 
 __device__ __forceinline__ float dv_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
+// The shapes the kernels of this file serve: one workgroup of H threads with 2 * 1024 / 4 * 1024 floats of LDS (H a multiple of the wavefront,
+// <= 1024), E <= 256 in whole float4 groups (dz_s[256], four wavefront partials; the GEMMs behind dz read rows of E floats as float4),
+// T >= 1 frames and n >= 1 workgroups.  DVector::init and the C entries of kernel_api.inc refuse everything else through this one predicate.
+inline bool dvec_bad_shape(int H, int E, int T, int n) { return H < 64 || H > 1024 || (H & 63) || E < 4 || E > 256 || (E & 3) || T < 1 || n < 1; }
+constexpr int kDvChunk = 32;   // terms per partial sum of the recurrent dot products (H is a multiple of 64)
+inline unsigned dvec_emb_block(int E) { return (unsigned)((E + 63) & ~63); }   // workgroup of the head / utterance kernels: E rounded up to whole wavefronts
+
 // xp: [N][T][4H] input projections (biases included); whhT: [H][4H]; hseq: [N][T][H] (all hidden states, the next layer's input);
 // hlast: [N][H] final hidden state.  blockDim.x == H.  Training passes also keep what the backward sweep needs: gates [N][T][4H]
 // (i, f, g, o AFTER their non-linearities), cseq [N][T][H], hprev [N][T][H] (the hidden state each step started from).
@@ -42,11 +49,16 @@ __global__ void lstm_recurrent_kernel(const float* xp, const float* whhT, float*
         float gi = px[(long long)t * 4 * H + j], gf = px[(long long)t * 4 * H + H + j];
         float gg = px[(long long)t * 4 * H + 2 * H + j], go = px[(long long)t * 4 * H + 3 * H + j];
         const float* w = whhT + j;
+        // partial sums of kDvChunk terms, added up afterwards: the rounding error grows with kDvChunk + H / kDvChunk terms, not with H
+        for (int k0 = 0; k0 < H; k0 += kDvChunk) {
+            float si = 0.f, sf = 0.f, sg = 0.f, so = 0.f;
 #pragma unroll 4
-        for (int k = 0; k < H; ++k) {
-            const float hk = hin[k];
-            gi += w[0] * hk; gf += w[H] * hk; gg += w[2 * H] * hk; go += w[3 * H] * hk;
-            w += 4 * H;
+            for (int k = k0; k < k0 + kDvChunk; ++k) {
+                const float hk = hin[k];
+                si += w[0] * hk; sf += w[H] * hk; sg += w[2 * H] * hk; so += w[3 * H] * hk;
+                w += 4 * H;
+            }
+            gi += si; gf += sf; gg += sg; go += so;
         }
         gi = dv_sigmoid(gi); gf = dv_sigmoid(gf); gg = tanhf(gg); go = dv_sigmoid(go);
         c = gf * c + gi * gg;
@@ -63,6 +75,11 @@ __global__ void lstm_recurrent_kernel(const float* xp, const float* whhT, float*
         __syncthreads();
     }
     hlast[(long long)n * H + j] = hv;
+}
+// N partial utterances of T frames; hseq may be null (top layer of an inference pass); gates / cseq / hprev: all three or none
+inline void launch_lstm_recurrent(int N, int T, int H, const float* xp, const float* whhT, float* hseq, float* hlast, float* gates, float* cseq,
+                                  float* hprev, hipStream_t st) {
+    MTTS_LAUNCH(lstm_recurrent_kernel, dim3((unsigned)N), dim3((unsigned)H), st, xp, whhT, hseq, hlast, T, H, gates, cseq, hprev);
 }
 
 // Backward sweep of one layer (BPTT), one workgroup per partial utterance, thread j = hidden unit j.  dh_ext [N][T][H]: gradient
@@ -93,11 +110,19 @@ __global__ void lstm_bptt_kernel(const float* gates, const float* cseq, const fl
         __syncthreads();
         float acc = 0.f;
         const float* w = whh + j;
+        for (int r0 = 0; r0 < 4 * H; r0 += kDvChunk) {   // chunked as in the forward: 4H terms
+            float sacc = 0.f;
 #pragma unroll 4
-        for (int r = 0; r < 4 * H; ++r) { acc += dg_s[r] * w[0]; w += H; }
+            for (int r = r0; r < r0 + kDvChunk; ++r) { sacc += dg_s[r] * w[0]; w += H; }
+            acc += sacc;
+        }
         dh_rec = acc;
         __syncthreads();
     }
+}
+inline void launch_lstm_bptt(int N, int T, int H, const float* gates, const float* cseq, const float* dh_ext, const float* dh_last, const float* whh,
+                             float* dgates, hipStream_t st) {
+    MTTS_LAUNCH(lstm_bptt_kernel, dim3((unsigned)N), dim3((unsigned)H), st, gates, cseq, dh_ext, dh_last, whh, dgates, T, H);
 }
 
 // e = relu(W h + b), then e / ||e||   (one workgroup per partial utterance, blockDim.x = E rounded up to whole wavefronts; wT: [H][E]);
@@ -109,9 +134,9 @@ __global__ void dvec_head_kernel(const float* hlast, const float* wT, const floa
     __syncthreads();
     float e = 0.f;
     if (j < E) {
-        e = bias[j];
-        for (int k = 0; k < H; ++k) e += wT[(long long)k * E + j] * dv_smem[k];
-        e = e > 0.f ? e : 0.f;
+        double acc = (double)bias[j];   // (N * E short dot products per launch: float64 accumulation costs nothing here and rounds once)
+        for (int k = 0; k < H; ++k) acc += (double)wT[(long long)k * E + j] * (double)dv_smem[k];
+        e = acc > 0.0 ? (float)acc : 0.f;
     }
     const float ss = wave_sum(e * e);
     if ((j & 63) == 0) dv_smem[H + (j >> 6)] = ss;   // E <= 256: at most four wavefronts
@@ -119,6 +144,9 @@ __global__ void dvec_head_kernel(const float* hlast, const float* wT, const floa
     float tot = 0.f;
     for (int w = 0; w < (int)(blockDim.x + 63) / 64; ++w) tot += dv_smem[H + w];
     if (j < E) { part[(long long)n * E + j] = e / sqrtf(tot); if (eraw) eraw[(long long)n * E + j] = e; }
+}
+inline void launch_dvec_head(int N, int H, int E, const float* hlast, const float* wT, const float* bias, float* part, float* eraw, hipStream_t st) {
+    MTTS_LAUNCH(dvec_head_kernel, dim3((unsigned)N), dim3(dvec_emb_block(E)), st, hlast, wT, bias, part, H, E, eraw);
 }
 
 // backward of the utterance reduction: out_b = m / max(||m||, 1e-12), m = mean of the utterance's partials -> dpart[n] for its partials
@@ -144,6 +172,9 @@ __global__ void dvec_utterance_bwd_kernel(const float* part, const int* off, con
     else dm = d / 1e-12f;                              // clamped branch of F.normalize
     dm /= (float)(hi - lo);
     if (j < E) for (int n = lo; n < hi; ++n) dpart[(long long)n * E + j] = dm;
+}
+inline void launch_dvec_utterance_bwd(int B, int E, const float* part, const int* off, const float* dout, float* dpart, hipStream_t st) {
+    MTTS_LAUNCH(dvec_utterance_bwd_kernel, dim3((unsigned)B), dim3(dvec_emb_block(E)), st, part, off, dout, dpart, E);
 }
 
 // backward of the head: y = e / ||e||, e = relu(z): dz [N][E] (gradient of the Linear output) and dh_last [N][H] = dz W  (w: [E][H])
@@ -173,6 +204,9 @@ __global__ void dvec_head_bwd_kernel(const float* eraw, const float* dpart, cons
         dh_last[(long long)n * H + k] = acc;
     }
 }
+inline void launch_dvec_head_bwd(int N, int H, int E, const float* eraw, const float* dpart, const float* w, float* dz, float* dh_last, hipStream_t st) {
+    MTTS_LAUNCH(dvec_head_bwd_kernel, dim3((unsigned)N), dim3(dvec_emb_block(E)), st, eraw, dpart, w, dz, dh_last, H, E);
+}
 
 // utterance b: mean of the partial embeddings [off[b], off[b+1]), then F.normalize (x / max(||x||, 1e-12))
 __global__ void dvec_utterance_kernel(const float* part, const int* off, float* out, int E) {
@@ -192,6 +226,9 @@ __global__ void dvec_utterance_kernel(const float* part, const int* off, float* 
     const float nrm = sqrtf(tot);
     if (j < E) out[(long long)b * E + j] = m / (nrm > 1e-12f ? nrm : 1e-12f);
 }
+inline void launch_dvec_utterance(int B, int E, const float* part, const int* off, float* out, hipStream_t st) {
+    MTTS_LAUNCH(dvec_utterance_kernel, dim3((unsigned)B), dim3(dvec_emb_block(E)), st, part, off, out, E);
+}
 
 // dst[c][r] = src[r][c]
 __global__ void dv_transpose_kernel(const float* src, float* dst, int R, int Cc) {
@@ -199,6 +236,9 @@ __global__ void dv_transpose_kernel(const float* src, float* dst, int R, int Cc)
         const int r = (int)(i / Cc), c = (int)(i % Cc);
         dst[(long long)c * R + r] = src[i];
     }
+}
+inline void launch_dv_transpose(const float* src, float* dst, int R, int Cc, unsigned blocks, hipStream_t st) {   // (grid-stride: any block count)
+    MTTS_LAUNCH(dv_transpose_kernel, dim3(blocks), dim3(256), st, src, dst, R, Cc);
 }
 __global__ void dv_add_kernel(const float* a, const float* b, float* o, int n) {
     for (int i = blockIdx.x * (int)blockDim.x + threadIdx.x; i < n; i += (int)(gridDim.x * blockDim.x)) o[i] = a[i] + b[i];
@@ -243,9 +283,8 @@ public:
 
     int init(int n_mels_, int hidden, int layers_, int emb, int max_partials, int frames, int max_utts) {
         n_mels = n_mels_; H = hidden; layers = layers_; E = emb; cap_N = max_partials; T = frames; cap_B = max_utts;
-        if (n_mels < 4 || (n_mels & 3) || H < 64 || H > 1024 || (H & 63) || E < 4 || E > 256 || layers < 1 || layers > 8 || cap_N < 1 || T < 1 ||
-            cap_B < 1) {
-            set_error("unsupported d-vector configuration (n_mels % 4, hidden % 64 <= 1024, emb <= 256)");
+        if (n_mels < 4 || (n_mels & 3) || dvec_bad_shape(H, E, T, cap_N < cap_B ? cap_N : cap_B) || layers < 1 || layers > 8) {
+            set_error("unsupported d-vector configuration (n_mels % 4, hidden % 64 <= 1024, emb % 4 <= 256)");
             return -1;
         }
         for (int l = 0; l < layers; ++l) {
@@ -304,12 +343,11 @@ public:
     int refresh() {
         for (int l = 0; l < layers; ++l) {
             const std::string s = std::to_string(l);
-            MTTS_LAUNCH(dv_transpose_kernel, dim3(512), dim3(256), stream, P("lstm.weight_hh_l" + s),
-                        whhT + (long long)l * 4 * H * H, 4 * H, H);
+            launch_dv_transpose(P("lstm.weight_hh_l" + s), whhT + (long long)l * 4 * H * H, 4 * H, H, 512, stream);
             MTTS_LAUNCH(dv_add_kernel, dim3(8), dim3(256), stream, P("lstm.bias_ih_l" + s),
                         P("lstm.bias_hh_l" + s), bsum + (long long)l * 4 * H, 4 * H);
         }
-        MTTS_LAUNCH(dv_transpose_kernel, dim3(256), dim3(256), stream, P("linear.weight"), linT, E, H);
+        launch_dv_transpose(P("linear.weight"), linT, E, H, 256, stream);
         DEV_CHECK(hipGetLastError());
         dirty = false;
         return 0;
@@ -356,15 +394,13 @@ public:
             g.bias = bsum + (long long)l * 4 * H;
             gemm_launch(gx, GEMM_NT, g, (int)rows, 4 * H, 1, stream, tile, 2.0 * rows * 4.0 * H * in_dim(l), 0);
             float* hs = train ? hkeep[l] : ((l + 1 < layers) ? hseq[l & 1] : nullptr);
-            MTTS_LAUNCH(lstm_recurrent_kernel, dim3((unsigned)N), dim3((unsigned)H), stream, (const float*)xp,
-                        (const float*)(whhT + (long long)l * 4 * H * H), hs, hlast, T, H, train ? gates[l] : (float*)nullptr,
-                        train ? cseq[l] : (float*)nullptr, train ? hprev[l] : (float*)nullptr);
+            launch_lstm_recurrent(N, T, H, xp, whhT + (long long)l * 4 * H * H, hs, hlast, train ? gates[l] : nullptr, train ? cseq[l] : nullptr,
+                                  train ? hprev[l] : nullptr, stream);
             x = hs;
         }
-        MTTS_LAUNCH(dvec_head_kernel, dim3((unsigned)N), dim3((unsigned)((E + 63) & ~63)), stream, (const float*)hlast, (const float*)linT,
-                    P("linear.bias"), part, H, E, train ? eraw : (float*)nullptr);
+        launch_dvec_head(N, H, E, hlast, linT, P("linear.bias"), part, train ? eraw : nullptr, stream);
         if (train) { last_N = N; last_B = B; have_forward = true; }
-        MTTS_LAUNCH(dvec_utterance_kernel, dim3((unsigned)B), dim3((unsigned)((E + 63) & ~63)), stream, (const float*)part, (const int*)off_dev, out, E);
+        launch_dvec_utterance(B, E, part, off_dev, out, stream);
         if (gx.error) { set_error(std::string("GEMM launcher: ") + gx.error); gx.error = nullptr; return -1; }
         DEV_CHECK(hipGetLastError());
         DEV_CHECK(hipMemcpyAsync(out_host, out, (size_t)B * E * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -386,18 +422,15 @@ public:
         if (!train_ready || !have_forward || !dout_host) { set_error("d-vector backward without a training forward"); return -1; }
         const int N = last_N, B = last_B;
         const long long rows = (long long)N * T;
-        const unsigned eb = (unsigned)((E + 63) & ~63);
         DEV_CHECK(hipMemsetAsync(grads, 0, (size_t)tab.n_params * sizeof(float), stream));
         DEV_CHECK(hipMemcpyAsync(dout, dout_host, (size_t)B * E * sizeof(float), hipMemcpyHostToDevice, stream));
-        MTTS_LAUNCH(dvec_utterance_bwd_kernel, dim3((unsigned)B), dim3(eb), stream, (const float*)part, (const int*)off_dev, (const float*)dout, dpart, E);
-        MTTS_LAUNCH(dvec_head_bwd_kernel, dim3((unsigned)N), dim3(eb), stream, (const float*)eraw, (const float*)dpart,
-                    P("linear.weight"), dz, dh_last, H, E);
+        launch_dvec_utterance_bwd(B, E, part, off_dev, dout, dpart, stream);
+        launch_dvec_head_bwd(N, H, E, eraw, dpart, P("linear.weight"), dz, dh_last, stream);
         wgrad(dz, E, hlast, H, N, grads + find("linear.weight"), grads + find("linear.bias"));
         const float* dh_ext = nullptr;
         for (int l = layers - 1; l >= 0; --l) {
             const std::string s = std::to_string(l);
-            MTTS_LAUNCH(lstm_bptt_kernel, dim3((unsigned)N), dim3((unsigned)H), stream, (const float*)gates[l], (const float*)cseq[l], dh_ext,
-                        (const float*)(l == layers - 1 ? dh_last : nullptr), P("lstm.weight_hh_l" + s), dgates, T, H);
+            launch_lstm_bptt(N, T, H, gates[l], cseq[l], dh_ext, l == layers - 1 ? dh_last : nullptr, P("lstm.weight_hh_l" + s), dgates, stream);
             const float* x = l == 0 ? mels : hkeep[l - 1];
             wgrad(dgates, 4 * H, x, in_dim(l), rows, grads + find("lstm.weight_ih_l" + s), grads + find("lstm.bias_ih_l" + s));
             wgrad(dgates, 4 * H, hprev[l], H, rows, grads + find("lstm.weight_hh_l" + s), nullptr);
@@ -411,6 +444,8 @@ public:
                 dh_ext = dx;
             }
         }
+        // (a refused GEMM launch would leave its gradient at the zeros of the memset above: report it, and keep the forward's state for another try)
+        if (gx.error) { set_error(std::string("GEMM launcher: ") + gx.error); gx.error = nullptr; return -1; }
         DEV_CHECK(hipGetLastError());
         have_forward = false;
         return 0;

@@ -395,3 +395,49 @@ int mtts_rowdot_jvp_bwd(int rows, int C, const float* dout, const float* tgout, 
     launch_rowdot_jvp_bwd(one_task(k, rows, META_MP, nullptr, stream), T0(dout), T0(tgout), T0(w), T0(tw), T0(dx), T0(tdx), C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// d-vector speaker encoder kernels (dvector.h), each through the launcher DVector::forward / backward use.  No scratch: `ws` is not needed.
+// Shapes: dvec_bad_shape, the predicate of DVector::init (H a multiple of 64 in 64 .. 1024, E a multiple of 4 in 4 .. 256, T, N, B >= 1).
+// lstm_recurrent: xp [N][T][4H] gate pre-activations from the input (biases included; gate order i, f, g, o), whhT [H][4H] the TRANSPOSED
+// recurrent weight -> hlast [N][H], hseq [N][T][H] (or null) and, for a training pass, gates [N][T][4H] (after their non-linearities),
+// cseq [N][T][H], hprev [N][T][H] — all three or none.
+int mtts_lstm_recurrent(int N, int T, int H, const float* xp, const float* whhT, float* hseq, float* hlast, float* gates, float* cseq, float* hprev,
+                        void* stream) {
+    const int kept = (gates != nullptr) + (cseq != nullptr) + (hprev != nullptr);
+    if (dvec_bad_shape(H, 4, T, N) || !xp || !whhT || !hlast || (kept != 0 && kept != 3)) return -1;
+    launch_lstm_recurrent(N, T, H, xp, whhT, hseq, hlast, gates, cseq, hprev, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// BPTT of one layer on the gates / cseq of the launch above: dh_ext [N][T][H] (gradient reaching every h_t from above, or null), dh_last
+// [N][H] (gradient of the final hidden state, or null), whh [4H][H] in torch's layout -> dgates [N][T][4H], the gradient of the gate pre-activations
+int mtts_lstm_bptt(int N, int T, int H, const float* gates, const float* cseq, const float* dh_ext, const float* dh_last, const float* whh,
+                   float* dgates, void* stream) {
+    if (dvec_bad_shape(H, 4, T, N) || !gates || !cseq || !whh || !dgates) return -1;
+    launch_lstm_bptt(N, T, H, gates, cseq, dh_ext, dh_last, whh, dgates, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// head: raw = relu(hlast W^T + bias), part = raw / ||raw||  (hlast [N][H], wT [H][E] the TRANSPOSED Linear weight, part [N][E], eraw [N][E] = raw or null)
+int mtts_dvec_head(int N, int H, int E, const float* hlast, const float* wT, const float* bias, float* part, float* eraw, void* stream) {
+    if (dvec_bad_shape(H, E, 1, N) || !hlast || !wT || !bias || !part) return -1;
+    launch_dvec_head(N, H, E, hlast, wT, bias, part, eraw, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// its backward: dpart [N][E] -> dz [N][E] (gradient of the Linear output) and dh_last [N][H] = dz W  (w [E][H] in torch's layout)
+int mtts_dvec_head_bwd(int N, int H, int E, const float* eraw, const float* dpart, const float* w, float* dz, float* dh_last, void* stream) {
+    if (dvec_bad_shape(H, E, 1, N) || !eraw || !dpart || !w || !dz || !dh_last) return -1;
+    launch_dvec_head_bwd(N, H, E, eraw, dpart, w, dz, dh_last, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// utterance b: out[b] = m / max(||m||, 1e-12), m = mean of part[off[b] .. off[b + 1]); off [B + 1] DEVICE ints, non-decreasing (not read
+// here: the caller's part / dpart hold off[B] rows)
+int mtts_dvec_utterance(int B, int E, const float* part, const int* off, float* out, void* stream) {
+    if (dvec_bad_shape(64, E, 1, B) || !part || !off || !out) return -1;
+    launch_dvec_utterance(B, E, part, off, out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// its backward: dout [B][E] -> dpart [off[B]][E] (an utterance without partials writes nothing)
+int mtts_dvec_utterance_bwd(int B, int E, const float* part, const int* off, const float* dout, float* dpart, void* stream) {
+    if (dvec_bad_shape(64, E, 1, B) || !part || !off || !dout || !dpart) return -1;
+    launch_dvec_utterance_bwd(B, E, part, off, dout, dpart, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -10,9 +10,10 @@ import numpy as np
 import torch
 
 
-def build(sd, n_mels=40, hidden=256, emb=256, layers=3):
-    lstm = torch.nn.LSTM(n_mels, hidden, layers, batch_first=True)
-    linear = torch.nn.Linear(hidden, emb)
+def build(sd, n_mels=40, hidden=256, emb=256, layers=3, dtype=torch.float32):
+    """The modules with the float32 weights of `sd`, held and evaluated in `dtype` (float64: the arbiter of the float32 parties)."""
+    lstm = torch.nn.LSTM(n_mels, hidden, layers, batch_first=True).to(dtype)
+    linear = torch.nn.Linear(hidden, emb).to(dtype)
     with torch.no_grad():
         for k in range(layers):
             for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
@@ -26,7 +27,7 @@ def partial_embeds(sd, mels, **kw):
     """resemblyzer VoiceEncoder.forward: (N, T, n_mels) -> (N, emb), L2-normalised."""
     lstm, linear = build(sd, **kw)
     with torch.no_grad():
-        _, (hidden, _) = lstm(torch.as_tensor(np.asarray(mels, np.float32)))
+        _, (hidden, _) = lstm(torch.as_tensor(np.asarray(mels, np.float32)).to(linear.weight.dtype))
         raw = torch.relu(linear(hidden[-1]))
         return raw / torch.norm(raw, dim=1, keepdim=True)
 

@@ -1,6 +1,6 @@
-"""A kernel defined in meta_tts_amd/csrc/rowops.h or tangent.h is launched from exactly ONE place in csrc/: its inline host launcher
+"""A kernel defined in meta_tts_amd/csrc/rowops.h, tangent.h or dvector.h is launched from exactly ONE place in csrc/: its inline host launcher
 (launch_*) next to the kernel.  The engine and the raw C entries of kernel_api.inc both go through that launcher, so the float64 pins of
-test_kernel_entries.py / test_tangent_entries.py hold for the launch the product uses.  Source-level, CPU only."""
+test_kernel_entries.py / test_tangent_entries.py / test_dvector_kernels.py hold for the launch the product uses.  Source-level, CPU only."""
 from __future__ import annotations
 
 import glob
@@ -19,8 +19,9 @@ def _read(path):
 
 
 def test_one_launch_site_per_row_kernel():
-    kernels = [k for h in ("rowops.h", "tangent.h") for k in KERNEL.findall(_read(os.path.join(CSRC, h)))]
-    assert len(kernels) > 60 and len(set(kernels)) == len(kernels), kernels
+    kernels = [k for h in ("rowops.h", "tangent.h", "dvector.h") for k in KERNEL.findall(_read(os.path.join(CSRC, h)))]
+    assert len(kernels) > 70 and {"lstm_recurrent_kernel", "lstm_bptt_kernel", "dvec_head_kernel", "dvec_head_bwd_kernel", "dvec_utterance_kernel",
+                                  "dvec_utterance_bwd_kernel"} <= set(kernels) and len(set(kernels)) == len(kernels), kernels
     sites = {}
     for path in sorted(glob.glob(os.path.join(CSRC, "*"))):
         for name in LAUNCH.findall(_read(path)):
