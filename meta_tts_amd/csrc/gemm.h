@@ -1105,457 +1105,7 @@ struct GemmProfiler {
         if (dump) fclose(dump);
     }
 };
-constexpr int kGemmXcdSwizzle = 1;     // XCD-grouped tile order of the plain grids (xcd_group_remap)
-constexpr int kGemmDefaultBk = 16;     // K-slice of the register-staged kernels (32 for long K-contiguous panels, see gemm_launch)
-constexpr bool kGemmDefaultPipe = true;  // software-pipelined K-loop
-inline int gemm_kloop_variant() { return knobs().kloop; }   // K-loop variant of the pipelined 64x64 kernels (gemm_f32_kloop: KL): same k order in every accumulator chain, bit-identical
-// The KL >= 1 loops step their operand pointers by loop-invariant distances, which needs conv taps that are whole multiples of the K-slice
-// (every channel count of the model is a multiple of 16; anything else keeps the generic KL = 0 loop)
-inline int gemm_kloop_for(const GemmArgs& g, int bk) {
-    const bool ok = (g.taps <= 1 || g.tap_k % bk == 0) && (g.a_tap_k >= 0x40000000 || g.a_tap_k % bk == 0);
-    return ok ? gemm_kloop_variant() : 0;
-}
-inline int gemm_xcd_swizzle() { return kGemmXcdSwizzle; }
-inline int gemm_default_bk() { return kGemmDefaultBk; }
-inline bool gemm_default_pipe() { return kGemmDefaultPipe; }
-
-// Split-K workspace (partial tiles + tile counters): used by one GemmCtx, allocated once from its owner's heap by the owner's create.
-struct GemmWorkspace { float* ws = nullptr; int* ctr = nullptr; };
-constexpr long long kSplitWsFloats = 16ll << 20;  // 64 MB of partial tiles
-constexpr int kSplitCtrs = 1 << 16;
-constexpr int kLnCtrs = 4096;                     // the last kLnCtrs counters: arrival counters of row-complete LayerNorm epilogues (LnFuse)
-
-// Launch batching: between gemm_batch_begin() and gemm_batch_end() every eligible gemm_launch (automatic tile choice) is queued
-// instead of launched; gemm_batch_end() issues the queue as ONE launch (gemm_f32_multi_kernel / gemm_glds_multi_kernel).
-// The caller guarantees the queued problems are mutually independent and that nothing launched before gemm_batch_end()
-// reads their outputs (engine: the wgrad / dgrad pair of a layer, dQ / dK / dV of an attention block).
-struct GemmPending { int form; GemmArgs g; int max_M, max_N, groups; double flops, rows, bytes; int tag = -1; };   // tag: GemmCtx::next_tag when it was queued
-struct GemmBatch { bool open = false; std::vector<GemmPending> q; int force_family = 0; int force_tile = 0; };   // force_family: 16 / 32 (BK of the register-staged multi-problem kernel) or 4064 (LDS-DMA) for the next flush (explicit tile codes of dual-source problems)
-
-// Every piece of MUTABLE launcher state — the launch-batching queue, the per-launch profiler, the split-K workspace —
-// lives in a context owned by one handle (Engine / Vocoder / ...), so two handles on two host threads share nothing
-// (include/mtts.h conventions).  The workspace is allocated by the owner's create, never lazily; a context without one (the
-// handle-less kernel entry points) never splits K.  One context = one stream (the split-K slabs / counters of consecutive
-// launches are reused in stream order).
-struct GemmCtx {
-    GemmBatch batch;
-    GemmProfiler prof;
-    GemmWorkspace wsp;
-    int last_kind = GK_OTHER;  // kernel kind of the last launch (profiler)
-    long long plane_problems = 0;   // problems launched on the plane-staged K-loop (bf16 mode; a test / diagnostic counter)
-    bool bf16 = false;         // numerics mode of the owner: bf16 operand family (gemm_bf16.h) for every problem it can take
-    const char* error = nullptr;   // sticky: a launch the launcher refused (the C ABI entry points turn it into an error return)
-    bool flushing = false;     // gemm_batch_end is issuing the queue
-    bool prefer_bk16 = false;   // multi-problem launches of this context take the BK = 16 kernels (20 KB of LDS per workgroup instead of 37) whatever their K
-    int wave_prio = 0;      // GemmArgs::wave_prio of every launch of this context (the engine sets it on the critical stream's context while side streams carry work)
-    bool no_glds = false;   // never pick the LDS-DMA kernels (48 KB of LDS per workgroup: a side-stream launch would leave no LDS for the main stream's)
-    bool no_splitk = false;   // never split K (the split factor follows the batch's size: an owner whose results must not depend on what else is in the batch sets it)
-    // What the launcher decided for the problems queued under a tag (next_tag >= 0 while they are queued: mtts_gemm_f32_grouped): the split
-    // factor and the placement (0 plain / XCD-grouped order, 1 task-per-XCD schedule, 2 panel order).  Host bookkeeping only.
-    int next_tag = -1;
-    int note_splitk[kGemmMultiMax] = {0}, note_place[kGemmMultiMax] = {0};
-    int last_place = 0;   // placement of the last stand-alone launch
-    void note(int tag, int S, int place) { if (tag >= 0 && tag < kGemmMultiMax) { note_splitk[tag] = S; note_place[tag] = place; } }
-    DevHeap* heap = nullptr;   // the owner's: the workspace and the profiler's events come from it and go back with it
-    int alloc_workspace(DevHeap& h) {
-        heap = &h;
-        if (wsp.ws) return 0;
-        if (h.alloc(wsp.ws, kSplitWsFloats * sizeof(float)) != hipSuccess || h.alloc_zeroed(wsp.ctr, (kSplitCtrs + 16) * sizeof(int)) != hipSuccess) {
-            h.give_back(wsp.ws);
-            h.give_back(wsp.ctr);
-            return -1;
-        }
-        return 0;
-    }
-};
-// LnFuse (requested by the caller through g.ln.y): can this launch carry it, and its counter slice.  `used` = counters already handed out
-// inside the same launch.  Returns false (and sets cx.error) when the request cannot be honoured — the engine asks gemm_ln_fusable first.
-inline bool gemm_ln_fusable(const GemmCtx& cx, int form, const GemmArgs& g, int max_M, int groups) {
-    return form == GEMM_NT && !cx.bf16 && cx.wsp.ctr != nullptr && gemm_kloop_variant() == 4 && g.N <= 256 && g.N % 4 == 0 && !g.table && !g.c_rowmap && !g.A2 &&
-           !(g.flags & GEMM_ACCUM) && !g.colsum && (long long)groups * ((max_M + 63) / 64) <= kLnCtrs;
-}
-inline bool gemm_ln_bind(GemmCtx& cx, int form, GemmArgs& g, int max_M, int groups, int tile, int& used) {
-    if (!g.ln.y) { g.ln.ctr = nullptr; return true; }
-    const int tiles_m = (max_M + 63) / 64;
-    if (tile != 64 || !gemm_ln_fusable(cx, form, g, max_M, groups) || used + groups * tiles_m > kLnCtrs) {
-        cx.error = "row-complete LayerNorm epilogue requested for a launch that cannot carry it";
-        return false;
-    }
-    g.ln.ctr = cx.wsp.ctr + (kSplitCtrs - kLnCtrs) + used;
-    g.tiles_pg = tiles_m;   // (counter stride between groups; the problem is never split, so the split-K meaning of the field is free)
-    g.splitk = 1;
-    used += groups * tiles_m;
-    return true;
-}
-inline void gemm_batch_begin(GemmCtx& cx) { cx.batch.open = true; }
-inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream);
-
-// LDS-DMA kernel family (gemm_glds.h, device builds only).  Round 5: with the interleaved K-loop (KL = 4) the register-staged kernels beat it in the
-// latency regime it was built for (profiles/r05_kloop_ab.md), so the automatic tile choice takes it only under MTTS_GLDS=1 (knobs.h) — GemmCtx::no_glds
-// (engine.h: set_regime) can then still veto it per pass; tile code 4064 selects the family explicitly (kernel tests, micro-benchmarks).
-inline int gemm_glds_mode() { return knobs().glds; }
-inline bool gemm_use_glds() { return gemm_glds_mode() != 0; }
-inline bool gemm_glds_ok(const GemmArgs& g) { return !(g.taps > 1 && g.tap_k % 32 != 0); }
-// n-tiles of a problem's grid: the tiles of C plus the column-sum tile (GemmArgs::colsum)
-inline int gemm_tiles_n(const GemmArgs& g, int max_N, int t) { return (max_N + t - 1) / t + (g.colsum ? 1 : 0); }
-// Launches up to this many workgroups take the LDS-DMA kernels (latency regime: few workgroups per CU, where the DMA
-// ring's two slices in flight replace the occupancy the register-staged kernel needs; measured +8 % / +14 % on the
-// single-task first- / second-order step), larger ones the register-staged kernels (5 vs 3 workgroups per CU resident:
-// +3 % on the full 8-task step).
-inline long gemm_glds_max_wgs() { return 768L; }
-#if !defined(MTTS_EMU)
-inline void gemm_glds_launch(int form, const GemmArgs& g, dim3 grid, hipStream_t stream);
-inline void gemm_glds_multi_launch(const GemmMulti& mp, dim3 grid, hipStream_t stream, bool dual = false);
-#endif
-
-// bf16 operand family (gemm_bf16.h)
-inline bool gemm_bf16_ok(const GemmArgs& g);
-inline bool gemm_bf16_planes_ok(int form, const GemmArgs& g);
-inline int gemm_bf16_launch(int form, const GemmArgs& g, int T, dim3 grid, hipStream_t stream, int pf);      // returns the GemmKind launched
-inline int gemm_bf16_multi_launch(const GemmMulti& mp, int T, bool dual, dim3 grid, hipStream_t stream);
-// block tile of a bf16 launch: 128x128 once the launch still fills the chip twice over with it (the MFMA rate is 16x the fp32 kernels':
-// a 64x64 tile moves 1 byte per 16 flop through the L2 -> LDS path), 64x64 for under-filled launches
-inline int gemm_bf16_tile(double rows, int tiles_n128) { return std::ceil(rows / 128.0) * tiles_n128 >= 512.0 ? 128 : 64; }
-
-// Task-per-XCD schedule (XcdSched) of a problem: exactly 8 groups whose sizes the caller knows on the host, whole tiles.  MTTS_XCD_SCHED=0: off.
-inline bool gemm_xcd_sched_for(GemmArgs& g, int max_M, int max_N, int groups, int S, int tile) {
-    g.xs.on = 0;
-    if (!knobs().xcd_sched || (groups != 8 && groups != 4 && groups != 2) || groups < knobs().xcd_sched_min_groups || !g.host_dims || !g.dimptr || g.table || S != 1) return false;
-    int dims[8] = {0};
-    for (int z = 0; z < groups; ++z) dims[z] = g.host_dims[z] * g.dim_mult;
-    const int tn = gemm_tiles_n(g, max_N, tile);
-    if (g.dim_sel == 0) xcd_sched_build(g.xs, dims, 1, tn, 0, tile, groups);
-    else xcd_sched_build(g.xs, dims, 2, 1, ((max_M + tile - 1) / tile) * tn, 64, groups);
-    if (g.xs.maxlen <= 0) g.xs.on = 0;
-    if (knobs().xcd_sched_debug && g.xs.on) fprintf(stderr, "xcd_sched cls %d tn %d maxlen %d pool %d\n", g.xs.on, g.xs.tn, g.xs.maxlen, g.xs.P[8]);
-    return g.xs.on != 0;
-}
-inline long gemm_xcd_sched_slots(const XcdSched& s) { return 8L * s.maxlen * (s.on == 1 ? s.tn : 1); }
-// Panel order (xcd_panel_locate) for a problem: TASK mode, fewer than 8 groups (the task-per-XCD schedule covers 8), an under-filled
-// launch, and a B operand (N x K: the weight image of a forward / input-gradient problem) that is the bigger of the two — otherwise the
-// m-tile-major grouping, which keeps an m-tile's A panel in one L2, is already the right one.  Measured (profiles/r04_ab_log.md): the
-// k = 9 input gradient of a single-task rank 212 -> 194 us, its step 35.17 -> 34.73 ms.  MTTS_PANEL_ORDER=0: off (A/B runs).
-inline bool gemm_panel_order_for(const GemmArgs& g, int form, double rows, int max_M, int max_N, int groups) {
-    if (!knobs().panel_order || g.table || groups >= 8 || groups < 1) return false;
-    if (std::ceil(rows / 64.0) * gemm_tiles_n(g, max_N, 64) > (double)gemm_glds_max_wgs()) return false;   // chip-filling launches: measured slightly worse (C2: +1 %)
-    const double K = (double)gemm_keff(g);
-    const double a_bytes = form == GEMM_TN ? rows * max_M : rows / groups * (g.lda > 0 ? g.lda : K);   // unique bytes behind the A operand (per group)
-    const double b_bytes = form == GEMM_TN ? rows * max_N : (double)max_N * K;
-    (void)max_M;
-    return b_bytes > a_bytes;
-}
-
-// Host launcher.  max_M / max_N bound the tile grid over all groups.  tile = 0: automatic — the problem goes through the launch
-// queue (alone if no batch is open): a plain 64x64 grid (LDS-DMA kernels in the latency regime, a multi-problem grid for a batch).
-// An explicit tile code picks one kernel: 64 / 128 (+1000 software pipeline, +2000 BK = 32), 4064 LDS-DMA (kernel tests, micro-benchmarks).
-// total_M = sum of the groups' row counts (0: max_M * groups).  alg_flops / alg_bytes: algorithmic (unpadded) work of this launch,
-// profiler only.
-inline void gemm_launch(GemmCtx& cx, int form, const GemmArgs& g_in, int max_M, int max_N, int groups, hipStream_t stream,
-                        int tile = 0, double alg_flops = 0.0, long long total_M = 0, double alg_bytes = 0.0) {
-    if (max_M <= 0 || max_N <= 0 || groups <= 0) return;
-    GemmArgs g = g_in;
-    g.swizzle = gemm_xcd_swizzle();
-    g.wave_prio = cx.wave_prio;
-    // bf16 planes: kept only where the plane-staged K-loop will run (bf16 mode, an NT problem it can take); the twin of C in bf16 mode only
-    if (!(cx.bf16 && gemm_bf16_ok(g) && gemm_bf16_planes_ok(form, g))) {
-        if (g.plane_only) { cx.error = "plane-only GEMM problem outside the bf16 plane path"; return; }
-        g.Ah = g.Bh = nullptr;
-    }
-    if (!cx.bf16) g.Ch = nullptr;
-    const int user_tile = tile;
-    const double rows = total_M > 0 ? (double)total_M : (double)max_M * groups;
-    auto ntiles = [&](int t) { return (long)((max_M + t - 1) / t) * gemm_tiles_n(g, max_N, t); };
-    if (g.A2 && user_tile != 0 && !cx.flushing && !cx.batch.open) {
-        // dual-source problems exist in the multi-problem kernels only: an explicit tile code picks the family (kernel tests)
-        const int code = user_tile % 10000;
-        cx.batch.force_family = code == 4064 ? 4064 : (code / 2000 ? 32 : 16);
-        cx.batch.force_tile = code % 1000 == 128 ? 128 : 64;   // (bf16 mode: the block tile of the forced launch)
-        cx.batch.q.push_back(GemmPending{form, g, max_M, max_N, groups, alg_flops, rows, alg_bytes});
-        gemm_batch_end(cx, stream);
-        cx.batch.force_family = 0; cx.batch.force_tile = 0;
-        return;
-    }
-    if (user_tile == 0) {
-        if (!cx.flushing) {
-            // through the queue: with the batch's other problems, or alone
-            cx.batch.q.push_back(GemmPending{form, g, max_M, max_N, groups, alg_flops, rows, alg_bytes, cx.next_tag});
-            if (!cx.batch.open) {
-                gemm_batch_end(cx, stream);
-            } else if ((int)cx.batch.q.size() == kGemmMultiMax) { gemm_batch_end(cx, stream); cx.batch.open = true; }
-            return;
-        }
-        tile = 64;
-    }
-    if (g.A2) {   // (unreachable from the engine: gemm_batch_end never sends a dual-source problem to the stand-alone kernels)
-        cx.error = "dual-source GEMM handed to a stand-alone kernel (explicit tile code inside an open batch)";   // reported by the C ABI entry
-        return;
-    }
-    // tile code: 64 / 128 (+1000 software pipeline, +2000 BK=32); plain 64 / 128 take the defaults
-    bool pipe = gemm_default_pipe();
-    int bk = gemm_default_bk();
-    bool glds = false;
-    const bool bf16 = cx.bf16 && gemm_bf16_ok(g) && !g.A2;
-    if (bf16 && user_tile == 0) tile = gemm_bf16_tile(rows, gemm_tiles_n(g, max_N, 128));
-#if !defined(MTTS_EMU)
-    if (bf16) { if (tile == 4064) tile = 64; }
-    else if (tile == 4064) { glds = gemm_glds_ok(g); tile = 64; }            // explicit request (kernel tests, microbenchmarks)
-    else if (user_tile == 0 && tile == 64) {
-        const long wgs = (long)std::ceil(rows / 64.0) * gemm_tiles_n(g, max_N, 64);
-        glds = gemm_use_glds() && gemm_glds_ok(g) && wgs <= gemm_glds_max_wgs() && !cx.no_glds && !g.ln.y;
-    }
-#else
-    if (tile == 4064) tile = 64;
-#endif
-    const int ablate = tile / 10000;  // diagnostic stage ablation (NT 64x64 pipelined BK=16 only), see gemm_f32_kloop
-    tile %= 10000;
-    if (tile >= 1000) { pipe = (tile / 1000) & 1; bk = (tile / 2000) ? 32 : 16; tile %= 1000; }
-    if (user_tile == 0 && !g.table && gemm_keff(g) >= 1024 && (form == GEMM_NT || form == GEMM_TN)) bk = 32;  // long K-contiguous panels: full 128-B lines per row
-    if (g.taps > 1 && g.tap_k % 32 != 0) bk = 16;  // a K-slice must not straddle two conv taps
-    if (bf16) bk = 32;
-    // split-K for under-filled grids (single-task ranks, the phoneme-side GEMMs, small wgrads): enough workgroups for
-    // ~4 per CU, each still reducing >= 4 K-chunks
-    const int S = 1;   // (stand-alone launches never split K: the long chains of under-filled batches are cut in gemm_batch_end)
-    { int used = 0; if (!gemm_ln_bind(cx, form, g, max_M, groups, bf16 ? 0 : tile, used)) return; }
-    const int nth = 256;
-    const long grid_tiles = ntiles(tile);
-    dim3 block(nth), grid((unsigned)(grid_tiles * S), 1, (unsigned)groups);
-    cx.last_place = 0;
-    if (gemm_xcd_sched_for(g, max_M, max_N, groups, S, tile)) { grid = dim3((unsigned)gemm_xcd_sched_slots(g.xs), 1, 1); cx.last_place = 1; }   // 1-D, task-per-XCD order
-    else if (gemm_panel_order_for(g, form, rows, max_M, max_N, groups)) {
-        g.swizzle = 2; g.po_tiles_m = (max_M + tile - 1) / tile;
-        grid = dim3((unsigned)xcd_panel_slots(g.po_tiles_m, gemm_tiles_n(g, max_N, tile), S), 1, (unsigned)groups);
-        cx.last_place = 2;
-    }
-    GemmProfiler& prof = cx.prof;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof.enabled) { e0 = prof.get(*cx.heap); e1 = prof.get(*cx.heap); hipEventRecord(e0, stream); }
-    int kind = GK_OTHER;
-#define MTTS_GEMM_CASE(F, T)                                                                              \
-    if (form == F && tile == T) {                                                                         \
-        if (pipe && T == 64) {                                                                            \
-            const int kl = gemm_kloop_for(g, bk);                                                         \
-            if (F == GEMM_NT && g.ln.ctr) {   /* row-complete LayerNorm epilogue (LnFuse): instantiations of their own */    \
-                if (bk == 32) MTTS_LAUNCH((gemm_f32_kernel<GEMM_NT, 64, 64, 32, true, 2, 2, 0, 4, true>), grid, block, stream, g);   \
-                else MTTS_LAUNCH((gemm_f32_kernel<GEMM_NT, 64, 64, 16, true, 2, 2, 0, 4, true>), grid, block, stream, g);            \
-                kind = (bk == 32 ? GK_F32_64_BK32 : GK_F32_64_BK16) + F;                                  \
-            } else if (bk == 32) {                                                                        \
-                if (kl == 4) MTTS_LAUNCH((gemm_f32_kernel<F, 64, 64, 32, true, 2, 2, 0, 4>), grid, block, stream, g);        \
-                else if (kl == 1) MTTS_LAUNCH((gemm_f32_kernel<F, 64, 64, 32, true, 2, 2, 0, 1>), grid, block, stream, g);   \
-                else MTTS_LAUNCH((gemm_f32_kernel<F, 64, 64, 32, true, 2, 2, 0, 0>), grid, block, stream, g);                \
-                kind = GK_F32_64_BK32 + F;                                                                \
-            } else {                                                                                      \
-                if (kl == 4) MTTS_LAUNCH((gemm_f32_kernel<F, 64, 64, 16, true, 2, 2, 0, 4>), grid, block, stream, g);        \
-                else MTTS_LAUNCH((gemm_f32_kernel<F, 64, 64, 16, true, 2, 2, 0, 0>), grid, block, stream, g);                \
-                kind = GK_F32_64_BK16 + F;                                                                \
-            }                                                                                             \
-        }                                                                                                 \
-        else if (bk == 32 && pipe) { MTTS_LAUNCH((gemm_f32_kernel<F, T, T, 32, true>), grid, block, stream, g); kind = (T == 64 ? GK_F32_64_BK32 : GK_F32_128) + F; }   \
-        else if (bk == 32) { MTTS_LAUNCH((gemm_f32_kernel<F, T, T, 32, false>), grid, block, stream, g); kind = T == 64 ? GK_OTHER : GK_F32_128 + F; }     \
-        else if (pipe) { MTTS_LAUNCH((gemm_f32_kernel<F, T, T, 16, true>), grid, block, stream, g); kind = (T == 64 ? GK_F32_64_BK16 : GK_F32_128) + F; }          \
-        else { MTTS_LAUNCH((gemm_f32_kernel<F, T, T, 16, false>), grid, block, stream, g); kind = T == 64 ? GK_OTHER : GK_F32_128 + F; }                   \
-    }
-    if (bf16) {
-        if (g.Ah) ++cx.plane_problems;
-        kind = gemm_bf16_launch(form, g, tile, grid, stream, (user_tile % 10000) / 1000);   // (bf16 tile codes: T + 1000 * slices in flight, 0 = default)
-    } else
-#if !defined(MTTS_EMU)
-    if (glds) {
-        gemm_glds_launch(form, g, grid, stream);
-        kind = GK_GLDS + form;
-    } else
-#endif
-    {
-#if defined(MTTS_GEMM_ABLATION)
-#define MTTS_ABL(A) if (ablate == A && form == GEMM_NT) { MTTS_LAUNCH((gemm_f32_kernel<GEMM_NT, 64, 64, 16, true, 2, 2, A>), grid, block, stream, g); return; }
-        MTTS_ABL(1) MTTS_ABL(2) MTTS_ABL(3) MTTS_ABL(4) MTTS_ABL(7) MTTS_ABL(8) MTTS_ABL(15) MTTS_ABL(6) MTTS_ABL(14)
-#undef MTTS_ABL
-#else
-        (void)ablate;
-#endif
-        MTTS_GEMM_CASE(GEMM_NT, 128) MTTS_GEMM_CASE(GEMM_NT, 64)
-        MTTS_GEMM_CASE(GEMM_NN, 128) MTTS_GEMM_CASE(GEMM_NN, 64)
-        MTTS_GEMM_CASE(GEMM_TN, 128) MTTS_GEMM_CASE(GEMM_TN, 64)
-    }
-#undef MTTS_GEMM_CASE
-    cx.last_kind = kind;
-    if (prof.enabled) {
-        hipEventRecord(e1, stream);
-        GemmProfiler::Rec rec{kind, alg_flops, e0, e1};
-        rec.form = form; rec.tile = bf16 ? 16000 + tile : (glds ? 4064 : tile); rec.N = max_N; rec.K = gemm_keff(g); rec.groups = groups; rec.splitk = S;
-        rec.rows = rows;
-        rec.bytes = alg_bytes; rec.tag = prof.tag;
-        prof.recs.push_back(rec);
-    }
-}
-
-inline bool batch_full_regime(const std::vector<GemmPending>& q) {  // more workgroups than the latency regime's limit
-    double wgs = 0.0;
-    for (const GemmPending& p : q) wgs += std::ceil(p.rows / 64.0) * gemm_tiles_n(p.g, p.max_N, 64);
-    return wgs > (double)gemm_glds_max_wgs();
-}
-inline void gemm_batch_end(GemmCtx& cx, hipStream_t stream) {
-    GemmBatch& b = cx.batch;
-    b.open = false;
-    if (b.q.empty()) return;
-    struct Flush { GemmCtx& c; Flush(GemmCtx& x) : c(x) { c.flushing = true; } ~Flush() { c.flushing = false; } } guard(cx);
-    std::stable_sort(b.q.begin(), b.q.end(), [](const GemmPending& x, const GemmPending& y) { return gemm_keff(x.g) > gemm_keff(y.g); });
-    GemmProfiler& prof = cx.prof;
-    // a single queued problem normally takes the stand-alone launcher; in the latency regime it stays here, where the long-chain
-    // split-K rule applies (the k=9 dgrad of a single-task rank is 124 tiles x 288 slices: alone it would run at one tile per CU)
-    bool solo = b.q.size() == 1 && (!knobs().single_multi || batch_full_regime(b.q));
-    bool any_dual = false;   // dual-source problems (GemmArgs::A2) exist in the multi-problem kernels only
-    for (const GemmPending& p : b.q) any_dual = any_dual || p.g.A2 != nullptr;
-    if (any_dual) solo = false;
-    if (solo) {
-        const std::vector<GemmPending> q = b.q;
-        b.q.clear();
-        for (const GemmPending& p : q) {
-            gemm_launch(cx, p.form, p.g, p.max_M, p.max_N, p.groups, stream, 0, p.flops, (long long)p.rows, p.bytes);
-            cx.note(p.tag, 1, cx.last_place);
-        }
-        return;
-    }
-    GemmMulti mp;
-    mp.n = (int)b.q.size();
-    int max_groups = 0;
-    double flops = 0.0, rows = 0.0, bytes = 0.0;
-    int max_split = 1;   // (profiler record: the largest split factor among the launch's problems)
-    // split-K for the long chains of an under-filled batch: a tile whose K-loop is longer than two thirds (swept: 1 / 1.25 .. 1 / 1.5)
-    // of the whole batch's per-CU work would finish last on its own (single-task ranks: the k=9 dgrad tile, 576 slices, beside a
-    // batch that is worth ~590 slices per CU), so it is cut into S workgroups (rendezvous in splitk_combine)
-    double work = 0.0;
-    for (const GemmPending& p : b.q) work += std::ceil(p.rows / 64.0) * gemm_tiles_n(p.g, p.max_N, 64) * std::max(1, (gemm_keff(p.g) + 15) / 16);
-    const double per_cu = work / 256.0;
-    double batch_wgs = 0.0, batch_wgs128 = 0.0;
-    for (const GemmPending& p : b.q) {
-        batch_wgs += std::ceil(p.rows / 64.0) * gemm_tiles_n(p.g, p.max_N, 64);
-        batch_wgs128 += std::ceil(p.rows / 128.0) * gemm_tiles_n(p.g, p.max_N, 128);
-    }
-    const bool small_batch = batch_wgs <= (double)gemm_glds_max_wgs();  // latency regime: split-K and the LDS-DMA kernels apply
-    // bf16 numerics mode: the whole launch takes the bf16 operand family when every problem qualifies (gemm_bf16_ok); block tile T
-    bool bf16 = cx.bf16;
-    for (const GemmPending& p : b.q) bf16 = bf16 && gemm_bf16_ok(p.g);
-    if (!bf16) {
-        // A batch that mixes plane-only problems (bf16 mode: the input-gradient conv over the weight's transposed shadow has no fp32 B operand)
-        // with problems the bf16 kernels cannot take (a dual-source tangent product whose tap length is not a multiple of 32: the
-        // Hessian-vector pass through the PostNet's output layer) goes out as two launches: the plane-only problems on the bf16 family, the
-        // rest on the fp32 family.  The problems of a batch are independent, so the split changes nothing but the launch count.
-        std::vector<GemmPending> planes, rest;
-        for (const GemmPending& p : b.q) (p.g.plane_only ? planes : rest).push_back(p);
-        if (!planes.empty()) {
-            bool ok = cx.bf16 && !rest.empty();
-            for (const GemmPending& p : planes) ok = ok && gemm_bf16_ok(p.g);
-            if (!ok) { cx.error = "plane-only GEMM problem queued outside the bf16 plane path"; b.q.clear(); return; }
-            const int ff = b.force_family, ft = b.force_tile;
-            b.q = planes; b.force_family = 0;
-            gemm_batch_end(cx, stream);
-            b.q = rest; b.force_family = ff; b.force_tile = ft;
-            gemm_batch_end(cx, stream);
-            return;
-        }
-    }
-    const int T = !bf16 ? 64 : (b.force_tile ? b.force_tile : (batch_wgs128 >= 512.0 ? 128 : 64));
-    GemmWorkspace* wsp = nullptr;
-    long long ws_off = 0, ctr_off = 0;
-    int ln_used = 0;
-    for (int i = 0; i < mp.n; ++i) {
-        const GemmPending& p = b.q[i];
-        mp.form[i] = p.form; mp.groups[i] = p.groups; mp.g[i] = p.g;
-        mp.g[i].swizzle = 0; mp.g[i].splitk = 1; mp.g[i].wave_prio = cx.wave_prio;
-        const int tiles = ((p.max_M + T - 1) / T) * gemm_tiles_n(p.g, p.max_N, T);
-        int S = 1;
-        const int nch = (gemm_keff(p.g) + 15) / 16;
-        constexpr double ratio = 1.5;
-        if (knobs().batch_splitk && !cx.no_splitk && small_batch && T == 64 && !p.g.table && !p.g.colsum && !p.g.ln.y && nch > per_cu / ratio) {
-            S = (int)std::min<double>(std::min<double>(std::ceil(nch / std::max(per_cu / ratio, 1.0)), nch / 16), 8);
-            const long long slots = (long long)tiles * p.groups;
-            if (S >= 2 && ((ws_off + slots * S * 4096) > kSplitWsFloats || ctr_off + slots > kSplitCtrs - kLnCtrs)) S = 1;
-            if (S >= 2) {
-                if (!wsp) wsp = &cx.wsp;
-                if (wsp->ws) {
-                    mp.g[i].splitk = S; mp.g[i].tiles_pg = tiles; mp.g[i].ws = wsp->ws + ws_off; mp.g[i].tile_ctr = wsp->ctr + ctr_off;
-                    max_split = std::max(max_split, S);
-                    ws_off += slots * S * 4096; ctr_off += slots;
-                } else S = 1;
-            } else S = 1;
-        }
-        if (!gemm_ln_bind(cx, p.form, mp.g[i], p.max_M, p.groups, bf16 ? 0 : T, ln_used)) { b.q.clear(); return; }
-        mp.xcd_group[i] = gemm_xcd_swizzle() ? std::min(gemm_tiles_n(p.g, p.max_N, T) * S, 64) : 0;
-        mp.tiles_pg[i] = tiles * S;
-        long slots = (long)tiles * S * p.groups;
-        if (gemm_xcd_sched_for(mp.g[i], p.max_M, p.max_N, p.groups, S, T)) { mp.xcd_group[i] = -2; slots = gemm_xcd_sched_slots(mp.g[i].xs); }
-        else if (gemm_panel_order_for(p.g, p.form, p.rows, p.max_M, p.max_N, p.groups)) {
-            mp.xcd_group[i] = -3;
-            mp.po_tm[i] = (short)((p.max_M + T - 1) / T); mp.po_tn[i] = (short)gemm_tiles_n(p.g, p.max_N, T); mp.po_s[i] = (short)S;
-            slots = (long)xcd_panel_slots(mp.po_tm[i], mp.po_tn[i], S) * p.groups;
-        }
-        cx.note(p.tag, S, mp.xcd_group[i] == -2 ? 1 : (mp.xcd_group[i] == -3 ? 2 : 0));
-        mp.start[i + 1] = mp.start[i] + (int)((slots + 7) & ~7L);   // (every problem starts on a multiple of 8: workgroup slot % 8 = XCD)
-        max_groups = std::max(max_groups, p.groups);
-        flops += p.flops; rows += p.rows; bytes += p.bytes;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof.enabled) { e0 = prof.get(*cx.heap); e1 = prof.get(*cx.heap); hipEventRecord(e0, stream); }
-    dim3 block(256), grid((unsigned)mp.start[mp.n], 1, 1);
-    // BK = 32 stages K-contiguous operands in full 128-byte lines (half the load instructions, TA transactions and barriers
-    // per flop); needs every tapped problem's tap length to be a multiple of 32 and pays off only for long K.  Default since round 3
-    // (profiles/r03_sk_queue.md: the multi-problem launches with K >= 1024 run at 0.676 instead of 0.646 of the fp32 matrix peak, the
-    // whole step is unchanged, a single-task rank gains 1.7 %).
-    bool bk32 = true;
-    int maxK = 0;
-    for (int i = 0; i < mp.n; ++i) {
-        if (mp.g[i].taps > 1 && mp.g[i].tap_k % 32 != 0) bk32 = false;
-        maxK = std::max(maxK, gemm_keff(mp.g[i]));
-    }
-    bool glds = gemm_use_glds() && small_batch && !cx.no_glds && ln_used == 0;
-    if (b.force_family) { glds = b.force_family == 4064; bk32 = bk32 && b.force_family == 32; if (bk32) maxK = std::max(maxK, 1024); }
-    for (int i = 0; i < mp.n; ++i) glds = glds && gemm_glds_ok(mp.g[i]);
-    int kind = GK_MULTI16;
-    if (bf16) {
-        for (int i = 0; i < mp.n; ++i) if (mp.g[i].Ah) ++cx.plane_problems;
-        kind = gemm_bf16_multi_launch(mp, T, any_dual, grid, stream);
-        glds = false;
-    } else
-#if !defined(MTTS_EMU)
-    if (glds) { gemm_glds_multi_launch(mp, grid, stream, any_dual); kind = any_dual ? GK_GLDS_MULTI_DUAL : GK_GLDS_MULTI; }
-    else
-#endif
-    if (bk32 && maxK >= 1024 && !cx.prefer_bk16) {
-        int kl = gemm_kloop_variant();
-        for (int i = 0; i < mp.n; ++i) kl = std::min(kl, gemm_kloop_for(mp.g[i], 32));
-        if (any_dual) {
-            if (kl == 4) MTTS_LAUNCH((gemm_f32_multi_dual_kernel<64, 64, 32, 4>), grid, block, stream, mp);
-            else if (kl == 1) MTTS_LAUNCH((gemm_f32_multi_dual_kernel<64, 64, 32, 1>), grid, block, stream, mp);
-            else MTTS_LAUNCH((gemm_f32_multi_dual_kernel<64, 64, 32, 0>), grid, block, stream, mp);
-            kind = GK_MULTI32_DUAL;
-        } else {
-            if (ln_used > 0) MTTS_LAUNCH((gemm_f32_multi_kernel<64, 64, 32, 4, true>), grid, block, stream, mp);
-            else if (kl == 4) MTTS_LAUNCH((gemm_f32_multi_kernel<64, 64, 32, 4>), grid, block, stream, mp);
-            else if (kl == 1) MTTS_LAUNCH((gemm_f32_multi_kernel<64, 64, 32, 1>), grid, block, stream, mp);
-            else MTTS_LAUNCH((gemm_f32_multi_kernel<64, 64, 32, 0>), grid, block, stream, mp);
-            kind = GK_MULTI32;
-        }
-    } else {
-        int kl = gemm_kloop_variant() == 4 ? 4 : 0;
-        for (int i = 0; i < mp.n; ++i) kl = std::min(kl, gemm_kloop_for(mp.g[i], 16) == 4 ? 4 : 0);
-        if (any_dual) {
-            if (kl == 4) MTTS_LAUNCH((gemm_f32_multi_dual_kernel<64, 64, 16, 4>), grid, block, stream, mp);
-            else MTTS_LAUNCH((gemm_f32_multi_dual_kernel<64, 64, 16, 0>), grid, block, stream, mp);
-            kind = GK_MULTI16_DUAL;
-        } else {
-            if (ln_used > 0) MTTS_LAUNCH((gemm_f32_multi_kernel<64, 64, 16, 4, true>), grid, block, stream, mp);
-            else if (kl == 4) MTTS_LAUNCH((gemm_f32_multi_kernel<64, 64, 16, 4>), grid, block, stream, mp);
-            else MTTS_LAUNCH((gemm_f32_multi_kernel<64, 64, 16, 0>), grid, block, stream, mp);
-        }
-    }
-    cx.last_kind = kind;
-    if (prof.enabled) {
-        hipEventRecord(e1, stream);
-        GemmProfiler::Rec rec{kind, flops, e0, e1};
-        rec.form = 3; rec.tile = bf16 ? 16000 + T : (glds ? 4064 : 64); rec.N = mp.n; rec.K = maxK; rec.groups = mp.start[mp.n]; rec.splitk = max_split; rec.rows = rows; rec.bytes = bytes; rec.tag = prof.tag;  // multi: N = problems, K = longest K, groups = workgroups
-        prof.recs.push_back(rec);
-    }
-    b.q.clear();
-}
 
 }  // namespace mtts
+
+#include "gemm_launch.h"   // the host half: launch plan (pure) and launch

@@ -442,22 +442,30 @@ inline bool gemm_bf16_planes_ok(int form, const GemmArgs& g) {
     return form == GEMM_NT && g.Ah != nullptr && g.Bh != nullptr && g.A2 == nullptr && g.table == nullptr && g.a_tap_rows == 0 &&
            g.K % 8 == 0 && g.lda % 8 == 0 && g.ldb % 8 == 0;
 }
-// stand-alone launch of one problem; T = 64 / 128; pf: 0 = the default depth, else an explicit one (MTTS_BF16_PF_SWEEP builds only)
-inline int gemm_bf16_launch(int form, const GemmArgs& g, int T, dim3 grid, hipStream_t stream, int pf_req = 0) {
-    int pf = 0; (void)pf_req;
-    dim3 block(256);
-    pf = T == 128 ? kBf16PF128 : kBf16PF64;   // (explicit depths exist in MTTS_BF16_PF_SWEEP builds only)
+// identity of the stand-alone kernel of one problem; T = 64 / 128; pf_req: 0 = the default depth, else an explicit one (MTTS_BF16_PF_SWEEP builds only)
+inline GemmKernelId gemm_bf16_id(int form, const GemmArgs& g, int T, int pf_req) {
+    GemmKernelId k;
+    k.family = GF_BF16; k.form = form; k.tile = T; k.bk = kBf16BK;
+    k.pf = T == 128 ? kBf16PF128 : kBf16PF64;
+    (void)pf_req;
 #if defined(MTTS_BF16_PF_SWEEP)
-    if (pf_req) pf = pf_req;
+    if (pf_req) k.pf = pf_req;
 #endif
     if (form == GEMM_NT && g.Ah != nullptr) {   // both planes exist (gemm_bf16_planes_ok): the plane-staged K-loop
-        constexpr int plane_bk = 64;   // (BK = 32 measured slower on the long convolutions: profiles/r04_c2_bf16_planes.md)
-        if (T == 128) { MTTS_LAUNCH((gemm_bf16_kernel<GEMM_NT_H, 128, 128, kBf16BK, 1>), grid, block, stream, g); return GK_BF16_128_H; }
-        if (plane_bk == 64 && g.K >= 512) { MTTS_LAUNCH((gemm_bf16_kernel<GEMM_NT_H, 64, 64, 64, 1>), grid, block, stream, g); return GK_BF16_64_H64; }   // whole 128-byte lines per row and slice
-        MTTS_LAUNCH((gemm_bf16_kernel<GEMM_NT_H, 64, 64, kBf16BK, 1>), grid, block, stream, g);
-        return GK_BF16_64_H32;
+        k.form = GEMM_NT_H; k.pf = 1;
+        if (T != 128 && g.K >= 512) k.bk = 64;   // whole 128-byte lines per row and slice (BK = 32 measured slower on the long convolutions: profiles/r04_c2_bf16_planes.md)
     }
-#define MTTS_BF16_CASE(F, TT, PP) if (form == F && T == TT && pf == PP) { MTTS_LAUNCH((gemm_bf16_kernel<F, TT, TT, kBf16BK, PP>), grid, block, stream, g); return (TT == 128 ? GK_BF16_128 : GK_BF16_64) + F; }
+    return k;
+}
+inline void gemm_bf16_launch(const GemmKernelId& k, const GemmArgs& g, dim3 grid, hipStream_t stream) {
+    dim3 block(256);
+    if (k.form == GEMM_NT_H) {
+        if (k.tile == 128) MTTS_LAUNCH((gemm_bf16_kernel<GEMM_NT_H, 128, 128, kBf16BK, 1>), grid, block, stream, g);
+        else if (k.bk == 64) MTTS_LAUNCH((gemm_bf16_kernel<GEMM_NT_H, 64, 64, 64, 1>), grid, block, stream, g);
+        else MTTS_LAUNCH((gemm_bf16_kernel<GEMM_NT_H, 64, 64, kBf16BK, 1>), grid, block, stream, g);
+        return;
+    }
+#define MTTS_BF16_CASE(F, TT, PP) if (k.form == F && k.tile == TT && k.pf == PP) { MTTS_LAUNCH((gemm_bf16_kernel<F, TT, TT, kBf16BK, PP>), grid, block, stream, g); return; }
 #define MTTS_BF16_FORMS(TT, PP) MTTS_BF16_CASE(GEMM_NT, TT, PP) MTTS_BF16_CASE(GEMM_NN, TT, PP) MTTS_BF16_CASE(GEMM_TN, TT, PP)
     MTTS_BF16_FORMS(64, 1) MTTS_BF16_FORMS(128, 1)
 #if defined(MTTS_BF16_PF_SWEEP)   // explicit slices-in-flight variants for micro-benchmarks (tile code T + 1000 * PF)
@@ -465,25 +473,25 @@ inline int gemm_bf16_launch(int form, const GemmArgs& g, int T, dim3 grid, hipSt
 #endif
 #undef MTTS_BF16_FORMS
 #undef MTTS_BF16_CASE
-    return GK_OTHER;
 }
-inline int gemm_bf16_multi_launch(const GemmMulti& mp, int T, bool dual, dim3 grid, hipStream_t stream) {
-    dim3 block(256);
-    if (T == 128) {
-        if (dual) MTTS_LAUNCH((gemm_bf16_multi_kernel<128, 128, kBf16BK, kBf16PF128, true>), grid, block, stream, mp);
-        else MTTS_LAUNCH((gemm_bf16_multi_kernel<128, 128, kBf16BK, kBf16PF128, false>), grid, block, stream, mp);
-        return dual ? GK_BF16_MULTI128_DUAL : GK_BF16_MULTI128;
-    }
+// a multi-problem launch: the planes kernel (form GEMM_NT_H) when a 64x64 launch without second sources carries plane problems
+inline GemmKernelId gemm_bf16_multi_id(const GemmMulti& mp, int T, bool dual) {
+    GemmKernelId k;
+    k.family = GF_BF16; k.multi = true; k.tile = T == 128 ? 128 : 64; k.bk = kBf16BK; k.dual = dual;
+    k.pf = T == 128 ? kBf16PF128 : kBf16PF64;
     bool planes = false;
     for (int i = 0; i < mp.n; ++i) planes = planes || mp.g[i].Ah != nullptr;
-    constexpr int plane_bk = 64;
-    if (planes && !dual && plane_bk == 64) {
-        MTTS_LAUNCH((gemm_bf16_multi_planes_kernel<64, 64, kBf16BK, 64, kBf16PF64>), grid, block, stream, mp);
-        return GK_BF16_MULTI64_PLANES;
-    }
-    if (dual) MTTS_LAUNCH((gemm_bf16_multi_kernel<64, 64, kBf16BK, kBf16PF64, true>), grid, block, stream, mp);
+    if (T != 128 && planes && !dual) k.form = GEMM_NT_H;
+    return k;
+}
+inline void gemm_bf16_multi_launch(const GemmKernelId& k, const GemmMulti& mp, dim3 grid, hipStream_t stream) {
+    dim3 block(256);
+    if (k.tile == 128) {
+        if (k.dual) MTTS_LAUNCH((gemm_bf16_multi_kernel<128, 128, kBf16BK, kBf16PF128, true>), grid, block, stream, mp);
+        else MTTS_LAUNCH((gemm_bf16_multi_kernel<128, 128, kBf16BK, kBf16PF128, false>), grid, block, stream, mp);
+    } else if (k.form == GEMM_NT_H) MTTS_LAUNCH((gemm_bf16_multi_planes_kernel<64, 64, kBf16BK, 64, kBf16PF64>), grid, block, stream, mp);
+    else if (k.dual) MTTS_LAUNCH((gemm_bf16_multi_kernel<64, 64, kBf16BK, kBf16PF64, true>), grid, block, stream, mp);
     else MTTS_LAUNCH((gemm_bf16_multi_kernel<64, 64, kBf16BK, kBf16PF64, false>), grid, block, stream, mp);
-    return dual ? GK_BF16_MULTI64_DUAL : GK_BF16_MULTI64;
 }
 
 }  // namespace mtts

@@ -272,13 +272,13 @@ __global__ __launch_bounds__(256) void gemm_glds_multi_dual_kernel(GemmMulti mp)
     else gemm_glds_body<GEMM_TN, true>(mp.g[p], z, bx, smem);
 }
 
-inline void gemm_glds_launch(int form, const GemmArgs& g, dim3 grid, hipStream_t stream) {
-    if (form == GEMM_NT) hipLaunchKernelGGL((gemm_glds_kernel<GEMM_NT>), grid, dim3(256), 0, stream, g);
-    else if (form == GEMM_NN) hipLaunchKernelGGL((gemm_glds_kernel<GEMM_NN>), grid, dim3(256), 0, stream, g);
+inline void gemm_glds_launch(const GemmKernelId& k, const GemmArgs& g, dim3 grid, hipStream_t stream) {
+    if (k.form == GEMM_NT) hipLaunchKernelGGL((gemm_glds_kernel<GEMM_NT>), grid, dim3(256), 0, stream, g);
+    else if (k.form == GEMM_NN) hipLaunchKernelGGL((gemm_glds_kernel<GEMM_NN>), grid, dim3(256), 0, stream, g);
     else hipLaunchKernelGGL((gemm_glds_kernel<GEMM_TN>), grid, dim3(256), 0, stream, g);
 }
-inline void gemm_glds_multi_launch(const GemmMulti& mp, dim3 grid, hipStream_t stream, bool dual) {
-    if (dual) hipLaunchKernelGGL(gemm_glds_multi_dual_kernel, grid, dim3(256), 0, stream, mp);
+inline void gemm_glds_multi_launch(const GemmKernelId& k, const GemmMulti& mp, dim3 grid, hipStream_t stream) {
+    if (k.dual) hipLaunchKernelGGL(gemm_glds_multi_dual_kernel, grid, dim3(256), 0, stream, mp);
     else hipLaunchKernelGGL(gemm_glds_multi_kernel, grid, dim3(256), 0, stream, mp);
 }
 

@@ -636,7 +636,6 @@ int mtts_gemm_f32_grouped(const mtts_gemm_desc* probs, int n, int family, float*
     }
     GemmCtx& cx = kernel_ctx();
     cx.wsp.ws = splitk_ws; cx.wsp.ctr = splitk_ctr;
-    cx.batch.force_family = family;
     cx.last_kind = GK_OTHER;
     gemm_batch_begin(cx);
     for (int i = 0; i < n; ++i) {
@@ -655,13 +654,10 @@ int mtts_gemm_f32_grouped(const mtts_gemm_desc* probs, int n, int family, float*
         if (d.taps > 1) { g.taps = d.taps; g.tap_k = d.tap_k; g.tap_bstride = d.tap_bstride; }
         if (d.a_tap_rows != 0) { g.a_tap_k = d.a_tap_k; g.a_tap_rows = d.a_tap_rows; }
         g.colsum = d.colsum; g.colsum_gs = d.colsum_gs; g.colsum_w = d.colsum_w; g.colsum_w_gs = d.colsum_w_gs;
-        cx.next_tag = i;
         cx.note(i, 0, 0);
-        gemm_launch(cx, d.form, g, d.max_M, d.max_N, d.groups, (hipStream_t)stream, 0);   // (the sixth problem flushes the queue by itself)
+        gemm_enqueue(cx, d.form, g, d.max_M, d.max_N, d.groups, i);
     }
-    cx.next_tag = -1;
-    gemm_batch_end(cx, (hipStream_t)stream);
-    cx.batch.force_family = 0;
+    gemm_batch_end(cx, (hipStream_t)stream, GemmRequest{0, family, 0});
     cx.wsp.ws = nullptr; cx.wsp.ctr = nullptr;
     if (report) for (int i = 0; i < n; ++i) { report[2 * i] = cx.note_splitk[i]; report[2 * i + 1] = cx.note_place[i]; }
     // a forced family that did not run is an error, never a silent fall-back: the caller's test would prove nothing about it
