@@ -92,6 +92,35 @@ inline void attn_group_descs(long long qo, long long oo, long long so, int L, in
     tab[TAB_DK] = GemmGroupDesc{so, qo, qo + d, L, dk, L, ldS, 0, 0};         // dK = dS^T Q
 }
 
+// The two records a Plan keeps per row space (P, F, R) and per attention side: what a launch reads instead of picking among per-space members.
+struct RowMask { unsigned char* m = nullptr; float* w = nullptr; };   // a row mask of a space and its [row][4] float image (plan.h)
+// What a launch needs to know about one row space of a plan.  cap / ts / the masks are fixed by the capacities (layout_rest), the rest by build_plan.
+struct RowSpace {
+    int mfield = 0, cap = 0;      // META_M* field of the per-task row count; row capacity of the space's buffers
+    long long ts = 0;             // task stride of the per-row arrays (masks, index lists)
+    RowMask valid, inrect;
+    std::vector<int> hM;          // host copy of the per-task row counts (8-task launches: task-per-XCD schedule, gemm.h)
+    int maxM = 0;
+    long long sumM = 0;           // total rows over tasks (tile heuristic)
+    double alg_rows = 0;          // rows that count as work (algorithmic flop accounting)
+};
+// One attention side: 0 = encoder (sequences of P), 1 = decoder (sequences of F)
+struct AttnSide {
+    AttnSeq* seqs = nullptr;
+    GemmGroupDesc* tab[6] = {};
+    long long S_ts = 0;           // task stride of the score matrices
+    int maxL = 0, groups = 0;
+    double sum_attn = 0;          // sum over (sequence, head) of L^2 (algorithmic flop accounting)
+    long long sumL = 0;
+};
+
+struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.h)
+    GemmCtx& cx;
+    hipStream_t s;
+    GemmBatchScope(GemmCtx& c, hipStream_t st) : cx(c), s(st) { gemm_batch_begin(cx); }
+    ~GemmBatchScope() { gemm_batch_end(cx, s); }
+};
+
 class Engine {
 public:
     ModelCfg cfg;
@@ -137,35 +166,31 @@ public:
         std::vector<int> spk_ids;
         std::vector<float> spk_emb;    // [B][d_model] external speaker embeddings (empty: table lookup)
     };
+    enum Space { SP_P = 0, SP_F = 1, SP_R = 2 };
+    static int side_of(Space s) { return (int)s; }   // (SP_P -> encoder, SP_F -> decoder; R has no attention)
     struct Plan {
         int tasks = 0;
-        std::vector<int> hB, hSmax, hTcap, hMp, hMf, hMr;
-        int maxMp = 0, maxMf = 0, maxMr = 0, maxB = 0, enc_maxL = 0, dec_maxL = 0, n_enc_groups = 0, n_dec_groups = 0;
+        RowSpace sp[3];               // indexed by Space
+        AttnSide at[2];
+        std::vector<int> hB, hSmax, hTcap;
+        int maxB = 0;
         int average_spk = 0;
         bool ext_spk = false;   // speaker vectors come with the batch (speaker_emb: dvec), no table lookup and no table gradient
         bool has_targets = false, frames_ready = false;
         bool over_max = false, truncated = true;  // some T_max > max_seq_len / frames beyond it dropped in the current row spaces
         unsigned drop_seed = 0;  // seed of the last train-mode forward on this plan (backward replays it)
         std::vector<TaskIn> in;
-        double sum_nP = 0, sum_nF = 0, sum_attn_p = 0, sum_attn_f = 0;
-        long long sumMp = 0, sumMf = 0, sumMr = 0, sumLp = 0, sumLf = 0;  // total rows over tasks (tile heuristic)  // valid rows / sum L^2 (algorithmic flop accounting)
         int* meta = nullptr;
         // P space
         int *p_row_b, *p_row_t, *p_tok, *p_first, *p_count, *p_dur, *p_seg_start, *p_seg_len;
-        unsigned char *p_valid, *p_inrect;
-        float *p_valid_w, *p_inrect_w, *f_valid_w, *r_valid_w, *r_inrect_w;   // [row][4] float images of the masks (plan.h)
         float *p_pitch_t, *p_energy_t;
         // F space
         int *f_row_b, *f_row_t, *f_src, *f_seg_start, *f_seg_len, *f2r;
-        unsigned char* f_valid;
         // R space
         int* r2f;
-        unsigned char *r_valid, *r_inrect;
         float *r_pitch_t = nullptr, *r_energy_t = nullptr;  // frame-level targets on the R rows
         float* mel_tgt;
         int* spk_ids;
-        AttnSeq *enc_seqs, *dec_seqs;
-        GemmGroupDesc *enc_tab[6], *dec_tab[6];
         // compact batch image (plan.h): device copy + two pinned staging buffers (the host may prepare step k+1 while the copy of
         // step k is still in flight)
         char* img_dev = nullptr;
@@ -177,9 +202,8 @@ public:
     };
     // byte offsets inside a compact image (fixed by the capacities; computed in init)
     size_t pe_cap_p = 0, pe_cap_e = 0;  // per-task floats of the pitch / energy areas of an image
-    struct ImgLayout { size_t meta, hdr, src_len, flen, foff, spk, spk_emb, texts, dur, pitch, energy, seq_e, seq_d, tab_e[6], tab_d[6], mels, total; } img;
+    struct ImgLayout { size_t meta, hdr, src_len, flen, foff, spk, spk_emb, texts, dur, pitch, energy, seq[2], tab[2][6], mels, total; } img;
     Plan plans[2];
-    long long row_ts_p, row_ts_f, row_ts_r;  // strides of per-row index arrays
 
     // ---------------- workspace -------------------------------------------------------
     struct LayerBuf { TS qkv, P, O, z1, st1, y1, h, z2, st2, y2; };
@@ -253,7 +277,6 @@ public:
     float *loss_partial = nullptr, *losses = nullptr, *col_partial = nullptr;
     int col_max_chunks = 0;
     long long col_partial_ts = 0;                 // floats per task of col_partial
-    long long S_ts_p = 0, S_ts_f = 0;
 
     char* arena = nullptr;
     size_t arena_bytes = 0;
@@ -274,12 +297,6 @@ public:
 
     struct Pass;
     GemmCtx gx;  // this handle's launcher state: batching queue, profiler, split-K workspace, numerics mode (gemm.h)
-struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.h)
-    GemmCtx& cx;
-    hipStream_t s;
-    GemmBatchScope(GemmCtx& c, hipStream_t st) : cx(c), s(st) { gemm_batch_begin(cx); }
-    ~GemmBatchScope() { gemm_batch_end(cx, s); }
-};
     // dropout (off by default: parity runs patch it to identity)
     // gradient accumulation (main.py:62 accumulate_grad_batches): meta_grad / plain_grad ADD their result to the outer buffer
     bool outer_accumulate = false;
@@ -449,6 +466,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     template <class T> T* arr(long long n_per_task) { return (T*)take((size_t)n_per_task * cap_tasks * sizeof(T)); }
 
     static long long attn_elems(int B, int H, int L) { return (long long)B * H * L * ((L + 3) & ~3); }
+    long long score_ts(int side) const { return side ? attn_elems(cap_B, cfg.dec_heads, cap_Tc) : attn_elems(cap_B, cfg.enc_heads, cap_S); }   // AttnSide::S_ts
 
     // The arena starts with everything a forward pass writes and a later backward (or tangent) pass reads — the activation set —
     // followed by the backward scratch and the plan arrays.  Second-order MAML binds the activation set to one buffer per inner
@@ -508,42 +526,38 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         }
         return true;
     }
+    // the saved activations of n FFT blocks / of a variance predictor on a space of capM rows (also their tangents: layout_so)
+    void layout_layers(std::vector<LayerBuf>& v, int n, int capM, long long S_ts) {
+        const int d = cfg.d_model;
+        v.resize(n);
+        for (LayerBuf& b : v) {
+            b.qkv = rows(capM, 3 * d); b.P = flat(S_ts); b.O = rows(capM, d); b.z1 = rows(capM, d); b.st1 = rows(capM, 2);
+            b.y1 = rows(capM, d); b.h = rows(capM, cfg.d_ff); b.z2 = rows(capM, d); b.st2 = rows(capM, 2); b.y2 = rows(capM, d);
+        }
+    }
+    void layout_pred(PredBuf& b, int capM) {
+        const int f = cfg.vp_filter;
+        b.r1 = rows(capM, f); b.st1 = rows(capM, 2); b.n1 = rows(capM, f); b.r2 = rows(capM, f); b.st2 = rows(capM, 2); b.n2 = rows(capM, f);
+        b.out = rows(capM, 1);
+    }
     void layout_act() {
         const int d = cfg.d_model, f = cfg.vp_filter;
-        S_ts_p = attn_elems(cap_B, cfg.enc_heads, cap_S);
-        S_ts_f = attn_elems(cap_B, cfg.dec_heads, cap_Tc);
-        auto layer = [&](int capM, long long S_ts, std::vector<LayerBuf>& v, int n) {
-            v.resize(n);
-            for (int i = 0; i < n; ++i) {
-                v[i].qkv = rows(capM, 3 * d); v[i].P = flat(S_ts); v[i].O = rows(capM, d); v[i].z1 = rows(capM, d);
-                v[i].st1 = rows(capM, 2); v[i].y1 = rows(capM, d); v[i].h = rows(capM, cfg.d_ff); v[i].z2 = rows(capM, d);
-                v[i].st2 = rows(capM, 2); v[i].y2 = rows(capM, d);
-            }
-        };
         emb_out = rows(capMp, d);
-        layer(capMp, S_ts_p, encB, cfg.enc_layers);
+        layout_layers(encB, cfg.enc_layers, capMp, score_ts(0));
         spk = flat((long long)cap_B * d);
         x0 = rows(capMp, d); x1 = rows(capMp, d); x2 = rows(capMp, d);
-        for (PredBuf* pb : {&durB, &pitB, &eneB}) {
-            pb->r1 = rows(capMp, f); pb->st1 = rows(capMp, 2); pb->n1 = rows(capMp, f);
-            pb->r2 = rows(capMp, f); pb->st2 = rows(capMp, 2); pb->n2 = rows(capMp, f);
-            pb->out = rows(capMp, 1);
-        }
+        for (PredBuf* pb : {&durB, &pitB, &eneB}) layout_pred(*pb, capMp);
         pidx = arr<int>(capMp); eidx = arr<int>(capMp);
         d_rounded = rows(capMp, 1);
         dec_in = rows(capMf, d);
         if (any_frame_level()) {
             xr0 = rows(capMr, d); xr1 = rows(capMr, d); xr2 = rows(capMr, d);
-            for (PredBuf* pb : {&pitR, &eneR}) {
-                pb->r1 = rows(capMr, f); pb->st1 = rows(capMr, 2); pb->n1 = rows(capMr, f);
-                pb->r2 = rows(capMr, f); pb->st2 = rows(capMr, 2); pb->n2 = rows(capMr, f);
-                pb->out = rows(capMr, 1);
-            }
+            for (PredBuf* pb : {&pitR, &eneR}) layout_pred(*pb, capMr);
             pidx_r = arr<int>(capMr); eidx_r = arr<int>(capMr);
             gRx = rows(capMr, d); gRf1 = rows(capMr, f); gRf2 = rows(capMr, f); gFx = rows(capMf, d);
             dpred_r[0] = rows(capMr, 1); dpred_r[1] = rows(capMr, 1);
         }
-        layer(capMf, S_ts_f, decB, cfg.dec_layers);
+        layout_layers(decB, cfg.dec_layers, capMf, score_ts(1));
         mel = rows(capMr, cfg.n_mel); mel_post = rows(capMr, cfg.n_mel);
         postB.resize(cfg.postnet_layers);
         for (int i = 0; i < cfg.postnet_layers; ++i) {
@@ -559,7 +573,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         gP0 = rows(capMp, d); gP1 = rows(capMp, d); gPqkv = rows(capMp, 3 * d); gPh = rows(capMp, cfg.d_ff);
         gPf1 = rows(capMp, f); gPf2 = rows(capMp, f);
         gF0 = rows(capMf, d); gF1 = rows(capMf, d); gFqkv = rows(capMf, 3 * d); gFh = rows(capMf, cfg.d_ff);
-        dSp = flat(S_ts_p); dSf = flat(S_ts_f);
+        dSp = flat(score_ts(0)); dSf = flat(score_ts(1));
         const int pc = std::max(cfg.postnet_dim, cfg.n_mel);
         gR0 = rows(capMr, pc); gR1 = rows(capMr, pc); gRm = rows(capMr, cfg.n_mel); gRp = rows(capMr, cfg.n_mel);
         gMelF = rows(capMf, cfg.n_mel);
@@ -575,20 +589,25 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         loss_partial = (float*)take((size_t)cap_tasks * kLossBlocks * 5 * sizeof(float));
         losses = (float*)take((size_t)cap_tasks * 6 * sizeof(float));
         // plans
-        row_ts_p = capMp; row_ts_f = capMf; row_ts_r = capMr;
         for (int s = 0; s < 2; ++s) {
             Plan& p = plans[s];
+            RowSpace &P = p.sp[SP_P], &F = p.sp[SP_F], &R = p.sp[SP_R];
+            P.mfield = META_MP; F.mfield = META_MF; R.mfield = META_MR;
+            P.cap = capMp; F.cap = capMf; R.cap = capMr;
+            for (RowSpace& rs : p.sp) rs.ts = rs.cap;
+            for (int k = 0; k < 2; ++k) p.at[k].S_ts = score_ts(k);
             p.p_row_b = arr<int>(capMp); p.p_row_t = arr<int>(capMp); p.p_tok = arr<int>(capMp);
             p.p_first = arr<int>(capMp); p.p_count = arr<int>(capMp); p.p_dur = arr<int>(capMp);
             p.p_seg_start = arr<int>(cap_B); p.p_seg_len = arr<int>(cap_B);
-            p.p_valid = arr<unsigned char>(capMp); p.p_inrect = arr<unsigned char>(capMp);
-            p.p_valid_w = arr<float>(4LL * capMp); p.p_inrect_w = arr<float>(4LL * capMp); p.f_valid_w = arr<float>(4LL * capMf);
-            p.r_valid_w = arr<float>(4LL * capMr); p.r_inrect_w = arr<float>(4LL * capMr);
+            P.valid.m = arr<unsigned char>(capMp); P.inrect.m = arr<unsigned char>(capMp);
+            P.valid.w = arr<float>(4LL * capMp); P.inrect.w = arr<float>(4LL * capMp); F.valid.w = arr<float>(4LL * capMf);
+            R.valid.w = arr<float>(4LL * capMr); R.inrect.w = arr<float>(4LL * capMr);
             p.p_pitch_t = arr<float>(capMp); p.p_energy_t = arr<float>(capMp);
             p.f_row_b = arr<int>(capMf); p.f_row_t = arr<int>(capMf); p.f_src = arr<int>(capMf);
             p.f_seg_start = arr<int>(cap_B); p.f_seg_len = arr<int>(cap_B); p.f2r = arr<int>(capMf);
-            p.f_valid = arr<unsigned char>(capMf);
-            p.r2f = arr<int>(capMr); p.r_valid = arr<unsigned char>(capMr); p.r_inrect = arr<unsigned char>(capMr);
+            F.valid.m = arr<unsigned char>(capMf);
+            F.inrect = F.valid;   // the packed space holds valid frames only: every row inside it is a valid one
+            p.r2f = arr<int>(capMr); R.valid.m = arr<unsigned char>(capMr); R.inrect.m = arr<unsigned char>(capMr);
             p.mel_tgt = rows(capMr, cfg.n_mel).p;
             if (any_frame_level()) { p.r_pitch_t = arr<float>(capMr); p.r_energy_t = arr<float>(capMr); }
             p.spk_ids = arr<int>(cap_B + 1);
@@ -679,10 +698,10 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         pe_cap_e = cfg.energy_frame ? (size_t)cap_B * cap_T : bs;
         img.pitch = o; o = al(o + nt * pe_cap_p * sizeof(float));
         img.energy = o; o = al(o + nt * pe_cap_e * sizeof(float));
-        img.seq_e = o; o = al(o + ne * sizeof(AttnSeq));
-        img.seq_d = o; o = al(o + nd * sizeof(AttnSeq));
-        for (int k = 0; k < 6; ++k) { img.tab_e[k] = o; o = al(o + ne * sizeof(GemmGroupDesc)); }
-        for (int k = 0; k < 6; ++k) { img.tab_d[k] = o; o = al(o + nd * sizeof(GemmGroupDesc)); }
+        const size_t ng[2] = {ne, nd};
+        for (int w = 0; w < 2; ++w) { img.seq[w] = o; o = al(o + ng[w] * sizeof(AttnSeq)); }
+        for (int w = 0; w < 2; ++w)
+            for (int k = 0; k < 6; ++k) { img.tab[w][k] = o; o = al(o + ng[w] * sizeof(GemmGroupDesc)); }
         img.mels = o; o = al(o + nt * (size_t)cap_B * cap_T * cfg.n_mel * sizeof(float));
         img.total = o;
         for (int sl = 0; sl < 2; ++sl) {
@@ -695,11 +714,9 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                 DEV_CHECK(mem.event(p.img_done[b]));
             }
             p.meta = (int*)(p.img_dev + img.meta);
-            p.enc_seqs = (AttnSeq*)(p.img_dev + img.seq_e);
-            p.dec_seqs = (AttnSeq*)(p.img_dev + img.seq_d);
-            for (int k = 0; k < 6; ++k) {
-                p.enc_tab[k] = (GemmGroupDesc*)(p.img_dev + img.tab_e[k]);
-                p.dec_tab[k] = (GemmGroupDesc*)(p.img_dev + img.tab_d[k]);
+            for (int w = 0; w < 2; ++w) {
+                p.at[w].seqs = (AttnSeq*)(p.img_dev + img.seq[w]);
+                for (int k = 0; k < 6; ++k) p.at[w].tab[k] = (GemmGroupDesc*)(p.img_dev + img.tab[w][k]);
             }
         }
         return 0;
@@ -1064,12 +1081,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         Plan& p = plans[slot];
         const int tasks = p.tasks;
         p.hB.assign(tasks, 0); p.hSmax.assign(tasks, 0); p.hTcap.assign(tasks, 0);
-        p.hMp.assign(tasks, 0); p.hMf.assign(tasks, 0); p.hMr.assign(tasks, 0);
-        p.maxMp = p.maxMf = p.maxMr = p.maxB = p.enc_maxL = p.dec_maxL = 0;
+        p.maxB = 0;
+        for (RowSpace& rs : p.sp) { rs.hM.assign(tasks, 0); rs.maxM = 0; rs.sumM = 0; rs.alg_rows = 0; }
+        for (AttnSide& a : p.at) { a.maxL = a.groups = 0; a.sum_attn = 0; a.sumL = 0; }
         p.frames_ready = with_frames;
         p.truncated = truncate;
-        p.sum_nP = p.sum_nF = p.sum_attn_p = p.sum_attn_f = 0;
-        p.sumMp = p.sumMf = p.sumMr = p.sumLp = p.sumLf = 0;
         const int par = p.img_parity;
         p.img_parity ^= 1;
         if (p.img_pending[par]) { DEV_CHECK(hipEventSynchronize(p.img_done[par])); p.img_pending[par] = false; }
@@ -1080,10 +1096,13 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         int* h_spk = (int*)(H + img.spk); int* h_txt = (int*)(H + img.texts); int* h_dur = (int*)(H + img.dur);
         float* h_pit = (float*)(H + img.pitch); float* h_ene = (float*)(H + img.energy);
         float* h_mel = (float*)(H + img.mels);
-        AttnSeq* seqs[2] = {(AttnSeq*)(H + img.seq_e), (AttnSeq*)(H + img.seq_d)};
+        AttnSeq* seqs[2];
         GemmGroupDesc* tabs[2][6];
-        for (int k = 0; k < 6; ++k) { tabs[0][k] = (GemmGroupDesc*)(H + img.tab_e[k]); tabs[1][k] = (GemmGroupDesc*)(H + img.tab_d[k]); }
-        int nseq[2] = {0, 0};
+        for (int w = 0; w < 2; ++w) {
+            seqs[w] = (AttnSeq*)(H + img.seq[w]);
+            for (int k = 0; k < 6; ++k) tabs[w][k] = (GemmGroupDesc*)(H + img.tab[w][k]);
+        }
+        const int heads[2] = {cfg.enc_heads, cfg.dec_heads};
         long long mel_used = 0;
         const int d = cfg.d_model;
         const size_t bs = (size_t)cap_B * cap_S;
@@ -1114,6 +1133,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             if (!b.pitches.empty() && cfg.pitch_frame) memcpy(h_pit + (size_t)t * pe_cap_p, b.pitches.data(), b.pitches.size() * sizeof(float));
             if (!b.energies.empty() && cfg.energy_frame) memcpy(h_ene + (size_t)t * pe_cap_e, b.energies.data(), b.energies.size() * sizeof(float));
             const int Mf = with_frames ? foff : 0, Mr = with_frames ? G + B * (Tcap + G) : 0;
+            const int M[3] = {Mp, Mf, Mr};
             if (Mf > capMf || Mr > capMr || Mp > capMp) { set_error("row space exceeds capacity"); return -1; }
             for (int i = 0; i <= cap_B; ++i) h_spk[(size_t)t * (cap_B + 1) + i] = b.spk_ids[i];
             if (!b.spk_emb.empty()) memcpy((float*)(H + img.spk_emb) + (size_t)t * cap_B * d, b.spk_emb.data(), b.spk_emb.size() * sizeof(float));
@@ -1130,20 +1150,20 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             long long soff[2] = {0, 0};
             for (int i = 0; i < B; ++i)
                 for (int which = 0; which < (with_frames ? 2 : 1); ++which) {
-                    const int Hh = which ? cfg.dec_heads : cfg.enc_heads, dk = d / Hh;
+                    AttnSide& a = p.at[which];
+                    const int Hh = heads[which], dk = d / Hh;
+                    // the sequence's length and first row: a source sentence in the phoneme rectangle / its frames in the packed space
                     const int L = which ? h_flen[(size_t)t * cap_B + i] : h_src[(size_t)t * cap_B + i];
                     const int ro = which ? h_foff[(size_t)t * cap_B + i] : G + i * (S + G);
-                    const long long task_s = which ? S_ts_f : S_ts_p;
-                    int& maxL = which ? p.dec_maxL : p.enc_maxL;
-                    maxL = std::max(maxL, L);
-                    (which ? p.sum_attn_f : p.sum_attn_p) += (double)Hh * L * L;
-                    (which ? p.sumLf : p.sumLp) += (long long)Hh * L;
+                    a.maxL = std::max(a.maxL, L);
+                    a.sum_attn += (double)Hh * L * L;
+                    a.sumL += (long long)Hh * L;
                     const int ldS = (L + 3) & ~3;
-                    const int capM = which ? capMf : capMp;
+                    const int capM = p.sp[which].cap;
                     for (int hh = 0; hh < Hh; ++hh) {
-                        const long long so = (long long)t * task_s + soff[which];
+                        const long long so = (long long)t * a.S_ts + soff[which];
                         soff[which] += (long long)L * ldS;
-                        const int n = nseq[which]++;
+                        const int n = a.groups++;
                         const long long qo = (long long)t * ((long long)(capM + 2 * G) * 3 * d) + (long long)ro * 3 * d + hh * dk;
                         const long long oo = (long long)t * ((long long)(capM + 2 * G) * d) + (long long)ro * d + hh * dk;
                         GemmGroupDesc gd[6];
@@ -1151,22 +1171,21 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                         for (int k = 0; k < 6; ++k) tabs[which][k][n] = gd[k];
                     }
                 }
-            p.hB[t] = B; p.hSmax[t] = S; p.hTcap[t] = Tcap; p.hMp[t] = Mp; p.hMf[t] = Mf; p.hMr[t] = Mr;
-            p.maxMp = std::max(p.maxMp, Mp); p.maxMf = std::max(p.maxMf, Mf); p.maxMr = std::max(p.maxMr, Mr);
+            p.hB[t] = B; p.hSmax[t] = S; p.hTcap[t] = Tcap;
+            for (int k = 0; k < 3; ++k) { p.sp[k].hM[t] = M[k]; p.sp[k].maxM = std::max(p.sp[k].maxM, M[k]); p.sp[k].sumM += M[k]; }
             p.maxB = std::max(p.maxB, B);
             int* m = &meta[(size_t)t * META_STRIDE];
             m[META_B] = B; m[META_SMAX] = S; m[META_TCAP] = Tcap; m[META_MP] = Mp; m[META_MF] = Mf; m[META_MR] = Mr;
             m[META_NP] = nP; m[META_NF] = nF;
-            p.sum_nP += nP; p.sum_nF += nF;
-            p.sumMp += Mp; p.sumMf += Mf; p.sumMr += Mr;
+            p.sp[SP_P].alg_rows += nP; p.sp[SP_F].alg_rows += nF;
         }
-        p.n_enc_groups = nseq[0]; p.n_dec_groups = nseq[1];
+        p.sp[SP_R].alg_rows = p.sp[SP_F].alg_rows;   // work on the mel rectangle is counted on its valid frames, which are F's rows
         // Attention groups longest first.  A (sequence, head) pair is ~L / 32 workgroups of cost ~L each and a grid is dispatched group by group, so in
         // batch order the last dispatch round of the fused forward (1.1 k workgroups on 512 slots at 8 tasks) and of the backward's grouped GEMMs is
         // whatever pairs happen to come last; sorted, the long pairs start first and the short ones fill the tail.  Every table entry carries its own
         // offsets, so the order is free; the sort is stable (the heads of a sequence stay neighbours).  MTTS_ATTN_SORT=0: batch order.
         for (int which = 0; knobs().attn_sort && which < 2; ++which) {
-            const int n = nseq[which];
+            const int n = p.at[which].groups;
             if (n < 2) continue;
             std::vector<int> idx((size_t)n);
             for (int i = 0; i < n; ++i) idx[(size_t)i] = i;
@@ -1195,18 +1214,19 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         PlanOut o;
         o.r_pitch_t = p.r_pitch_t; o.r_energy_t = p.r_energy_t;
         o.p_row_b = p.p_row_b; o.p_row_t = p.p_row_t; o.p_tok = p.p_tok; o.p_first = p.p_first; o.p_count = p.p_count; o.p_dur = p.p_dur;
-        o.p_seg_start = p.p_seg_start; o.p_seg_len = p.p_seg_len; o.p_valid = p.p_valid; o.p_inrect = p.p_inrect;
+        const RowSpace &sP = p.sp[SP_P], &sF = p.sp[SP_F], &sR = p.sp[SP_R];
+        o.p_seg_start = p.p_seg_start; o.p_seg_len = p.p_seg_len; o.p_valid = sP.valid.m; o.p_inrect = sP.inrect.m;
         o.p_pitch_t = p.p_pitch_t; o.p_energy_t = p.p_energy_t;
         o.f_row_b = p.f_row_b; o.f_row_t = p.f_row_t; o.f_src = p.f_src; o.f_seg_start = p.f_seg_start; o.f_seg_len = p.f_seg_len;
-        o.f2r = p.f2r; o.f_valid = p.f_valid; o.r2f = p.r2f; o.r_valid = p.r_valid; o.r_inrect = p.r_inrect; o.mel_tgt = p.mel_tgt;
+        o.f2r = p.f2r; o.f_valid = sF.valid.m; o.r2f = p.r2f; o.r_valid = sR.valid.m; o.r_inrect = sR.inrect.m; o.mel_tgt = p.mel_tgt;
         o.spk_ids = p.spk_ids;
-        o.p_valid_w = p.p_valid_w; o.p_inrect_w = p.p_inrect_w; o.f_valid_w = p.f_valid_w; o.r_valid_w = p.r_valid_w; o.r_inrect_w = p.r_inrect_w;
-        o.ts_p = row_ts_p; o.ts_f = row_ts_f; o.ts_r = row_ts_r; o.ts_mel = (long long)(capMr + 2 * G) * cfg.n_mel; o.ts_seg = cap_B; o.ts_spk = cap_B + 1;
-        MTTS_LAUNCH(plan_rows_p_kernel, dim3((unsigned)((p.maxMp + 255) / 256), 1, (unsigned)tasks), dim3(256), stream, im, o);
+        o.p_valid_w = sP.valid.w; o.p_inrect_w = sP.inrect.w; o.f_valid_w = sF.valid.w; o.r_valid_w = sR.valid.w; o.r_inrect_w = sR.inrect.w;
+        o.ts_p = sP.ts; o.ts_f = sF.ts; o.ts_r = sR.ts; o.ts_mel = (long long)(capMr + 2 * G) * cfg.n_mel; o.ts_seg = cap_B; o.ts_spk = cap_B + 1;
+        MTTS_LAUNCH(plan_rows_p_kernel, dim3((unsigned)((sP.maxM + 255) / 256), 1, (unsigned)tasks), dim3(256), stream, im, o);
         if (with_frames) {
-            MTTS_LAUNCH(plan_rows_f_kernel, dim3((unsigned)((p.maxMf + 255) / 256), 1, (unsigned)tasks), dim3(256), stream, im, o);
+            MTTS_LAUNCH(plan_rows_f_kernel, dim3((unsigned)((sF.maxM + 255) / 256), 1, (unsigned)tasks), dim3(256), stream, im, o);
             MTTS_LAUNCH(plan_prefix_kernel, dim3(1, 1, (unsigned)tasks), dim3(64), stream, im, o);
-            MTTS_LAUNCH(plan_rows_r_kernel, row_grid(p.maxMr, tasks), dim3(256), stream, im, o, cfg.n_mel);
+            MTTS_LAUNCH(plan_rows_r_kernel, row_grid(sR.maxM, tasks), dim3(256), stream, im, o, cfg.n_mel);
         }
         return 0;
     }
@@ -1226,46 +1246,28 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         bool update_bn = true;  // momentum update of the BatchNorm running buffers (off when a pass is re-run for a HVP)
         TS enc_out{nullptr, 0}; // set: the encoder output of this pass was computed ahead of time (run_encoder_ahead): skip embedding + encoder
     };
-    enum Space { SP_P = 0, SP_F = 1, SP_R = 2 };
-
     TS W(const Pass& ps, long long off) const {
         if (ps.use_fast && off >= adapt_start) return TS{fast_cur + (off - adapt_start), n_adapt};
         return TS{theta + off, 0};
     }
     TS Gd(long long off) const { return TS{grad_dst + off, n_total}; }
-    int mfield(Space s) const { return s == SP_P ? META_MP : (s == SP_F ? META_MF : META_MR); }
-    int maxM(const Plan& p, Space s) const { return s == SP_P ? p.maxMp : (s == SP_F ? p.maxMf : p.maxMr); }
-    long long row_ts(Space s) const { return s == SP_P ? row_ts_p : (s == SP_F ? row_ts_f : row_ts_r); }
     // what a rowops.h / tangent.h launcher needs to know about a row space of a plan (mask: the row mask the kernel applies, if any)
-    RowLaunch on_rows(const Plan& p, Space s, hipStream_t st, const unsigned char* mask = nullptr) const {
-        return RowLaunch{p.meta, mfield(s), maxM(p, s), p.tasks, mask, row_ts(s), st};
+    RowLaunch on_rows(const Plan& p, Space s, hipStream_t st, RowMask mask = RowMask()) const {
+        const RowSpace& rs = p.sp[s];
+        return RowLaunch{p.meta, rs.mfield, rs.maxM, p.tasks, mask.m, rs.ts, st};
     }
-    // [row][4] float image of one of the plan's byte masks
-    const float* mask_w(const Plan& p, const unsigned char* m) const {
-        if (m == p.p_valid) return p.p_valid_w;
-        if (m == p.p_inrect) return p.p_inrect_w;
-        if (m == p.f_valid) return p.f_valid_w;
-        if (m == p.r_valid) return p.r_valid_w;
-        if (m == p.r_inrect) return p.r_inrect_w;
-        return nullptr;
-    }
-    const unsigned char* valid_mask(const Plan& p, Space s) const { return s == SP_P ? p.p_valid : (s == SP_F ? p.f_valid : p.r_valid); }
-    const unsigned char* inrect_mask(const Plan& p, Space s) const { return s == SP_P ? p.p_inrect : (s == SP_F ? p.f_valid : p.r_inrect); }
-    long long sumM(const Plan& p, Space s) const { return s == SP_P ? p.sumMp : (s == SP_F ? p.sumMf : p.sumMr); }
-    double alg_rows(const Plan& p, Space s) const { return s == SP_P ? p.sum_nP : p.sum_nF; }
 
     // dst = dropout(src) with the mask stream (plan seed, site); no-op alias when dropout is off
     TS drop(const Pass& ps, Space s, TS src, TS dst, int C, float prob, int site) {
         if (!drop_active(ps) || prob <= 0.f) return src;
         const Plan& p = *ps.pl;
-        const unsigned seed = p.drop_seed * 0x9E3779B1u + (unsigned)site * 0x85EBCA6Bu + 0xC2B2AE35u;
-        const unsigned thr = (unsigned)std::lround((double)prob * 65536.0);
-        MTTS_LAUNCH(dropout_kernel, row_grid(maxM(p, s), p.tasks), dim3(256), stream, (const int*)p.meta, mfield(s), (const float*)src.p,
-                    src.ts, dst.p, dst.ts, C, seed, thr, 1.f / (1.f - prob));
+        const DropSpec d = drop_spec(ps, prob, site);
+        MTTS_LAUNCH(dropout_kernel, row_grid(p.sp[s].maxM, p.tasks), dim3(256), stream, (const int*)p.meta, p.sp[s].mfield, (const float*)src.p,
+                    src.ts, dst.p, dst.ts, C, d.seed, d.thr16, d.scale);
         return dst;
     }
     float block_dropout(Space s) const { return s == SP_P ? cfg.enc_dropout : cfg.dec_dropout; }
-    // the same mask stream as drop(), for kernels that apply the dropout in passing (LayerNorm fwd / bwd)
+    // the mask stream of a dropout site, for drop() and for kernels that apply the dropout in passing (LayerNorm fwd / bwd)
     DropSpec drop_spec(const Pass& ps, float prob, int site) const {
         DropSpec d;
         if (!drop_active(ps) || prob <= 0.f) return d;
@@ -1278,157 +1280,165 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // row-space GEMM over all tasks: C[M,N] (+)= op(A, B); M (or the reduction length for TN) is
     // the task's row count
     GemmArgs rowgemm(const Plan& p, Space s, int form) const {
+        const RowSpace& rs = p.sp[s];
         GemmArgs g;
-        g.dimptr = p.meta + mfield(s);
-        g.dim_stride = META_STRIDE;
-        g.dim_sel = (form == GEMM_TN) ? 2 : 0;
-        g.host_dims = (s == SP_P) ? p.hMp.data() : (s == SP_F) ? p.hMf.data() : p.hMr.data();   // (8-task launches: task-per-XCD schedule, gemm.h)
+        g.dimptr = p.meta + rs.mfield; g.dim_stride = META_STRIDE; g.dim_sel = (form == GEMM_TN) ? 2 : 0;
+        g.host_dims = rs.hM.data();   // (8-task launches: task-per-XCD schedule, gemm.h)
         return g;
     }
 
-    // Y[M,N] = conv_k(X)[M, k*Cin] * W[N][k*Cin]^T + b   (k = 1: Linear)
-    // (x2, w2): second source of a dual-source launch, y = conv(x; w) + conv(x2; w2) (GemmArgs::A2 — the tangent pairs of engine_so.inc)
-    // x_plane: x's operand plane is current (its producer wrote it); y_twin: write y's plane in the epilogue (bf16 mode, see H())
-    // ln (optional): row-complete epilogue — bias + dropout + residual + LayerNorm behind the GEMM (gemm.h: LnFuse; ln_fused_fwd below)
-    void conv_fwd(const Pass& ps, Space s, TS x, int cin, int k, TS w, TS b, int cout, TS y, int flags,
-                  const unsigned char* rowmask, TS relu_ref = TS{nullptr, 0}, TS x2 = TS{nullptr, 0}, TS w2 = TS{nullptr, 0},
-                  bool x_plane = false, bool y_twin = false, const LnFuse* ln = nullptr) {
+    // One Conv1d (k = 1: Linear) on a row space, Y[M, cout] = conv_k(X)[M, k * cin] * W[cout][k * cin]^T + b, as its three launches read it:
+    //   conv_fwd    y  = conv(x; w) + b           (+ conv(x2; w2): second source of a dual-source launch, GemmArgs::A2 — the tangent pairs of engine_so.inc)
+    //   conv_dgrad  x  (+)= sum_taps y[M +- tap] * w     (+ the same of (y2; w2)): x / y hold the GRADIENTS of the conv's input / output
+    //   conv_wgrad  Gd(w_off) = y^T conv_k(x), Gd(b_off) = colsum(y)   (+ y2^T conv_k(x2); the bias sum: y only): y the output gradient, x the input
+    // A call site sets what differs from the defaults.
+    struct ConvOp {
+        TS x{}; int cin = 0, k = 1;
+        TS w{}, b{};
+        TS y{}; int cout = 0;
+        int flags = 0;                  // GEMM_RELU / GEMM_ACCUM
+        RowMask mask;                   // rows of the result that are kept
+        TS relu_ref{};                  // result masked by relu_ref > 0
+        TS x2{}, y2{}, w2{};            // second source
+        bool in_plane = false;          // bf16 mode: the operand plane of the rows read is current (their producer wrote it; see H())
+        bool out_twin = false;          // ... and the epilogue writes the plane of the rows written
+        const LnFuse* ln = nullptr;     // conv_fwd: row-complete epilogue — bias + dropout + residual + LayerNorm behind the GEMM (gemm.h; ln_fused_fwd below)
+        // conv_wgrad only
+        long long w_off = -1, b_off = -1;   // parameter offsets of weight and bias (b_off < 0: no bias gradient)
+        RowMask bias_mask;                  // rows that count in the bias gradient
+        GemmCtx* cx = nullptr;              // launch context and stream (default: the engine's own; the deferred path passes the side stream's)
+        hipStream_t st = nullptr;
+    };
+    static ConvOp conv_op(TS x, int cin, int k, TS w, TS y, int cout, int flags = 0, RowMask mask = RowMask()) {
+        ConvOp c;
+        c.x = x; c.cin = cin; c.k = k; c.w = w; c.y = y; c.cout = cout; c.flags = flags; c.mask = mask;
+        return c;
+    }
+    static ConvOp wgrad_op(TS x, int cin, int k, TS dy, int cout, long long w_off, long long b_off, RowMask bias_mask) {
+        ConvOp c = conv_op(x, cin, k, TS{}, dy, cout);
+        c.w_off = w_off; c.b_off = b_off; c.bias_mask = bias_mask;
+        return c;
+    }
+    ConvOp on_side(ConvOp c) { c.cx = &gx_side; c.st = side; return c; }
+    // What the NT forward, the NT-over-shadow and the NN input gradient share: `in` (in_w channels, + in2) are the rows read with the taps' pad
+    // offset, `out` (out_w channels) the rows written; mask, ReLU reference, flags
+    GemmArgs conv_args(const Plan& p, Space s, int form, const ConvOp& c, TS in, TS in2, int in_w, TS out, int out_w) const {
+        GemmArgs g = rowgemm(p, s, form);
+        const long long po = (long long)(c.k / 2) * in_w;
+        g.A = in.p - po; g.a_gs = in.ts; g.lda = in_w;
+        g.B = c.w.p; g.b_gs = c.w.ts; g.ldb = c.k * c.cin;
+        if (in2.p) { g.A2 = in2.p - po; g.a2_gs = in2.ts; g.B2 = c.w2.p; g.b2_gs = c.w2.ts; }
+        g.C = out.p; g.c_gs = out.ts; g.ldc = out_w;
+        if (c.out_twin) g.Ch = H(out.p);
+        g.N = out_w; g.K = c.k * in_w;
+        g.flags = c.flags;
+        g.rowmask = c.mask.m; g.rowmask_gs = p.sp[s].ts;
+        if (c.relu_ref.p) { g.relu_ref = c.relu_ref.p; g.relu_ref_gs = c.relu_ref.ts; g.ld_relu = out_w; }
+        return g;
+    }
+    static double conv_flops(const Plan& p, Space s, const ConvOp& c, double nsrc) { return nsrc * 2.0 * p.sp[s].alg_rows * c.cout * c.k * c.cin; }
+    // ... and their launch, with the algorithmic flops and bytes the profiler gets (nsrc sources read, one result written, the weights once per task)
+    void conv_launch(const Plan& p, Space s, int form, const GemmArgs& g, const ConvOp& c, double nsrc, int in_w, int out_w) {
+        const RowSpace& rs = p.sp[s];
+        gemm_launch(gx, form, g, rs.maxM, out_w, p.tasks, stream, 0, conv_flops(p, s, c, nsrc), rs.sumM,
+                    4.0 * (rs.alg_rows * (nsrc * in_w + out_w) + nsrc * (double)p.tasks * c.cout * c.k * c.cin));
+    }
+    void conv_fwd(const Pass& ps, Space s, const ConvOp& c) {
         const Plan& p = *ps.pl;
-        GemmArgs g = rowgemm(p, s, GEMM_NT);
-        const int pad = k / 2;
-        const double nsrc = x2.p ? 2.0 : 1.0;
-        g.A = x.p - (long long)pad * cin; g.a_gs = x.ts; g.lda = cin;
-        g.B = w.p; g.b_gs = w.ts; g.ldb = k * cin;
-        if (x2.p) { g.A2 = x2.p - (long long)pad * cin; g.a2_gs = x2.ts; g.B2 = w2.p; g.b2_gs = w2.ts; }
-        g.C = y.p; g.c_gs = y.ts; g.ldc = cout;
-        g.N = cout; g.K = k * cin;
-        g.bias = b.p; g.bias_gs = b.ts;
-        g.flags = flags;
-        g.rowmask = rowmask; g.rowmask_gs = row_ts(s);
-        if (relu_ref.p) { g.relu_ref = relu_ref.p; g.relu_ref_gs = relu_ref.ts; g.ld_relu = cout; }
-        if (!x2.p) {   // bf16 mode: the operands' planes (the weight's shadow + the input slab's twin), where both exist
-            const HP wh = Wh(ps, w, false);
+        GemmArgs g = conv_args(p, s, GEMM_NT, c, c.x, c.x2, c.cin, c.y, c.cout);
+        g.bias = c.b.p; g.bias_gs = c.b.ts;
+        if (!c.x2.p) {   // bf16 mode: the operands' planes (the weight's shadow + the input slab's twin), where both exist
+            const HP wh = Wh(ps, c.w, false);
             if (wh.p) {
-                const bf16_t* xh = x_plane ? H(x.p) : make_plane(x, cin, p.tasks);
-                if (xh) { g.Ah = xh - (long long)pad * cin; g.Bh = wh.p; g.bh_gs = wh.ts; await_shadows(); }
+                const bf16_t* xh = c.in_plane ? H(c.x.p) : make_plane(c.x, c.cin, p.tasks);
+                if (xh) { g.Ah = xh - (long long)(c.k / 2) * c.cin; g.Bh = wh.p; g.bh_gs = wh.ts; await_shadows(); }
             }
         }
-        if (y_twin) g.Ch = H(y.p);
-        if (ln) g.ln = *ln;
-        gemm_launch(gx, GEMM_NT, g, maxM(p, s), cout, p.tasks, stream, 0, nsrc * 2.0 * alg_rows(p, s) * cout * k * cin, sumM(p, s),
-                    4.0 * (alg_rows(p, s) * (nsrc * cin + cout) + nsrc * (double)p.tasks * cout * k * cin));
+        if (c.ln) g.ln = *c.ln;
+        conv_launch(p, s, GEMM_NT, g, c, c.x2.p ? 2.0 : 1.0, c.cin, c.cout);
     }
     // sublayer GEMM + `LayerNorm(dropout(.) + residual)` (SubLayers.py:54-55,90-91): the GEMM followed by layernorm_fwd_kernel — or, with
     // MTTS_LN_FUSE=1, ONE launch when the GEMM can carry the row-complete epilogue (fp32 mode, C <= 256, a launcher context with counters): bit-identical,
     // but measured SLOWER (profiles/r05_ab_log.md: the write-through stores, the drain + counter rendezvous and the one-workgroup-per-m-tile tail
     // cost more than the 5-17 us launch they replace), so it stays opt-in.
-    // z receives the sublayer output a, then (in place) a' = dropout(a) + res — what the backward keeps; y the normalised rows.
-    void ln_fused_fwd(const Pass& ps, Space s, TS x, int cin, int k, TS w, TS b, TS z, TS res, long long g_off, long long b_off,
-                      const unsigned char* mask, TS y, TS st, int C, DropSpec din, bool x_plane, bool y_twin) {
+    // c.y receives the sublayer output a, then (in place) a' = dropout(a) + res — what the backward keeps; y the normalised rows.
+    void ln_fused_fwd(const Pass& ps, Space s, ConvOp c, TS res, long long g_off, long long b_off, RowMask mask, TS y, TS st, DropSpec din, bool y_twin) {
         const Plan& p = *ps.pl;
         GemmArgs probe;
-        probe.N = C;
-        if (knobs().ln_fuse && !ablate_ln() && !gx.batch.open && gemm_ln_fusable(gx, GEMM_NT, probe, maxM(p, s), p.tasks)) {
-            LnFuse f;
+        LnFuse f;
+        probe.N = c.cout;
+        if (knobs().ln_fuse && !ablate_ln() && !gx.batch.open && gemm_ln_fusable(gx, GEMM_NT, probe, p.sp[s].maxM, p.tasks)) {
             TS gm = W(ps, g_off), bt = W(ps, b_off);
-            f.res = res.p; f.res_gs = res.ts;
-            f.gamma = gm.p; f.beta = bt.p; f.par_gs = gm.ts;
-            f.mask = mask; f.mask_gs = row_ts(s);
-            f.y = y.p; f.y_gs = y.ts;
-            f.stats = st.p; f.st_gs = st.ts;
+            f.res = res.p; f.res_gs = res.ts; f.gamma = gm.p; f.beta = bt.p; f.par_gs = gm.ts;
+            f.mask = mask.m; f.mask_gs = p.sp[s].ts; f.y = y.p; f.y_gs = y.ts; f.stats = st.p; f.st_gs = st.ts;
             f.drop_seed = din.seed; f.drop_thr16 = din.thr16; f.drop_scale = din.scale;
-            conv_fwd(ps, s, x, cin, k, w, b, C, z, 0, nullptr, TS{nullptr, 0}, TS{nullptr, 0}, TS{nullptr, 0}, x_plane, false, &f);
-            return;
+            c.ln = &f;
         }
-        conv_fwd(ps, s, x, cin, k, w, b, C, z, 0, nullptr, TS{nullptr, 0}, TS{nullptr, 0}, TS{nullptr, 0}, x_plane, false);
-        ln_fwd(ps, s, z, res, g_off, b_off, mask, z, y, st, C, din, DropSpec(), y_twin);
+        conv_fwd(ps, s, c);
+        if (!c.ln) ln_fwd(ps, s, c.y, res, g_off, b_off, mask, c.y, y, st, c.cout, din, DropSpec(), y_twin);
     }
-    // dX[M,Cin] (+)= sum_taps dY[M +- tap, Cout] * W  (conv dgrad over the same [Cout][k][Cin] image)
-    void conv_dgrad(const Pass& ps, Space s, TS dy, int cout, int k, TS w, int cin, TS dx, int flags,
-                    const unsigned char* rowmask, TS relu_ref = TS{nullptr, 0}, TS dy2 = TS{nullptr, 0}, TS w2 = TS{nullptr, 0},
-                    bool dy_plane = false, bool dx_twin = false) {
+    void conv_dgrad(const Pass& ps, Space s, const ConvOp& c) {
         const Plan& p = *ps.pl;
-        const int pad = k / 2;
-        if (!dy2.p) {
+        if (!c.y2.p) {
             // bf16 mode with planes: dX = conv(dY; flipped transposed W) as an NT problem over the weight's input-gradient shadow — the
             // forward conv's kernel path with Cin and Cout exchanged (weight_shadow_kernel)
-            const HP wt = Wh(ps, w, true);
-            const bf16_t* dyh = !wt.p ? nullptr : (dy_plane ? H(dy.p) : make_plane(dy, cout, p.tasks));
+            const HP wt = Wh(ps, c.w, true);
+            const bf16_t* dyh = !wt.p ? nullptr : (c.in_plane ? H(c.y.p) : make_plane(c.y, c.cout, p.tasks));
             if (dyh) {
                 await_shadows();
-                GemmArgs g = rowgemm(p, s, GEMM_NT);
-                g.A = dy.p - (long long)pad * cout; g.a_gs = dy.ts; g.lda = cout;
-                g.Ah = dyh - (long long)pad * cout;
-                g.B = nullptr; g.b_gs = 0; g.ldb = k * cout; g.Bh = wt.p; g.bh_gs = wt.ts; g.plane_only = true;
-                g.C = dx.p; g.c_gs = dx.ts; g.ldc = cin;
-                if (dx_twin) g.Ch = H(dx.p);
-                g.N = cin; g.K = k * cout;
-                g.flags = flags;
-                g.rowmask = rowmask; g.rowmask_gs = row_ts(s);
-                if (relu_ref.p) { g.relu_ref = relu_ref.p; g.relu_ref_gs = relu_ref.ts; g.ld_relu = cin; }
-                gemm_launch(gx, GEMM_NT, g, maxM(p, s), cin, p.tasks, stream, 0, 2.0 * alg_rows(p, s) * cout * k * cin, sumM(p, s),
-                            4.0 * (alg_rows(p, s) * (cin + cout) + (double)p.tasks * cout * k * cin));
+                GemmArgs g = conv_args(p, s, GEMM_NT, c, c.y, TS{}, c.cout, c.x, c.cin);
+                g.Ah = dyh - (long long)(c.k / 2) * c.cout;
+                g.B = nullptr; g.b_gs = 0; g.ldb = c.k * c.cout; g.Bh = wt.p; g.bh_gs = wt.ts; g.plane_only = true;
+                conv_launch(p, s, GEMM_NT, g, c, 1.0, c.cout, c.cin);
                 return;
             }
         }
-        GemmArgs g = rowgemm(p, s, GEMM_NN);
-        const double nsrc = dy2.p ? 2.0 : 1.0;
-        g.A = dy.p - (long long)pad * cout; g.a_gs = dy.ts; g.lda = cout;
-        g.B = w.p; g.b_gs = w.ts; g.ldb = k * cin;
-        if (dy2.p) { g.A2 = dy2.p - (long long)pad * cout; g.a2_gs = dy2.ts; g.B2 = w2.p; g.b2_gs = w2.ts; }
-        g.C = dx.p; g.c_gs = dx.ts; g.ldc = cin;
-        if (dx_twin) g.Ch = H(dx.p);
-        g.N = cin; g.K = k * cout;
-        g.taps = k; g.tap_k = cout; g.tap_bstride = cin;
-        g.flags = flags;
-        g.rowmask = rowmask; g.rowmask_gs = row_ts(s);
-        if (relu_ref.p) { g.relu_ref = relu_ref.p; g.relu_ref_gs = relu_ref.ts; g.ld_relu = cin; }
-        gemm_launch(gx, GEMM_NN, g, maxM(p, s), cin, p.tasks, stream, 0, nsrc * 2.0 * alg_rows(p, s) * cout * k * cin, sumM(p, s),
-                    4.0 * (alg_rows(p, s) * (cin + nsrc * cout) + nsrc * (double)p.tasks * cout * k * cin));
+        GemmArgs g = conv_args(p, s, GEMM_NN, c, c.y, c.y2, c.cout, c.x, c.cin);
+        g.taps = c.k; g.tap_k = c.cout; g.tap_bstride = c.cin;   // the tap walk over the same [cout][k][cin] image
+        conv_launch(p, s, GEMM_NN, g, c, c.y2.p ? 2.0 : 1.0, c.cout, c.cin);
     }
-    // dW[Cout][k*Cin] = dY^T * conv_k(X), db = colsum(dY)
-    // cx / st: launch context (default: the engine's own context and stream; the deferred path passes the side stream's)
-    void conv_wgrad(const Pass& ps, Space s, TS dy, int cout, int k, TS x, int cin, long long w_off, long long b_off,
-                    const unsigned char* bias_mask, int flags = 0, GemmCtx* cx = nullptr, hipStream_t st = nullptr,
-                    TS dy2 = TS{nullptr, 0}, TS x2 = TS{nullptr, 0}) {
+    void conv_wgrad(const Pass& ps, Space s, const ConvOp& c) {
         const Plan& p = *ps.pl;
-        GemmCtx& gcx = cx ? *cx : gx;
-        const hipStream_t gst = cx ? st : stream;
+        const RowSpace& rs = p.sp[s];
         GemmArgs g = rowgemm(p, s, GEMM_TN);
-        const int pad = k / 2;
-        g.A = dy.p; g.a_gs = dy.ts; g.lda = cout;
-        g.B = x.p - (long long)pad * cin; g.b_gs = x.ts; g.ldb = cin;
-        const double nsrc = dy2.p ? 2.0 : 1.0;
-        if (dy2.p) { g.A2 = dy2.p; g.a2_gs = dy2.ts; g.B2 = x2.p - (long long)pad * cin; g.b2_gs = x2.ts; }   // dW = dy^T x + dy2^T x2 (the bias sum: dy only)
-        TS gw = Gd(w_off);
-        g.C = gw.p; g.c_gs = gw.ts; g.ldc = k * cin;
-        g.M = cout; g.N = k * cin;
-        g.K = maxM(p, s);  // upper bound of the per-task reduction length (the kernel reads the exact one through dimptr)
-        g.flags = flags;
+        const long long po = (long long)(c.k / 2) * c.cin;   // (the padded operand of this form is B)
+        const double nsrc = c.y2.p ? 2.0 : 1.0;
+        g.A = c.y.p; g.a_gs = c.y.ts; g.lda = c.cout;
+        g.B = c.x.p - po; g.b_gs = c.x.ts; g.ldb = c.cin;
+        if (c.y2.p) { g.A2 = c.y2.p; g.a2_gs = c.y2.ts; g.B2 = c.x2.p - po; g.b2_gs = c.x2.ts; }
+        TS gw = Gd(c.w_off);
+        g.C = gw.p; g.c_gs = gw.ts; g.ldc = c.k * c.cin;
+        g.M = c.cout; g.N = c.k * c.cin; g.flags = c.flags;
+        g.K = rs.maxM;  // upper bound of the per-task reduction length (the kernel reads the exact one through dimptr)
         // the bias gradient rides on the weight-gradient GEMM (GemmArgs::colsum: one extra n-tile against the mask's float image)
         // instead of two reduction launches per layer
-        const float* mw = mask_w(p, bias_mask);
-        const bool fused = b_off >= 0 && mw != nullptr;
+        const bool fused = c.b_off >= 0 && c.bias_mask.w != nullptr;
         if (fused) {
-            TS gb = Gd(b_off);
-            g.colsum = gb.p; g.colsum_gs = gb.ts; g.colsum_w = mw; g.colsum_w_gs = 4 * row_ts(s);
+            TS gb = Gd(c.b_off);
+            g.colsum = gb.p; g.colsum_gs = gb.ts; g.colsum_w = c.bias_mask.w; g.colsum_w_gs = 4 * rs.ts;
         }
-        gemm_launch(gcx, GEMM_TN, g, cout, k * cin, p.tasks, gst, 0, nsrc * 2.0 * alg_rows(p, s) * cout * k * cin, (long long)cout * p.tasks,
-                    4.0 * (nsrc * alg_rows(p, s) * (cin + cout) + (double)p.tasks * cout * k * cin));
-        if (b_off >= 0 && !fused) colsum(ps, s, dy, cout, bias_mask, TS{nullptr, 0}, Gd(b_off));   // (main stream: never reached on the deferred path)
+        gemm_launch(c.cx ? *c.cx : gx, GEMM_TN, g, c.cout, c.k * c.cin, p.tasks, c.cx ? c.st : stream, 0, conv_flops(p, s, c, nsrc), (long long)c.cout * p.tasks,
+                    4.0 * (nsrc * rs.alg_rows * (c.cin + c.cout) + (double)p.tasks * c.cout * c.k * c.cin));
+        if (c.b_off >= 0 && !fused) colsum(ps, s, c.y, c.cout, c.bias_mask, TS{}, Gd(c.b_off));   // (main stream: never reached on the deferred path)
     }
     // two-stage deterministic column reduction (rowops.h colpart/colfinal)
     void colreduce(const Plan& p, ColArgs a, float* out0, float* out1, long long out_ts, Space s, bool on_side = false) {
         // on_side: the deferred path's reductions — side stream, its own partial buffer
         // (single-launch variants were built and measured slower in rounds 2-3: a workgroup per 32-column stripe walking all rows is latency-
         // bound, +10 % on the 8-task step; a last-arriver fold needs an agent-scope release / acquire amid the GEMMs' dirty L2 lines, +10 %)
-        launch_colreduce(on_rows(p, s, on_side ? (hipStream_t)side : stream, a.mask), a, on_side ? col_partial_side : col_partial, col_max_chunks, out0, out1, out_ts);
+        RowLaunch r = on_rows(p, s, on_side ? (hipStream_t)side : stream); r.mask = a.mask;
+        launch_colreduce(r, a, on_side ? col_partial_side : col_partial, col_max_chunks, out0, out1, out_ts);
     }
-    void colsum(const Pass& ps, Space s, TS x, int C, const unsigned char* mask, TS roww, TS out, bool on_side = false) {
-        const Plan& p = *ps.pl;
+    // the ColArgs fields every masked reduction over space s sets
+    ColArgs col_args(const Plan& p, Space s, RowMask mask, int C, int mode) const {
         ColArgs a;
-        a.X = x.p; a.x_ts = x.ts; a.mask = mask; a.mask_ts = row_ts(s); a.roww = roww.p; a.roww_ts = roww.ts;
-        a.C = C; a.mode = 0; a.mfield = mfield(s);
+        a.mask = mask.m; a.mask_ts = p.sp[s].ts; a.C = C; a.mode = mode; a.mfield = p.sp[s].mfield;
+        return a;
+    }
+    void colsum(const Pass& ps, Space s, TS x, int C, RowMask mask, TS roww, TS out, bool on_side = false) {
+        const Plan& p = *ps.pl;
+        ColArgs a = col_args(p, s, mask, C, 0);
+        a.X = x.p; a.x_ts = x.ts; a.roww = roww.p; a.roww_ts = roww.ts;
         colreduce(p, a, out.p, nullptr, out.ts, s, on_side);
     }
     // MEASUREMENT ONLY (results are wrong): MTTS_ABLATE_LN=1 drops every LayerNorm forward / backward launch of the FFT blocks and predictors — the
@@ -1439,7 +1449,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
 #else
     static constexpr bool ablate_ln() { return false; }
 #endif
-    void ln_fwd(const Pass& ps, Space s, TS a, TS res, long long g_off, long long b_off, const unsigned char* mask,
+    void ln_fwd(const Pass& ps, Space s, TS a, TS res, long long g_off, long long b_off, RowMask mask,
                 TS zout, TS y, TS st, int C, DropSpec din = DropSpec(), DropSpec dout = DropSpec(), bool y_twin = false) {
         // y_twin: bf16 mode — also write y's operand plane (H(y)): the next conv reads it instead of a conversion pass
         if (ablate_ln()) return;
@@ -1452,7 +1462,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // part: null = the gamma / beta reduction completes here (the kernel's 8-row partials in the shared scratch + one colfinal launch on this
     //       stream); set = the partials are left in `part` ([tasks][ln_chunks][3][C], a buffer of the site's own) and ln_param_grads_side
     //       folds them later on the side stream (deferred parameter gradients)
-    void ln_bwd(const Pass& ps, Space s, TS dy, TS z, TS st, long long g_off, long long b_off, const unsigned char* mask,
+    void ln_bwd(const Pass& ps, Space s, TS dy, TS z, TS st, long long g_off, long long b_off, RowMask mask,
                 TS dz, int C, int relu_on_z, TS dz_drop = TS{nullptr, 0}, DropSpec dd = DropSpec(), bool copy_always = false,
                 float* part = nullptr, DropSpec din = DropSpec(), int twin_sel = 0) {
         // twin_sel: bf16 mode — also write the operand plane of dz (1) or of dz_drop (2)
@@ -1470,37 +1480,37 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     }
     void attn_gemm(const Pass& ps, Space s, int which, int form, const float* A, int lda, const float* B, int ldb,
                    float* C, int ldc, float alpha, int heads, int flags = 0, const float* A2 = nullptr, const float* B2 = nullptr) {
-        const Plan& p = *ps.pl;
+        const AttnSide& a = ps.pl->at[side_of(s)];
         GemmArgs g;
-        g.table = (s == SP_P) ? p.enc_tab[which] : p.dec_tab[which];
+        g.table = a.tab[which];
         g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.alpha = alpha; g.flags = flags;
         g.A2 = A2; g.B2 = B2;   // dual source: the same per-(sequence, head) offsets into a second pair of buffers
         const double nsrc = A2 ? 2.0 : 1.0;
-        const int L = (s == SP_P) ? p.enc_maxL : p.dec_maxL, dk = cfg.d_model / heads;
-        const int groups = (s == SP_P) ? p.n_enc_groups : p.n_dec_groups;
+        const int L = a.maxL, dk = cfg.d_model / heads;
         int mM = L, mN = L;
         if (which == TAB_PV || which == TAB_DV || which == TAB_DQ || which == TAB_DK) mN = dk;
         g.K = (which == TAB_QK || which == TAB_DP) ? dk : L;  // cost hint for launch batching (the table carries the real K)
         // per (sequence, head): two L x dk operands and one L x L matrix, each moved once
-        const double sumL2 = (s == SP_P) ? p.sum_attn_p : p.sum_attn_f, sumL = (double)((s == SP_P) ? p.sumLp : p.sumLf);
-        gemm_launch(gx, form, g, mM, mN, groups, stream, 0, nsrc * 2.0 * sumL2 * dk, (s == SP_P) ? p.sumLp : p.sumLf,
-                    4.0 * nsrc * (sumL2 + 2.0 * sumL * dk));
+        gemm_launch(gx, form, g, mM, mN, a.groups, stream, 0, nsrc * 2.0 * a.sum_attn * dk, a.sumL,
+                    4.0 * nsrc * (a.sum_attn + 2.0 * (double)a.sumL * dk));
     }
 
     // =================================================================================
     // FFT block (transformer/Layers.py:21-30)
     // =================================================================================
-    void fft_fwd(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, TS xin, TS S_unused) {
+    void fft_fwd(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, TS xin) {
         TagScope tag_scope(*this, s == SP_P ? 1 : 2);
-        (void)S_unused;
         const Plan& p = *ps.pl;
+        const AttnSide& at = p.at[side_of(s)];
         const int d = cfg.d_model, dk = d / heads;
-        const unsigned char* vm = valid_mask(p, s);
-        const unsigned char* im = inrect_mask(p, s);
-        conv_fwd(ps, s, xin, d, 1, W(ps, P.wqkv), W(ps, P.bqkv), 3 * d, b.qkv, 0, nullptr);
-        const int groups = (s == SP_P) ? p.n_enc_groups : p.n_dec_groups;
-        const int L = (s == SP_P) ? p.enc_maxL : p.dec_maxL;
-        const AttnSeq* seqs = (s == SP_P) ? p.enc_seqs : p.dec_seqs;
+        const RowMask vm = p.sp[s].valid, im = p.sp[s].inrect;
+        ConvOp qkv = conv_op(xin, d, 1, W(ps, P.wqkv), b.qkv, 3 * d), fc = conv_op(b.O, d, 1, W(ps, P.wfc), b.z1, d);
+        ConvOp c1 = conv_op(b.y1, d, cfg.k1, W(ps, P.w1), b.h, cfg.d_ff, GEMM_RELU, im), c2 = conv_op(b.h, cfg.d_ff, cfg.k2, W(ps, P.w2), b.z2, d);
+        qkv.b = W(ps, P.bqkv); fc.b = W(ps, P.bfc); c1.b = W(ps, P.b1); c2.b = W(ps, P.b2);
+        c1.in_plane = c1.out_twin = c2.in_plane = true;   // (bf16 mode: y1's and h's operand planes are written by their producers — the LayerNorm kernel, conv1's epilogue)
+        conv_fwd(ps, s, qkv);
+        const int groups = at.groups, L = at.maxL;
+        const AttnSeq* seqs = at.seqs;
         // scaled-dot-product attention (Modules.py:14-25): ONE fused launch (attention.h) — the score tile of 32 query rows lives in LDS
         // between Q K^T, the softmax and P V; the probabilities go to HBM once, for the backward.  MTTS_FUSED_ATTN=0 (A/B runs), the bf16
         // numerics mode (measured on C2: 7.28 ms with this fp32 kernel, 7.15 ms with bf16 grouped GEMMs around the softmax kernel) and
@@ -1508,8 +1518,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         if (knobs().fused_attn && !gx.bf16 && attn_fused_ok(L, dk) && groups > 0) {
             AttnFwdArgs fa;
             fa.seqs = seqs;
-            fa.tab_qk = (s == SP_P) ? p.enc_tab[TAB_QK] : p.dec_tab[TAB_QK];
-            fa.tab_pv = (s == SP_P) ? p.enc_tab[TAB_PV] : p.dec_tab[TAB_PV];
+            fa.tab_qk = at.tab[TAB_QK]; fa.tab_pv = at.tab[TAB_PV];
             fa.Q = fa.K = fa.V = b.qkv.p; fa.ld_q = fa.ld_k = fa.ld_v = 3 * d;
             fa.P = b.P.p; fa.O = b.O.p; fa.ld_o = d;
             fa.scale = 1.f / sqrtf((float)dk); fa.dk = dk; fa.rot = 0; fa.prio = gx.wave_prio;
@@ -1522,7 +1531,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             attn_fwd_launch(fa, L, groups, stream);
             if (prof.enabled) {
                 hipEventRecord(e1, stream);
-                const double sumL2 = (s == SP_P) ? p.sum_attn_p : p.sum_attn_f, sumL = (double)((s == SP_P) ? p.sumLp : p.sumLf);
+                const double sumL2 = at.sum_attn, sumL = (double)at.sumL;
                 GemmProfiler::Rec rec{GK_ATTN_FWD, 2.0 * 2.0 * sumL2 * dk, e0, e1};   // both products
                 rec.form = 4; rec.tile = 32; rec.N = dk; rec.K = L; rec.groups = groups; rec.rows = sumL;
                 rec.bytes = 4.0 * (sumL2 + 4.0 * sumL * dk);                          // Q, K, V read, O and P written once
@@ -1536,14 +1545,11 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             attn_gemm(ps, s, TAB_PV, GEMM_NN, b.P.p, 0, b.qkv.p, 3 * d, b.O.p, d, 1.f, heads);
         }
         // self.dropout(self.fc(output)) + residual -> LayerNorm (SubLayers.py:54-55): in the fc GEMM's launch (row-complete epilogue), or
-        // the dropout riding in the LayerNorm kernel (bf16 mode: y1's and h's operand planes are written by their producers — the LayerNorm
-        // kernel, conv1's epilogue)
-        ln_fused_fwd(ps, s, b.O, d, 1, W(ps, P.wfc), W(ps, P.bfc), b.z1, xin, P.ln1g, P.ln1b, vm, b.y1, b.st1, d,
-                     drop_spec(ps, block_dropout(s), site_base), false, true);
-        conv_fwd(ps, s, b.y1, d, cfg.k1, W(ps, P.w1), W(ps, P.b1), cfg.d_ff, b.h, GEMM_RELU, im, TS{nullptr, 0}, TS{nullptr, 0}, TS{nullptr, 0}, true, true);
+        // the dropout riding in the LayerNorm kernel
+        ln_fused_fwd(ps, s, fc, xin, P.ln1g, P.ln1b, vm, b.y1, b.st1, drop_spec(ps, block_dropout(s), site_base), true);
+        conv_fwd(ps, s, c1);
         // self.dropout(output) + residual -> LayerNorm (SubLayers.py:90-91)
-        ln_fused_fwd(ps, s, b.h, cfg.d_ff, cfg.k2, W(ps, P.w2), W(ps, P.b2), b.z2, b.y1, P.ln2g, P.ln2b, vm, b.y2, b.st2, d,
-                     drop_spec(ps, block_dropout(s), site_base + 1), true, false);
+        ln_fused_fwd(ps, s, c2, b.y1, P.ln2g, P.ln2b, vm, b.y2, b.st2, drop_spec(ps, block_dropout(s), site_base + 1), false);
     }
 
     // g0_in holds dL/dy2; K.g0 receives dL/dx, K.gh / K.dy1 / K.dO / K.gqkv the gradients in between (LayerKeep: by default aliases of
@@ -1556,9 +1562,9 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                  TS dS, LayerGrad* lg = nullptr, float* const* fold_part = nullptr) {
         TagScope tag_scope(*this, s == SP_P ? 1 : 2);
         const Plan& p = *ps.pl;
+        const AttnSide& at = p.at[side_of(s)];
         const int d = cfg.d_model, dk = d / heads, ff = cfg.d_ff;
-        const unsigned char* vm = valid_mask(p, s);
-        const unsigned char* im = inrect_mask(p, s);
+        const RowMask vm = p.sp[s].valid, im = p.sp[s].inrect;
         const bool df = lg != nullptr;
         TS g0 = K.g0, g1 = K.dy1, gqkv = K.gqkv, gh = K.gh;
         if (df && K.dy1.p == K.dO.p) { gh = lg->gh; gqkv = lg->gqkv; }   // (a set of its own already has a buffer per layer)
@@ -1572,59 +1578,61 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                (df || dd2.thr16) ? 2 : 1);
         TS dc = df ? lg->dc : (dd2.thr16 ? gm : g1);
         // conv2
+        // the layer's four weight (+ bias) gradients, here beside their input gradients or (deferred) together at the end
+        const ConvOp w2g = wgrad_op(b.h, ff, cfg.k2, dc, d, P.w2, P.b2, vm), w1g = wgrad_op(b.y1, d, cfg.k1, gh, ff, P.w1, P.b1, im);
         {   // wgrad and dgrad of a layer are independent: one multi-problem launch (gemm.h: gemm_f32_multi_kernel)
             GemmBatchScope pair(gx, stream);
-            if (!df) conv_wgrad(ps, s, dc, d, cfg.k2, b.h, ff, P.w2, P.b2, vm);
-            conv_dgrad(ps, s, dc, d, cfg.k2, W(ps, P.w2), ff, gh, 0, im, b.h, TS{nullptr, 0}, TS{nullptr, 0}, true, true);
+            if (!df) conv_wgrad(ps, s, w2g);
+            ConvOp c = conv_op(gh, ff, cfg.k2, W(ps, P.w2), dc, d, 0, im);
+            c.relu_ref = b.h; c.in_plane = c.out_twin = true;
+            conv_dgrad(ps, s, c);
         }
         // conv1: g1 += dgrad -> dy1
         {
             GemmBatchScope pair(gx, stream);
-            if (!df) conv_wgrad(ps, s, gh, ff, cfg.k1, b.y1, d, P.w1, P.b1, im);
-            conv_dgrad(ps, s, gh, ff, cfg.k1, W(ps, P.w1), d, g1, GEMM_ACCUM, im, TS{nullptr, 0}, TS{nullptr, 0}, TS{nullptr, 0}, true, false);
+            if (!df) conv_wgrad(ps, s, w1g);
+            ConvOp c = conv_op(g1, d, cfg.k1, W(ps, P.w1), gh, ff, GEMM_ACCUM, im);
+            c.in_plane = true;
+            conv_dgrad(ps, s, c);
         }
         // LN1 backward -> g0 = dz1
         const DropSpec dd1 = drop_spec(ps, block_dropout(s), site_base);
         ln_bwd(ps, s, g1, b.z1, b.st1, P.ln1g, P.ln1b, vm, g0, d, 0, df ? lg->da : gm, dd1, df, df ? lg->part1 : fp1);
         TS da = df ? lg->da : (dd1.thr16 ? gm : g0);
         // fc
+        const ConvOp fcg = wgrad_op(b.O, d, 1, da, d, P.wfc, P.bfc, vm);
         {
             GemmBatchScope pair(gx, stream);
-            if (!df) conv_wgrad(ps, s, da, d, 1, b.O, d, P.wfc, P.bfc, vm);
-            conv_dgrad(ps, s, da, d, 1, W(ps, P.wfc), d, K.dO, 0, nullptr);
+            if (!df) conv_wgrad(ps, s, fcg);
+            conv_dgrad(ps, s, conv_op(K.dO, d, 1, W(ps, P.wfc), da, d));
         }
         g1 = K.dO;
         // attention
-        const int groups = (s == SP_P) ? p.n_enc_groups : p.n_dec_groups;
-        const int L = (s == SP_P) ? p.enc_maxL : p.dec_maxL;
-        const AttnSeq* seqs = (s == SP_P) ? p.enc_seqs : p.dec_seqs;
         {
             GemmBatchScope pair(gx, stream);
             attn_gemm(ps, s, TAB_DP, GEMM_NT, g1.p, d, b.qkv.p, 3 * d, dS.p, 0, 1.f, heads);
             attn_gemm(ps, s, TAB_DV, GEMM_TN, b.P.p, 0, g1.p, d, gqkv.p, 3 * d, 1.f, heads);
         }
-        if (groups > 0 && L > 0)
-            launch_softmax_bwd(seqs, L, groups, b.P.p, dS.p, 1.f / sqrtf((float)dk), stream);
+        if (at.groups > 0 && at.maxL > 0)
+            launch_softmax_bwd(at.seqs, at.maxL, at.groups, b.P.p, dS.p, 1.f / sqrtf((float)dk), stream);
         {
             GemmBatchScope pair(gx, stream);
             attn_gemm(ps, s, TAB_DQ, GEMM_NN, dS.p, 0, b.qkv.p, 3 * d, gqkv.p, 3 * d, 1.f, heads);
             attn_gemm(ps, s, TAB_DK, GEMM_TN, dS.p, 0, b.qkv.p, 3 * d, gqkv.p, 3 * d, 1.f, heads);
         }
         // fused q/k/v projection
+        const ConvOp qkvg = wgrad_op(xin, d, 1, gqkv, 3 * d, P.wqkv, P.bqkv, vm);
         {
             GemmBatchScope pair(gx, stream);
-            if (!df) conv_wgrad(ps, s, gqkv, 3 * d, 1, xin, d, P.wqkv, P.bqkv, vm);
-            conv_dgrad(ps, s, gqkv, 3 * d, 1, W(ps, P.wqkv), d, g0, GEMM_ACCUM, nullptr);
+            if (!df) conv_wgrad(ps, s, qkvg);
+            conv_dgrad(ps, s, conv_op(g0, d, 1, W(ps, P.wqkv), gqkv, 3 * d, GEMM_ACCUM));
         }
         if (df) {
             // the layer's four weight (+ bias) gradients: one multi-problem launch on the side stream, after everything above
             fork_side();
             {
                 GemmBatchScope batch(gx_side, side);
-                conv_wgrad(ps, s, gh, ff, cfg.k1, b.y1, d, P.w1, P.b1, im, 0, &gx_side, side);
-                conv_wgrad(ps, s, dc, d, cfg.k2, b.h, ff, P.w2, P.b2, vm, 0, &gx_side, side);
-                conv_wgrad(ps, s, gqkv, 3 * d, 1, xin, d, P.wqkv, P.bqkv, vm, 0, &gx_side, side);
-                conv_wgrad(ps, s, da, d, 1, b.O, d, P.wfc, P.bfc, vm, 0, &gx_side, side);
+                for (const ConvOp* g : {&w1g, &w2g, &qkvg, &fcg}) conv_wgrad(ps, s, on_side(*g));
             }
             ln_param_grads_side(ps, s, lg->part2, P.ln2g, P.ln2b, d);
             ln_param_grads_side(ps, s, lg->part1, P.ln1g, P.ln1b, d);
@@ -1639,7 +1647,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // gradient rides on the GEMM — the separate column reduction would run on the main stream)
     bool defer_ok(const Plan& p) const {
         constexpr long long kDeferMaxRows = 16000;   // beyond this the launches fill the chip and the wgrad + dgrad pairing wins (measured: 4 / 8 tasks per rank neutral / -1 %)
-        return knobs().defer_wgrad && defer_tasks > 0 && p.tasks <= defer_tasks && p.sumMf <= kDeferMaxRows && side != nullptr;
+        return knobs().defer_wgrad && defer_tasks > 0 && p.tasks <= defer_tasks && p.sp[SP_F].sumM <= kDeferMaxRows && side != nullptr;
     }
     // call-site class of the GEMM launches issued from here on (the profiler's per-launch records carry it: GemmProfiler::tag)
     void set_tag(int t) { gx.prof.tag = gx_side.prof.tag = gx_side2.prof.tag = t; }
@@ -1829,7 +1837,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     void set_regime(const Plan& p) {
         gx.no_glds = gemm_glds_mode() == 0;
         const int mp = knobs().main_prio;
-        gx.wave_prio = (mp == 2 || (mp == 1 && defer_ok(p) && p.sumMf <= kPrioMaxRows)) ? 1 : 0;
+        gx.wave_prio = (mp == 2 || (mp == 1 && defer_ok(p) && p.sp[SP_F].sumM <= kPrioMaxRows)) ? 1 : 0;
     }
 
     // everything enqueued on the main stream so far happens before what is enqueued on the side stream next
@@ -1847,18 +1855,24 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // =================================================================================
     // variance predictor (lightning/model/modules.py:242-250)
     // =================================================================================
+    // a predictor's conv + ReLU (cin -> vp_filter channels, vp_kernel taps)
+    ConvOp pred_conv(const Pass& ps, TS x, int cin, long long w_off, long long b_off, TS y, RowMask im) const {
+        ConvOp c = conv_op(x, cin, cfg.vp_kernel, W(ps, w_off), y, cfg.vp_filter, GEMM_RELU, im);
+        c.b = W(ps, b_off);
+        return c;
+    }
     void pred_fwd(const Pass& ps, const PredP& P, PredBuf& b, TS xin, Space s = SP_P) {
         TagScope tag_scope(*this, 4);
         const Plan& p = *ps.pl;
-        const int d = cfg.d_model, f = cfg.vp_filter, k = cfg.vp_kernel;
-        const unsigned char* im = inrect_mask(p, s);   // conv outputs / LayerNorm live on every position of the rectangle
+        const int d = cfg.d_model, f = cfg.vp_filter;
+        const RowMask im = p.sp[s].inrect;   // conv outputs / LayerNorm live on every position of the rectangle
         TS none{nullptr, 0};
-        conv_fwd(ps, s, xin, d, k, W(ps, P.c1w), W(ps, P.c1b), f, b.r1, GEMM_RELU, im);
+        conv_fwd(ps, s, pred_conv(ps, xin, d, P.c1w, P.c1b, b.r1, im));
         ln_fwd(ps, s, b.r1, none, P.l1g, P.l1b, im, none, b.n1, b.st1, f, DropSpec(), drop_spec(ps, cfg.vp_dropout, site_base));
-        conv_fwd(ps, s, b.n1, f, k, W(ps, P.c2w), W(ps, P.c2b), f, b.r2, GEMM_RELU, im);
+        conv_fwd(ps, s, pred_conv(ps, b.n1, f, P.c2w, P.c2b, b.r2, im));
         ln_fwd(ps, s, b.r2, none, P.l2g, P.l2b, im, none, b.n2, b.st2, f, DropSpec(), drop_spec(ps, cfg.vp_dropout, site_base + 1));
         TS w = W(ps, P.lw), bb = W(ps, P.lb);
-        launch_rowdot(on_rows(p, s, stream, valid_mask(p, s)), b.n2, w, bb, b.out, f);
+        launch_rowdot(on_rows(p, s, stream, p.sp[s].valid), b.n2, w, bb, b.out, f);
     }
     // The three predictors of a teacher-forced pass are independent (their inputs come from the TARGET embeddings): run them stage by
     // stage so that the three conv1 (then the three conv2) GEMMs — 28 workgroups each on a single-task rank — go out as ONE
@@ -1866,24 +1880,24 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     void pred_fwd3(const Pass& ps, const PredP* const P[3], PredBuf* const b[3], const TS xin[3], const int sites[3]) {
         TagScope tag_scope(*this, 4);
         const Plan& p = *ps.pl;
-        const int d = cfg.d_model, f = cfg.vp_filter, k = cfg.vp_kernel;
-        const unsigned char* im = inrect_mask(p, SP_P);
+        const int d = cfg.d_model, f = cfg.vp_filter;
+        const RowMask im = p.sp[SP_P].inrect;
         TS none{nullptr, 0};
         {
             GemmBatchScope batch(gx, stream);
-            for (int i = 0; i < 3; ++i) conv_fwd(ps, SP_P, xin[i], d, k, W(ps, P[i]->c1w), W(ps, P[i]->c1b), f, b[i]->r1, GEMM_RELU, im);
+            for (int i = 0; i < 3; ++i) conv_fwd(ps, SP_P, pred_conv(ps, xin[i], d, P[i]->c1w, P[i]->c1b, b[i]->r1, im));
         }
         for (int i = 0; i < 3; ++i)
             ln_fwd(ps, SP_P, b[i]->r1, none, P[i]->l1g, P[i]->l1b, im, none, b[i]->n1, b[i]->st1, f, DropSpec(), drop_spec(ps, cfg.vp_dropout, sites[i]));
         {
             GemmBatchScope batch(gx, stream);
-            for (int i = 0; i < 3; ++i) conv_fwd(ps, SP_P, b[i]->n1, f, k, W(ps, P[i]->c2w), W(ps, P[i]->c2b), f, b[i]->r2, GEMM_RELU, im);
+            for (int i = 0; i < 3; ++i) conv_fwd(ps, SP_P, pred_conv(ps, b[i]->n1, f, P[i]->c2w, P[i]->c2b, b[i]->r2, im));
         }
         for (int i = 0; i < 3; ++i)
             ln_fwd(ps, SP_P, b[i]->r2, none, P[i]->l2g, P[i]->l2b, im, none, b[i]->n2, b[i]->st2, f, DropSpec(), drop_spec(ps, cfg.vp_dropout, sites[i] + 1));
         for (int i = 0; i < 3; ++i) {
             TS w = W(ps, P[i]->lw), bb = W(ps, P[i]->lb);
-            launch_rowdot(on_rows(p, SP_P, stream, valid_mask(p, SP_P)), b[i]->n2, w, bb, b[i]->out, f);
+            launch_rowdot(on_rows(p, SP_P, stream, p.sp[SP_P].valid), b[i]->n2, w, bb, b[i]->out, f);
         }
     }
     // dout: [Mp] gradient of the prediction (0 on masked rows); dx accumulates the input gradient
@@ -1894,7 +1908,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         TagScope tag_scope(*this, 4);
         const Plan& p = *ps.pl;
         const int d = cfg.d_model, f = cfg.vp_filter, k = cfg.vp_kernel;
-        const unsigned char* im = inrect_mask(p, s);
+        const RowMask im = p.sp[s].inrect;
         TS g1 = (s == SP_P) ? gPf1 : gRf1, g2 = (s == SP_P) ? gPf2 : gRf2;
         TS none{nullptr, 0};
         if (pg) {
@@ -1902,37 +1916,37 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             launch_rowdot_bwd(on_rows(p, s, stream), dout, w, g1, f);
             // (the backward of the dropout behind each LayerNorm rides in the LayerNorm backward's load of its incoming gradient)
             ln_bwd(ps, s, g1, b.r2, b.st2, P.l2g, P.l2b, im, pg->g2a, f, 1, none, DropSpec(), false, pg->part2, drop_spec(ps, cfg.vp_dropout, site_base + 1));
-            conv_dgrad(ps, s, pg->g2a, f, k, W(ps, P.c2w), f, g1, 0, im);
+            conv_dgrad(ps, s, conv_op(g1, f, k, W(ps, P.c2w), pg->g2a, f, 0, im));
             ln_bwd(ps, s, g1, b.r1, b.st1, P.l1g, P.l1b, im, pg->g2b, f, 1, none, DropSpec(), false, pg->part1, drop_spec(ps, cfg.vp_dropout, site_base));
-            conv_dgrad(ps, s, pg->g2b, f, k, W(ps, P.c1w), d, dx, GEMM_ACCUM, im);
+            conv_dgrad(ps, s, conv_op(dx, d, k, W(ps, P.c1w), pg->g2b, f, GEMM_ACCUM, im));
             fork_side();
             {
                 GemmBatchScope batch(gx_side, side);
-                conv_wgrad(ps, s, pg->g2a, f, k, b.n1, f, P.c2w, P.c2b, im, 0, &gx_side, side);
-                conv_wgrad(ps, s, pg->g2b, f, k, xin, d, P.c1w, P.c1b, im, 0, &gx_side, side);
+                conv_wgrad(ps, s, on_side(wgrad_op(b.n1, f, k, pg->g2a, f, P.c2w, P.c2b, im)));
+                conv_wgrad(ps, s, on_side(wgrad_op(xin, d, k, pg->g2b, f, P.c1w, P.c1b, im)));
             }
             ln_param_grads_side(ps, s, pg->part2, P.l2g, P.l2b, f);
             ln_param_grads_side(ps, s, pg->part1, P.l1g, P.l1b, f);
-            colsum(ps, s, dout, 1, nullptr, none, Gd(P.lb), true);
-            colsum(ps, s, b.n2, f, nullptr, dout, Gd(P.lw), true);
+            colsum(ps, s, dout, 1, RowMask(), none, Gd(P.lb), true);
+            colsum(ps, s, b.n2, f, RowMask(), dout, Gd(P.lw), true);
             defer_live = true;
             return;
         }
-        colsum(ps, s, dout, 1, nullptr, none, Gd(P.lb));
-        colsum(ps, s, b.n2, f, nullptr, dout, Gd(P.lw));
+        colsum(ps, s, dout, 1, RowMask(), none, Gd(P.lb));
+        colsum(ps, s, b.n2, f, RowMask(), dout, Gd(P.lw));
         TS w = W(ps, P.lw);
         launch_rowdot_bwd(on_rows(p, s, stream), dout, w, g1, f);
         ln_bwd(ps, s, g1, b.r2, b.st2, P.l2g, P.l2b, im, g2, f, 1, none, DropSpec(), false, nullptr, drop_spec(ps, cfg.vp_dropout, site_base + 1));       // g2 = d conv2 out
         {
             GemmBatchScope pair(gx, stream);
-            conv_wgrad(ps, s, g2, f, k, b.n1, f, P.c2w, P.c2b, im);
-            conv_dgrad(ps, s, g2, f, k, W(ps, P.c2w), f, g1, 0, im);     // g1 = d n1
+            conv_wgrad(ps, s, wgrad_op(b.n1, f, k, g2, f, P.c2w, P.c2b, im));
+            conv_dgrad(ps, s, conv_op(g1, f, k, W(ps, P.c2w), g2, f, 0, im));     // g1 = d n1
         }
         ln_bwd(ps, s, g1, b.r1, b.st1, P.l1g, P.l1b, im, g2, f, 1, none, DropSpec(), false, nullptr, drop_spec(ps, cfg.vp_dropout, site_base));       // g2 = d conv1 out
         {
             GemmBatchScope pair(gx, stream);
-            conv_wgrad(ps, s, g2, f, k, xin, d, P.c1w, P.c1b, im);
-            conv_dgrad(ps, s, g2, f, k, W(ps, P.c1w), d, dx, dx_flags, im);
+            conv_wgrad(ps, s, wgrad_op(xin, d, k, g2, f, P.c1w, P.c1b, im));
+            conv_dgrad(ps, s, conv_op(dx, d, k, W(ps, P.c1w), g2, f, dx_flags, im));
         }
     }
     // The phoneme-level predictors' backward needs only the loss gradient and the forward's activations, and nothing reads its input
@@ -1966,11 +1980,10 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     // embedding + positions + encoder blocks (ps.pl->drop_seed already set); returns the encoder output
     TS encoder_fwd(const Pass& ps) {
         const Plan& p = *ps.pl;
-        TS none{nullptr, 0};
         TS we = W(ps, word_emb);
-        launch_embed_pos(on_rows(p, SP_P, stream, p.p_valid), emb_out, we, pos_table, p.p_tok, p.p_row_t, cfg.d_model);
+        launch_embed_pos(on_rows(p, SP_P, stream, p.sp[SP_P].valid), emb_out, we, pos_table, p.p_tok, p.p_row_t, cfg.d_model);
         TS x = emb_out;
-        for (int l = 0; l < cfg.enc_layers; ++l) { site_base = 2 * l; fft_fwd(ps, SP_P, cfg.enc_heads, encP[l], encB[l], x, none); x = encB[l].y2; }
+        for (int l = 0; l < cfg.enc_layers; ++l) { site_base = 2 * l; fft_fwd(ps, SP_P, cfg.enc_heads, encP[l], encB[l], x); x = encB[l].y2; }
         return x;
     }
     // Run-ahead (see kAhead): enqueue the encoder forwards of `steps` train-mode passes over plan `pl` on side2; seeds[s] / enc_ahead[s] /
@@ -1994,7 +2007,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             pl.drop_seed = seeds[s];
             if (per_step_sets) bind_act(s + 1);
             TS x = encoder_fwd(pe);
-            launch_copy_tasks(x, enc_ahead[s], (long long)pl.maxMp * cfg.d_model / 4, pl.tasks, stream);
+            launch_copy_tasks(x, enc_ahead[s], (long long)pl.sp[SP_P].maxM * cfg.d_model / 4, pl.tasks, stream);
             hipEventRecord(ev_enc[s], stream);
         }
         if (per_step_sets) bind_act(0);
@@ -2011,8 +2024,8 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     int forward(const Pass& ps) {
         const Plan& p = *ps.pl;
         set_regime(p);
+        const RowSpace &sP = p.sp[SP_P], &sF = p.sp[SP_F], &sR = p.sp[SP_R];
         const int d = cfg.d_model, nt = p.tasks;
-        TS none{nullptr, 0};
         if (ps.train) ps.pl->drop_seed = ps.seed_override ? ps.seed_override : next_drop_seed();
         refresh_shadows(ps, !ps.enc_out.p);   // (bf16 mode: the weight shadows this pass and its backward read)
         // encoder
@@ -2023,19 +2036,19 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             launch_copy_tasks(TS{(float*)(p.img_dev + img.spk_emb), (long long)cap_B * d}, spk, (long long)p.maxB * d / 4, nt, stream, ~0u);
         else
         launch_speaker_vec(on_rows(p, SP_P, stream), p.maxB, tb, p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, spk, d);
-        launch_add_rowvec(on_rows(p, SP_P, stream, p.p_inrect), x, spk, p.p_row_b, x0, d);
+        launch_add_rowvec(on_rows(p, SP_P, stream, sP.inrect), x, spk, p.p_row_b, x0, d);
         // variance adaptor: targets select the embeddings when given, else the (controlled) predictions.  A phoneme-level feature
         // (modules.py:118-127) is handled on the phoneme rectangle before the length regulator, a frame-level one (:139-148) on the
         // frame rectangle after it.
         TS pe = W(ps, pitch_emb), ee = W(ps, energy_emb);
         const bool tf = p.has_targets;
         TS xp = x0;
-        if (tf && knobs().pred_batch && !any_frame_level() && p.sumMp <= 2048) {   // (measured neutral once the launches fill the chip: 8-task meta-batches)
+        if (tf && knobs().pred_batch && !any_frame_level() && sP.sumM <= 2048) {   // (measured neutral once the launches fill the chip: 8-task meta-batches)
             // teacher-forced: both embeddings come from the targets, so x1 / x2 do not wait for a predictor — embed first, then the three
             // predictors side by side
-            launch_bucket_embed_add(on_rows(p, SP_P, stream, p.p_inrect), x0, TS{(float*)p.p_pitch_t, row_ts_p}, 1.f, pitch_bins, cfg.n_bins - 1, pe, pidx, x1,
+            launch_bucket_embed_add(on_rows(p, SP_P, stream, sP.inrect), x0, TS{(float*)p.p_pitch_t, sP.ts}, 1.f, pitch_bins, cfg.n_bins - 1, pe, pidx, x1,
                                     d);
-            launch_bucket_embed_add(on_rows(p, SP_P, stream, p.p_inrect), x1, TS{(float*)p.p_energy_t, row_ts_p}, 1.f, energy_bins, cfg.n_bins - 1, ee, eidx,
+            launch_bucket_embed_add(on_rows(p, SP_P, stream, sP.inrect), x1, TS{(float*)p.p_energy_t, sP.ts}, 1.f, energy_bins, cfg.n_bins - 1, ee, eidx,
                                     x2, d);
             const PredP* const PP[3] = {&durP, &pitP, &eneP};
             PredBuf* const BB[3] = {&durB, &pitB, &eneB};
@@ -2058,13 +2071,13 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         site_base = 128; pred_fwd(ps, durP, durB, x0);
         if (!cfg.pitch_frame) {
             site_base = 132; pred_fwd(ps, pitP, pitB, xp);
-            launch_bucket_embed_add(on_rows(p, SP_P, stream, p.p_inrect), xp, tf ? TS{(float*)p.p_pitch_t, row_ts_p} : pitB.out, tf ? 1.f : ps.p_control,
+            launch_bucket_embed_add(on_rows(p, SP_P, stream, sP.inrect), xp, tf ? TS{(float*)p.p_pitch_t, sP.ts} : pitB.out, tf ? 1.f : ps.p_control,
                                     pitch_bins, cfg.n_bins - 1, pe, pidx, x1, d);
             xp = x1;
         }
         if (!cfg.energy_frame) {
             site_base = 136; pred_fwd(ps, eneP, eneB, xp);
-            launch_bucket_embed_add(on_rows(p, SP_P, stream, p.p_inrect), xp, tf ? TS{(float*)p.p_energy_t, row_ts_p} : eneB.out, tf ? 1.f : ps.e_control,
+            launch_bucket_embed_add(on_rows(p, SP_P, stream, sP.inrect), xp, tf ? TS{(float*)p.p_energy_t, sP.ts} : eneB.out, tf ? 1.f : ps.e_control,
                                     energy_bins, cfg.n_bins - 1, ee, eidx, x2, d);
             xp = x2;
         }
@@ -2075,17 +2088,17 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             // length regulator + speaker + decoder positions
             launch_length_regulate_fwd(on_rows(p, SP_F, stream), xp, p.f_src, p.f_row_b, p.f_row_t, spk, pos_table, dec_in, d);
         } else {
-            launch_length_regulate_rect(on_rows(p, SP_R, stream), xp, p.f_src, row_ts_f, p.r2f, xr0, d);
+            launch_length_regulate_rect(on_rows(p, SP_R, stream), xp, p.f_src, sF.ts, p.r2f, xr0, d);
             TS xr = xr0;
             if (cfg.pitch_frame) {
                 site_base = 132; pred_fwd(ps, pitP, pitR, xr, SP_R);
-                launch_bucket_embed_add(on_rows(p, SP_R, stream, p.r_inrect), xr, tf ? TS{(float*)p.r_pitch_t, row_ts_r} : pitR.out, tf ? 1.f : ps.p_control,
+                launch_bucket_embed_add(on_rows(p, SP_R, stream, sR.inrect), xr, tf ? TS{(float*)p.r_pitch_t, sR.ts} : pitR.out, tf ? 1.f : ps.p_control,
                                         pitch_bins, cfg.n_bins - 1, pe, pidx_r, xr1, d);
                 xr = xr1;
             }
             if (cfg.energy_frame) {
                 site_base = 136; pred_fwd(ps, eneP, eneR, xr, SP_R);
-                launch_bucket_embed_add(on_rows(p, SP_R, stream, p.r_inrect), xr, tf ? TS{(float*)p.r_energy_t, row_ts_r} : eneR.out, tf ? 1.f : ps.e_control,
+                launch_bucket_embed_add(on_rows(p, SP_R, stream, sR.inrect), xr, tf ? TS{(float*)p.r_energy_t, sR.ts} : eneR.out, tf ? 1.f : ps.e_control,
                                         energy_bins, cfg.n_bins - 1, ee, eidx_r, xr2, d);
                 xr = xr2;
             }
@@ -2093,7 +2106,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             launch_length_regulate_fwd(on_rows(p, SP_F, stream), xr, p.f2r, p.f_row_b, p.f_row_t, spk, pos_table, dec_in, d);
         }
         x = dec_in;
-        for (int l = 0; l < cfg.dec_layers; ++l) { site_base = 64 + 2 * l; fft_fwd(ps, SP_F, cfg.dec_heads, decP[l], decB[l], x, none); x = decB[l].y2; }
+        for (int l = 0; l < cfg.dec_layers; ++l) { site_base = 64 + 2 * l; fft_fwd(ps, SP_F, cfg.dec_heads, decP[l], decB[l], x); x = decB[l].y2; }
         // mel_linear: packed frames -> mel rectangle; padded frames carry the bias
         {
             GemmArgs g = rowgemm(p, SP_F, GEMM_NT);
@@ -2103,10 +2116,10 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             g.C = mel.p; g.c_gs = mel.ts; g.ldc = cfg.n_mel;
             g.N = cfg.n_mel; g.K = d;
             g.bias = b.p; g.bias_gs = b.ts;
-            g.c_rowmap = p.f2r; g.c_rowmap_gs = row_ts_f;
-            gemm_launch(gx, GEMM_NT, g, p.maxMf, cfg.n_mel, nt, stream, 0, 2.0 * p.sum_nF * cfg.n_mel * d, p.sumMf,
-                        4.0 * (p.sum_nF * (d + cfg.n_mel) + (double)nt * cfg.n_mel * d));
-            launch_fill_padded_rows(on_rows(p, SP_R, stream, p.r_inrect), mel, b, p.r_valid, cfg.n_mel);
+            g.c_rowmap = p.f2r; g.c_rowmap_gs = sF.ts;
+            gemm_launch(gx, GEMM_NT, g, sF.maxM, cfg.n_mel, nt, stream, 0, 2.0 * sF.alg_rows * cfg.n_mel * d, sF.sumM,
+                        4.0 * (sF.alg_rows * (d + cfg.n_mel) + (double)nt * cfg.n_mel * d));
+            launch_fill_padded_rows(on_rows(p, SP_R, stream, sR.inrect), mel, b, sR.valid.m, cfg.n_mel);
         }
         // PostNet
         TS cur = mel;
@@ -2114,12 +2127,12 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         for (int i = 0; i < cfg.postnet_layers; ++i) {
             const PostP& P = postP[i];
             PostBuf& b = postB[i];
-            conv_fwd(ps, SP_R, cur, P.cin, cfg.postnet_kernel, W(ps, P.w), W(ps, P.b), P.cout, b.c, 0, p.r_inrect, TS{nullptr, 0}, TS{nullptr, 0},
-                     TS{nullptr, 0}, i > 0, false);   // (bf16 mode: the previous layer's bn_apply wrote its output's operand plane)
+            ConvOp c = conv_op(cur, P.cin, cfg.postnet_kernel, W(ps, P.w), b.c, P.cout, 0, sR.inrect);
+            c.b = W(ps, P.b); c.in_plane = i > 0;   // (bf16 mode: the previous layer's bn_apply wrote its output's operand plane)
+            conv_fwd(ps, SP_R, c);
             if (ps.train) {
-                ColArgs ca;
-                ca.X = b.c.p; ca.x_ts = b.c.ts; ca.mask = p.r_inrect; ca.mask_ts = row_ts_r; ca.C = P.cout; ca.mode = 2;
-                ca.mfield = META_MR;
+                ColArgs ca = col_args(p, SP_R, sR.inrect, P.cout, 2);
+                ca.X = b.c.p; ca.x_ts = b.c.ts;
                 colreduce(p, ca, b.stats.p, nullptr, b.stats.ts, SP_R);
                 if (ps.update_bn && cfg.postnet_layers > kBnRunMax) {
                     MTTS_LAUNCH(bn_running_update_kernel, dim3((P.cout + 63) / 64), dim3(64), stream, (const float*)b.stats.p,
@@ -2131,7 +2144,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
                             (const float*)bn_rv[i], b.stats.p, b.stats.ts, nt, P.cout, 1e-5f);
             }
             TS gm = W(ps, P.g), bt = W(ps, P.beta);
-            launch_bn_apply(on_rows(p, SP_R, stream, p.r_inrect), b.c, b.stats, gm, bt, (int)(i < cfg.postnet_layers - 1), b.a, P.cout,
+            launch_bn_apply(on_rows(p, SP_R, stream, sR.inrect), b.c, b.stats, gm, bt, (int)(i < cfg.postnet_layers - 1), b.a, P.cout,
                             drop_spec(ps, cfg.postnet_dropout, 192 + i),   // F.dropout(..., 0.5, self.training), Layers.py:133-134, in passing
                             i + 1 < cfg.postnet_layers ? H(b.a.p) : (bf16_t*)nullptr);
             cur = b.a;
@@ -2166,7 +2179,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         Plan& p = *ps.pl;
         const int nt = p.tasks;
         MTTS_LAUNCH(duration_round_kernel, dim3(4, 1, nt), dim3(256), stream, (const int*)p.meta, (const float*)durB.out.p, durB.out.ts,
-                    ps.d_control, (const unsigned char*)p.p_valid, row_ts_p, d_rounded.p);
+                    ps.d_control, (const unsigned char*)p.sp[SP_P].valid.m, p.sp[SP_P].ts, d_rounded.p);
         const long long bs = (long long)cap_B * cap_S;
         MTTS_LAUNCH(plan_gather_durations_kernel, dim3(2, 1, nt), dim3(256), stream, (const int*)p.meta, (const float*)d_rounded.p, d_rounded.ts,
                     p.dur_readback, cap_B, cap_S);
@@ -2204,10 +2217,10 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     LossArgs loss_args(const Plan& p) const {
         LossArgs a;
         a.mel = mel.p; a.mel_post = mel_post.p; a.mel_tgt = p.mel_tgt;
-        a.rvalid = p.r_valid;
+        a.rvalid = p.sp[SP_R].valid.m;
         a.pp = pitB.out.p; a.ep = eneB.out.p; a.logd = durB.out.p;
-        a.p_tgt = p.p_pitch_t; a.e_tgt = p.p_energy_t; a.dur = p.p_dur; a.pvalid = p.p_valid;
-        a.mel_ts = mel.ts; a.rrow_ts = row_ts_r; a.prow_ts = row_ts_p; a.pred_ts = pitB.out.ts;
+        a.p_tgt = p.p_pitch_t; a.e_tgt = p.p_energy_t; a.dur = p.p_dur; a.pvalid = p.sp[SP_P].valid.m;
+        a.mel_ts = mel.ts; a.rrow_ts = p.sp[SP_R].ts; a.prow_ts = p.sp[SP_P].ts; a.pred_ts = pitB.out.ts;
         a.n_mel = cfg.n_mel;
         a.pitch_frame = cfg.pitch_frame; a.energy_frame = cfg.energy_frame;
         if (any_frame_level()) {
@@ -2221,7 +2234,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     int loss(const Pass& ps, float* losses_out) {
         const Plan& p = *ps.pl;
         if (!p.has_targets) { set_error("loss needs a teacher-forced batch (targets)"); return -1; }
-        if (durB.out.ts != row_ts_p + 2 * G || pitB.out.ts != durB.out.ts) { set_error("internal: prediction stride"); return -1; }
+        if (durB.out.ts != p.sp[SP_P].ts + 2 * G || pitB.out.ts != durB.out.ts) { set_error("internal: prediction stride"); return -1; }
         LossArgs a = loss_args(p);
         MTTS_LAUNCH(loss_partial_kernel, dim3(kLossBlocks, 1, p.tasks), dim3(256), stream, (const int*)p.meta, a, loss_partial);
         MTTS_LAUNCH(loss_final_kernel, dim3(p.tasks), dim3(64), stream, (const int*)p.meta, (const float*)loss_partial,
@@ -2240,6 +2253,7 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
     }
     int backward_impl(const Pass& ps, float scale, bool need_encoder) {
         const Plan& p = *ps.pl;
+        const RowSpace& sR = p.sp[SP_R];
         set_regime(p);
         const int d = cfg.d_model, nt = p.tasks, nm = cfg.n_mel;
         if (!ps.train) { set_error("backward needs a train-mode forward (batch statistics)"); return -1; }
@@ -2260,35 +2274,36 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
             const float ysc = drop_active(ps) ? 1.f - cfg.postnet_dropout : 1.f;
             const DropSpec pdrop = drop_spec(ps, cfg.postnet_dropout, 192 + i);   // gradient through the mask: applied where dY is read
             TS dgm = Gd(P.g), dbt = Gd(P.beta);
-            ColArgs ca;
+            ColArgs ca = col_args(p, SP_R, sR.inrect, P.cout, 3);
             ca.yscale = ysc; ca.xdrop = pdrop;
             ca.X = cur.p; ca.x_ts = cur.ts; ca.Y = b.a.p; ca.y_ts = b.a.ts; ca.Z = b.c.p; ca.z_ts = b.c.ts;
-            ca.stats = b.stats.p; ca.st_ts = b.stats.ts; ca.mask = p.r_inrect; ca.mask_ts = row_ts_r; ca.C = P.cout;
-            ca.mode = 3; ca.do_tanh = act; ca.mfield = META_MR;
+            ca.stats = b.stats.p; ca.st_ts = b.stats.ts; ca.do_tanh = act;
             colreduce(p, ca, dgm.p, dbt.p, dgm.ts, SP_R);
             TS gm = W(ps, P.g);
             const bool dfp = defer_ok(p);
             TS dc = dfp ? postG[i] : gR0;  // [rows][Cout] inside a scratch sized for max(postnet_dim, n_mel) channels (deferred: a buffer of the layer's own)
-            launch_bn_bwd_apply(on_rows(p, SP_R, stream, p.r_inrect), cur, b.a, b.c, b.stats, gm, dgm, dbt, act, dc, P.cout, ysc, pdrop, H(dc.p));
+            launch_bn_bwd_apply(on_rows(p, SP_R, stream, sR.inrect), cur, b.a, b.c, b.stats, gm, dgm, dbt, act, dc, P.cout, ysc, pdrop, H(dc.p));
             TS xin = (i == 0) ? mel : postB[i - 1].a;
+            const ConvOp wg = wgrad_op(xin, P.cin, cfg.postnet_kernel, dc, P.cout, P.w, P.b, sR.inrect);
             if (dfp) {   // this layer's weight gradient on the side stream, overlapping the rest of the backward chain
                 fork_side();
                 GemmBatchScope batch(gx_side, side);
-                conv_wgrad(ps, SP_R, dc, P.cout, cfg.postnet_kernel, xin, P.cin, P.w, P.b, p.r_inrect, 0, &gx_side, side);
+                conv_wgrad(ps, SP_R, on_side(wg));
                 defer_live = true;
             }
             GemmBatchScope pair(gx, stream);
-            if (!dfp) conv_wgrad(ps, SP_R, dc, P.cout, cfg.postnet_kernel, xin, P.cin, P.w, P.b, p.r_inrect);
+            if (!dfp) conv_wgrad(ps, SP_R, wg);
+            ConvOp dg = conv_op(gRm, P.cin, cfg.postnet_kernel, W(ps, P.w), dc, P.cout, GEMM_ACCUM, sR.inrect);   // (layer 0: into the mel gradient)
+            dg.in_plane = true;
             if (i > 0) {
-                conv_dgrad(ps, SP_R, dc, P.cout, cfg.postnet_kernel, W(ps, P.w), P.cin, K.post_cur[i - 1], 0, p.r_inrect, TS{nullptr, 0}, TS{nullptr, 0},
-                           TS{nullptr, 0}, true, false);
+                dg.x = K.post_cur[i - 1]; dg.flags = 0;
+                conv_dgrad(ps, SP_R, dg);
                 cur = K.post_cur[i - 1];
             } else {
                 // dL/d(mel) total = direct L1 term + residual path + PostNet input gradient
                 const long long n4 = (gRm.ts * nt) / 4;
                 launch_add2(gRm.p - (long long)G * nm, gRp.p - (long long)G * nm, gRm.p - (long long)G * nm, n4, stream);
-                conv_dgrad(ps, SP_R, dc, P.cout, cfg.postnet_kernel, W(ps, P.w), P.cin, gRm, GEMM_ACCUM, p.r_inrect, TS{nullptr, 0}, TS{nullptr, 0},
-                           TS{nullptr, 0}, true, false);
+                conv_dgrad(ps, SP_R, dg);
             }
         }
         // ---- mel_linear -------------------------------------------------------------------
@@ -2296,22 +2311,23 @@ struct GemmBatchScope {  // RAII around gemm_batch_begin / gemm_batch_end (gemm.
         TS none{nullptr, 0};
         module_done(ar_idx_postnet());
         const bool dfm = defer_ok(p);   // gRm / gMelF are final from here on: their parameter gradients can run on the side stream
-        if (!dfm) colsum(ps, SP_R, gRm, nm, nullptr, none, Gd(mel_b));
+        if (!dfm) colsum(ps, SP_R, gRm, nm, RowMask(), none, Gd(mel_b));
         launch_gather_rows(on_rows(p, SP_F, stream), gRm, p.f2r, gMelF, nm);
         TS dec_out = cfg.dec_layers ? decB[cfg.dec_layers - 1].y2 : dec_in;
+        const ConvOp melg = wgrad_op(dec_out, d, 1, gMelF, nm, mel_w, -1, RowMask());   // (the bias: the column sums of gRm, above / below)
         if (dfm) {
             fork_side();
             {
                 GemmBatchScope batch(gx_side, side);
-                conv_wgrad(ps, SP_F, gMelF, nm, 1, dec_out, d, mel_w, -1, nullptr, 0, &gx_side, side);
+                conv_wgrad(ps, SP_F, on_side(melg));
             }
-            colsum(ps, SP_R, gRm, nm, nullptr, none, Gd(mel_b), true);
+            colsum(ps, SP_R, gRm, nm, RowMask(), none, Gd(mel_b), true);
             defer_live = true;
         }
         {
             GemmBatchScope pair(gx, stream);
-            if (!dfm) conv_wgrad(ps, SP_F, gMelF, nm, 1, dec_out, d, mel_w, -1, nullptr);
-            conv_dgrad(ps, SP_F, gMelF, nm, 1, W(ps, mel_w), d, K.dec_top, 0, nullptr);
+            if (!dfm) conv_wgrad(ps, SP_F, melg);
+            conv_dgrad(ps, SP_F, conv_op(K.dec_top, d, 1, W(ps, mel_w), gMelF, nm));
         }
         // ---- decoder ----------------------------------------------------------------------
         for (int l = cfg.dec_layers - 1; l >= 0; --l) {

@@ -45,34 +45,18 @@ char* arena_so_defer = nullptr;
 
 void layout_so() {
     const int d = cfg.d_model, f = cfg.vp_filter;
-    tdecB.resize(cfg.dec_layers);
-    for (int i = 0; i < cfg.dec_layers; ++i) {
-        LayerBuf& v = tdecB[i];
-        v.qkv = rows(capMf, 3 * d); v.P = flat(S_ts_f); v.O = rows(capMf, d); v.z1 = rows(capMf, d); v.st1 = rows(capMf, 2);
-        v.y1 = rows(capMf, d); v.h = rows(capMf, cfg.d_ff); v.z2 = rows(capMf, d); v.st2 = rows(capMf, 2); v.y2 = rows(capMf, d);
-    }
+    layout_layers(tdecB, cfg.dec_layers, capMf, score_ts(1));
     if (encoder_adapted()) {
-        tencB.resize(cfg.enc_layers);
-        for (int i = 0; i < cfg.enc_layers; ++i) {
-            LayerBuf& v = tencB[i];
-            v.qkv = rows(capMp, 3 * d); v.P = flat(S_ts_p); v.O = rows(capMp, d); v.z1 = rows(capMp, d); v.st1 = rows(capMp, 2);
-            v.y1 = rows(capMp, d); v.h = rows(capMp, cfg.d_ff); v.z2 = rows(capMp, d); v.st2 = rows(capMp, 2); v.y2 = rows(capMp, d);
-        }
-        t_emb = rows(capMp, d); tgP1 = rows(capMp, d); tgPqkv = rows(capMp, 3 * d); tgPh = rows(capMp, cfg.d_ff); tdSp = flat(S_ts_p);
+        layout_layers(tencB, cfg.enc_layers, capMp, score_ts(0));
+        t_emb = rows(capMp, d); tgP1 = rows(capMp, d); tgPqkv = rows(capMp, 3 * d); tgPh = rows(capMp, cfg.d_ff); tdSp = flat(score_ts(0));
         tgPm = rows(capMp, d);
     }
     if (any_frame_level()) {
         t_xr0 = rows(capMr, d); t_xr1 = rows(capMr, d); t_xr2 = rows(capMr, d); tgRx = rows(capMr, d); tgFx = rows(capMf, d);
         tgRf1 = rows(capMr, f); tgRf2 = rows(capMr, f); tdpred_r[0] = rows(capMr, 1); tdpred_r[1] = rows(capMr, 1);
-        for (PredBuf* pb : {&tpitR, &teneR}) {
-            pb->r1 = rows(capMr, f); pb->st1 = rows(capMr, 2); pb->n1 = rows(capMr, f);
-            pb->r2 = rows(capMr, f); pb->st2 = rows(capMr, 2); pb->n2 = rows(capMr, f); pb->out = rows(capMr, 1);
-        }
+        for (PredBuf* pb : {&tpitR, &teneR}) layout_pred(*pb, capMr);
     }
-    for (PredBuf* pb : {&tdurB, &tpitB, &teneB}) {
-        pb->r1 = rows(capMp, f); pb->st1 = rows(capMp, 2); pb->n1 = rows(capMp, f);
-        pb->r2 = rows(capMp, f); pb->st2 = rows(capMp, 2); pb->n2 = rows(capMp, f); pb->out = rows(capMp, 1);
-    }
+    for (PredBuf* pb : {&tdurB, &tpitB, &teneB}) layout_pred(*pb, capMp);
     tpostB.resize(cfg.postnet_layers);
     for (int i = 0; i < cfg.postnet_layers; ++i) {
         const int c = postP[i].cout;
@@ -82,7 +66,7 @@ void layout_so() {
     t_dec_in = rows(capMf, d); t_mel = rows(capMr, cfg.n_mel);
     tgFm = rows(capMf, d);
     tgPf1 = rows(capMp, f); tgPf2 = rows(capMp, f); tgP0 = rows(capMp, d);
-    tgF0 = rows(capMf, d); tgF1 = rows(capMf, d); tgFqkv = rows(capMf, 3 * d); tgFh = rows(capMf, cfg.d_ff); tdSf = flat(S_ts_f);
+    tgF0 = rows(capMf, d); tgF1 = rows(capMf, d); tgFqkv = rows(capMf, 3 * d); tgFh = rows(capMf, cfg.d_ff); tdSf = flat(score_ts(1));
     const int pc = std::max(cfg.postnet_dim, cfg.n_mel);
     tgR0 = rows(capMr, pc); tgR1 = rows(capMr, pc); tgRm = rows(capMr, cfg.n_mel); tgRz = rows(capMr, cfg.n_mel);
     tgMelF = rows(capMf, cfg.n_mel);
@@ -159,31 +143,40 @@ TS Hv(long long off) const { return TS{hv + off, n_total}; }
 // (GemmArgs::A2, gemm.h) — round 3 measured it against a plain launch followed by an accumulating one: 492 -> 476 ms on the 8-task step.
 // ty = conv(tx; W) + conv(x; tW) + tb, masks applied to the sum
 void conv_fwd_t(const Pass& ps, Space s, TS x, TS tx, int cin, int k, long long w_off, long long b_off, int cout, TS ty,
-                const unsigned char* rowmask, TS relu_ref = TS{nullptr, 0}) {
-    TS tw = Wt(w_off), tb = b_off >= 0 ? Wt(b_off) : TS{nullptr, 0};
-    if (tw.p) {
-        conv_fwd(ps, s, tx, cin, k, W(ps, w_off), tb, cout, ty, 0, rowmask, relu_ref, x, tw);   // one K-loop over both products
-    } else {
-        conv_fwd(ps, s, tx, cin, k, W(ps, w_off), TS{nullptr, 0}, cout, ty, 0, rowmask, relu_ref);
+                RowMask rowmask, TS relu_ref = TS{}) {
+    ConvOp c = conv_op(tx, cin, k, W(ps, w_off), ty, cout, 0, rowmask);
+    c.relu_ref = relu_ref;
+    if (Wt(w_off).p) {   // one K-loop over both products (a non-adapted weight has no tangent, and neither has its bias)
+        c.x2 = x; c.w2 = Wt(w_off);
+        if (b_off >= 0) c.b = Wt(b_off);
     }
+    conv_fwd(ps, s, c);
 }
 // One conv's second-order backward = five products.  The three that start an output (hv(W) = tdy^T x, the primal dgrad,
 // tdx = tdy W) are independent, and so are the two that complete one (hv(W) += dy^T tx, tdx += dy tW): two multi-problem
 // launches instead of five stand-alone ones.  dx == nullptr: no primal dgrad wanted.
 void conv_bwd_t(const Pass& ps, Space s, TS dy, TS tdy, int cout, int k, TS x, TS tx, int cin, long long w_off, long long b_off,
-                const unsigned char* bias_mask, TS dx, int dx_flags, TS tdx, bool tdx_accumulate, const unsigned char* rowmask,
-                TS relu_ref = TS{nullptr, 0}, bool defer_wgrad = false) {
-    TS tw = Wt(w_off);
+                RowMask bias_mask, TS dx, int dx_flags, TS tdx, bool tdx_accumulate, RowMask rowmask,
+                TS relu_ref = TS{}, bool defer_wgrad = false) {
     // each completed output in one dual-source K-loop: ONE multi-problem launch of three problems (defer_wgrad: the hv(W) product is
     // left to hv_wgrad_side, which the caller issues on the side stream once the layer's tangent gradients are all written)
     GemmBatchScope all(gx, stream);
-    if (!defer_wgrad) conv_wgrad(ps, s, tdy, cout, k, x, cin, w_off, b_off, bias_mask, 0, nullptr, nullptr, dy, tx);
-    if (dx.p) conv_dgrad(ps, s, dy, cout, k, W(ps, w_off), cin, dx, dx_flags, rowmask, relu_ref);
-    if (tw.p) conv_dgrad(ps, s, tdy, cout, k, W(ps, w_off), cin, tdx, tdx_accumulate ? GEMM_ACCUM : 0, rowmask, relu_ref, dy, tw);
-    else conv_dgrad(ps, s, tdy, cout, k, W(ps, w_off), cin, tdx, tdx_accumulate ? GEMM_ACCUM : 0, rowmask, relu_ref);
+    if (!defer_wgrad) conv_wgrad(ps, s, hv_wgrad_op(x, tx, cin, k, dy, tdy, cout, w_off, b_off, bias_mask));
+    ConvOp c = conv_op(dx, cin, k, W(ps, w_off), dy, cout, dx_flags, rowmask);
+    c.relu_ref = relu_ref;
+    if (dx.p) conv_dgrad(ps, s, c);
+    c.x = tdx; c.y = tdy; c.flags = tdx_accumulate ? GEMM_ACCUM : 0;
+    if (Wt(w_off).p) { c.y2 = dy; c.w2 = Wt(w_off); }
+    conv_dgrad(ps, s, c);
+}
+// hv(W) = tdy^T x + dy^T tx (one dual-source problem), hv(b) = colsum(tdy)
+static ConvOp hv_wgrad_op(TS x, TS tx, int cin, int k, TS dy, TS tdy, int cout, long long w_off, long long b_off, RowMask bias_mask) {
+    ConvOp c = wgrad_op(x, cin, k, tdy, cout, w_off, b_off, bias_mask);
+    c.y2 = dy; c.x2 = tx;
+    return c;
 }
 // din: dropout applied to ta on load (see ln_jvp_fwd_kernel)
-void ln_fwd_t(const Pass& ps, Space s, TS ta, TS tres, TS z, TS st, long long g_off, long long b_off, const unsigned char* mask,
+void ln_fwd_t(const Pass& ps, Space s, TS ta, TS tres, TS z, TS st, long long g_off, long long b_off, RowMask mask,
               TS tz_out, TS ty, TS tst, int C, DropSpec din = DropSpec(), DropSpec dout = DropSpec()) {
     const Plan& p = *ps.pl;
     launch_ln_jvp_fwd(on_rows(p, s, stream, mask), ta, tres, z, st, W(ps, g_off), Wt(g_off), Wt(b_off), tz_out, ty, tst, C, din, dout);
@@ -193,7 +186,7 @@ void ln_fwd_t(const Pass& ps, Space s, TS ta, TS tres, TS z, TS st, long long g_
 static bool so_fuse_drop() { return knobs().so_fuse_drop != 0; }
 // primal dz + tangent tgz, and hv(gamma), hv(beta); dz_drop / tgz_drop (optional): dropout(dz) / dropout(tgz) with the forward site's mask dd
 void ln_bwd_t(const Pass& ps, Space s, TS dy, TS tgy, TS z, TS st, TS tz, TS tst, long long g_off, long long b_off,
-              const unsigned char* mask, TS dz, TS tgz, int C, int relu_on_z, TS dz_drop = TS{nullptr, 0}, TS tgz_drop = TS{nullptr, 0},
+              RowMask mask, TS dz, TS tgz, int C, int relu_on_z, TS dz_drop = TS{nullptr, 0}, TS tgz_drop = TS{nullptr, 0},
               DropSpec dd = DropSpec(), DropSpec din = DropSpec()) {   // din: dropout applied to dy and tgy on load (both kernels)
     const Plan& p = *ps.pl;
     // stage 1 of hv(gamma) / hv(beta) rides in the tangent kernel (8-row partials, folded by one colfinal launch); MTTS_SO_LN_PART=0: the two-launch
@@ -206,24 +199,21 @@ void ln_bwd_t(const Pass& ps, Space s, TS dy, TS tgy, TS z, TS st, TS tz, TS tst
 void fft_fwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, LayerBuf& t, TS xin, TS txin) {
     TagScope tag_scope(*this, s == SP_P ? 1 : 2);
     const Plan& p = *ps.pl;
+    const AttnSide& at = p.at[side_of(s)];
     const int d = cfg.d_model, dk = d / heads;
-    const unsigned char* vm = valid_mask(p, s);
-    const unsigned char* im = inrect_mask(p, s);
+    const RowMask vm = p.sp[s].valid, im = p.sp[s].inrect, all;
     const float alpha = 1.f / sqrtf((float)dk);
-    conv_fwd_t(ps, s, xin, txin, d, 1, P.wqkv, P.bqkv, 3 * d, t.qkv, nullptr);
+    conv_fwd_t(ps, s, xin, txin, d, 1, P.wqkv, P.bqkv, 3 * d, t.qkv, all);
     attn_gemm(ps, s, TAB_QK, GEMM_NT, t.qkv.p, 3 * d, b.qkv.p, 3 * d, t.P.p, 0, alpha, heads, 0, b.qkv.p, t.qkv.p);
-    const int groups = (s == SP_P) ? p.n_enc_groups : p.n_dec_groups;
-    const int L = (s == SP_P) ? p.enc_maxL : p.dec_maxL;
-    const AttnSeq* seqs = (s == SP_P) ? p.enc_seqs : p.dec_seqs;
-    if (groups > 0 && L > 0)
-        launch_softmax_jvp_fwd(seqs, L, groups, b.P.p, t.P.p, stream);
+    if (at.groups > 0 && at.maxL > 0)
+        launch_softmax_jvp_fwd(at.seqs, at.maxL, at.groups, b.P.p, t.P.p, stream);
     attn_gemm(ps, s, TAB_PV, GEMM_NN, t.P.p, 0, b.qkv.p, 3 * d, t.O.p, d, 1.f, heads, 0, b.P.p, t.qkv.p);
-    conv_fwd_t(ps, s, b.O, t.O, d, 1, P.wfc, P.bfc, d, t.z1, nullptr);
+    conv_fwd_t(ps, s, b.O, t.O, d, 1, P.wfc, P.bfc, d, t.z1, all);
     const bool fuse = so_fuse_drop();
     if (!fuse) drop(ps, s, t.z1, t.z1, d, block_dropout(s), site_base);
     ln_fwd_t(ps, s, t.z1, txin, b.z1, b.st1, P.ln1g, P.ln1b, vm, t.z1, t.y1, t.st1, d, fuse ? drop_spec(ps, block_dropout(s), site_base) : DropSpec());
     conv_fwd_t(ps, s, b.y1, t.y1, d, cfg.k1, P.w1, P.b1, cfg.d_ff, t.h, im, b.h);
-    conv_fwd_t(ps, s, b.h, t.h, cfg.d_ff, cfg.k2, P.w2, P.b2, d, t.z2, nullptr);
+    conv_fwd_t(ps, s, b.h, t.h, cfg.d_ff, cfg.k2, P.w2, P.b2, d, t.z2, all);
     if (!fuse) drop(ps, s, t.z2, t.z2, d, block_dropout(s), site_base + 1);
     ln_fwd_t(ps, s, t.z2, t.y1, b.z2, b.st2, P.ln2g, P.ln2b, vm, t.z2, t.y2, t.st2, d, fuse ? drop_spec(ps, block_dropout(s), site_base + 1) : DropSpec());
 }
@@ -237,9 +227,9 @@ void fft_bwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, L
                const LayerKeep& K, bool skip_primal, TS sh_g0, TS sh_g1, TS tg1, TS tgqkv, TS tgh, TS dS, TS tdS, TLayerGrad* tl = nullptr) {
     TagScope tag_scope(*this, s == SP_P ? 1 : 2);
     const Plan& p = *ps.pl;
+    const AttnSide& at = p.at[side_of(s)];
     const int d = cfg.d_model, dk = d / heads, ff = cfg.d_ff;
-    const unsigned char* vm = valid_mask(p, s);
-    const unsigned char* im = inrect_mask(p, s);
+    const RowMask vm = p.sp[s].valid, im = p.sp[s].inrect, all;
     TS none{nullptr, 0};
     const bool sk = skip_primal;
     const bool df = tl != nullptr && sk;
@@ -255,7 +245,7 @@ void fft_bwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, L
     auto masked = [&](TS src, TS shared, TS own, int site) {
         if (!df) return drop(ps, s, src, shared, d, block_dropout(s), site);
         if (drop_active(ps) && block_dropout(s) > 0.f) return drop(ps, s, src, own, d, block_dropout(s), site);
-        launch_copy_tasks(src, own, (long long)maxM(p, s) * d / 4, p.tasks, stream);
+        launch_copy_tasks(src, own, (long long)p.sp[s].maxM * d / 4, p.tasks, stream);
         return own;
     };
     TS dc = fuse2 ? (df ? tl->dc : gm) : masked(dz2, gm, df ? tl->dc : gm, site_base + 1), tdc = fuse2 ? (df ? tl->tdc : tgm) : masked(tg1, tgm, df ? tl->tdc : tgm, site_base + 1);
@@ -263,11 +253,8 @@ void fft_bwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, L
     conv_bwd_t(ps, s, gh, tgh, ff, cfg.k1, b.y1, t.y1, d, P.w1, P.b1, im, sk ? none : K.dy1, GEMM_ACCUM, tg1, true, im, none, df);   // K.dy1: dz2 + dgrad = dy1
     ln_bwd_t(ps, s, K.dy1, tg1, b.z1, b.st1, t.z1, t.st1, P.ln1g, P.ln1b, vm, dz1, tg0, d, 0, fuse1 ? (df ? tl->da : gm) : none, fuse1 ? (df ? tl->tda : tgm) : none, dd1);
     TS da = fuse1 ? (df ? tl->da : gm) : masked(dz1, gm, df ? tl->da : gm, site_base), tda = fuse1 ? (df ? tl->tda : tgm) : masked(tg0, tgm, df ? tl->tda : tgm, site_base);
-    conv_bwd_t(ps, s, da, tda, d, 1, b.O, t.O, d, P.wfc, P.bfc, vm, sk ? none : K.dO, 0, tg1, false, nullptr, none, df);   // K.dO = dO, tg1 = its tangent
+    conv_bwd_t(ps, s, da, tda, d, 1, b.O, t.O, d, P.wfc, P.bfc, vm, sk ? none : K.dO, 0, tg1, false, all, none, df);   // K.dO = dO, tg1 = its tangent
     TS g1 = K.dO;
-    const int groups = (s == SP_P) ? p.n_enc_groups : p.n_dec_groups;
-    const int L = (s == SP_P) ? p.enc_maxL : p.dec_maxL;
-    const AttnSeq* seqs = (s == SP_P) ? p.enc_seqs : p.dec_seqs;
     // dP = dO V^T ; tg_P = tg_O V^T + dO tV^T
     // dV = P^T dO ; tg_V = tP^T dO + P^T tg_O
     {
@@ -277,8 +264,8 @@ void fft_bwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, L
         if (!sk) attn_gemm(ps, s, TAB_DV, GEMM_TN, b.P.p, 0, g1.p, d, gqkv.p, 3 * d, 1.f, heads);
         attn_gemm(ps, s, TAB_DV, GEMM_TN, t.P.p, 0, g1.p, d, tgqkv.p, 3 * d, 1.f, heads, 0, b.P.p, tg1.p);
     }
-    if (groups > 0 && L > 0)
-        launch_softmax_jvp_bwd(seqs, L, groups, b.P.p, t.P.p, dS.p, tdS.p, 1.f / sqrtf((float)dk), stream);
+    if (at.groups > 0 && at.maxL > 0)
+        launch_softmax_jvp_bwd(at.seqs, at.maxL, at.groups, b.P.p, t.P.p, dS.p, tdS.p, 1.f / sqrtf((float)dk), stream);
     // dQ = dS K ; tg_Q = tg_S K + dS tK
     // dK = dS^T Q ; tg_K = tg_S^T Q + dS^T tQ
     {
@@ -288,16 +275,16 @@ void fft_bwd_t(const Pass& ps, Space s, int heads, const FFTP& P, LayerBuf& b, L
         if (!sk) attn_gemm(ps, s, TAB_DK, GEMM_TN, dS.p, 0, b.qkv.p, 3 * d, gqkv.p, 3 * d, 1.f, heads);
         attn_gemm(ps, s, TAB_DK, GEMM_TN, tdS.p, 0, b.qkv.p, 3 * d, tgqkv.p, 3 * d, 1.f, heads, 0, dS.p, t.qkv.p);
     }
-    conv_bwd_t(ps, s, gqkv, tgqkv, 3 * d, 1, xin, txin, d, P.wqkv, P.bqkv, vm, sk ? none : K.g0, GEMM_ACCUM, tg0, true, nullptr, none, df);   // K.g0: dz1 + dgrad = dL/dx
+    conv_bwd_t(ps, s, gqkv, tgqkv, 3 * d, 1, xin, txin, d, P.wqkv, P.bqkv, vm, sk ? none : K.g0, GEMM_ACCUM, tg0, true, all, none, df);   // K.g0: dz1 + dgrad = dL/dx
     if (df) {
         // the layer's four hv(W) (+ bias) products, each one dual-source K-loop (hv(W) = tdy^T x + dy^T tx): one multi-problem launch on
         // the side stream, after everything above
         fork_side();
         GemmBatchScope batch(gx_side, side);
-        conv_wgrad(ps, s, tgh, ff, cfg.k1, b.y1, d, P.w1, P.b1, im, 0, &gx_side, side, gh, t.y1);
-        conv_wgrad(ps, s, tdc, d, cfg.k2, b.h, ff, P.w2, P.b2, vm, 0, &gx_side, side, dc, t.h);
-        conv_wgrad(ps, s, tgqkv, 3 * d, 1, xin, d, P.wqkv, P.bqkv, vm, 0, &gx_side, side, gqkv, txin);
-        conv_wgrad(ps, s, tda, d, 1, b.O, d, P.wfc, P.bfc, vm, 0, &gx_side, side, da, t.O);
+        conv_wgrad(ps, s, on_side(hv_wgrad_op(b.y1, t.y1, d, cfg.k1, gh, tgh, ff, P.w1, P.b1, im)));
+        conv_wgrad(ps, s, on_side(hv_wgrad_op(b.h, t.h, ff, cfg.k2, dc, tdc, d, P.w2, P.b2, vm)));
+        conv_wgrad(ps, s, on_side(hv_wgrad_op(xin, txin, d, 1, gqkv, tgqkv, 3 * d, P.wqkv, P.bqkv, vm)));
+        conv_wgrad(ps, s, on_side(hv_wgrad_op(b.O, t.O, d, 1, da, tda, d, P.wfc, P.bfc, vm)));
         defer_live = true;
     }
 }
@@ -308,7 +295,7 @@ void pred_fwd_t(const Pass& ps, const PredP& P, PredBuf& b, PredBuf& t, TS xin, 
     TagScope tag_scope(*this, 4);
     const Plan& p = *ps.pl;
     const int d = cfg.d_model, f = cfg.vp_filter, k = cfg.vp_kernel;
-    const unsigned char* im = inrect_mask(p, s);
+    const RowMask im = p.sp[s].inrect;
     TS none{nullptr, 0};
     conv_fwd_t(ps, s, xin, txin, d, k, P.c1w, P.c1b, f, t.r1, im, b.r1);
     const bool fuse = so_fuse_drop();   // (the dropout behind each LayerNorm rides in its tangent kernel: ln_jvp_fwd_kernel: dout)
@@ -318,7 +305,7 @@ void pred_fwd_t(const Pass& ps, const PredP& P, PredBuf& b, PredBuf& t, TS xin, 
     ln_fwd_t(ps, s, t.r2, none, b.r2, b.st2, P.l2g, P.l2b, im, none, t.n2, t.st2, f, DropSpec(), fuse ? drop_spec(ps, cfg.vp_dropout, site_base + 1) : DropSpec());
     if (!fuse) drop(ps, s, t.n2, t.n2, f, cfg.vp_dropout, site_base + 1);
     TS w = W(ps, P.lw), tw = Wt(P.lw), tbb = Wt(P.lb);
-    launch_rowdot_jvp(on_rows(p, s, stream, valid_mask(p, s)), b.n2, t.n2, w, tw, tbb, t.out, f);
+    launch_rowdot_jvp(on_rows(p, s, stream, p.sp[s].valid), b.n2, t.n2, w, tw, tbb, t.out, f);
 }
 // dout / tgout: gradient of the prediction and its tangent; tdx accumulates the tangent of the input gradient, dx (optional: only an
 // adapted encoder upstream needs it) the primal input gradient
@@ -327,7 +314,7 @@ void pred_bwd_t(const Pass& ps, const PredP& P, PredBuf& b, PredBuf& t, TS xin, 
     TagScope tag_scope(*this, 4);
     const Plan& p = *ps.pl;
     const int d = cfg.d_model, f = cfg.vp_filter, k = cfg.vp_kernel;
-    const unsigned char* im = inrect_mask(p, s);
+    const RowMask im = p.sp[s].inrect;
     TS none{nullptr, 0};
     TS g1 = (s == SP_P) ? gPf1 : gRf1, g2 = (s == SP_P) ? gPf2 : gRf2;
     TS tg1 = (s == SP_P) ? tgPf1 : tgRf1, tg2 = (s == SP_P) ? tgPf2 : tgRf2;
@@ -336,11 +323,11 @@ void pred_bwd_t(const Pass& ps, const PredP& P, PredBuf& b, PredBuf& t, TS xin, 
     // pass's other side-stream work).  MTTS_SO_PRED_SIDE=0: on the critical stream.
     const bool os = knobs().so_pred_side && side != nullptr && col_partial_side != nullptr;
     if (os) fork_side();
-    colsum(ps, s, tgout, 1, nullptr, none, Gd(P.lb), os);
-    colsum(ps, s, b.n2, f, nullptr, tgout, Gd(P.lw), os);
+    colsum(ps, s, tgout, 1, RowMask(), none, Gd(P.lb), os);
+    colsum(ps, s, b.n2, f, RowMask(), tgout, Gd(P.lw), os);
     {   // + sum_m dout[m] * t_n2[m]
         ColArgs a;
-        a.X = t.n2.p; a.x_ts = t.n2.ts; a.roww = dout.p; a.roww_ts = dout.ts; a.C = f; a.mode = 0; a.mfield = mfield(s); a.accumulate = 1;
+        a.X = t.n2.p; a.x_ts = t.n2.ts; a.roww = dout.p; a.roww_ts = dout.ts; a.C = f; a.mode = 0; a.mfield = p.sp[s].mfield; a.accumulate = 1;
         TS o = Gd(P.lw);
         colreduce(p, a, o.p, nullptr, o.ts, s, os);
     }
@@ -359,9 +346,9 @@ void pred_bwd_t(const Pass& ps, const PredP& P, PredBuf& b, PredBuf& t, TS xin, 
 // ---- tangent forward of the adapted part (the primal forward of the same batch has just run) ------------
 int forward_t(const Pass& ps) {
     const Plan& p = *ps.pl;
+    const RowSpace &sP = p.sp[SP_P], &sF = p.sp[SP_F], &sR = p.sp[SP_R];
     set_regime(p);
     const int d = cfg.d_model, nt = p.tasks;
-    TS none{nullptr, 0};
     TS ttab = Wt(spk_table);
     if (ttab.p && !p.ext_spk) {   // external speaker embeddings (speaker_emb: dvec) are inputs of the batch: no tangent
         launch_speaker_vec(on_rows(p, SP_P, stream), p.maxB, ttab, p.spk_ids, (long long)cap_B + 1, cap_B, p.average_spk, t_spk, d);
@@ -379,9 +366,9 @@ int forward_t(const Pass& ps) {
             fft_fwd_t(ps, SP_P, cfg.enc_heads, encP[l], encB[l], tencB[l], xe, txe);
             xe = encB[l].y2; txe = tencB[l].y2;
         }
-        launch_add_rowvec(on_rows(p, SP_P, stream, p.p_inrect), txe, t_spk, p.p_row_b, t_x0, d);
+        launch_add_rowvec(on_rows(p, SP_P, stream, sP.inrect), txe, t_spk, p.p_row_b, t_x0, d);
     } else
-    launch_bcast_rowvec(on_rows(p, SP_P, stream, p.p_inrect), t_spk, p.p_row_b, t_x0, d);
+    launch_bcast_rowvec(on_rows(p, SP_P, stream, sP.inrect), t_spk, p.p_row_b, t_x0, d);
     // variance adaptor (teacher-forced: the embeddings are looked up at the TARGET buckets, so only the table tangents flow through them);
     // a phoneme-level feature sits on the phoneme rectangle before the length regulator, a frame-level one on the frame rectangle after it
     // (engine.h: forward)
@@ -401,7 +388,7 @@ int forward_t(const Pass& ps) {
     if (!any_frame_level()) {
         launch_length_regulate_fwd(on_rows(p, SP_F, stream), txp, p.f_src, p.f_row_b, p.f_row_t, t_spk, nullptr, t_dec_in, d);
     } else {
-        launch_length_regulate_rect(on_rows(p, SP_R, stream), txp, p.f_src, row_ts_f, p.r2f, t_xr0, d);
+        launch_length_regulate_rect(on_rows(p, SP_R, stream), txp, p.f_src, sF.ts, p.r2f, t_xr0, d);
         TS xr = xr0, txr = t_xr0;
         if (cfg.pitch_frame) {
             site_base = 132; pred_fwd_t(ps, pitP, pitR, tpitR, xr, txr, SP_R);
@@ -424,22 +411,19 @@ int forward_t(const Pass& ps) {
     {   // t_mel = t_dec W^T + dec tW^T + tb on valid frames, tb on padded frames, 0 on guards
         TS w = W(ps, mel_w), tw = Wt(mel_w), tb = Wt(mel_b);
         const bool dual = tw.p != nullptr;
-        for (int pass = 0; pass < 1; ++pass) {
-            GemmArgs g = rowgemm(p, SP_F, GEMM_NT);
-            g.A = pass ? x.p : tx.p; g.a_gs = pass ? x.ts : tx.ts; g.lda = d;
-            g.B = pass ? tw.p : w.p; g.b_gs = pass ? tw.ts : w.ts; g.ldb = d;
-            if (dual) { g.A2 = x.p; g.a2_gs = x.ts; g.B2 = tw.p; g.b2_gs = tw.ts; }
-            g.C = t_mel.p; g.c_gs = t_mel.ts; g.ldc = cfg.n_mel; g.N = cfg.n_mel; g.K = d;
-            if (!pass && tb.p) { g.bias = tb.p; g.bias_gs = tb.ts; }
-            g.flags = pass ? GEMM_ACCUM : 0;
-            g.c_rowmap = p.f2r; g.c_rowmap_gs = row_ts_f;
-            gemm_launch(gx, GEMM_NT, g, p.maxMf, cfg.n_mel, nt, stream, 0, (dual ? 2.0 : 1.0) * 2.0 * p.sum_nF * cfg.n_mel * d, p.sumMf,
-                        4.0 * (p.sum_nF * ((dual ? 2 : 1) * d + cfg.n_mel) + (dual ? 2.0 : 1.0) * nt * cfg.n_mel * d));
-        }
+        GemmArgs g = rowgemm(p, SP_F, GEMM_NT);
+        g.A = tx.p; g.a_gs = tx.ts; g.lda = d;
+        g.B = w.p; g.b_gs = w.ts; g.ldb = d;
+        if (dual) { g.A2 = x.p; g.a2_gs = x.ts; g.B2 = tw.p; g.b2_gs = tw.ts; }
+        g.C = t_mel.p; g.c_gs = t_mel.ts; g.ldc = cfg.n_mel; g.N = cfg.n_mel; g.K = d;
+        if (tb.p) { g.bias = tb.p; g.bias_gs = tb.ts; }
+        g.c_rowmap = p.f2r; g.c_rowmap_gs = sF.ts;
+        gemm_launch(gx, GEMM_NT, g, sF.maxM, cfg.n_mel, nt, stream, 0, (dual ? 2.0 : 1.0) * 2.0 * sF.alg_rows * cfg.n_mel * d, sF.sumM,
+                    4.0 * (sF.alg_rows * ((dual ? 2 : 1) * d + cfg.n_mel) + (dual ? 2.0 : 1.0) * nt * cfg.n_mel * d));
         if (tb.p) {
-            launch_fill_padded_rows(on_rows(p, SP_R, stream, p.r_inrect), t_mel, tb, p.r_valid, cfg.n_mel);
+            launch_fill_padded_rows(on_rows(p, SP_R, stream, sR.inrect), t_mel, tb, sR.valid.m, cfg.n_mel);
         } else {  // zero bias tangent: padded + guard rows are 0 — valid rows were just written
-            launch_fill_padded_rows(on_rows(p, SP_R, stream, p.r_inrect), t_mel, TS{(float*)tgRz.p, 0}, p.r_valid, cfg.n_mel);
+            launch_fill_padded_rows(on_rows(p, SP_R, stream, sR.inrect), t_mel, TS{(float*)tgRz.p, 0}, sR.valid.m, cfg.n_mel);
         }
     }
     TS cur = mel, tcur = t_mel;
@@ -448,13 +432,12 @@ int forward_t(const Pass& ps) {
         const PostP& P = postP[i];
         PostBuf& b = postB[i];
         PostBuf& t = tpostB[i];
-        conv_fwd_t(ps, SP_R, cur, tcur, P.cin, cfg.postnet_kernel, P.w, P.b, P.cout, t.c, p.r_inrect);
-        ColArgs ca;  // S1 = sum tc*xhat, S0 = sum tc
-        ca.X = t.c.p; ca.x_ts = t.c.ts; ca.Z = b.c.p; ca.z_ts = b.c.ts; ca.stats = b.stats.p; ca.st_ts = b.stats.ts;
-        ca.mask = p.r_inrect; ca.mask_ts = row_ts_r; ca.C = P.cout; ca.mode = 3; ca.do_tanh = 0; ca.mfield = META_MR;
+        conv_fwd_t(ps, SP_R, cur, tcur, P.cin, cfg.postnet_kernel, P.w, P.b, P.cout, t.c, sR.inrect);
+        ColArgs ca = col_args(p, SP_R, sR.inrect, P.cout, 3);  // S1 = sum tc*xhat, S0 = sum tc
+        ca.X = t.c.p; ca.x_ts = t.c.ts; ca.Z = b.c.p; ca.z_ts = b.c.ts; ca.stats = b.stats.p; ca.st_ts = b.stats.ts; ca.do_tanh = 0;
         colreduce(p, ca, t.stats.p, t.stats.p + P.cout, t.stats.ts, SP_R);
         TS gm = W(ps, P.g), tgm = Wt(P.g), tbt = Wt(P.beta);
-        launch_bn_jvp_apply(on_rows(p, SP_R, stream, p.r_inrect), b.c, t.c, b.stats, t.stats, gm, tgm, tbt, b.a, (int)(i < cfg.postnet_layers - 1), t.a, P.cout,
+        launch_bn_jvp_apply(on_rows(p, SP_R, stream, sR.inrect), b.c, t.c, b.stats, t.stats, gm, tgm, tbt, b.a, (int)(i < cfg.postnet_layers - 1), t.a, P.cout,
                             drop_active(ps) ? 1.f - cfg.postnet_dropout : 1.f, so_fuse_drop() ? drop_spec(ps, cfg.postnet_dropout, 192 + i) : DropSpec());
         if (!so_fuse_drop()) drop(ps, SP_R, t.a, t.a, P.cout, cfg.postnet_dropout, 192 + i);
         cur = b.a; tcur = t.a;
@@ -467,6 +450,7 @@ int forward_t(const Pass& ps) {
 // decoder's, the PostNet's and mel_linear's primal input-gradient GEMMs are not repeated (meta_grad_so's reverse sweep).
 int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
     const Plan& p = *ps.pl;
+    const RowSpace &sP = p.sp[SP_P], &sR = p.sp[SP_R];
     set_regime(p);
     const int d = cfg.d_model, nt = p.tasks, nm = cfg.n_mel;
     TS none{nullptr, 0};
@@ -477,11 +461,11 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
     LossArgs a = loss_args(p);
     launch_loss_grad(p.meta, nt, a, scale, gRm_direct.p, gRp.p, dpred[1].p, dpred[2].p, dpred[0].p, dpred_r[0].p, dpred_r[1].p, stream);
     MTTS_LAUNCH(loss_tangent_kernel, dim3(4, 1, nt), dim3(256), stream, (const int*)p.meta, (const float*)tpitB.out.p,
-                (const float*)teneB.out.p, (const float*)tdurB.out.p, tpitB.out.ts, (const unsigned char*)p.p_valid, row_ts_p, scale,
+                (const float*)teneB.out.p, (const float*)tdurB.out.p, tpitB.out.ts, (const unsigned char*)sP.valid.m, sP.ts, scale,
                 tdpred[1].p, tdpred[2].p, tdpred[0].p, cfg.pitch_frame, cfg.energy_frame);
     if (any_frame_level())   // MSE over the valid FRAMES (loss.py:54-63): tangent of its gradient = 2 scale / n_frames * tangent of the prediction
         MTTS_LAUNCH(loss_tangent_r_kernel, dim3(16, 1, nt), dim3(256), stream, (const int*)p.meta, (const float*)tpitR.out.p,
-                    (const float*)teneR.out.p, tpitR.out.ts, (const unsigned char*)p.r_valid, row_ts_r, scale, tdpred_r[0].p, tdpred_r[1].p,
+                    (const float*)teneR.out.p, tpitR.out.ts, (const unsigned char*)sR.valid.m, sR.ts, scale, tdpred_r[0].p, tdpred_r[1].p,
                     cfg.pitch_frame, cfg.energy_frame);
     // PostNet.  The L1 terms have no second derivative: the gradient tangents of mel_post / mel start at zero (tgRz).
     TS cur = gRp, tcur = tgRz;
@@ -498,55 +482,53 @@ int backward_t(const Pass& ps, float scale, bool skip_primal = false) {
             cur = drop(ps, SP_R, cur, gR1, P.cout, cfg.postnet_dropout, 192 + i);
             tcur = drop(ps, SP_R, tcur, tgR1, P.cout, cfg.postnet_dropout, 192 + i);
         }
-        ColArgs ca;  // primal sums (dgamma, dbeta) -> scratch
+        ColArgs ca = col_args(p, SP_R, sR.inrect, P.cout, 3);  // primal sums (dgamma, dbeta) -> scratch
         ca.yscale = ysc; ca.xdrop = pdrop;
         ca.X = cur.p; ca.x_ts = cur.ts; ca.Y = b.a.p; ca.y_ts = b.a.ts; ca.Z = b.c.p; ca.z_ts = b.c.ts;
-        ca.stats = b.stats.p; ca.st_ts = b.stats.ts; ca.mask = p.r_inrect; ca.mask_ts = row_ts_r; ca.C = P.cout;
-        ca.mode = 3; ca.do_tanh = act; ca.mfield = META_MR;
+        ca.stats = b.stats.p; ca.st_ts = b.stats.ts; ca.do_tanh = act;
         colreduce(p, ca, b.dgamma_tmp.p, b.dgamma_tmp.p + P.cout, b.dgamma_tmp.ts, SP_R);
         TS hg = Gd(P.g), hb = Gd(P.beta);
-        ColArgs cb;  // tangent sums = hv(gamma), hv(beta)
+        ColArgs cb = col_args(p, SP_R, sR.inrect, P.cout, 6);  // tangent sums = hv(gamma), hv(beta)
         cb.yscale = ysc; cb.xdrop = pdrop;
         cb.X = tcur.p; cb.x_ts = tcur.ts; cb.X2 = cur.p; cb.x2_ts = cur.ts; cb.Y = b.a.p; cb.y_ts = b.a.ts; cb.Y2 = t.a.p; cb.y2_ts = t.a.ts;
         cb.Z = b.c.p; cb.z_ts = b.c.ts; cb.Z2 = t.c.p; cb.z2_ts = t.c.ts; cb.stats = b.stats.p; cb.st_ts = b.stats.ts;
-        cb.stats2 = t.stats.p; cb.st2_ts = t.stats.ts; cb.mask = p.r_inrect; cb.mask_ts = row_ts_r; cb.C = P.cout;
-        cb.mode = 6; cb.do_tanh = act; cb.mfield = META_MR;
+        cb.stats2 = t.stats.p; cb.st2_ts = t.stats.ts; cb.do_tanh = act;
         colreduce(p, cb, hg.p, hb.p, hg.ts, SP_R);
         TS gm = W(ps, P.g), tgm = Wt(P.g);
         // under-filled plans: the layer's hv(W) product leaves the tangent launch for the side stream (as the decoder layers' do: TLayerGrad);
         // the BatchNorm backward then writes into buffers of the layer's own, which outlive the shared scratch the next layer reuses
         const bool dfp = knobs().so_defer_post && !tpostG.empty() && defer_ok(p) && p.tasks <= defer_tasks;
         const TS gR0 = dfp ? TS{tpostG[i].dc.p, tpostG[i].dc.ts} : this->gR0, tgR0 = dfp ? TS{tpostG[i].tdc.p, tpostG[i].tdc.ts} : this->tgR0;
-        launch_bn_jvp_bwd(on_rows(p, SP_R, stream, p.r_inrect), cur, tcur, b.a, t.a, b.c, t.c, b.stats, t.stats, gm, tgm, b.dgamma_tmp,
+        launch_bn_jvp_bwd(on_rows(p, SP_R, stream, sR.inrect), cur, tcur, b.a, t.a, b.c, t.c, b.stats, t.stats, gm, tgm, b.dgamma_tmp,
                           TS{b.dgamma_tmp.p + P.cout, b.dgamma_tmp.ts}, hg, hb, act, gR0, tgR0, P.cout, ysc, pdrop);
         TS xin = (i == 0) ? mel : postB[i - 1].a, txin = (i == 0) ? t_mel : tpostB[i - 1].a;
         if (i > 0) {
-            conv_bwd_t(ps, SP_R, gR0, tgR0, P.cout, cfg.postnet_kernel, xin, txin, P.cin, P.w, P.b, p.r_inrect, sk ? none : K.post_cur[i - 1], 0, tgR1, false, p.r_inrect,
-                       TS{nullptr, 0}, dfp);
+            conv_bwd_t(ps, SP_R, gR0, tgR0, P.cout, cfg.postnet_kernel, xin, txin, P.cin, P.w, P.b, sR.inrect, sk ? none : K.post_cur[i - 1], 0, tgR1, false, sR.inrect,
+                       none, dfp);
             cur = K.post_cur[i - 1]; tcur = tgR1;
         } else {
             const long long n4 = (gRm.ts * nt) / 4;
             if (!sk)
                 launch_add2(gRm.p - (long long)G * nm, gRp.p - (long long)G * nm, gRm.p - (long long)G * nm, n4, stream);
-            conv_bwd_t(ps, SP_R, gR0, tgR0, P.cout, cfg.postnet_kernel, xin, txin, P.cin, P.w, P.b, p.r_inrect, sk ? none : gRm, GEMM_ACCUM, tgRm, false, p.r_inrect,
-                       TS{nullptr, 0}, dfp);
+            conv_bwd_t(ps, SP_R, gR0, tgR0, P.cout, cfg.postnet_kernel, xin, txin, P.cin, P.w, P.b, sR.inrect, sk ? none : gRm, GEMM_ACCUM, tgRm, false, sR.inrect,
+                       none, dfp);
         }
         if (dfp) {   // hv(W_i) = tdY^T X + dY^T tX (one dual-source problem) on the side stream, after everything above
             fork_side();
             GemmBatchScope batch(gx_side, side);
-            conv_wgrad(ps, SP_R, tgR0, P.cout, cfg.postnet_kernel, xin, P.cin, P.w, P.b, p.r_inrect, 0, &gx_side, side, gR0, txin);
+            conv_wgrad(ps, SP_R, on_side(hv_wgrad_op(xin, txin, P.cin, cfg.postnet_kernel, gR0, tgR0, P.cout, P.w, P.b, sR.inrect)));
             defer_live = true;
         }
     }
     set_tag(0);
     ar_ready(ar_idx_postnet());   // (overlapped exchange of the last reverse step, engine.h)
     // mel_linear
-    colsum(ps, SP_R, tgRm, nm, nullptr, none, Gd(mel_b));
+    colsum(ps, SP_R, tgRm, nm, RowMask(), none, Gd(mel_b));
     launch_gather_rows(on_rows(p, SP_F, stream), gRm, p.f2r, gMelF, nm);
     launch_gather_rows(on_rows(p, SP_F, stream), tgRm, p.f2r, tgMelF, nm);
     TS dec_out = cfg.dec_layers ? decB[cfg.dec_layers - 1].y2 : dec_in;
     TS tdec_out = cfg.dec_layers ? tdecB[cfg.dec_layers - 1].y2 : t_dec_in;
-    conv_bwd_t(ps, SP_F, gMelF, tgMelF, nm, 1, dec_out, tdec_out, d, mel_w, -1, nullptr, sk ? none : K.dec_top, 0, tgF0, false, nullptr);
+    conv_bwd_t(ps, SP_F, gMelF, tgMelF, nm, 1, dec_out, tdec_out, d, mel_w, -1, RowMask(), sk ? none : K.dec_top, 0, tgF0, false, RowMask());
     for (int l = cfg.dec_layers - 1; l >= 0; --l) {
         TS xin = l == 0 ? dec_in : decB[l - 1].y2, txin = l == 0 ? t_dec_in : tdecB[l - 1].y2;
         site_base = 64 + 2 * l;
@@ -632,7 +614,7 @@ void table_hv(const Plan& p, TS g, TS snap, const int* idx, int n_rows, int skip
     }
     TS src = g;
     if (snapshot) {
-        launch_copy_tasks(g, snap, (long long)p.maxMp * d / 4, nt, stream);
+        launch_copy_tasks(g, snap, (long long)p.sp[SP_P].maxM * d / 4, nt, stream);
         src = snap;
     }
     fork_side();
