@@ -22,6 +22,7 @@
 #ifndef MTTS_H
 #define MTTS_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -557,6 +558,53 @@ int mtts_dvector_adam_step(mtts_dvector* h, const float* norm_dev, float max_nor
 int mtts_dvector_set_optimizer_step(mtts_dvector* h, int step);
 int mtts_dvector_export(mtts_dvector* h, const char* name, int which, float* out, int64_t numel);
 int mtts_dvector_import(mtts_dvector* h, const char* name, int which, const float* data, int64_t numel);
+
+/* ---- GE2E training of the d-vector encoder ------------------------------------------------
+ * The objective the reference's from-scratch encoder class is named after (`GE2E`, speaker_encoder.py:11-31).  No GE2E loss code exists
+ * in the reference tree: what follows is the softmax variant of Wan et al. 2018 ("Generalized end-to-end loss for speaker
+ * verification") as the Real-Time-Voice-Cloning trainer states it, written down from memory.  Parity with any published GE2E code is
+ * UNPINNED; what is pinned is THIS definition, restated in float64 torch with autograd by tests/ge2e_oracle.py.
+ *
+ * Definition.  Embeddings e[j][i], speaker j of N >= 2, utterance i of M >= 2, dimension E, rows speaker-major (row = j * M + i).  They
+ * arrive L2-normalised from the encoder; the loss does not rely on that.  S_k = sum_i e[k][i].
+ *   1. inclusive centroid  c_k = S_k / |S_k|  (the normalised mean)
+ *   2. exclusive centroid  chat_ji = u / |u|,  u = (S_j - e[j][i]) / (M - 1)
+ *   3. similarities        s[ji][k] = w * (e[j][i] . c_k) + b  for k != j,   s[ji][j] = w * (e[j][i] . chat_ji) + b
+ *                          (a plain dot product: e is not renormalised to a cosine)
+ *   4. loss                L = 1 / (N M) * sum_ji ( logsumexp_k s[ji][k] - s[ji][j] )
+ *   5. gradients           dL/de does NOT detach the centroids; with g = (softmax - onehot) / (N M):
+ *                          dL/dw = sum g[ji][k] * (e . centroid)[ji][k],   dL/db = sum g[ji][k]
+ *   6. trainer rule        w0 = 10, b0 = -5; the gradients of w and b are multiplied by 0.01; then the joint L2 norm of ALL gradients
+ *                          (LSTM, linear, w, b) is clipped to 3 (coefficient min(1, 3 / (norm + 1e-6))); then Adam with lr 1e-4, betas
+ *                          (0.9, 0.999), eps 1e-8, no weight decay, bias-corrected as the adam_step entry above.  All are arguments.
+ * Limits, refused before any launch with the argument named: 2 <= N <= 1024, 2 <= M <= 64, E a multiple of 4 in 4 .. 256, w finite
+ * and not 0.  The limits bound indices and on-chip arrays; the kernels are sized for training batches (64 x 10), and no time has been
+ * measured near the limits, where the gradient kernel's serial walks (about 1.3e5 loop trips per thread at 1024 x 64) dominate.
+ * Embeddings of a speaker that cancel (S_k = 0 or u = 0) give NaN, as the definition does.  No atomics: a loss and its
+ * gradients are the same bits on every run.
+ *
+ * ge2e_loss: the loss kernels alone on raw DEVICE pointers, asynchronous on hip_stream.  emb [n_spk * n_utt][E] -> loss3 [3] = L, dL/dw,
+ * dL/db; demb [n_spk * n_utt][E]; sim [n_spk * n_utt][n_spk] = s, or NULL; ws: scratch of at least ge2e_ws_bytes bytes (0: shape refused).
+ * The refusal is read through the d-vector last_error entry with a NULL handle.
+ *
+ * Handle entries (enable_training first).  w and b live on the device with their own gradient and Adam state; they are NOT tensors of
+ * the encoder: load / export / import and the state-dict names are what they were.
+ *   ge2e_enable: allocates the loss scratch for any n_spk * n_utt <= max_utts and sets (w, b) = (w0, b0), their Adam state to 0.
+ *   ge2e_forward_backward: mels [n_spk * n_utt][frames][n_mels] speaker-major, one partial utterance per utterance, on the host or
+ *     (mels_on_device = 1) already on the device, read in place; training forward, loss, dL/de straight into the backward sweep.
+ *     Everything is enqueued on the handle's stream; the call waits only when loss_host [1] or sim_host [n_spk * n_utt][n_spk] is given.
+ *     n_spk * n_utt <= max_utts and <= max_partials.
+ *   ge2e_step: rule 6 on the device, no host round trip: scale, joint norm, clip + Adam on the encoder and on (w, b); the optimizer
+ *     step count is the one set_optimizer_step sets.
+ *   ge2e_get / ge2e_set: which = 0 value, 1 gradient, 2 Adam m, 3 Adam v of (w, b); wb2_host [2]. */
+int mtts_ge2e_loss(int n_spk, int n_utt, int E, const float* emb, float w, float b, float* loss3, float* demb, float* sim, void* ws, size_t ws_bytes,
+                   void* hip_stream);
+size_t mtts_ge2e_ws_bytes(int n_spk, int n_utt, int E);
+int mtts_dvector_ge2e_enable(mtts_dvector* h, float w0, float b0);
+int mtts_dvector_ge2e_forward_backward(mtts_dvector* h, const float* mels, int mels_on_device, int n_spk, int n_utt, float* loss_host, float* sim_host);
+int mtts_dvector_ge2e_step(mtts_dvector* h, float lr, float b1, float b2, float eps, float max_norm, float scalar_grad_scale);
+int mtts_dvector_ge2e_get(mtts_dvector* h, int which, float* wb2_host);
+int mtts_dvector_ge2e_set(mtts_dvector* h, int which, const float* wb2_host);
 
 /* ---- waveform -> log-mel spectrogram + frame energy (front-end STFT / mel extraction) ------
  * Replaces `TacotronSTFT.mel_spectrogram` behind `Audio.tools.get_mel_from_wav` (audio/stft.py:128-178, audio/tools.py:8-15):

@@ -162,6 +162,13 @@ EXPORTS = {
     "mtts_dvector_set_optimizer_step": (C.c_int, [C.c_void_p, C.c_int]),
     "mtts_dvector_export": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int64]),
     "mtts_dvector_import": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int64]),
+    "mtts_ge2e_loss": (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mtts_ge2e_ws_bytes": (C.c_size_t, [C.c_int] * 3),
+    "mtts_dvector_ge2e_enable": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
+    "mtts_dvector_ge2e_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mtts_dvector_ge2e_step": (C.c_int, [C.c_void_p] + [C.c_float] * 6),
+    "mtts_dvector_ge2e_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "mtts_dvector_ge2e_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mtts_dvector_embed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mtts_dvector_embed_wavs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "ge2e.h"
 #include "gemm.h"
 #include "params.h"
 #include "rowops.h"
@@ -273,6 +274,14 @@ public:
     float *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr, *ones4 = nullptr, *sq_partial = nullptr, *sq_out = nullptr;
     int last_N = 0, last_B = 0, adam_steps = 0;
     bool have_forward = false;
+    const float* last_x0 = nullptr;   // the input of the last training forward: the handle's `mels`, or the caller's device stack
+    // ---- GE2E training (ge2e.h; allocated by ge2e_enable).  ge2e_wb: four groups of 4 floats — value, gradient, Adam m, Adam v of (w, b, 0, 0):
+    // one float4 for launch_adam_clip; NOT entries of `tab`, so the encoder's state dict is what it was ----
+    bool ge2e_ready = false, ge2e_have_grad = false;
+    void* ge2e_ws = nullptr;
+    float *ge2e_wb = nullptr, *ge2e_loss = nullptr, *ge2e_norm = nullptr, *ge2e_sim = nullptr;
+    int ge2e_cap_spk = 0;
+    std::vector<int> ge2e_off;        // 0 .. max_utts: one partial per utterance
 
     DevHeap mem;   // every device block of this handle, the scoring workspace included (devres.h)
     int err(const std::string& s) { last_error = s; return -1; }
@@ -379,7 +388,7 @@ public:
             if (utt_off[b + 1] <= utt_off[b]) { set_error("every utterance needs at least one partial utterance (offsets must increase)"); return -1; }
         return 0;
     }
-    // x0: [N][T][n_mels] on the device; tile: the input projections' GEMM tile code (0: through the launch queue)
+    // x0: [N][T][n_mels] on the device; out_host may be null (the GE2E step reads `out` on the device); tile: the input projections' GEMM tile code (0: through the launch queue)
     int forward(const float* x0, int N, const int* utt_off, int B, float* out_host, float* part_host, bool train, int tile) {
         const long long rows = (long long)N * T;
         DEV_CHECK(hipMemcpyAsync(off_dev, utt_off, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
@@ -399,11 +408,11 @@ public:
             x = hs;
         }
         launch_dvec_head(N, H, E, hlast, linT, P("linear.bias"), part, train ? eraw : nullptr, stream);
-        if (train) { last_N = N; last_B = B; have_forward = true; }
+        if (train) { last_N = N; last_B = B; have_forward = true; last_x0 = x0; }
         launch_dvec_utterance(B, E, part, off_dev, out, stream);
         if (gx.error) { set_error(std::string("GEMM launcher: ") + gx.error); gx.error = nullptr; return -1; }
         DEV_CHECK(hipGetLastError());
-        DEV_CHECK(hipMemcpyAsync(out_host, out, (size_t)B * E * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (out_host) DEV_CHECK(hipMemcpyAsync(out_host, out, (size_t)B * E * sizeof(float), hipMemcpyDeviceToHost, stream));
         if (part_host) DEV_CHECK(hipMemcpyAsync(part_host, part, (size_t)N * E * sizeof(float), hipMemcpyDeviceToHost, stream));
         return 0;
     }
@@ -420,10 +429,15 @@ public:
     // dout_host [B][E]: gradient of the loss w.r.t. the embeddings returned by the last embed(train = true)
     int backward(const float* dout_host) {
         if (!train_ready || !have_forward || !dout_host) { set_error("d-vector backward without a training forward"); return -1; }
+        DEV_CHECK(hipMemcpyAsync(dout, dout_host, (size_t)last_B * E * sizeof(float), hipMemcpyHostToDevice, stream));
+        return backward_from_device();
+    }
+    // the same sweep from the handle's own `dout` [B][E], wherever it was written (the copy above, or the GE2E loss kernels)
+    int backward_from_device() {
+        if (!train_ready || !have_forward) { set_error("d-vector backward without a training forward"); return -1; }
         const int N = last_N, B = last_B;
         const long long rows = (long long)N * T;
         DEV_CHECK(hipMemsetAsync(grads, 0, (size_t)tab.n_params * sizeof(float), stream));
-        DEV_CHECK(hipMemcpyAsync(dout, dout_host, (size_t)B * E * sizeof(float), hipMemcpyHostToDevice, stream));
         launch_dvec_utterance_bwd(B, E, part, off_dev, dout, dpart, stream);
         launch_dvec_head_bwd(N, H, E, eraw, dpart, P("linear.weight"), dz, dh_last, stream);
         wgrad(dz, E, hlast, H, N, grads + find("linear.weight"), grads + find("linear.bias"));
@@ -431,7 +445,7 @@ public:
         for (int l = layers - 1; l >= 0; --l) {
             const std::string s = std::to_string(l);
             launch_lstm_bptt(N, T, H, gates[l], cseq[l], dh_ext, l == layers - 1 ? dh_last : nullptr, P("lstm.weight_hh_l" + s), dgates, stream);
-            const float* x = l == 0 ? mels : hkeep[l - 1];
+            const float* x = l == 0 ? last_x0 : hkeep[l - 1];
             wgrad(dgates, 4 * H, x, in_dim(l), rows, grads + find("lstm.weight_ih_l" + s), grads + find("lstm.bias_ih_l" + s));
             wgrad(dgates, 4 * H, hprev[l], H, rows, grads + find("lstm.weight_hh_l" + s), nullptr);
             launch_copy_tasks(TS{grads + find("lstm.bias_ih_l" + s), 0}, TS{grads + find("lstm.bias_hh_l" + s), 0}, (long long)H, 1, stream, 4);   // 4H floats = H float4: d b_hh == d b_ih
@@ -464,6 +478,85 @@ public:
         launch_adam_clip(tab.data, grads, adam_m, adam_v, tab.n_params / 4, norm_dev, norm_dev ? max_norm : 0.f, lr, b1, b2, eps, bc1, bc2, weight_decay, stream, 256);
         DEV_CHECK(hipGetLastError());
         dirty = true;
+        return 0;
+    }
+
+    // ---- GE2E: loss + backward + optimizer step without leaving the device (ge2e.h) ---------------------------------------------------
+    // needs enable_training; sizes the loss scratch for any N x M <= max_utts (N <= max_utts / 2 at M = 2)
+    int ge2e_enable(float w0, float b0) {
+        if (!train_ready) return err("mtts_dvector_enable_training first");
+        ge2e_cap_spk = cap_B / 2 < GE2E_MAX_SPK ? cap_B / 2 : GE2E_MAX_SPK;
+        if (const char* bad = ge2e_bad_shape(ge2e_cap_spk < 2 ? 2 : ge2e_cap_spk, 2, E, w0)) return err(std::string("mtts_dvector_ge2e_enable: ") + bad);
+        if (cap_B < 4) return err("mtts_dvector_ge2e_enable: max_utts must hold 2 speakers x 2 utterances");
+        if (!ge2e_ready) {
+            DEV_CHECK(mem.alloc(ge2e_ws, ge2e_ws_bytes(cap_B, ge2e_cap_spk, E)));
+            DEV_CHECK(mem.alloc(ge2e_wb, 16 * sizeof(float)));
+            DEV_CHECK(mem.alloc(ge2e_loss, 4 * sizeof(float)));
+            DEV_CHECK(mem.alloc(ge2e_norm, 4 * sizeof(float)));
+            DEV_CHECK(mem.alloc(ge2e_sim, (size_t)cap_B * ge2e_cap_spk * sizeof(float)));
+            ge2e_off.resize(cap_B + 1);
+            for (int i = 0; i <= cap_B; ++i) ge2e_off[i] = i;
+        }
+        const float init[16] = {w0, b0};
+        DEV_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpy(ge2e_wb, init, sizeof(init), hipMemcpyHostToDevice));
+        ge2e_ready = true;
+        ge2e_have_grad = false;
+        return 0;
+    }
+    // mels_any [N M][T][n_mels], speaker-major, on the host or (on_device) already on the device; one partial per utterance.  Enqueued on the
+    // handle's stream; synchronises only when loss_host [1] or sim_host [N M][N] is given.
+    int ge2e_forward_backward(const float* mels_any, bool on_device, int N, int M, float* loss_host, float* sim_host) {
+        if (!ge2e_ready) return err("mtts_dvector_ge2e_enable first");
+        if (!mels_any) return err("mtts_dvector_ge2e_forward_backward: mels is NULL");
+        if (const char* bad = ge2e_bad_shape(N, M, E, 1.f)) return err(std::string("mtts_dvector_ge2e_forward_backward: ") + bad);
+        const int B = N * M;
+        if (B > cap_B) return err("mtts_dvector_ge2e_forward_backward: n_spk * n_utt exceeds max_utts");
+        if (B > cap_N) return err("mtts_dvector_ge2e_forward_backward: n_spk * n_utt exceeds max_partials");
+        if (dirty && refresh() != 0) return -1;
+        const float* x0 = mels_any;
+        if (!on_device) {
+            DEV_CHECK(hipMemcpyAsync(mels, mels_any, (size_t)B * T * n_mels * sizeof(float), hipMemcpyHostToDevice, stream));
+            x0 = mels;
+        }
+        if (forward(x0, B, ge2e_off.data(), B, nullptr, nullptr, true, 0) != 0) return -1;
+        launch_ge2e_loss(N, M, E, out, Ge2eScal{ge2e_wb, 0.f, 0.f}, ge2e_loss, ge2e_wb + 4, dout, sim_host ? ge2e_sim : nullptr, ge2e_carve(ge2e_ws, B, N, E), stream);
+        if (backward_from_device() != 0) return -1;
+        ge2e_have_grad = true;
+        if (loss_host) DEV_CHECK(hipMemcpyAsync(loss_host, ge2e_loss, sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (sim_host) DEV_CHECK(hipMemcpyAsync(sim_host, ge2e_sim, (size_t)B * N * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (loss_host || sim_host) DEV_CHECK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    // scale dw / db, joint norm of every gradient on the device, clip + Adam on the encoder and on (w, b) with the same step count
+    int ge2e_step(float lr, float b1, float b2, float eps, float max_norm, float scalar_grad_scale) {
+        if (!ge2e_ready) return err("mtts_dvector_ge2e_enable first");
+        if (!ge2e_have_grad) return err("mtts_dvector_ge2e_step without mtts_dvector_ge2e_forward_backward");
+        const float* sumsq = grad_sumsq();
+        float *gwb = ge2e_wb + 4, *norm = ge2e_norm;
+        MTTS_LAUNCH(ge2e_joint_norm_kernel, dim3(1), dim3(64), stream, sumsq, gwb, scalar_grad_scale, norm);
+        if (adam_step(ge2e_norm, max_norm, lr, b1, b2, eps, 0.f) != 0) return -1;
+        const float bc1 = 1.f - (float)std::pow((double)b1, (double)adam_steps), bc2 = 1.f - (float)std::pow((double)b2, (double)adam_steps);
+        launch_adam_clip(ge2e_wb, ge2e_wb + 4, ge2e_wb + 8, ge2e_wb + 12, 1, ge2e_norm, max_norm, lr, b1, b2, eps, bc1, bc2, 0.f, stream, 1);
+        DEV_CHECK(hipGetLastError());
+        ge2e_have_grad = false;
+        return 0;
+    }
+    // which: 0 value, 1 gradient, 2 Adam m, 3 Adam v of (w, b)
+    int ge2e_get(int which, float* wb2_host) {
+        if (!ge2e_ready) return err("mtts_dvector_ge2e_enable first");
+        if (which < 0 || which > 3 || !wb2_host) return err("mtts_dvector_ge2e_get: which must be 0 .. 3 and the output not NULL");
+        DEV_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpy(wb2_host, ge2e_wb + 4 * which, 2 * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    int ge2e_set(int which, const float* wb2_host) {
+        if (!ge2e_ready) return err("mtts_dvector_ge2e_enable first");
+        if (which < 0 || which > 3 || !wb2_host) return err("mtts_dvector_ge2e_set: which must be 0 .. 3 and the input not NULL");
+        if (which == 0)
+            if (const char* bad = ge2e_bad_shape(2, 2, E, wb2_host[0])) return err(std::string("mtts_dvector_ge2e_set: ") + bad);
+        DEV_CHECK(hipStreamSynchronize(stream));
+        DEV_CHECK(hipMemcpy(ge2e_wb + 4 * which, wb2_host, 2 * sizeof(float), hipMemcpyHostToDevice));
         return 0;
     }
     // which: 0 parameter, 1 gradient, 2 Adam m, 3 Adam v

@@ -441,3 +441,23 @@ int mtts_dvec_utterance_bwd(int B, int E, const float* part, const int* off, con
     launch_dvec_utterance_bwd(B, E, part, off, dout, dpart, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// GE2E loss and its backward (ge2e.h; the definition: include/mtts.h).  emb [n_spk * n_utt][E] speaker-major, loss3 [3] = L, dL/dw, dL/db,
+// demb [n_spk * n_utt][E], sim [n_spk * n_utt][n_spk] or null, ws of mtts_ge2e_ws_bytes bytes — all on the device.  Four launches, nothing
+// copied.  A refusal launches nothing and leaves its reason, with the argument named, where mtts_dvector_last_error(NULL) reads it.
+size_t mtts_ge2e_ws_bytes(int n_spk, int n_utt, int E) {
+    return ge2e_bad_shape(n_spk, n_utt, E, 1.f) ? 0 : ge2e_ws_bytes((long long)n_spk * n_utt, n_spk, E);
+}
+int mtts_ge2e_loss(int n_spk, int n_utt, int E, const float* emb, float w, float b, float* loss3, float* demb, float* sim, void* ws, size_t ws_bytes,
+                   void* stream) {
+    const char* bad = ge2e_bad_shape(n_spk, n_utt, E, w);
+    if (!bad && !emb) bad = "emb is NULL";
+    if (!bad && !loss3) bad = "loss3 is NULL";
+    if (!bad && !demb) bad = "demb is NULL";
+    if (!bad && !ws) bad = "ws is NULL";
+    if (!bad && ws_bytes < ge2e_ws_bytes((long long)n_spk * n_utt, n_spk, E)) bad = "ws_bytes is smaller than mtts_ge2e_ws_bytes";
+    if (bad) { g_create_error = std::string("mtts_ge2e_loss: ") + bad; return -1; }
+    launch_ge2e_loss(n_spk, n_utt, E, emb, Ge2eScal{nullptr, w, b}, loss3, loss3 + 1, demb, sim, ge2e_carve(ws, (long long)n_spk * n_utt, n_spk, E),
+                     (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -928,6 +928,19 @@ int mtts_dvector_adam_step(mtts_dvector* h, const float* norm_dev, float max_nor
 int mtts_dvector_set_optimizer_step(mtts_dvector* h, int step) { h->d.adam_steps = step; return 0; }
 int mtts_dvector_export(mtts_dvector* h, const char* name, int which, float* out, int64_t numel) { return h->d.export_state(name, which, out, numel); }
 int mtts_dvector_import(mtts_dvector* h, const char* name, int which, const float* data, int64_t numel) { return h->d.import_state(name, which, data, numel); }
+// GE2E training of the encoder (ge2e.h; the definition: include/mtts.h).  A NULL handle: the message goes where mtts_dvector_last_error(NULL) reads it
+static int dvector_null(const char* entry) { g_create_error = std::string(entry) + ": NULL handle"; return -1; }
+int mtts_dvector_ge2e_enable(mtts_dvector* h, float w0, float b0) { return h ? h->d.ge2e_enable(w0, b0) : dvector_null("mtts_dvector_ge2e_enable"); }
+int mtts_dvector_ge2e_forward_backward(mtts_dvector* h, const float* mels, int mels_on_device, int n_spk, int n_utt, float* loss_host, float* sim_host) {
+    if (!h) return dvector_null("mtts_dvector_ge2e_forward_backward");
+    return h->d.ge2e_forward_backward(mels, mels_on_device != 0, n_spk, n_utt, loss_host, sim_host);
+}
+int mtts_dvector_ge2e_step(mtts_dvector* h, float lr, float b1, float b2, float eps, float max_norm, float scalar_grad_scale) {
+    if (!h) return dvector_null("mtts_dvector_ge2e_step");
+    return h->d.ge2e_step(lr, b1, b2, eps, max_norm, scalar_grad_scale);
+}
+int mtts_dvector_ge2e_get(mtts_dvector* h, int which, float* wb2_host) { return h ? h->d.ge2e_get(which, wb2_host) : dvector_null("mtts_dvector_ge2e_get"); }
+int mtts_dvector_ge2e_set(mtts_dvector* h, int which, const float* wb2_host) { return h ? h->d.ge2e_set(which, wb2_host) : dvector_null("mtts_dvector_ge2e_set"); }
 
 // ---- waveform -> log-mel + energy (melfront.h, whose MelFront also holds the STFT front-end and the workspace that griffin.h and
 // preprocess.h share; reference audio/stft.py:128-178, audio/tools.py:8-15) ----------------------

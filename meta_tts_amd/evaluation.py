@@ -665,6 +665,14 @@ def auc(x, y) -> float:
     return float(direction * trapezoid(y, x))
 
 
+def equal_error_rate(y_true, y_score, drop_intermediate: bool = False):
+    """(EER, threshold) as speaker_verification.py:32-59 reads them off the DET curve: the point where |fpr - fnr| is smallest, the mean of
+    the two rates there.  The one routine behind SpeakerVerification.get_eer and the batch EER of ge2e.GE2ETrainer."""
+    fpr, fnr, thresholds = det_curve(y_true, y_score, drop_intermediate)
+    min_index = np.argmin(np.abs(fpr - fnr))
+    return np.mean((fpr[min_index], fnr[min_index])), thresholds[min_index]
+
+
 class SpeakerVerification:
     """speaker_verification.py:32-59 (EER and its threshold per mode from the pair similarities, written to txt/<corpus>/<output>)
     and :281-315 (AUC per mode: real positives against the mode's positives)."""
@@ -683,10 +691,7 @@ class SpeakerVerification:
             y_score = s_list.flatten()
             y_true = np.ones_like(s_list)
             y_true[1, :] = 0
-            fpr, fnr, thresholds = det_curve(y_true.flatten(), y_score, self.det_drop_intermediate)
-            min_index = np.argmin(np.abs(fpr - fnr))
-            self.eer_dict[mode] = np.mean((fpr[min_index], fnr[min_index]))
-            self.threshold_dict[mode] = thresholds[min_index]
+            self.eer_dict[mode], self.threshold_dict[mode] = equal_error_rate(y_true.flatten(), y_score, self.det_drop_intermediate)
         if write:
             with open(self.output_path, "w+") as f:
                 for mode in self.pair_similarity_dict:

@@ -84,8 +84,14 @@ class DVectorEncoder:
             self._check(self.lib.mtts_dvector_load(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size))
         self.state = {n: np.asarray(sd[next(k for k in (prefix + n, "speaker_emb.model." + n, "model.speaker_emb.model." + n) if k in sd)], np.float32)
                       for n in tensor_shapes(**self.cfg)}
+        self.state_stale = False
+
+    state_stale = False   # True: the device weights moved without a download (ge2e.GE2ETrainer.step); state_dict() exports them first
 
     def state_dict(self):
+        if self.state_stale:
+            self.state = {n: self.export(n, 0) for n in tensor_shapes(**self.cfg)}
+            self.state_stale = False
         return dict(self.state)
 
     def embed(self, ref_mels, ref_slices, return_partials=False):
@@ -169,6 +175,7 @@ class DVectorEncoder:
         self._check(self.lib.mtts_dvector_adam_step(self.h, norm_dev, float(max_norm), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                                     float(weight_decay)))
         self.state = {n: self.export(n, 0) for n in tensor_shapes(**self.cfg)}
+        self.state_stale = False
 
     def set_optimizer_step(self, step):
         self._check(self.lib.mtts_dvector_set_optimizer_step(self.h, int(step)))
