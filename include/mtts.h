@@ -930,6 +930,68 @@ int mtts_dtw_cepstra(mtts_dtw* h, int n_utts, const int* n_frames, const float* 
 int mtts_dtw_mcd_batch(mtts_dtw* h, int n_pairs, const int* frames_a, const float* mel_a, const int* frames_b, const float* mel_b, const int* f0_frames_a,
                        const double* f0_a, const int* f0_frames_b, const double* f0_b, double* out, int* path_len, int* path);
 
+/* ---- forced alignment: flat-start monophone EM, Viterbi to durations (csrc/align.h) -----------------------------
+ * Phoneme durations from features and phone sequences, so that a corpus without third-party TextGrids gets past preprocessing.  The
+ * classical first pass of an HMM forced aligner and no more: one diagonal Gaussian per phone class, Baum-Welch re-estimation in closed
+ * form, Viterbi to durations; no network, no optimiser.  The definition is this project's own, restated in float64 numpy by
+ * tests/align_oracle.py.  Parity with MFA, Kaldi and HTK is UNPINNED, and alignment quality on real speech is not measured.
+ *   features  x[t][f] float32, t < T, f < F = n_feat, 1 <= F <= 128; any packed [sum T][F] rows (the Python layer feeds natural-log mels).
+ *   model     V = n_classes phone classes, 1 <= V <= 512, each a float64 mean mu[v][f] and variance var[v][f] > 0; beside them the
+ *             flat-start variance g[f] > 0 of every feature (global_var), which scales the variance floor.
+ *   utterance S states, 1 <= S <= max_states <= 2048; state s has a class c[s] and a flag opt[s] (1: the state may be skipped, e.g. a
+ *             silence between words).  Two adjacent optional states are refused, and so are more mandatory states than frames.
+ *   emission  b(t, s) = -1/2 sum_f [ (x[t][f] - mu[c][f])^2 (1 / var[c][f]) + log(2 pi var[c][f]) ], c = c[s]; float64, the reciprocal rounded
+ *             once, the bracket added in ascending f.
+ *   lattice   left to right, every allowed transition of weight 1 (no transition probabilities): into (t, s) come (t-1, s) stay,
+ *             (t-1, s-1) advance and, only if opt[s-1], (t-1, s-2) skip.  A path starts at t = 0 in state 0, or in state 1 if opt[0]; it
+ *             ends at t = T-1 in state S-1, or in state S-2 if opt[S-1].
+ *   forward   alpha(t, s) = b(t, s) + logsumexp(stay, advance, skip) in that order; logsumexp = m + log(sum exp(. - m)), m the largest
+ *             term (a missing predecessor is -inf; all -inf gives -inf).  LL = logsumexp(alpha(T-1, S-1), alpha(T-1, S-2)).  beta is the
+ *             mirror image (beta(T-1, end) = 0; successors stay, advance, skip, each with its emission at t+1 added first);
+ *             gamma(t, s) = exp((alpha + beta) - LL).
+ *   Viterbi   the same recursion with max; ties go to stay, then advance, then skip; among the end states ties go to S-1.  dur[s] = the
+ *             frames the path spends in state s (0 for a skipped optional state); sum dur = T.
+ *   flat start  every class gets the mean and variance (two passes, float64, rows in call order) of all frames of the call; g = that variance.
+ *   EM        em_begin; any number of em_accumulate(batch); em_finish.  accumulate adds per class occ = sum gamma, sum gamma x and
+ *             sum gamma x^2 over the batch's states of that class: per state in ascending t, then one utterance's per-class sum (its
+ *             states in ascending s, from zero) after another's, in call order.  finish sets mu = sum gamma x / occ and
+ *             var = max(sum gamma x^2 / occ - mu^2, var_floor g[f]) (var_floor 0.01 by default); a class with occ < min_occ (default 1e-3)
+ *             keeps its parameters; it returns sum LL of the iteration's utterances, added in call order.
+ * create: max_frames <= 2^20, max_states <= 2048 (two float64 rows of the sweep live in a workgroup's LDS), max_cells <= 2^30 bounds
+ *   sum T S of one chunk (the alpha / gamma workspace, float64 per cell, and the back-pointers, a byte per cell, which the handle owns
+ *   and grows on demand), max_utts <= 65535 the utterances of one chunk.
+ * Batches: n_frames [n_utts], n_states [n_utts], classes [sum S] int32, optional [sum S] bytes, x [sum T][F] host float32, utterances one
+ *   after another.  A call is a plan: validate; cut the utterances, in order, into chunks of sum T S <= max_cells and at most max_utts;
+ *   reserve every buffer for the largest chunk; run chunk by chunk.  Synchronous.
+ *   em_accumulate: ll_out [n_utts]; a refusal leaves the open iteration as it was, a runtime failure after the call's first launch closes it
+ *   (its sums may hold part of the call; start again with em_begin).  em_finish: total_ll_out [1].  posteriors: ll_out [n_utts], gamma_out packed [sum T S], utterance u's
+ *   block row-major [T][S].  align: durations_out [sum S] int32, score_out [n_utts] = the Viterbi path's log-likelihood.
+ *   set_model / get_model: mean and var [V][F], global_var [F], host float64.
+ * No atomics and no wavefront intrinsics; every reduction is an ascending loop.  An utterance's LL, gamma and durations are bit-identical
+ *   alone, in any batch, at any position and under any chunking; the model after em_finish is bit-identical for any max_cells and for
+ *   any cut of the corpus into em_accumulate calls.
+ * Refused with < 0, the reason (naming the utterance and the limit) in last_error, before any launch, the handle staying usable: T < 1 or
+ *   > max_frames; S < 1 or > max_states; T S > max_cells; more mandatory states than frames; adjacent optional states; a class id outside
+ *   0 .. V-1; non-finite features; var <= 0 or non-finite model values; em_accumulate or em_finish without em_begin; no model loaded; NULL
+ *   required pointers; a feature that is constant over all frames of flat_start. */
+typedef struct mtts_align mtts_align;
+int mtts_align_create(int n_feat, int n_classes, int max_frames, int max_states, int64_t max_cells, int max_utts, int device, mtts_align** out);
+void mtts_align_destroy(mtts_align* h);
+const char* mtts_align_last_error(mtts_align* h);
+int mtts_align_set_stream(mtts_align* h, void* hip_stream);
+int mtts_align_set_model(mtts_align* h, const double* mean, const double* var, const double* global_var);
+int mtts_align_get_model(mtts_align* h, double* mean, double* var, double* global_var);
+int mtts_align_set_floor(mtts_align* h, double var_floor, double min_occ);
+int mtts_align_flat_start(mtts_align* h, int n_utts, const int* n_frames, const float* x);
+int mtts_align_em_begin(mtts_align* h);
+int mtts_align_em_accumulate(mtts_align* h, int n_utts, const int* n_frames, const int* n_states, const int* classes, const unsigned char* optional, const float* x,
+                             double* ll_out);
+int mtts_align_em_finish(mtts_align* h, double* total_ll_out);
+int mtts_align_posteriors(mtts_align* h, int n_utts, const int* n_frames, const int* n_states, const int* classes, const unsigned char* optional, const float* x,
+                          double* ll_out, double* gamma_out);
+int mtts_align_align(mtts_align* h, int n_utts, const int* n_frames, const int* n_states, const int* classes, const unsigned char* optional, const float* x,
+                     int* durations_out, double* score_out);
+
 /* ---- MOSNet: magnitude spectrograms / waveforms -> naturalness scores -------------------------------
  * Stands behind evaluation/compute_mos.py (NeuralMOS.compute_mosnet, speechmetrics' MOSNet on one wav at a time).  Neither speechmetrics,
  * its TensorFlow model nor cnn_blstm.h5 is part of the reference tree: parity with the published weights is UNPINNED, and so are the

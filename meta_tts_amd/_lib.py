@@ -251,6 +251,19 @@ EXPORTS = {
     "mtts_dtw_load_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mtts_dtw_cepstra": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_dtw_mcd_batch": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 11),
+    "mtts_align_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mtts_align_destroy": (None, [C.c_void_p]),
+    "mtts_align_last_error": (C.c_char_p, [C.c_void_p]),
+    "mtts_align_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mtts_align_set_model": (C.c_int, [C.c_void_p] * 4),
+    "mtts_align_get_model": (C.c_int, [C.c_void_p] * 4),
+    "mtts_align_set_floor": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "mtts_align_flat_start": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mtts_align_em_begin": (C.c_int, [C.c_void_p]),
+    "mtts_align_em_accumulate": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "mtts_align_em_finish": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mtts_align_posteriors": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
+    "mtts_align_align": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
     "mtts_mosnet_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mtts_mosnet_destroy": (None, [C.c_void_p]),
     "mtts_mosnet_last_error": (C.c_char_p, [C.c_void_p]),

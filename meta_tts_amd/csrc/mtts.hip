@@ -17,6 +17,7 @@
 #include "speakereval.h"
 #include "tsne.h"
 #include "dtw.h"
+#include "align.h"
 #include "mosnet.h"
 
 using namespace mtts;
@@ -60,6 +61,9 @@ struct mtts_tsne {
 };
 struct mtts_dtw {
     Dtw d;
+};
+struct mtts_align {
+    Align a;
 };
 struct mtts_mosnet {
     MosNet n;
@@ -892,6 +896,46 @@ int mtts_dtw_cepstra(mtts_dtw* h, int n_utts, const int* n_frames, const float* 
 int mtts_dtw_mcd_batch(mtts_dtw* h, int n_pairs, const int* frames_a, const float* mel_a, const int* frames_b, const float* mel_b, const int* f0_frames_a,
                        const double* f0_a, const int* f0_frames_b, const double* f0_b, double* out, int* path_len, int* path) {
     return h ? h->d.mcd_batch(n_pairs, frames_a, mel_a, frames_b, mel_b, f0_frames_a, f0_a, f0_frames_b, f0_b, out, path_len, path) : dtw_null("mtts_dtw_mcd_batch");
+}
+
+// ---- forced alignment: flat-start monophone EM, Viterbi to durations (align.h; this project's own stage) -------------------------------------
+int mtts_align_create(int n_feat, int n_classes, int max_frames, int max_states, int64_t max_cells, int max_utts, int device, mtts_align** out) {
+    if (!out) { g_create_error = "mtts_align_create: NULL out"; return -1; }
+    if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed (no MI355X visible?)"; return -1; }
+    mtts_align* h = new mtts_align();
+    AlignLimits l;
+    l.n_feat = n_feat; l.n_classes = n_classes; l.max_frames = max_frames; l.max_states = max_states; l.max_cells = (long long)max_cells; l.max_utts = max_utts;
+    if (h->a.init(l) != 0) { g_create_error = h->a.last_error; delete h; return -1; }
+    *out = h;
+    return 0;
+}
+void mtts_align_destroy(mtts_align* h) {
+    if (!h) return;
+    hipDeviceSynchronize();
+    delete h;
+}
+const char* mtts_align_last_error(mtts_align* h) { return h ? h->a.last_error.c_str() : g_create_error.c_str(); }
+static int align_null(const char* entry) { g_create_error = std::string(entry) + ": NULL handle"; return -1; }
+int mtts_align_set_stream(mtts_align* h, void* s) { if (!h) return align_null("mtts_align_set_stream"); h->a.stream = (hipStream_t)s; return 0; }
+int mtts_align_set_model(mtts_align* h, const double* mean, const double* var, const double* global_var) {
+    return h ? h->a.set_model(mean, var, global_var) : align_null("mtts_align_set_model");
+}
+int mtts_align_get_model(mtts_align* h, double* mean, double* var, double* global_var) { return h ? h->a.get_model(mean, var, global_var) : align_null("mtts_align_get_model"); }
+int mtts_align_set_floor(mtts_align* h, double var_floor, double min_occ) { return h ? h->a.set_floor(var_floor, min_occ) : align_null("mtts_align_set_floor"); }
+int mtts_align_flat_start(mtts_align* h, int n_utts, const int* n_frames, const float* x) { return h ? h->a.flat_start(n_utts, n_frames, x) : align_null("mtts_align_flat_start"); }
+int mtts_align_em_begin(mtts_align* h) { return h ? h->a.em_begin() : align_null("mtts_align_em_begin"); }
+int mtts_align_em_accumulate(mtts_align* h, int n_utts, const int* n_frames, const int* n_states, const int* classes, const unsigned char* optional, const float* x,
+                             double* ll_out) {
+    return h ? h->a.em_accumulate(n_utts, n_frames, n_states, classes, optional, x, ll_out) : align_null("mtts_align_em_accumulate");
+}
+int mtts_align_em_finish(mtts_align* h, double* total_ll_out) { return h ? h->a.em_finish(total_ll_out) : align_null("mtts_align_em_finish"); }
+int mtts_align_posteriors(mtts_align* h, int n_utts, const int* n_frames, const int* n_states, const int* classes, const unsigned char* optional, const float* x,
+                          double* ll_out, double* gamma_out) {
+    return h ? h->a.posteriors(n_utts, n_frames, n_states, classes, optional, x, ll_out, gamma_out) : align_null("mtts_align_posteriors");
+}
+int mtts_align_align(mtts_align* h, int n_utts, const int* n_frames, const int* n_states, const int* classes, const unsigned char* optional, const float* x,
+                     int* durations_out, double* score_out) {
+    return h ? h->a.align(n_utts, n_frames, n_states, classes, optional, x, durations_out, score_out) : align_null("mtts_align_align");
 }
 
 // ---- d-vector speaker encoder (dvector.h; reference lightning/model/speaker_encoder.py:11-31,54-60,71-76) ----------------
