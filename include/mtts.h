@@ -421,6 +421,61 @@ int mtts_rowdot_jvp(int rows, int C, const float* x, const float* tx, const floa
                     float* tout, void* ws, void* hip_stream);
 int mtts_rowdot_jvp_bwd(int rows, int C, const float* dout, const float* tgout, const float* w, const float* tw, float* dx, float* tdx, void* ws,
                         void* hip_stream);
+/* Multi-task entries of the loss, optimizer and variance-adaptor row kernels (csrc/rowops.h), each through the launcher the engine uses.
+ * `tasks` in 1 .. 8; rows / B / Mr / Mp / nF / nP are HOST int arrays [tasks] (per-task counts, >= 0, the largest >= 1); `ts` is a HOST
+ * int64 array of task strides in elements (>= 0), one per array in the order given below ("row": the per-row masks and index lists of the
+ * entry); task t of an array starts at t * stride.  `ws` = mtts_kernel_ws_bytes(largest count, 0) bytes.  Rows at or past a task's count are
+ * not touched.  C % 4 == 0, 4 <= C <= 1024; -1 (nothing launched) on a bad argument.
+ *   embed_pos            out = valid ? emb[tok] + pos[row_t] : 0 (pos shared)                                    ts: emb, row, out
+ *   speaker_vec          spk[b] = table[ids[b]], or (average) the mean of table[ids[0 .. n)], n = ids[n_ids_max]    ts: table, ids, spk
+ *   speaker_table_grad   its transpose, dtable [n_speaker][C] fully written                                      ts: dspk, ids, dtable
+ *   add_rowvec           out = inrect ? x + vec[row_b] : 0                                                       ts: x, vec, row, out
+ *   bucket_embed_add     out = inrect ? x + table[bucketize(val * control, bins[nb])] : 0; idx_out = bucket | -1 ts: x, val, table, row, out
+ *   rowdot / rowdot_bwd  out = valid ? dot(x, w) + b : 0 (w, b share "par") / dx = dout * w                  ts: x, par, row, out / dout, par, dx
+ *   segsum               out[b] (+)= sum of X rows [start[b], start[b] + len[b])                                 ts: X, seg, out
+ *   duration_round       d = max(round(exp(logd) - 1) * d_control, 0)  (modules.py:132-136)                      ts: pred
+ *   fill_padded          X rows with valid == 0 := inrect ? bias : 0, in place                                   ts: X, bias, row
+ *   gather               out = rowmap >= 0 ? src[rowmap] : 0                                                     ts: src, row, out
+ *   length_regulate_rect out = x[f_src[r2f]] where both indices are >= 0, else 0                                 ts: x, f, row, out
+ *   loss / loss_grad     loss.py:19-92.  ptr[15] (HOST array of device pointers): mel, mel_post, mel_tgt [Mr][n_mel], rvalid [Mr] (bytes), pp, ep,
+ *                        logd, p_tgt, e_tgt [Mp], dur [Mp] (ints), pvalid [Mp] (bytes), pp_r, ep_r, p_tgt_r, e_tgt_r [Mr] (NULL unless that level is
+ *                        frame); nF / nP = the valid rows among Mr / Mp (the divisors).  losses [tasks][6] = total, mel, postnet mel, pitch, energy,
+ *                        duration; the gradients are scale * d(total)/d(prediction).                ts: mel, rrow, prow, pred, pred_r
+ * The flat optimizer kernels take n4 = float4 per task array and the grid cap (n_partials in 1 .. 4096 / max_blocks >= 1):
+ *   sumsq_norm  out_norm[0] = sqrt(sum g^2 (+ extra[0])), partial [n_partials] caller scratch;  adam_clip  clip_grad_norm_(max_norm; <= 0: none) on the
+ *   device norm + Adam step `step` on w, m, v in place;  sgd_update  w[t] -= lr g[t];  sum_tasks  out (+)= scale * sum_t g[t];  broadcast  dst[t] = src. */
+int mtts_rows_embed_pos(int tasks, const int* rows, int C, const float* emb, const float* pos, const int* tok, const int* row_t, const unsigned char* valid,
+                        float* out, const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_speaker_vec(int tasks, const int* B, int C, const float* table, const int* ids, int n_ids_max, int average, float* spk, const int64_t* ts,
+                          void* ws, void* hip_stream);
+int mtts_rows_speaker_table_grad(int tasks, const int* B, int C, int n_speaker, const float* dspk, const int* ids, int n_ids_max, int average, float* dtable,
+                                 const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_add_rowvec(int tasks, const int* rows, int C, const float* x, const float* vec, const int* row_b, const unsigned char* inrect, float* out,
+                         const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_bucket_embed_add(int tasks, const int* rows, int C, const float* x, const float* val, float control, const float* bins, int nb,
+                               const float* table, const unsigned char* inrect, int* idx_out, float* out, const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_rowdot(int tasks, const int* rows, int C, const float* x, const float* w, const float* b, const unsigned char* valid, float* out,
+                     const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_rowdot_bwd(int tasks, const int* rows, int C, const float* dout, const float* w, float* dx, const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_segsum(int tasks, const int* B, int C, const float* X, const int* start, const int* len, float* out, int accumulate, const int64_t* ts,
+                     void* ws, void* hip_stream);
+int mtts_rows_duration_round(int tasks, const int* rows, const float* logd, float d_control, float* d_rounded, const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_fill_padded(int tasks, const int* rows, int C, float* X, const float* bias, const unsigned char* inrect, const unsigned char* valid,
+                          const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_gather(int tasks, const int* rows, int C, const float* src, const int* rowmap, float* out, const int64_t* ts, void* ws, void* hip_stream);
+int mtts_rows_length_regulate_rect(int tasks, const int* rows, int C, const float* x, const int* f_src, const int* r2f, float* out, const int64_t* ts,
+                                   void* ws, void* hip_stream);
+int mtts_rows_loss(int tasks, const int* Mr, const int* Mp, const int* nF, const int* nP, int n_mel, int pitch_frame, int energy_frame,
+                   const void* const* ptr, const int64_t* ts, float* losses, void* ws, void* hip_stream);
+int mtts_rows_loss_grad(int tasks, const int* Mr, const int* Mp, const int* nF, const int* nP, int n_mel, int pitch_frame, int energy_frame,
+                        const void* const* ptr, const int64_t* ts, float scale, float* dmel, float* dpost, float* dpp, float* dep, float* dlogd, float* dpp_r,
+                        float* dep_r, void* ws, void* hip_stream);
+int mtts_sumsq_norm(const float* g, int64_t n4, int n_partials, const float* extra, float* partial, float* out_norm, void* hip_stream);
+int mtts_adam_clip(float* w, const float* g, float* m, float* v, int64_t n4, const float* norm, float max_norm, float lr, float b1, float b2, float eps,
+                   int step, float weight_decay, int max_blocks, void* hip_stream);
+int mtts_sgd_update(int tasks, float* w, int64_t w_ts, const float* g, int64_t g_ts, int64_t n4, float lr, int max_blocks, void* hip_stream);
+int mtts_sum_tasks(int tasks, const float* g, int64_t g_ts, float scale, float* out, int64_t n4, int accumulate, int max_blocks, void* hip_stream);
+int mtts_broadcast(int tasks, const float* src, float* dst, int64_t dst_ts, int64_t n4, int max_blocks, void* hip_stream);
 /* The d-vector speaker encoder's kernels (mtts_dvector_* below), one at a time: raw device pointers, no scratch, asynchronous on the
  * stream, -1 (nothing launched) on a null required pointer or a shape mtts_dvector_create refuses: H a multiple of 64 in 64 .. 1024, E a
  * multiple of 4 in 4 .. 256, N, T, B >= 1.  Gate order i, f, g, o.

@@ -142,6 +142,26 @@ EXPORTS = {
     "mtts_batchnorm_jvp_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13 + [C.c_int] + [C.c_void_p] * 6),
     "mtts_rowdot_jvp": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 9),
     "mtts_rowdot_jvp_bwd": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 8),
+    # multi-task row entries: (tasks, counts, [C,] ..., ts, ws, stream)
+    "mtts_rows_embed_pos": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9),
+    "mtts_rows_speaker_vec": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "mtts_rows_speaker_table_grad": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "mtts_rows_add_rowvec": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    "mtts_rows_bucket_embed_add": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int] + [C.c_void_p] * 7),
+    "mtts_rows_rowdot": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    "mtts_rows_rowdot_bwd": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "mtts_rows_segsum": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3),
+    "mtts_rows_duration_round": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
+    "mtts_rows_fill_padded": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7),
+    "mtts_rows_gather": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "mtts_rows_length_regulate_rect": (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7),
+    "mtts_rows_loss": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 5),
+    "mtts_rows_loss_grad": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_float] + [C.c_void_p] * 9),
+    "mtts_sumsq_norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
+    "mtts_adam_clip": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p] + [C.c_float] * 5 + [C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "mtts_sgd_update": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
+    "mtts_sum_tasks": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "mtts_broadcast": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "mtts_lstm_recurrent": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 8),
     "mtts_lstm_bptt": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 7),
     "mtts_dvec_head": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 6),

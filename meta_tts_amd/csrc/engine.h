@@ -2178,8 +2178,7 @@ public:
     int frames_from_predictions_impl(const Pass& ps) {
         Plan& p = *ps.pl;
         const int nt = p.tasks;
-        MTTS_LAUNCH(duration_round_kernel, dim3(4, 1, nt), dim3(256), stream, (const int*)p.meta, (const float*)durB.out.p, durB.out.ts,
-                    ps.d_control, (const unsigned char*)p.sp[SP_P].valid.m, p.sp[SP_P].ts, d_rounded.p);
+        launch_duration_round(p.meta, nt, durB.out, ps.d_control, p.sp[SP_P].valid.m, p.sp[SP_P].ts, d_rounded.p, stream);
         const long long bs = (long long)cap_B * cap_S;
         MTTS_LAUNCH(plan_gather_durations_kernel, dim3(2, 1, nt), dim3(256), stream, (const int*)p.meta, (const float*)d_rounded.p, d_rounded.ts,
                     p.dur_readback, cap_B, cap_S);
@@ -2236,9 +2235,8 @@ public:
         if (!p.has_targets) { set_error("loss needs a teacher-forced batch (targets)"); return -1; }
         if (durB.out.ts != p.sp[SP_P].ts + 2 * G || pitB.out.ts != durB.out.ts) { set_error("internal: prediction stride"); return -1; }
         LossArgs a = loss_args(p);
-        MTTS_LAUNCH(loss_partial_kernel, dim3(kLossBlocks, 1, p.tasks), dim3(256), stream, (const int*)p.meta, a, loss_partial);
-        MTTS_LAUNCH(loss_final_kernel, dim3(p.tasks), dim3(64), stream, (const int*)p.meta, (const float*)loss_partial,
-                    (int)kLossBlocks, cfg.n_mel, losses_out, cfg.pitch_frame, cfg.energy_frame);
+        launch_loss_partial(p.meta, p.tasks, a, loss_partial, stream);
+        launch_loss_final(p.meta, p.tasks, loss_partial, cfg.n_mel, losses_out, cfg.pitch_frame, cfg.energy_frame, stream);
         return 0;
     }
 
@@ -2560,10 +2558,9 @@ public:
         if (ar_issued) ar_join();  // (an overlapped exchange nobody joined with mtts_allreduce_outer: the clip must still see the reduced buffer)
         shadows_current = false;   // theta is about to move
         launch_sumsq_partial(g, n_total / 4, norm_partial, nb, stream);
-        MTTS_LAUNCH(sumsq_final_kernel, dim3(1), dim3(64), stream, (const float*)norm_partial, nb, norm_out, extra_sumsq);
+        launch_sumsq_final(norm_partial, nb, norm_out, extra_sumsq, stream);
         ++adam_step_count;
-        const float bc1 = 1.f - (float)std::pow((double)b1, (double)adam_step_count);
-        const float bc2 = 1.f - (float)std::pow((double)b2, (double)adam_step_count);
+        const float bc1 = adam_bias_correction(b1, adam_step_count), bc2 = adam_bias_correction(b2, adam_step_count);
         launch_adam_clip(theta, g, adam_m, adam_v, n_total / 4, norm_out, max_norm, lr, b1, b2, eps, bc1, bc2, weight_decay, stream);
         if (norm_out_host) {
             DEV_CHECK(hipStreamSynchronize(stream));

@@ -461,3 +461,228 @@ int mtts_ge2e_loss(int n_spk, int n_utt, int E, const float* emb, float w, float
                      (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ---- Multi-task entries of the loss, optimizer and variance-adaptor row kernels (rowops.h), each through the kernel's one launcher.  What the
+// one-task entries above cannot show is pinned here: blockIdx.z * stride addressing and the per-task row count of a ragged launch.  `tasks` in
+// 1 .. 8; rows[t] (HOST ints, >= 0, the largest >= 1) is task t's row count; ts[] (HOST int64, elements, >= 0) holds one task stride per array
+// in the order each entry documents; per-row arrays (masks, index lists) of one entry share the "row" stride.  `ws` = mtts_kernel_ws_bytes(largest
+// row count, 0) bytes.  Nothing is checked against the callers' allocation sizes: task t of an array spans [t * stride, t * stride + its extent).
+namespace {
+constexpr int kApiTasks = 8;   // the 256-byte meta block of KernelWs holds 8 x META_STRIDE ints
+inline int max_of(int tasks, const int* n) { int m = 0; for (int t = 0; t < tasks; ++t) m = std::max(m, n[t]); return m; }
+inline bool bad_tasks(int tasks, const int* n) {
+    if (tasks < 1 || tasks > kApiTasks || !n) return true;
+    for (int t = 0; t < tasks; ++t) if (n[t] < 0) return true;
+    return max_of(tasks, n) < 1;
+}
+inline bool bad_strides(const int64_t* ts, int n) {
+    if (!ts) return true;
+    for (int i = 0; i < n; ++i) if (ts[i] < 0) return true;
+    return false;
+}
+// per-task meta table from the arguments: B, Mp, Mf, Mr, nP, nF independent per task (Smax = Mp, Tcap = Mr: not read by these kernels)
+inline int put_meta_tasks(const KernelWs& k, int tasks, const int* B, const int* Mp, const int* Mf, const int* Mr, const int* nP, const int* nF) {
+    int m[kApiTasks * META_STRIDE] = {0};
+    for (int t = 0; t < tasks; ++t) {
+        int* q = m + t * META_STRIDE;
+        q[META_B] = B[t]; q[META_SMAX] = Mp[t]; q[META_TCAP] = Mr[t]; q[META_MP] = Mp[t]; q[META_MF] = Mf[t]; q[META_MR] = Mr[t]; q[META_NP] = nP[t]; q[META_NF] = nF[t];
+    }
+    return hipMemcpy(k.meta, m, sizeof(m), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+// every count field of task t = rows[t]
+inline int put_meta_rows(const KernelWs& k, int tasks, const int* rows) { return put_meta_tasks(k, tasks, rows, rows, rows, rows, rows, rows); }
+inline RowLaunch n_tasks(const KernelWs& k, int tasks, const int* rows, int mfield, const unsigned char* mask, int64_t row_ts, void* stream) {
+    return RowLaunch{k.meta, mfield, max_of(tasks, rows), tasks, mask, (long long)row_ts, (hipStream_t)stream};
+}
+inline TS TT(const float* p, int64_t ts) { return TS{const_cast<float*>(p), (long long)ts}; }
+inline bool bad_rows_tasks(int tasks, const int* rows, int C) { return bad_tasks(tasks, rows) || C < 4 || (C & 3) || C > 1024; }
+inline int api_rc() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+}  // namespace
+
+// out[row] = valid ? emb[tok[row]] + pos[row_t[row]] : 0 (pos shared by the tasks).  ts: emb, row, out
+int mtts_rows_embed_pos(int tasks, const int* rows, int C, const float* emb, const float* pos, const int* tok, const int* row_t, const unsigned char* valid,
+                        float* out, const int64_t* ts, void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, rows, C) || bad_strides(ts, 3) || !emb || !pos || !tok || !row_t || !valid || !out || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_embed_pos(n_tasks(k, tasks, rows, META_MP, valid, ts[1], stream), TT(out, ts[2]), TT(emb, ts[0]), pos, tok, row_t, C);
+    return api_rc();
+}
+// spk[b] = table[ids[b]] (average 0) or the mean of table[ids[0 .. n)] with n = ids[n_ids_max] (average 1), for b < B[t].  ts: table, ids, spk
+int mtts_rows_speaker_vec(int tasks, const int* B, int C, const float* table, const int* ids, int n_ids_max, int average, float* spk, const int64_t* ts,
+                          void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, B, C) || bad_strides(ts, 3) || n_ids_max < 1 || !table || !ids || !spk || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, B), 0);
+    if (put_meta_rows(k, tasks, B)) return -1;
+    launch_speaker_vec(n_tasks(k, tasks, B, META_B, nullptr, 0, stream), max_of(tasks, B), TT(table, ts[0]), ids, ts[1], n_ids_max, average, TT(spk, ts[2]), C);
+    return api_rc();
+}
+// its transpose: dtable [n_speaker][C] fully written per task.  ts: dspk, ids, dtable
+int mtts_rows_speaker_table_grad(int tasks, const int* B, int C, int n_speaker, const float* dspk, const int* ids, int n_ids_max, int average, float* dtable,
+                                 const int64_t* ts, void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, B, C) || bad_strides(ts, 3) || n_ids_max < 1 || n_speaker < 1 || !dspk || !ids || !dtable || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, B), 0);
+    if (put_meta_rows(k, tasks, B)) return -1;
+    launch_speaker_table_grad(n_tasks(k, tasks, B, META_B, nullptr, 0, stream), n_speaker, TT(dspk, ts[0]), ids, ts[1], n_ids_max, average, TT(dtable, ts[2]), C);
+    return api_rc();
+}
+// out[row] = inrect ? x[row] + vec[row_b[row]] : 0.  ts: x, vec, row, out
+int mtts_rows_add_rowvec(int tasks, const int* rows, int C, const float* x, const float* vec, const int* row_b, const unsigned char* inrect, float* out,
+                         const int64_t* ts, void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, rows, C) || bad_strides(ts, 4) || !x || !vec || !row_b || !inrect || !out || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_add_rowvec(n_tasks(k, tasks, rows, META_MP, inrect, ts[2], stream), TT(x, ts[0]), TT(vec, ts[1]), row_b, TT(out, ts[3]), C);
+    return api_rc();
+}
+// out[row] = inrect ? x[row] + table[bucketize(val[row] * control, bins[nb])] : 0, idx_out[row] = the bucket or -1 (bins shared by the tasks).
+// ts: x, val, table, row, out
+int mtts_rows_bucket_embed_add(int tasks, const int* rows, int C, const float* x, const float* val, float control, const float* bins, int nb,
+                               const float* table, const unsigned char* inrect, int* idx_out, float* out, const int64_t* ts, void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, rows, C) || bad_strides(ts, 5) || nb < 1 || !x || !val || !bins || !table || !inrect || !idx_out || !out || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_bucket_embed_add(n_tasks(k, tasks, rows, META_MP, inrect, ts[3], stream), TT(x, ts[0]), TT(val, ts[1]), control, bins, nb, TT(table, ts[2]), idx_out,
+                            TT(out, ts[4]), C);
+    return api_rc();
+}
+// out[row] = valid ? dot(x[row], w) + b : 0; w [C] and b [1] share the "par" stride.  ts: x, par, row, out
+int mtts_rows_rowdot(int tasks, const int* rows, int C, const float* x, const float* w, const float* b, const unsigned char* valid, float* out,
+                     const int64_t* ts, void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, rows, C) || bad_strides(ts, 4) || !x || !w || !b || !valid || !out || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_rowdot(n_tasks(k, tasks, rows, META_MP, valid, ts[2], stream), TT(x, ts[0]), TT(w, ts[1]), TT(b, ts[1]), TT(out, ts[3]), C);
+    return api_rc();
+}
+// dx[row] = dout[row] * w.  ts: dout, par, dx
+int mtts_rows_rowdot_bwd(int tasks, const int* rows, int C, const float* dout, const float* w, float* dx, const int64_t* ts, void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, rows, C) || bad_strides(ts, 3) || !dout || !w || !dx || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_rowdot_bwd(n_tasks(k, tasks, rows, META_MP, nullptr, 0, stream), TT(dout, ts[0]), TT(w, ts[1]), TT(dx, ts[2]), C);
+    return api_rc();
+}
+// out[b] (+)= sum of the rows [start[b], start[b] + len[b]) of X, for b < B[t].  ts: X, seg (start / len), out
+int mtts_rows_segsum(int tasks, const int* B, int C, const float* X, const int* start, const int* len, float* out, int accumulate, const int64_t* ts,
+                     void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, B, C) || bad_strides(ts, 3) || !X || !start || !len || !out || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, B), 0);
+    if (put_meta_rows(k, tasks, B)) return -1;
+    launch_segsum_rows(n_tasks(k, tasks, B, META_B, nullptr, 0, stream), max_of(tasks, B), TT(X, ts[0]), start, len, ts[1], TT(out, ts[2]), C, accumulate);
+    return api_rc();
+}
+// d_rounded[row] = max(round(exp(logd[row]) - 1) * d_control, 0); logd and d_rounded share the stride.  ts: pred
+int mtts_rows_duration_round(int tasks, const int* rows, const float* logd, float d_control, float* d_rounded, const int64_t* ts, void* ws, void* stream) {
+    if (bad_tasks(tasks, rows) || bad_strides(ts, 1) || !logd || !d_rounded || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_duration_round(k.meta, tasks, TT(logd, ts[0]), d_control, nullptr, 0, d_rounded, (hipStream_t)stream);
+    return api_rc();
+}
+// in place on X: rows with valid == 0 become bias (inrect != 0) or 0; valid rows are left alone.  ts: X, bias, row
+int mtts_rows_fill_padded(int tasks, const int* rows, int C, float* X, const float* bias, const unsigned char* inrect, const unsigned char* valid,
+                          const int64_t* ts, void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, rows, C) || bad_strides(ts, 3) || !X || !bias || !inrect || !valid || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_fill_padded_rows(n_tasks(k, tasks, rows, META_MR, inrect, ts[2], stream), TT(X, ts[0]), TT(bias, ts[1]), valid, C);
+    return api_rc();
+}
+// out[row] = rowmap[row] >= 0 ? src[rowmap[row]] : 0.  ts: src, row (rowmap), out
+int mtts_rows_gather(int tasks, const int* rows, int C, const float* src, const int* rowmap, float* out, const int64_t* ts, void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, rows, C) || bad_strides(ts, 3) || !src || !rowmap || !out || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_gather_rows(n_tasks(k, tasks, rows, META_MP, nullptr, ts[1], stream), TT(src, ts[0]), rowmap, TT(out, ts[2]), C);
+    return api_rc();
+}
+// out[row] = x[f_src[r2f[row]]] where r2f[row] >= 0 and f_src[..] >= 0, else 0.  ts: x, f (f_src), row (r2f), out
+int mtts_rows_length_regulate_rect(int tasks, const int* rows, int C, const float* x, const int* f_src, const int* r2f, float* out, const int64_t* ts,
+                                   void* ws, void* stream) {
+    if (bad_rows_tasks(tasks, rows, C) || bad_strides(ts, 4) || !x || !f_src || !r2f || !out || !ws) return -1;
+    const KernelWs k = carve(ws, max_of(tasks, rows), 0);
+    if (put_meta_rows(k, tasks, rows)) return -1;
+    launch_length_regulate_rect(n_tasks(k, tasks, rows, META_MR, nullptr, ts[2], stream), TT(x, ts[0]), f_src, ts[1], r2f, TT(out, ts[3]), C);
+    return api_rc();
+}
+
+// The 5-term loss (loss.py:19-92) and its gradient.  Per task: Mr mel rows of which nF have rvalid != 0, Mp phoneme rows of which nP have
+// pvalid != 0 (the caller states nF / nP: they are the divisors).  ptr[15] (HOST array of device pointers): mel, mel_post, mel_tgt [Mr][n_mel];
+// rvalid [Mr] (bytes); pp, ep, logd (predictions [Mp]); p_tgt, e_tgt [Mp]; dur [Mp] (ints); pvalid [Mp] (bytes); pp_r, ep_r (frame-level
+// predictions [Mr]), p_tgt_r, e_tgt_r [Mr] — the last four may be NULL unless their level is frame.  ts: mel, rrow (rvalid, *_tgt_r), prow
+// (pvalid, dur, p_tgt, e_tgt), pred (pp, ep, logd and their gradients), pred_r (pp_r, ep_r and their gradients).
+namespace {
+inline bool loss_setup(int tasks, const int* Mr, const int* Mp, const int* nF, const int* nP, int n_mel, int pitch_frame, int energy_frame,
+                       const void* const* ptr, const int64_t* ts, void* ws, KernelWs& k, LossArgs& a) {
+    if (bad_tasks(tasks, Mr) || bad_tasks(tasks, Mp) || !nF || !nP || n_mel < 4 || (n_mel & 3) || n_mel > 1024 || !ptr || bad_strides(ts, 5) || !ws) return false;
+    for (int t = 0; t < tasks; ++t) if (nF[t] < 1 || nF[t] > Mr[t] || nP[t] < 1 || nP[t] > Mp[t]) return false;
+    for (int i = 0; i < 11; ++i) if (!ptr[i]) return false;
+    if (pitch_frame && (!ptr[11] || !ptr[13])) return false;
+    if (energy_frame && (!ptr[12] || !ptr[14])) return false;
+    if ((long long)tasks * kLossBlocks * 5 > 3 * 1024) return false;   // the partial sums live in the scratch block's column partials
+    k = carve(ws, std::max(max_of(tasks, Mr), max_of(tasks, Mp)), 0);
+    if (put_meta_tasks(k, tasks, Mp, Mp, Mr, Mr, nP, nF)) return false;
+    a.mel = (const float*)ptr[0]; a.mel_post = (const float*)ptr[1]; a.mel_tgt = (const float*)ptr[2]; a.rvalid = (const unsigned char*)ptr[3];
+    a.pp = (const float*)ptr[4]; a.ep = (const float*)ptr[5]; a.logd = (const float*)ptr[6]; a.p_tgt = (const float*)ptr[7]; a.e_tgt = (const float*)ptr[8];
+    a.dur = (const int*)ptr[9]; a.pvalid = (const unsigned char*)ptr[10];
+    a.pp_r = (const float*)ptr[11]; a.ep_r = (const float*)ptr[12]; a.p_tgt_r = (const float*)ptr[13]; a.e_tgt_r = (const float*)ptr[14];
+    a.mel_ts = ts[0]; a.rrow_ts = ts[1]; a.prow_ts = ts[2]; a.pred_ts = ts[3]; a.pred_r_ts = ts[4];
+    a.n_mel = n_mel; a.pitch_frame = pitch_frame ? 1 : 0; a.energy_frame = energy_frame ? 1 : 0;
+    return true;
+}
+}  // namespace
+// losses [tasks][6] = total, mel, postnet mel, pitch, energy, duration (partial + final)
+int mtts_rows_loss(int tasks, const int* Mr, const int* Mp, const int* nF, const int* nP, int n_mel, int pitch_frame, int energy_frame,
+                   const void* const* ptr, const int64_t* ts, float* losses, void* ws, void* stream) {
+    KernelWs k; LossArgs a;
+    if (!losses || !loss_setup(tasks, Mr, Mp, nF, nP, n_mel, pitch_frame, energy_frame, ptr, ts, ws, k, a)) return -1;
+    launch_loss_partial(k.meta, tasks, a, k.col_partial, (hipStream_t)stream);
+    launch_loss_final(k.meta, tasks, k.col_partial, n_mel, losses, a.pitch_frame, a.energy_frame, (hipStream_t)stream);
+    return api_rc();
+}
+// scale * d(total)/d(prediction): dmel, dpost (mel stride), dpp, dep, dlogd (pred stride), dpp_r, dep_r (pred_r stride; NULL unless frame-level)
+int mtts_rows_loss_grad(int tasks, const int* Mr, const int* Mp, const int* nF, const int* nP, int n_mel, int pitch_frame, int energy_frame,
+                        const void* const* ptr, const int64_t* ts, float scale, float* dmel, float* dpost, float* dpp, float* dep, float* dlogd, float* dpp_r,
+                        float* dep_r, void* ws, void* stream) {
+    KernelWs k; LossArgs a;
+    if (!dmel || !dpost || !dpp || !dep || !dlogd || (pitch_frame && !dpp_r) || (energy_frame && !dep_r)) return -1;
+    if (!loss_setup(tasks, Mr, Mp, nF, nP, n_mel, pitch_frame, energy_frame, ptr, ts, ws, k, a)) return -1;
+    launch_loss_grad(k.meta, tasks, a, scale, dmel, dpost, dpp, dep, dlogd, dpp_r, dep_r, (hipStream_t)stream);
+    return api_rc();
+}
+
+// The flat-array kernels of the optimizer: n4 = number of float4 of one task's array (arrays 16-byte aligned), grid capped by the argument.
+// sumsq_norm: out_norm[0] = sqrt(sum g^2 (+ extra[0])) through n_partials (1 .. 4096) workgroup partials [n_partials] (partial + final).
+int mtts_sumsq_norm(const float* g, int64_t n4, int n_partials, const float* extra, float* partial, float* out_norm, void* stream) {
+    if (!g || n4 < 1 || n_partials < 1 || n_partials > 4096 || !partial || !out_norm) return -1;
+    launch_sumsq_partial(g, n4, partial, n_partials, (hipStream_t)stream);
+    launch_sumsq_final(partial, n_partials, out_norm, extra, (hipStream_t)stream);
+    return api_rc();
+}
+// clip_grad_norm_(max_norm) (norm[0] on the device; max_norm <= 0: no clip) + torch.optim.Adam step number `step` (>= 1) on w, m, v in place
+int mtts_adam_clip(float* w, const float* g, float* m, float* v, int64_t n4, const float* norm, float max_norm, float lr, float b1, float b2, float eps,
+                   int step, float weight_decay, int max_blocks, void* stream) {
+    if (!w || !g || !m || !v || !norm || n4 < 1 || step < 1 || max_blocks < 1) return -1;
+    launch_adam_clip(w, g, m, v, n4, norm, max_norm, lr, b1, b2, eps, adam_bias_correction(b1, step), adam_bias_correction(b2, step), weight_decay,
+                     (hipStream_t)stream, (unsigned)max_blocks);
+    return api_rc();
+}
+// w[t] -= lr * g[t] for every task
+int mtts_sgd_update(int tasks, float* w, int64_t w_ts, const float* g, int64_t g_ts, int64_t n4, float lr, int max_blocks, void* stream) {
+    if (tasks < 1 || tasks > kApiTasks || !w || !g || w_ts < 0 || g_ts < 0 || n4 < 1 || max_blocks < 1) return -1;
+    launch_sgd_update(TT(w, w_ts), TT(g, g_ts), n4, lr, tasks, (hipStream_t)stream, (unsigned)max_blocks);
+    return api_rc();
+}
+// out (+)= scale * sum_t g[t], tasks added in ascending order
+int mtts_sum_tasks(int tasks, const float* g, int64_t g_ts, float scale, float* out, int64_t n4, int accumulate, int max_blocks, void* stream) {
+    if (tasks < 1 || tasks > kApiTasks || !g || !out || g_ts < 0 || n4 < 1 || max_blocks < 1) return -1;
+    launch_sum_tasks(TT(g, g_ts), tasks, scale, out, n4, accumulate, (hipStream_t)stream, (unsigned)max_blocks);
+    return api_rc();
+}
+// dst[t] = src for every task
+int mtts_broadcast(int tasks, const float* src, float* dst, int64_t dst_ts, int64_t n4, int max_blocks, void* stream) {
+    if (tasks < 1 || tasks > kApiTasks || !src || !dst || dst_ts < 0 || n4 < 1 || max_blocks < 1) return -1;
+    launch_broadcast(src, TT(dst, dst_ts), n4, tasks, (hipStream_t)stream, (unsigned)max_blocks);
+    return api_rc();
+}

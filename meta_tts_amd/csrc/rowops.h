@@ -12,6 +12,7 @@
 // are deterministic (no float atomics anywhere).
 #pragma once
 #include "compat.h"
+#include <cmath>
 
 namespace mtts {
 
@@ -1217,8 +1218,8 @@ __global__ void broadcast_kernel(const float* src, float* dst, long long n4, lon
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x)
         st4(d + i * 4, ld4(src + i * 4));
 }
-inline void launch_broadcast(const float* src, TS dst, long long n4, int tasks, hipStream_t st) {
-    MTTS_LAUNCH(broadcast_kernel, dim3(flat_blocks(n4), 1, tasks), dim3(256), st, src, dst.p, n4, dst.ts);
+inline void launch_broadcast(const float* src, TS dst, long long n4, int tasks, hipStream_t st, unsigned max_blocks = 4096) {
+    MTTS_LAUNCH(broadcast_kernel, dim3(flat_blocks(n4, max_blocks), 1, tasks), dim3(256), st, src, dst.p, n4, dst.ts);
 }
 
 // MAML inner update  theta' = theta - lr * g   (learn2learn maml_update via systems/utils.py:39-47)
@@ -1232,8 +1233,8 @@ __global__ void sgd_update_kernel(float* w, const float* g, long long n4, float 
         st4(pw + i * 4, x);
     }
 }
-inline void launch_sgd_update(TS w, TS g, long long n4, float lr, int tasks, hipStream_t st) {
-    MTTS_LAUNCH(sgd_update_kernel, dim3(flat_blocks(n4), 1, tasks), dim3(256), st, w.p, (const float*)g.p, n4, lr, w.ts, g.ts);
+inline void launch_sgd_update(TS w, TS g, long long n4, float lr, int tasks, hipStream_t st, unsigned max_blocks = 4096) {
+    MTTS_LAUNCH(sgd_update_kernel, dim3(flat_blocks(n4, max_blocks), 1, tasks), dim3(256), st, w.p, (const float*)g.p, n4, lr, w.ts, g.ts);
 }
 
 // out[i] (+)= scale * sum_t g[t][i]   (fixed task order; accumulate: gradient accumulation over several batches, main.py:62)
@@ -1249,8 +1250,8 @@ __global__ void sum_tasks_kernel(const float* g, long long g_ts, int tasks, floa
         st4(out + i * 4, o);
     }
 }
-inline void launch_sum_tasks(TS g, int tasks, float scale, float* out, long long n4, int accumulate, hipStream_t st) {
-    MTTS_LAUNCH(sum_tasks_kernel, dim3(flat_blocks(n4)), dim3(256), st, (const float*)g.p, g.ts, tasks, scale, out, n4, accumulate);
+inline void launch_sum_tasks(TS g, int tasks, float scale, float* out, long long n4, int accumulate, hipStream_t st, unsigned max_blocks = 4096) {
+    MTTS_LAUNCH(sum_tasks_kernel, dim3(flat_blocks(n4, max_blocks)), dim3(256), st, (const float*)g.p, g.ts, tasks, scale, out, n4, accumulate);
 }
 
 // The exchange step's tail (engine.h: sync_pack / sync_unpack): what DDP moves between ranks besides the gradient — the 6 loss scalars
@@ -1305,6 +1306,11 @@ __global__ void sumsq_final_kernel(const float* partial, int n, float* out_norm,
         out_norm[0] = (float)sqrt(s);
     }
 }
+inline void launch_sumsq_final(const float* partial, int n_partials, float* out_norm, const float* extra, hipStream_t st) {
+    MTTS_LAUNCH(sumsq_final_kernel, dim3(1), dim3(64), st, partial, n_partials, out_norm, extra);
+}
+// Adam's bias correction 1 - beta^step, as the outer update computes it (the power in double, the difference in float)
+inline float adam_bias_correction(float beta, long long step) { return 1.f - (float)std::pow((double)beta, (double)step); }
 
 // fused clip_grad_norm_(max_norm) + Adam (optimizer.py:9-15, main.py:61); norm read on device
 __global__ void adam_clip_kernel(float* w, const float* g, float* m, float* v, long long n4, const float* norm,
@@ -1396,6 +1402,9 @@ __global__ void loss_partial_kernel(const int* meta, LossArgs a, float* partial)
         partial[((long long)z * gridDim.x + blockIdx.x) * 5 + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
     }
 }
+inline void launch_loss_partial(const int* meta, int tasks, const LossArgs& a, float* partial, hipStream_t st) {   // partial: [tasks][kLossBlocks][5]
+    MTTS_LAUNCH(loss_partial_kernel, dim3(kLossBlocks, 1, tasks), dim3(256), st, meta, a, partial);
+}
 
 // losses[task][6] = (total, mel, postnet mel, pitch, energy, duration)
 __global__ void loss_final_kernel(const int* meta, const float* partial, int nblocks, int n_mel, float* losses, int pitch_frame = 0,
@@ -1410,6 +1419,9 @@ __global__ void loss_final_kernel(const int* meta, const float* partial, int nbl
                 e = (float)(s[3] / (energy_frame ? nFr : nP)), d = (float)(s[4] / nP);
     float* o = losses + (long long)z * 6;
     o[0] = mel + post + d + p + e; o[1] = mel; o[2] = post; o[3] = p; o[4] = e; o[5] = d;
+}
+inline void launch_loss_final(const int* meta, int tasks, const float* partial, int n_mel, float* losses, int pitch_frame, int energy_frame, hipStream_t st) {
+    MTTS_LAUNCH(loss_final_kernel, dim3(tasks), dim3(64), st, meta, partial, (int)kLossBlocks, n_mel, losses, pitch_frame, energy_frame);
 }
 
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
@@ -1476,6 +1488,10 @@ __global__ void duration_round_kernel(const int* meta, const float* logd, long l
         d_rounded[q] = (d > 0.f) ? d : 0.f;
         (void)pvalid; (void)prow_ts;
     }
+}
+inline void launch_duration_round(const int* meta, int tasks, TS logd, float d_control, const unsigned char* pvalid, long long prow_ts, float* d_rounded,
+                                  hipStream_t st) {   // d_rounded shares logd's task stride
+    MTTS_LAUNCH(duration_round_kernel, dim3(4, 1, tasks), dim3(256), st, meta, (const float*)logd.p, logd.ts, d_control, pvalid, prow_ts, d_rounded);
 }
 
 }  // namespace mtts
