@@ -253,7 +253,7 @@ __device__ __forceinline__ int xcd_group_remap(int lin, int total, int G) {
 // tile list is ordered B-panel-major ((n, split) outermost, m innermost) and dealt to the XCDs in contiguous eighths (slot 8 j + x runs
 // on XCD x): an XCD works through one or two (n, split) units, whose B panel (64 columns x its K range: 0.6-2.4 MB) stays in its L2
 // while the m-tiles' A rows stream past — the weight image crosses the fabric once.  Placement only: any order gives the same results.
-// Returns false for padding slots; bxs = (m * tiles_n + n) * S + split as gemm_*_body decodes it.
+// Returns false for padding slots; bxs = (m * tiles_n + n) * S + split as gemm_tile_frame decodes it.
 __host__ __device__ __forceinline__ int xcd_panel_slots(int tiles_m, int tiles_n, int S) { return 8 * ((tiles_m * tiles_n * S + 7) / 8); }
 __host__ __device__ __forceinline__ bool xcd_panel_locate(int lin, int tiles_m, int tiles_n, int S, int& bxs) {
     const int total = tiles_m * tiles_n * S, R = (total + 7) / 8;
@@ -927,17 +927,36 @@ __device__ __forceinline__ void gemm_finish(const GemmArgs& g, const GemmProb& p
     if constexpr (LNF) { if (g.ln.ctr) gemm_ln_tail<32 * TM * WGM, 64 * WGM * WGN>(g, pr, z, m0); }
 }
 
-// One workgroup's share of one problem: output tile `bxs` (times split) of group `z`.
+// K-loop policy of the register-staged fp32 family (gemm_f32_kloop).  A policy states the tile (FORM, BM, BN, BK, WGM, WGN), its LDS
+// floats, three traits, and run(): the K-chunks [c_lo, c_hi) of one tile of a resolved problem, added into acc.
+template <int FORM_, int BM_, int BN_, int BK_, bool PIPE, int WGM_ = 2, int WGN_ = 2, int ABL = 0, int KL = 0>
+struct KLoopF32 {
+    static constexpr int FORM = FORM_, BM = BM_, BN = BN_, BK = BK_, WGM = WGM_, WGN = WGN_;
+    static constexpr int kSmemFloats = GemmSmem<FORM, BM, BN, BK>::FLOATS;
+    static constexpr bool kRaisesPrio = true;                  // GemmArgs::wave_prio: the critical stream's launches beside side-stream work
+    static constexpr bool kBarrierBeforeSecondSource = true;   // the pipelined loops end on MFMAs: waves may still read the last LDS stage
+    static constexpr bool kHasSecondSource = true;
+    static __device__ __forceinline__ void run(const GemmArgs& g, const GemmProb& pr, int z, int m0, int n0, bool cs_tile, int c_lo, int c_hi,
+                                               float* smem, f32x16 (&acc)[(BM / WGM) / 32][(BN / WGN) / 32]) {
+        gemm_f32_kloop<FORM, BM, BN, BK, PIPE, WGM, WGN, ABL, KL>(g, pr, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
+    }
+};
+
+// The tile frame, shared by every GEMM family: one workgroup's share of one problem — output tile `bxs` (times split) of group `z`.
+// It owns which slot has which tile (the column-sum n-tile included), what a padded slot does, how a split's K-range is cut, when the
+// second source runs, the split-K rendezvous and the epilogue; the launcher plans ONE grid for all families on these rules.
+// KLoop: the family's K-loop policy (KLoopF32, gemm_glds.h: KLoopGlds, gemm_bf16.h: KLoopBf16).  LNF: the fused-LayerNorm epilogue.
 // DUAL: the kernel also runs the second source of dual-source problems (GemmArgs::A2) — a second, separately inlined K-loop into the
 // same accumulators.  (A runtime loop over the sources around ONE inlined K-loop costs every kernel ~10 VGPRs of spilled SGPR state
 // — the multi-problem BK = 32 kernel drops from 4 to 3 workgroups per CU — so only the kernels that may be handed such problems pay for it.)
-template <int FORM, int BM, int BN, int BK, bool PIPE, int WGM = 2, int WGN = 2, int ABL = 0, bool DUAL = false, int KL = 0, bool LNF = false>
-__device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, int z, int bxs, float* smem) {
+template <class KLoop, bool DUAL = false, bool LNF = false>
+__device__ __forceinline__ void gemm_tile_frame(const GemmArgs& g, int z, int bxs, float* smem) {
+    constexpr int BM = KLoop::BM, BN = KLoop::BN, BK = KLoop::BK, WGM = KLoop::WGM, WGN = KLoop::WGN;
     constexpr int NTH = 64 * WGM * WGN;
     constexpr int TM = (BM / WGM) / 32, TN = (BN / WGN) / 32;
-    if (g.wave_prio > 0) MTTS_SETPRIO_HIGH();
+    if constexpr (KLoop::kRaisesPrio) { if (g.wave_prio > 0) MTTS_SETPRIO_HIGH(); }
     const GemmProb pr = gemm_resolve(g, z);
-    const bool has_cs = gemm_has_colsum<FORM>(g);
+    const bool has_cs = gemm_has_colsum<KLoop::FORM>(g);
     const int tiles_nc = (pr.N + BN - 1) / BN, tiles_n = tiles_nc + (has_cs ? 1 : 0), tiles_m = (pr.M + BM - 1) / BM;
     const int S = g.splitk > 1 ? g.splitk : 1;
     const int tile_lin = bxs / S, split = bxs - tile_lin * S;
@@ -953,27 +972,36 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, int z, int bxs,
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     const int nch_all = (pr.K + BK - 1) / BK, cps = (nch_all + S - 1) / S;
     const int c_lo = split * cps, c_hi = (c_lo + cps < nch_all) ? c_lo + cps : nch_all;   // (all chunks when S == 1)
-    gemm_f32_kloop<FORM, BM, BN, BK, PIPE, WGM, WGN, ABL, KL>(g, pr, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
-    if (DUAL) {
+    KLoop::run(g, pr, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
+    if constexpr (DUAL && KLoop::kHasSecondSource) {
         if (g.A2 != nullptr && !cs_tile) {
-            __syncthreads();   // every wave is done with the first source's LDS tiles
+            if constexpr (KLoop::kBarrierBeforeSecondSource) __syncthreads();   // every wave is done with the first source's LDS tiles
             const GemmProb p2 = gemm_resolve2(g, z, pr);
-            gemm_f32_kloop<FORM, BM, BN, BK, PIPE, WGM, WGN, ABL, KL>(g, p2, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
+            KLoop::run(g, p2, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
         }
     }
     if (S > 1 && !splitk_combine<TM, TN, NTH>(g, z, tile_lin, split, S, acc)) return;
     gemm_finish<TM, TN, WGM, WGN, LNF>(g, pr, z, m0, n0, cs_tile, acc);
 }
 
+// Tile order of a single-problem launch: workgroup -> (group z, tile slot bxs); false: the slot is padding.
+template <int FORM, int BN>
+__device__ __forceinline__ bool gemm_single_locate(const GemmArgs& g, int& z, int& bxs) {
+    z = blockIdx.z;
+    bxs = blockIdx.x;
+    if (g.xs.on) return xcd_sched_locate(g.xs, bxs, z, bxs);   // 1-D grid, task-per-XCD order
+    if (g.swizzle == 2) return xcd_panel_locate(bxs, g.po_tiles_m, (g.N + BN - 1) / BN + (gemm_has_colsum<FORM>(g) ? 1 : 0), g.splitk > 1 ? g.splitk : 1, bxs);
+    if (g.swizzle) bxs = xcd_group_remap(bxs, (int)gridDim.x, xcd_group_size((g.N + BN - 1) / BN, g.splitk));
+    return true;
+}
+
 template <int FORM, int BM, int BN, int BK, bool PIPE, int WGM = 2, int WGN = 2, int ABL = 0, int KL = 0, bool LNF = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_kernel(GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) float smem[GemmSmem<FORM, BM, BN, BK>::FLOATS];
-    int z = blockIdx.z;
-    int bxs = blockIdx.x;
-    if (g.xs.on) { if (!xcd_sched_locate(g.xs, bxs, z, bxs)) return; }   // 1-D grid, task-per-XCD order
-    else if (g.swizzle == 2) { if (!xcd_panel_locate(bxs, g.po_tiles_m, (g.N + BN - 1) / BN + (gemm_has_colsum<FORM>(g) ? 1 : 0), g.splitk > 1 ? g.splitk : 1, bxs)) return; }
-    else if (g.swizzle) bxs = xcd_group_remap(bxs, (int)gridDim.x, xcd_group_size((g.N + BN - 1) / BN, g.splitk));
-    gemm_f32_body<FORM, BM, BN, BK, PIPE, WGM, WGN, ABL, false, KL, LNF>(g, z, bxs, smem);
+    using KLoop = KLoopF32<FORM, BM, BN, BK, PIPE, WGM, WGN, ABL, KL>;
+    __shared__ __attribute__((aligned(16))) float smem[KLoop::kSmemFloats];
+    int z, bxs;
+    if (!gemm_single_locate<FORM, BN>(g, z, bxs)) return;
+    gemm_tile_frame<KLoop, false, LNF>(g, z, bxs, smem);
 }
 
 // Several independent problems (any mix of forms, e.g. the dgrad and the wgrad of one layer) in ONE launch: workgroups
@@ -1014,31 +1042,39 @@ __device__ __forceinline__ bool gemm_multi_locate(const GemmMulti& mp, int& p, i
     bx = lin - z * tiles;
     return true;
 }
+
+// LDS floats of a multi-problem kernel: the largest need of the K-loop policies it may run
+template <class... KLoops>
+constexpr int gemm_smem_floats() { return std::max({KLoops::kSmemFloats...}); }
+
+// (the form dispatch stays written out in every multi-problem kernel: behind one shared function the compiler scheduled all of them
+// differently — profiles/gemm_frame_ab.md.  LNF reaches the NT form only: the fused LayerNorm follows a Linear.)
 template <int BM, int BN, int BK, int KL = 0, bool LNF = false>
 __global__ __launch_bounds__(256) void gemm_f32_multi_kernel(GemmMulti mp) {
-    constexpr int F0 = GemmSmem<GEMM_NT, BM, BN, BK>::FLOATS, F1 = GemmSmem<GEMM_NN, BM, BN, BK>::FLOATS, F2 = GemmSmem<GEMM_TN, BM, BN, BK>::FLOATS;
-    constexpr int FL = F0 > F1 ? (F0 > F2 ? F0 : F2) : (F1 > F2 ? F1 : F2);
-    __shared__ __attribute__((aligned(16))) float smem[FL];
+    using NT = KLoopF32<GEMM_NT, BM, BN, BK, true, 2, 2, 0, KL>;
+    using NN = KLoopF32<GEMM_NN, BM, BN, BK, true, 2, 2, 0, KL>;
+    using TN = KLoopF32<GEMM_TN, BM, BN, BK, true, 2, 2, 0, KL>;
+    __shared__ __attribute__((aligned(16))) float smem[gemm_smem_floats<NT, NN, TN>()];
     int p, z, bx;
     if (!gemm_multi_locate(mp, p, z, bx)) return;
     const int form = mp.form[p];
-    if (form == GEMM_NT) gemm_f32_body<GEMM_NT, BM, BN, BK, true, 2, 2, 0, false, KL, LNF>(mp.g[p], z, bx, smem);
-    else if (form == GEMM_NN) gemm_f32_body<GEMM_NN, BM, BN, BK, true, 2, 2, 0, false, KL>(mp.g[p], z, bx, smem);
-    else gemm_f32_body<GEMM_TN, BM, BN, BK, true, 2, 2, 0, false, KL>(mp.g[p], z, bx, smem);
+    if (form == GEMM_NT) gemm_tile_frame<NT, false, LNF>(mp.g[p], z, bx, smem);
+    else if (form == GEMM_NN) gemm_tile_frame<NN>(mp.g[p], z, bx, smem);
+    else gemm_tile_frame<TN>(mp.g[p], z, bx, smem);
 }
-
 // the same grid for launches that carry dual-source problems (GemmArgs::A2)
 template <int BM, int BN, int BK, int KL = 0>
 __global__ __launch_bounds__(256) void gemm_f32_multi_dual_kernel(GemmMulti mp) {
-    constexpr int F0 = GemmSmem<GEMM_NT, BM, BN, BK>::FLOATS, F1 = GemmSmem<GEMM_NN, BM, BN, BK>::FLOATS, F2 = GemmSmem<GEMM_TN, BM, BN, BK>::FLOATS;
-    constexpr int FL = F0 > F1 ? (F0 > F2 ? F0 : F2) : (F1 > F2 ? F1 : F2);
-    __shared__ __attribute__((aligned(16))) float smem[FL];
+    using NT = KLoopF32<GEMM_NT, BM, BN, BK, true, 2, 2, 0, KL>;
+    using NN = KLoopF32<GEMM_NN, BM, BN, BK, true, 2, 2, 0, KL>;
+    using TN = KLoopF32<GEMM_TN, BM, BN, BK, true, 2, 2, 0, KL>;
+    __shared__ __attribute__((aligned(16))) float smem[gemm_smem_floats<NT, NN, TN>()];
     int p, z, bx;
     if (!gemm_multi_locate(mp, p, z, bx)) return;
     const int form = mp.form[p];
-    if (form == GEMM_NT) gemm_f32_body<GEMM_NT, BM, BN, BK, true, 2, 2, 0, true, KL>(mp.g[p], z, bx, smem);
-    else if (form == GEMM_NN) gemm_f32_body<GEMM_NN, BM, BN, BK, true, 2, 2, 0, true, KL>(mp.g[p], z, bx, smem);
-    else gemm_f32_body<GEMM_TN, BM, BN, BK, true, 2, 2, 0, true, KL>(mp.g[p], z, bx, smem);
+    if (form == GEMM_NT) gemm_tile_frame<NT, true>(mp.g[p], z, bx, smem);
+    else if (form == GEMM_NN) gemm_tile_frame<NN, true>(mp.g[p], z, bx, smem);
+    else gemm_tile_frame<TN, true>(mp.g[p], z, bx, smem);
 }
 
 // Kernel kinds of the launcher: one per real kernel symbol, so that a profiler line can be matched to a rocprofv3 kernel-trace row.

@@ -346,53 +346,31 @@ __device__ __forceinline__ void gemm_bf16_kloop(const GemmArgs& g, const GemmPro
     }
 }
 
-// One workgroup's share of one problem (the bf16 twin of gemm_f32_body: same tile / split-K / column-sum / dual-source logic).
-template <int FORM, int BM, int BN, int BK, int PF, bool DUAL = false>
-__device__ __forceinline__ void gemm_bf16_body(const GemmArgs& g, int z, int bxs, float* smem) {
-    constexpr int WGM = 2, WGN = 2, NTH = 256;
-    constexpr int TM = (BM / WGM) / 32, TN = (BN / WGN) / 32;
-    if (g.wave_prio > 0) MTTS_SETPRIO_HIGH();   // (the critical stream's launches beside side-stream work: GemmArgs::wave_prio)
-    const GemmProb pr = gemm_resolve(g, z);
-    const bool has_cs = gemm_has_colsum<FORM>(g);
-    const int tiles_nc = (pr.N + BN - 1) / BN, tiles_n = tiles_nc + (has_cs ? 1 : 0), tiles_m = (pr.M + BM - 1) / BM;
-    const int S = g.splitk > 1 ? g.splitk : 1;
-    const int tile_lin = bxs / S, split = bxs - tile_lin * S;
-    if (tile_lin >= tiles_m * tiles_n || pr.K <= 0) return;
-    const int m0 = (tile_lin / tiles_n) * BM, n0 = (tile_lin % tiles_n) * BN;
-    const bool cs_tile = has_cs && n0 == tiles_nc * BN;
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const int nch_all = (pr.K + BK - 1) / BK, cps = (nch_all + S - 1) / S;
-    const int c_lo = split * cps, c_hi = (c_lo + cps < nch_all) ? c_lo + cps : nch_all;
-    if constexpr (FORM == GEMM_NT_H) gemm_bf16_kloop_h<BM, BN, BK, WGM, WGN>(g, pr, z, m0, n0, c_lo, c_hi, smem, acc);
-    else gemm_bf16_kloop<FORM, BM, BN, BK, PF, WGM, WGN>(g, pr, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
-    if constexpr (DUAL && FORM != GEMM_NT_H) {
-        if (g.A2 != nullptr && !cs_tile) {
-            const GemmProb p2 = gemm_resolve2(g, z, pr);   // (the first K-loop ends on a barrier: its LDS stages are free)
-            gemm_bf16_kloop<FORM, BM, BN, BK, PF, WGM, WGN>(g, p2, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
-        }
+// K-loop policy of the bf16 family (see gemm.h: KLoopF32, gemm_tile_frame); FORM GEMM_NT_H: the plane-staged loop.
+template <int FORM_, int BM_, int BN_, int BK_, int PF>
+struct KLoopBf16 {
+    static constexpr int FORM = FORM_, BM = BM_, BN = BN_, BK = BK_, WGM = 2, WGN = 2;
+    static constexpr int kSmemFloats = GemmBf16Smem<BM, BN, BK>::FLOATS;
+    static constexpr bool kRaisesPrio = true;                   // GemmArgs::wave_prio: the critical stream's launches beside side-stream work
+    static constexpr bool kBarrierBeforeSecondSource = false;   // both loops end on a barrier: the LDS stages are free
+    static constexpr bool kHasSecondSource = FORM != GEMM_NT_H; // gemm_bf16_planes_ok: a plane problem is single-source
+    static __device__ __forceinline__ void run(const GemmArgs& g, const GemmProb& pr, int z, int m0, int n0, bool cs_tile, int c_lo, int c_hi,
+                                               float* smem, f32x16 (&acc)[(BM / WGM) / 32][(BN / WGN) / 32]) {
+        if constexpr (FORM == GEMM_NT_H) gemm_bf16_kloop_h<BM, BN, BK, WGM, WGN>(g, pr, z, m0, n0, c_lo, c_hi, smem, acc);
+        else gemm_bf16_kloop<FORM, BM, BN, BK, PF, WGM, WGN>(g, pr, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
     }
-    if (S > 1 && !splitk_combine<TM, TN, NTH>(g, z, tile_lin, split, S, acc)) return;
-    gemm_finish<TM, TN, WGM, WGN>(g, pr, z, m0, n0, cs_tile, acc);
-}
+};
 
 template <int FORM, int BM, int BN, int BK, int PF>
 __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) float smem[GemmBf16Smem<BM, BN, BK>::FLOATS];
-    int z = blockIdx.z;
-    int bxs = blockIdx.x;
-    if (g.xs.on) { if (!xcd_sched_locate(g.xs, bxs, z, bxs)) return; }
-    else if (g.swizzle == 2) { if (!xcd_panel_locate(bxs, g.po_tiles_m, (g.N + BN - 1) / BN + (gemm_has_colsum<FORM>(g) ? 1 : 0), g.splitk > 1 ? g.splitk : 1, bxs)) return; }
-    else if (g.swizzle) bxs = xcd_group_remap(bxs, (int)gridDim.x, xcd_group_size((g.N + BN - 1) / BN, g.splitk));
-    gemm_bf16_body<FORM, BM, BN, BK, PF>(g, z, bxs, smem);
+    using KLoop = KLoopBf16<FORM, BM, BN, BK, PF>;
+    __shared__ __attribute__((aligned(16))) float smem[KLoop::kSmemFloats];
+    int z, bxs;
+    if (!gemm_single_locate<FORM, BN>(g, z, bxs)) return;
+    gemm_tile_frame<KLoop>(g, z, bxs, smem);
 }
 
-// several independent problems in ONE launch (see gemm_f32_multi_kernel); DUAL: the launch may carry dual-source problems
+// several independent problems in ONE launch; DUAL: the launch may carry dual-source problems
 template <int BM, int BN, int BK, int PF, bool DUAL>
 __global__ __launch_bounds__(256) void gemm_bf16_multi_kernel(GemmMulti mp) {
     __shared__ __attribute__((aligned(16))) float smem[GemmBf16Smem<BM, BN, BK>::FLOATS];
@@ -400,27 +378,25 @@ __global__ __launch_bounds__(256) void gemm_bf16_multi_kernel(GemmMulti mp) {
     if (!gemm_multi_locate(mp, p, z, bx)) return;
     const int form = mp.form[p];
     if (form == GEMM_NT) {
-        if (mp.g[p].Ah != nullptr) gemm_bf16_body<GEMM_NT_H, BM, BN, BK, PF, DUAL>(mp.g[p], z, bx, smem);   // (set by the launcher only when both planes exist)
-        else gemm_bf16_body<GEMM_NT, BM, BN, BK, PF, DUAL>(mp.g[p], z, bx, smem);
-    } else if (form == GEMM_NN) gemm_bf16_body<GEMM_NN, BM, BN, BK, PF, DUAL>(mp.g[p], z, bx, smem);
-    else gemm_bf16_body<GEMM_TN, BM, BN, BK, PF, DUAL>(mp.g[p], z, bx, smem);
+        if (mp.g[p].Ah != nullptr) gemm_tile_frame<KLoopBf16<GEMM_NT_H, BM, BN, BK, PF>, DUAL>(mp.g[p], z, bx, smem);   // (set by the launcher only when both planes exist)
+        else gemm_tile_frame<KLoopBf16<GEMM_NT, BM, BN, BK, PF>, DUAL>(mp.g[p], z, bx, smem);
+    } else if (form == GEMM_NN) gemm_tile_frame<KLoopBf16<GEMM_NN, BM, BN, BK, PF>, DUAL>(mp.g[p], z, bx, smem);
+    else gemm_tile_frame<KLoopBf16<GEMM_TN, BM, BN, BK, PF>, DUAL>(mp.g[p], z, bx, smem);
 }
-
 // a multi-problem launch that carries plane problems (non-dual, 64x64): the plane K-loop runs at HBK (64: whole 128-byte lines per row and
 // slice) in an LDS allocation sized for it; the launch's other problems keep BK.  A kernel of its own: launches without planes keep the
 // smaller allocation (7 instead of 4 workgroups per CU).
 template <int BM, int BN, int BK, int HBK, int PF>
 __global__ __launch_bounds__(256) void gemm_bf16_multi_planes_kernel(GemmMulti mp) {
-    constexpr int F0 = GemmBf16Smem<BM, BN, BK>::FLOATS, F1 = GemmBf16Smem<BM, BN, HBK>::FLOATS;
-    __shared__ __attribute__((aligned(16))) float smem[F0 > F1 ? F0 : F1];
+    __shared__ __attribute__((aligned(16))) float smem[gemm_smem_floats<KLoopBf16<GEMM_NT, BM, BN, BK, PF>, KLoopBf16<GEMM_NT_H, BM, BN, HBK, PF>>()];
     int p, z, bx;
     if (!gemm_multi_locate(mp, p, z, bx)) return;
     const int form = mp.form[p];
     if (form == GEMM_NT) {
-        if (mp.g[p].Ah != nullptr) gemm_bf16_body<GEMM_NT_H, BM, BN, HBK, PF, false>(mp.g[p], z, bx, smem);
-        else gemm_bf16_body<GEMM_NT, BM, BN, BK, PF, false>(mp.g[p], z, bx, smem);
-    } else if (form == GEMM_NN) gemm_bf16_body<GEMM_NN, BM, BN, BK, PF, false>(mp.g[p], z, bx, smem);
-    else gemm_bf16_body<GEMM_TN, BM, BN, BK, PF, false>(mp.g[p], z, bx, smem);
+        if (mp.g[p].Ah != nullptr) gemm_tile_frame<KLoopBf16<GEMM_NT_H, BM, BN, HBK, PF>, false>(mp.g[p], z, bx, smem);
+        else gemm_tile_frame<KLoopBf16<GEMM_NT, BM, BN, BK, PF>, false>(mp.g[p], z, bx, smem);
+    } else if (form == GEMM_NN) gemm_tile_frame<KLoopBf16<GEMM_NN, BM, BN, BK, PF>, false>(mp.g[p], z, bx, smem);
+    else gemm_tile_frame<KLoopBf16<GEMM_TN, BM, BN, BK, PF>, false>(mp.g[p], z, bx, smem);
 }
 
 constexpr int kBf16BK = 32;

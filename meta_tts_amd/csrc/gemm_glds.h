@@ -214,62 +214,44 @@ __device__ __forceinline__ void gemm_glds_kloop(const GemmArgs& g, const GemmPro
     for (int r = 0; r < 16; ++r) acc[0][0][r] += acc0[r] + acc1[r];
 }
 
-template <int FORM, bool DUAL = false>
-__device__ __forceinline__ void gemm_glds_body(const GemmArgs& g, int z, int bxs, float* smem) {
-    constexpr int BM = 64, BN = 64, BK = kGldsBK;
-    const GemmProb pr = gemm_resolve(g, z);
-    const bool has_cs = gemm_has_colsum<FORM>(g);
-    const int tiles_nc = (pr.N + BN - 1) / BN, tiles_n = tiles_nc + (has_cs ? 1 : 0), tiles_m = (pr.M + BM - 1) / BM;
-    const int S = g.splitk > 1 ? g.splitk : 1;
-    const int tile_lin = bxs / S, split = bxs - tile_lin * S;
-    if (tile_lin >= tiles_m * tiles_n || pr.K <= 0) return;
-    const int m0 = (tile_lin / tiles_n) * BM, n0 = (tile_lin % tiles_n) * BN;
-    const bool cs_tile = has_cs && n0 == tiles_nc * BN;
-    f32x16 acc[1][1];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
-    const int nch_all = (pr.K + BK - 1) / BK, cps = (nch_all + S - 1) / S;
-    const int c_lo = split * cps, c_hi = (c_lo + cps < nch_all) ? c_lo + cps : nch_all;
-    gemm_glds_kloop<FORM>(g, pr, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
-    if (DUAL) {   // second source of a dual-source problem (gemm.h: gemm_f32_body)
-        if (g.A2 != nullptr && !cs_tile) {
-            __syncthreads();   // every wave is done with the ring slots of the first source
-            const GemmProb p2 = gemm_resolve2(g, z, pr);
-            gemm_glds_kloop<FORM>(g, p2, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
-        }
+// K-loop policy of the LDS-DMA family (see gemm.h: KLoopF32, gemm_tile_frame): one 64x64 tile shape, the 3-stage ring.
+template <int FORM_>
+struct KLoopGlds {
+    static constexpr int FORM = FORM_, BM = 64, BN = 64, BK = kGldsBK, WGM = 2, WGN = 2;
+    static constexpr int kSmemFloats = kGldsSmemFloats;
+    static constexpr bool kRaisesPrio = false;                 // the family was off the automatic tile choice when GemmArgs::wave_prio came: never measured with it
+    static constexpr bool kBarrierBeforeSecondSource = true;   // the loop ends on MFMAs: waves may still read the ring slots of the first source
+    static constexpr bool kHasSecondSource = true;
+    static __device__ __forceinline__ void run(const GemmArgs& g, const GemmProb& pr, int z, int m0, int n0, bool cs_tile, int c_lo, int c_hi,
+                                               float* smem, f32x16 (&acc)[1][1]) {
+        gemm_glds_kloop<FORM>(g, pr, z, m0, n0, cs_tile, c_lo, c_hi, smem, acc);
     }
-    if (S > 1 && !splitk_combine<1, 1, 256>(g, z, tile_lin, split, S, acc)) return;
-    gemm_finish<1, 1, 2, 2>(g, pr, z, m0, n0, cs_tile, acc);
-}
+};
 
 template <int FORM>
 __global__ __launch_bounds__(256) void gemm_glds_kernel(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) float smem[kGldsSmemFloats];
-    int bx = blockIdx.x, z = blockIdx.z;
-    if (g.xs.on) { if (!xcd_sched_locate(g.xs, bx, z, bx)) return; }
-    else if (g.swizzle == 2) { if (!xcd_panel_locate(bx, g.po_tiles_m, (g.N + 63) / 64 + (gemm_has_colsum<FORM>(g) ? 1 : 0), g.splitk > 1 ? g.splitk : 1, bx)) return; }
-    else if (g.swizzle) bx = xcd_group_remap(bx, (int)gridDim.x, xcd_group_size((g.N + 63) / 64, g.splitk));
-    gemm_glds_body<FORM>(g, z, bx, smem);
+    int z, bx;
+    if (!gemm_single_locate<FORM, KLoopGlds<FORM>::BN>(g, z, bx)) return;
+    gemm_tile_frame<KLoopGlds<FORM>>(g, z, bx, smem);
 }
-
 __global__ __launch_bounds__(256) void gemm_glds_multi_kernel(GemmMulti mp) {
     __shared__ __attribute__((aligned(16))) float smem[kGldsSmemFloats];
     int p, z, bx;
     if (!gemm_multi_locate(mp, p, z, bx)) return;
     const int form = mp.form[p];
-    if (form == GEMM_NT) gemm_glds_body<GEMM_NT>(mp.g[p], z, bx, smem);
-    else if (form == GEMM_NN) gemm_glds_body<GEMM_NN>(mp.g[p], z, bx, smem);
-    else gemm_glds_body<GEMM_TN>(mp.g[p], z, bx, smem);
+    if (form == GEMM_NT) gemm_tile_frame<KLoopGlds<GEMM_NT>>(mp.g[p], z, bx, smem);
+    else if (form == GEMM_NN) gemm_tile_frame<KLoopGlds<GEMM_NN>>(mp.g[p], z, bx, smem);
+    else gemm_tile_frame<KLoopGlds<GEMM_TN>>(mp.g[p], z, bx, smem);
 }
-
 __global__ __launch_bounds__(256) void gemm_glds_multi_dual_kernel(GemmMulti mp) {
     __shared__ __attribute__((aligned(16))) float smem[kGldsSmemFloats];
     int p, z, bx;
     if (!gemm_multi_locate(mp, p, z, bx)) return;
     const int form = mp.form[p];
-    if (form == GEMM_NT) gemm_glds_body<GEMM_NT, true>(mp.g[p], z, bx, smem);
-    else if (form == GEMM_NN) gemm_glds_body<GEMM_NN, true>(mp.g[p], z, bx, smem);
-    else gemm_glds_body<GEMM_TN, true>(mp.g[p], z, bx, smem);
+    if (form == GEMM_NT) gemm_tile_frame<KLoopGlds<GEMM_NT>, true>(mp.g[p], z, bx, smem);
+    else if (form == GEMM_NN) gemm_tile_frame<KLoopGlds<GEMM_NN>, true>(mp.g[p], z, bx, smem);
+    else gemm_tile_frame<KLoopGlds<GEMM_TN>, true>(mp.g[p], z, bx, smem);
 }
 
 inline void gemm_glds_launch(const GemmKernelId& k, const GemmArgs& g, dim3 grid, hipStream_t stream) {
